@@ -31,6 +31,11 @@ Other workloads (side metrics and BASELINE configs[2..4]): `--env portfolio|cryp
 cashpenalty|stoploss`, `--tickers 100 --turbulence-pct 90` (configs[3] per-GPU slice),
 `--env crypto --envs-per-gpu 32768 --rollout 16` (configs[4] per-GPU slice: steps write straight
 into [n_steps, E, .] rollout buffers, one GAE scan per segment, one hipGraph replay per segment).
+
+`--dump-outputs DIR`: after the timed region, rank 0 writes what the timed path handed its caller in
+the last step (obs / reward / done of the env, or the rollout buffers) as DIR/<name>.npy, float32 or
+float64.  Inputs are seeded, so two builds run with the same arguments can be compared array for
+array.  Above 64 MB in all, the same fixed, seeded sample of envs is taken from every array.
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ E_PER_GPU = 65_536
 N_TICKERS, N_TECH, N_DAYS = 30, 8, 2893
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8 TB/s spec
 PREWARM_DEFAULT = 2048
+DUMP_BUDGET_BYTES = 64 << 20
 
 
 def algorithmic_bytes(N, K):
@@ -238,6 +244,32 @@ class Workload:
 
     def episode_return(self):
         return self.env.episode_return()
+
+    def outputs(self):
+        """(name -> device tensor, env axis): what the last step() handed its caller."""
+        return dict(obs=self.env.obs, reward=self.env.reward, done=self.env.done), 0
+
+
+def dump_outputs(work, out_dir):
+    """Write work.outputs() as out_dir/<name>.npy (float64 stays float64, all else float32).  When
+    the arrays exceed DUMP_BUDGET_BYTES, every one keeps the same sorted sample of env indices,
+    drawn from default_rng(0): fixed for a given shape, so two runs stay comparable."""
+    import torch
+    outs, axis = work.outputs()
+    E = work.E
+    dt = {k: torch.float64 if v.dtype == torch.float64 else torch.float32 for k, v in outs.items()}
+    per_env = sum(v.numel() // E * (8 if dt[k] == torch.float64 else 4) for k, v in outs.items())
+    idx = None
+    if per_env * E > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // per_env
+        idx = np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in outs.items():
+        if idx is not None:
+            v = v.index_select(axis, torch.from_numpy(idx).to(v.device))
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.to(dt[k]).cpu().numpy())
+    return dict(dir=out_dir, arrays=sorted(outs), envs=E if idx is None else int(idx.size),
+                of_envs=E)
 
 
 def build_workload(args, torch, dev, rank):
@@ -431,6 +463,8 @@ def attach_rollout(w, args, torch, dev, gen):
         state["t"] = 0
 
     w.step, w.reset = step, reset
+    w.outputs = lambda: (dict(obs=buf.obs, rewards=buf.rewards, dones=buf.dones,
+                              advantages=buf.advantages, returns=buf.returns), 1)
 
 
 # ------------------------------------------------------------------------------- timed region
@@ -613,7 +647,11 @@ def main(argv=None):
     ap.add_argument("--rollout", type=int, default=0,
                     help="collect into [n_steps, E, .] rollout buffers + GAE scan per segment "
                          "(BASELINE configs[4])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.env in ("riskpre", "launcher-selftest"):
+        raise SystemExit(f"--dump-outputs: --env {args.env} has no env step outputs")
     if args.env == "riskpre":
         riskpre_lines(cpu_baseline=not args.no_cpu_baseline)
         return 0
@@ -667,6 +705,9 @@ def main(argv=None):
         tt = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        print("bench.py: outputs written: " + json.dumps(dump_outputs(work, args.dump_outputs)),
+              file=sys.stderr, flush=True)
 
     if rank == 0 and selftest:
         print(json.dumps({"metric": "launcher self-test (no kernel runs; value is meaningless)",

@@ -759,6 +759,39 @@ RISKPRE_SCENARIOS = {
 }
 
 
+# ----------------------------------------------------------------- data helpers
+def frame_to_arrays(prefix, df):
+    """DataFrame -> plain arrays under `prefix`: index, column names, one array per column (text
+    columns as unicode arrays); tests/test_data_formats.py rebuilds the frame from them."""
+    out = {f"{prefix}__index": df.index.to_numpy(np.int64),
+           f"{prefix}__columns": np.asarray(list(df.columns))}
+    for c in df.columns:
+        v = df[c].to_numpy()
+        out[f"{prefix}__col__{c}"] = v.astype(str) if v.dtype == object else v
+    return out
+
+
+def run_data_formats():
+    """preprocessors.py data_split (:24-33) and FeatureEngineer.clean_data (:107-131), unmodified,
+    on the seeded frames tests/test_data_formats.py builds; inputs and outputs are stored."""
+    import pandas as pd
+    pre = _load_preprocessors()
+    from tests.test_data_formats import _frame, _ragged
+    df = _frame()
+    ragged = _ragged(df)
+    out = dict(frame_to_arrays("frame", df), **frame_to_arrays("ragged", ragged))
+    out.update(frame_to_arrays("split", pre.data_split(df, "2020-01-02", "2020-01-08")))
+    out.update(frame_to_arrays("clean", pre.FeatureEngineer(use_technical_indicator=False)
+                               .clean_data(ragged)))
+    out["meta"] = np.array([f"numpy={np.__version__}", f"pandas={pd.__version__}",
+                            "source=finrl/meta/preprocessor/preprocessors.py:24-33,107-131 "
+                            "(unmodified)"])
+    path = os.path.join(HERE, "data_formats.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB)")
+    return out
+
+
 # ----------------------------------------------------------------- harness (caller loops)
 def _df_columns(df):
     """DataFrame -> plain arrays (object columns holding arrays are stacked)."""
@@ -1013,7 +1046,7 @@ def main(argv):
                      + ["cashpenalty:" + k for k in CASHPENALTY_SCENARIOS]
                      + ["stoploss:" + k for k in STOPLOSS_SCENARIOS]
                      + ["riskpre:" + k for k in RISKPRE_SCENARIOS]
-                     + ["harness:" + k for k in HARNESS_SCENARIOS])
+                     + ["harness:" + k for k in HARNESS_SCENARIOS] + ["data_formats"])
     for n in names:
         if n in STOCK_SCENARIOS:
             run_stock(n, **STOCK_SCENARIOS[n])
@@ -1031,6 +1064,8 @@ def main(argv):
             run_stocknp(n[8:], **STOCKNP_SCENARIOS[n[8:]])
         elif n.startswith("crypto:") and n[7:] in CRYPTO_SCENARIOS:
             run_crypto(n[7:], **CRYPTO_SCENARIOS[n[7:]])
+        elif n == "data_formats":
+            run_data_formats()
         else:
             raise SystemExit(f"unknown scenario {n}")
 

@@ -1,5 +1,5 @@
-"""data_split / df_to_array restatements vs the reference functions (build container only:
-skipped where /root/reference is absent) and vs their documented contracts everywhere."""
+"""data_split / df_to_array / clean_data restatements vs the reference functions' recorded outputs
+(tests/golden/data_formats.npz) and vs their documented contracts."""
 import os
 
 import numpy as np
@@ -54,35 +54,34 @@ def test_df_to_array_contract():
     assert np.isfinite(tech).all()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/finrl"), reason="reference not present")
-def test_matches_reference_functions():
-    """Against the reference's own data_split (preprocessors.py:24-33; imported behind a
-    stockstats stub) and the body of df_to_array as YahooFinanceProcessor defines it."""
-    import sys
-    import types
-    from oracle import ref_harness as rh
-    rh.install()
-    sys.modules.setdefault("stockstats", types.SimpleNamespace(StockDataFrame=object))
-    cfg = types.ModuleType("finrl.config")
-    cfg.INDICATORS = []
-    sys.modules.setdefault("finrl.config", cfg)
-    yd = types.ModuleType("finrl.meta.preprocessor.yahoodownloader")
-    yd.YahooDownloader = object
-    sys.modules.setdefault("finrl.meta.preprocessor.yahoodownloader", yd)
-    import importlib
-    sys.modules["finrl"].config = cfg
-    pre = importlib.import_module("finrl.meta.preprocessor.preprocessors")
-    df = _frame()
-    a = pre.data_split(df, "2020-01-02", "2020-01-08")
-    b = data_split(df, "2020-01-02", "2020-01-08")
-    pd.testing.assert_frame_equal(a, b)
-    # FeatureEngineer.clean_data (:107-131) on a ragged frame: one ticker misses a date, one a close
-    from finrl_amd.data import clean_data
+def _ragged(df):
+    """The frame clean_data is checked on: one ticker misses the last date, one the first close."""
     t_a, t_b = sorted(df.tic.unique())[:2]
     ragged = df.drop(df.index[(df.tic == t_a) & (df.date == df.date.max())]).copy()
     ragged.loc[(ragged.tic == t_b) & (ragged.date == ragged.date.min()), "close"] = np.nan
-    fe = pre.FeatureEngineer(use_technical_indicator=False)
-    pd.testing.assert_frame_equal(fe.clean_data(ragged), clean_data(ragged))
+    return ragged
+
+
+def _stored_frame(z, prefix):
+    cols = z[f"{prefix}__columns"].tolist()
+    data = {}
+    for c in cols:
+        v = z[f"{prefix}__col__{c}"]
+        data[c] = v.astype(object) if v.dtype.kind == "U" else v
+    return pd.DataFrame(data, columns=cols, index=z[f"{prefix}__index"])
+
+
+def test_matches_reference_functions(golden_dir):
+    """Against the reference's own data_split (preprocessors.py:24-33) and FeatureEngineer.clean_data
+    (:107-131) on a ragged frame, as recorded in tests/golden/data_formats.npz by make_golden.py."""
+    from finrl_amd.data import clean_data
+    with np.load(os.path.join(golden_dir, "data_formats.npz"), allow_pickle=False) as z:
+        df, ragged = _stored_frame(z, "frame"), _stored_frame(z, "ragged")
+        split, clean = _stored_frame(z, "split"), _stored_frame(z, "clean")
+    pd.testing.assert_frame_equal(_frame(), df)           # the fixture's inputs are this file's frames
+    pd.testing.assert_frame_equal(_ragged(_frame()), ragged)
+    pd.testing.assert_frame_equal(data_split(df, "2020-01-02", "2020-01-08"), split)
+    pd.testing.assert_frame_equal(clean_data(ragged), clean)
     assert clean_data(ragged).tic.nunique() == df.tic.nunique() - 2
 
 

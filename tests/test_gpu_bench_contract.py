@@ -80,3 +80,26 @@ def test_two_rank_rehearsal_of_the_scaling_command():
     assert j["rccl"]["world"] == 2 and j["rccl"]["gathers"] >= 1 and j["rccl"]["gathered"] == 16384
     assert abs(j["value"] - 16384 * 40 / (j["ms_per_step"] * 1e-3 * 40)) / j["value"] < 1e-9
     assert "REHEARSAL" in j["data"] and "cpu_baseline" not in j
+
+
+def test_dump_outputs_repeat_run_for_run(tmp_path):
+    """--dump-outputs on the headline workload: the last timed step's obs / reward / done, a fixed sample of
+    envs within 64 MB, and the same arrays from a second run with the same arguments."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        j = _bench("--gpus", "1", "--steps", "24", "--warmup", "4", "--prewarm", "0", "--no-cpu-baseline",
+                   "--dump-outputs", str(d))
+        _check_common(j, 24, 4)
+        runs.append({k: np.load(d / f"{k}.npy") for k in ("obs", "reward", "done")})
+        assert sorted(os.listdir(d)) == ["done.npy", "obs.npy", "reward.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    a, b = runs
+    n = a["reward"].shape[0]
+    assert 32768 < n < 65536 and a["obs"].shape == (n, 301) and a["done"].shape == (n,)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.isfinite(a["obs"]).all() and set(np.unique(a["done"])) <= {0.0, 1.0}
+    assert (a["obs"][:, 0] >= 0).all()                  # cash of every sampled env
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
