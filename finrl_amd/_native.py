@@ -51,6 +51,9 @@ class StockPanelPtrs(C.Structure):
 STOCK_F64_FIELDS = ("cash", "cost", "last_reward", "turbulence", "asset0", "ret_sum", "ret_sumsq",
                     "cash0", "begin_asset")
 STOCK_I32_FIELDS = ("day", "price_day", "trades", "episode", "start_day")
+# Field order of the last-episode block (FINENV_SL_*): f64 [field][E]
+STOCK_LAST_FIELDS = ("count", "episode", "begin_asset", "end_asset", "cost", "trades", "ret_n",
+                     "ret_sum", "ret_sumsq")
 
 
 class StockStatePtrs(C.Structure):
@@ -68,6 +71,9 @@ class PortfolioPanelPtrs(C.Structure):
 
 PORTFOLIO_F64_FIELDS = ("value", "last_reward")
 PORTFOLIO_I32_FIELDS = ("day",)
+# Field order of the portfolio env's last-episode block (FINENV_PL_*): f64 [field][E]
+PORTFOLIO_LAST_FIELDS = ("count", "begin_value", "end_value", "ret_n", "ret_sum", "ret_sumsq",
+                         "run_sum", "run_sumsq")
 
 
 class PortfolioStatePtrs(C.Structure):
@@ -256,6 +262,14 @@ def lib():
     L.finenv_stoploss_set_random_start.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
     L.finenv_cashpenalty_set_audit.argtypes = [C.c_void_p, C.c_void_p]
     L.finenv_stoploss_set_audit.argtypes = [C.c_void_p, C.c_void_p]
+    # Last-episode block.  Bound only where exported: tools/exp_ab_inproc.py loads a build of an
+    # earlier commit through this function beside the current one (tests/test_native_abi.py checks
+    # that the current build exports every symbol the header declares).
+    for name, n in (("finenv_stock_set_last_episode", 2), ("finenv_stock_last_episode_stats", 3),
+                    ("finenv_portfolio_set_last_episode", 2),
+                    ("finenv_portfolio_last_episode_stats", 3)):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p] * n
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]

@@ -35,6 +35,19 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// Terminal Sharpe from running sums of n daily returns: sqrt(252) * mean / std(ddof=1), NaN where
+// the reference prints none (fewer than two returns, zero or negative variance).
+__device__ __forceinline__ double sharpe_from_sums(int n, double s1, double s2)
+{
+    double sharpe = __builtin_nan("");
+    if (n >= 2) {
+        const double mean = s1 / (double)n;
+        const double var = (s2 - s1 * mean) / (double)(n - 1);
+        if (var > 0.0) sharpe = sqrt(252.0) * mean / sqrt(var);
+    }
+    return sharpe;
+}
+
 // Counter-based uniform draw in [0, hi): splitmix64 of (seed, env, episode), multiply-shift.
 __device__ __forceinline__ int draw_start(unsigned long long seed, int env, int episode, int hi)
 {

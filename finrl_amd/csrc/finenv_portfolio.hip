@@ -47,10 +47,13 @@ struct PfParams {
     int32_t D;
     int32_t mode;          // aux kernel: 1 = reset
     uint32_t magicN;
+    double *last;          // last-episode block [FINENV_PORTFOLIO_LAST_FIELDS][E] or NULL
+    double *stats_out;     // last_episode_stats: [E][3]
 };
 
 #define PF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define PI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
+#define PL(fld) (*at(p.last, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 
 // Stream rows [el_lo, el_hi) of the block's observation tile.  row_day: per-lane panel row.
 __device__ __forceinline__ void pf_write_rows(float *__restrict__ dst,
@@ -187,12 +190,28 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
             value = value * (1 + ret);                                        // :187-188
             last_reward = value;                                              // :196
             day = day_next;
+            if (p.last != nullptr && valid) {  // portfolio_return_memory (:190), as running sums
+                PL(FINENV_PL_RUN_SUM) = PL(FINENV_PL_RUN_SUM) + ret;
+                PL(FINENV_PL_RUN_SUMSQ) = PL(FINENV_PL_RUN_SUMSQ) + ret * ret;
+            }
             if (p.weights != nullptr && valid)
                 for (int i = 0; i < N; ++i) *at(p.weights, (unsigned)(e * N + i)) = row[i];
         }
         if (valid) {
             *at(p.reward, (unsigned)e) = (float)last_reward;
             *at(p.done, (unsigned)e) = term ? 1 : 0;
+        }
+        if (term && p.last != nullptr && valid) {  // terminal summary :130-155, before any reset
+            PL(FINENV_PL_COUNT) = PL(FINENV_PL_COUNT) + 1.0;
+            PL(FINENV_PL_BEGIN_VALUE) = p.cfg.initial_amount;                 // asset_memory[0]
+            PL(FINENV_PL_END_VALUE) = value;
+            PL(FINENV_PL_RET_N) = (double)(day + 1);    // the memory's leading 0 (:217) counts
+            PL(FINENV_PL_RET_SUM) = PL(FINENV_PL_RUN_SUM);
+            PL(FINENV_PL_RET_SUMSQ) = PL(FINENV_PL_RUN_SUMSQ);
+            if (p.auto_reset) {
+                PL(FINENV_PL_RUN_SUM) = 0.0;
+                PL(FINENV_PL_RUN_SUMSQ) = 0.0;
+            }
         }
         if (term && p.auto_reset) {                                           // :202-220
             day = 0;
@@ -226,10 +245,30 @@ __global__ void __launch_bounds__(kThreads) portfolio_reset_kernel(const PfParam
     if (wib == 0 && sel) {
         PF(FINENV_PF_VALUE) = p.cfg.initial_amount;
         PI(FINENV_PI_DAY) = 0;
+        if (p.last != nullptr) {
+            PL(FINENV_PL_RUN_SUM) = 0.0;
+            PL(FINENV_PL_RUN_SUMSQ) = 0.0;
+        }
     }
     if (p.obs == nullptr) return;
     const int el_lo = wib * 32, el_hi = min(nenv_w, el_lo + 32);
     pf_write_rows(p.obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, 0, __ballot(sel), lane);
+}
+
+// {begin, end, Sharpe} of the latched episodes; NaN rows where none has finished yet.
+__global__ void portfolio_last_stats_kernel(const PfParams p)
+{
+    const int E = p.cfg.n_envs;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double *out = p.stats_out + (size_t)e * 3;
+    if (PL(FINENV_PL_COUNT) == 0.0) {
+        out[0] = out[1] = out[2] = __builtin_nan("");
+        return;
+    }
+    out[0] = PL(FINENV_PL_BEGIN_VALUE);
+    out[1] = PL(FINENV_PL_END_VALUE);
+    out[2] = sharpe_from_sums((int)PL(FINENV_PL_RET_N), PL(FINENV_PL_RET_SUM), PL(FINENV_PL_RET_SUMSQ));
 }
 
 }  // namespace
@@ -243,6 +282,7 @@ struct finenv_portfolio {
     int D;
     uint32_t magicN;
     char err[256];
+    double *last;         // finenv_portfolio_set_last_episode (appended: the layout above is unchanged)
 };
 
 namespace {
@@ -269,6 +309,7 @@ PfParams pf_params(const finenv_portfolio *h)
     p.st = h->st;
     p.D = h->D;
     p.magicN = h->magicN;
+    p.last = h->last;
     return p;
 }
 }  // namespace
@@ -348,6 +389,26 @@ int finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs,
     hipLaunchKernelGGL(portfolio_step_kernel, dim3((h->cfg.n_envs + kWave - 1) / kWave),
                        dim3(kThreads), 0, (hipStream_t)stream, p);
     return pf_check(h, "portfolio_step");
+}
+
+int finenv_portfolio_set_last_episode(finenv_portfolio *h, double *last)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->last = last;
+    return FINENV_OK;
+}
+
+int finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (!h->last) return pf_fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
+    if (!h->bound) return pf_fail(h, FINENV_ERR_UNBOUND, "last_episode_stats: bind first");
+    const finenv_host::DeviceGuard guard(h->device);
+    PfParams p = pf_params(h);
+    p.stats_out = out;
+    hipLaunchKernelGGL(portfolio_last_stats_kernel, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return pf_check(h, "portfolio_last_episode_stats");
 }
 
 }  // extern "C"

@@ -44,15 +44,28 @@ __global__ void stock_stats_kernel(const Params p)
     out[2] = end - a0;
     out[3] = SF(FINENV_SF_COST);
     out[4] = (double)SI(FINENV_SI_TRADES);
-    double sharpe = __builtin_nan("");
     const int n = SI(FINENV_SI_DAY) - SI(FINENV_SI_START_DAY);   // daily returns accumulated
-    if (n >= 2) {        // sqrt(252) * mean / std(ddof=1) from the running sums
-        const double s1 = SF(FINENV_SF_RET_SUM), s2 = SF(FINENV_SF_RET_SUMSQ);
-        const double mean = s1 / (double)n;
-        const double var = (s2 - s1 * mean) / (double)(n - 1);
-        if (var > 0.0) sharpe = sqrt(252.0) * mean / sqrt(var);
+    out[5] = sharpe_from_sums(n, SF(FINENV_SF_RET_SUM), SF(FINENV_SF_RET_SUMSQ));
+}
+
+// The same six columns for the episodes latched in the last-episode block (finenv_stock_step).
+__global__ void stock_last_stats_kernel(const Params p)
+{
+    const int E = p.cfg.n_envs;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double *out = p.stats_out + (size_t)e * 6;
+    if (SL(FINENV_SL_COUNT) == 0.0) {
+        for (int j = 0; j < 6; ++j) out[j] = __builtin_nan("");
+        return;
     }
-    out[5] = sharpe;
+    const double a0 = SL(FINENV_SL_BEGIN_ASSET), end = SL(FINENV_SL_END_ASSET);
+    out[0] = a0;
+    out[1] = end;
+    out[2] = end - a0;
+    out[3] = SL(FINENV_SL_COST);
+    out[4] = SL(FINENV_SL_TRADES);
+    out[5] = sharpe_from_sums((int)SL(FINENV_SL_RET_N), SL(FINENV_SL_RET_SUM), SL(FINENV_SL_RET_SUMSQ));
 }
 
 }  // namespace
@@ -71,6 +84,7 @@ struct finenv_stock {
     int desync_hint;      // finenv_stock_set_desync_hint
     uint32_t magicN;
     char err[256];
+    double *last;         // finenv_stock_set_last_episode (appended: the layout above is unchanged)
 };
 
 namespace {
@@ -102,6 +116,7 @@ Params make_params(const finenv_stock *h)
     p.obs_pitch = h->obs_pitch;
     p.desync_hint = h->desync_hint;
     p.magicN = h->magicN;
+    p.last = h->last;
     return p;
 }
 
@@ -341,6 +356,27 @@ int finenv_stock_episode_stats(finenv_stock *h, double *out, void *stream)
     hipLaunchKernelGGL(stock_stats_kernel, dim3((E + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
     return check_launch(h, "stock_episode_stats");
+}
+
+int finenv_stock_set_last_episode(finenv_stock *h, double *last)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->last = last;
+    return FINENV_OK;
+}
+
+int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (!h->last) return fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set%s");
+    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "last_episode_stats: bind first%s");
+    const finenv_host::DeviceGuard guard(h->device);
+    Params p = make_params(h);
+    p.stats_out = out;
+    const int E = h->cfg.n_envs;
+    hipLaunchKernelGGL(stock_last_stats_kernel, dim3((E + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return check_launch(h, "stock_last_episode_stats");
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cstddef>
 #include <new>
 #include <type_traits>
 
@@ -39,6 +40,7 @@ struct Params {
                           // blocks are stepped as several launches: launch_rounds below)
     int32_t diag;         // FINENV_DIAG builds only: phase-skip bitmask (timing experiments)
     unsigned long long *dbg;   // FINENV_DIAG builds only: [block][role][16] s_memrealtime stamps
+    double *last;         // last-episode block [FINENV_STOCK_LAST_FIELDS][E] or NULL
 };
 }  // namespace finenv_stock_impl
 
@@ -113,6 +115,41 @@ inline void launch_rounds(const Params &p, Kernel kernel, size_t lds_bytes, Laun
 #define SI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define HOLD(i) SI(FINENV_STOCK_I32_FIELDS + (i))
 #define SH0(i) SI(FINENV_STOCK_I32_FIELDS + N + (i))
+#define SL(fld) (*at(p.last, (unsigned)(fld) * (unsigned)E + (unsigned)e))
+
+// Latch the finished episode of lane e into the last-episode block `last` (p.last).  Called by the step
+// kernels in their once-per-episode branch (term_mask != 0), before an auto-reset rewrites the state: at
+// `term` no trade happens and nothing has been written back, so the state in memory IS the terminal state.
+// Everything but the end asset is loaded afresh here, so no value is carried from the top of the kernel
+// into this branch (the step kernels sit at the register-file edge).
+__device__ __forceinline__ void latch_last_episode(const Params &p, double *last, int E, int e,
+                                                   double end_asset)
+{
+#define LB(fld) (*at(last, (unsigned)(fld) * (unsigned)E + (unsigned)e))
+    LB(FINENV_SL_COUNT) = LB(FINENV_SL_COUNT) + 1.0;
+    LB(FINENV_SL_EPISODE) = (double)SI(FINENV_SI_EPISODE);
+    LB(FINENV_SL_BEGIN_ASSET) = SF(FINENV_SF_ASSET0);
+    LB(FINENV_SL_END_ASSET) = end_asset;
+    LB(FINENV_SL_COST) = SF(FINENV_SF_COST);
+    LB(FINENV_SL_TRADES) = (double)SI(FINENV_SI_TRADES);
+    LB(FINENV_SL_RET_N) = (double)(SI(FINENV_SI_DAY) - SI(FINENV_SI_START_DAY));
+    LB(FINENV_SL_RET_SUM) = SF(FINENV_SF_RET_SUM);
+    LB(FINENV_SL_RET_SUMSQ) = SF(FINENV_SF_RET_SUMSQ);
+#undef LB
+}
+
+// Params::last of a step kernel's argument (its only one), read from the kernel-argument segment in the
+// once-per-episode branch.  A plain `p.last` there is loaded at the top of the kernel with the other
+// arguments.  The kernels of finenv_stock_kernels.inc are at the SGPR limit, and that one more pair live
+// across the whole step moved their SGPR spills into the trade loops (DOW30 step 1 % slower with the block
+// detached, in-process A/B).  The empty asm keeps the load below it.  (stock_step_wide_kernel measured the
+// other way round: it reads p.last.)
+__device__ __forceinline__ double *last_block()
+{
+    const char *ka = (const char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return *reinterpret_cast<double *const *>(ka + offsetof(Params, last));
+}
 
 __device__ __forceinline__ void ce(int &a, int &b)
 {

@@ -1079,6 +1079,11 @@ stock_step_kernel(const Params p)
     // ---- terminal observation; auto-reset (once per episode, wave-uniform) ---------------------
     int episode_inc = 0;
     if (term_mask != 0ull) {
+        // last-episode block: before the auto-reset below rewrites the state.  At `term` the end
+        // asset equals the carried begin asset (no trade, same row); the STATS kernels keep `end`
+        // live for the Sharpe sums anyway, the others hand over end_carry (live until write-back).
+        double *const last = last_block();       // (not p.last: see last_block)
+        if (last != nullptr && term && valid) latch_last_episode(p, last, E, e, STATS ? end : end_carry);
         if (p.term_obs != nullptr)
             write_obs_rows(p.term_obs, p.panel.obs_tmpl, D, D, N, e0, nenv_w, pd_cur, term_mask,
                            rows, lane, 0, kpatch);

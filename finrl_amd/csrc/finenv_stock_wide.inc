@@ -529,6 +529,10 @@ stock_step_wide_kernel(const Params p)
     // ---- terminal observation; auto-reset (once per episode, wave-uniform) ---------------------
     int episode_inc = 0;
     if (term_mask != 0ull) {
+        // last-episode block: before the auto-reset below rewrites the state.  At `term` the end
+        // asset equals the carried begin asset (no trade, same row); the STATS kernels keep `end`
+        // live for the Sharpe sums anyway, the others hand over end_carry (live until write-back).
+        if (p.last != nullptr && term && valid) latch_last_episode(p, p.last, E, e, STATS ? end : end_carry);
         if (p.term_obs != nullptr)
             write_obs_rows_fn(p.term_obs, p.panel.obs_tmpl, D, D, N, e0, nenv_w, pd_cur, term_mask,
                               patch, lane, 0, kpatch);       // (once per episode: compact generic form)

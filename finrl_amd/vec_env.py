@@ -56,6 +56,9 @@ class VecStockTradingEnv:
     if_discrete = False
     env_name = "StockTradingEnv-MI355X"
     target_return = 10.0
+    # names of the last_episode_stats() columns, as the reference prints them (:257-264)
+    last_episode_keys = ("begin_total_asset", "end_total_asset", "total_reward", "total_cost",
+                         "total_trades", "sharpe")
 
     def __init__(self, panel: StockPanel, num_envs: int, *, hmax=100,
                  initial_amount=1_000_000, num_stock_shares=None, buy_cost_pct=1e-3,
@@ -142,6 +145,9 @@ class VecStockTradingEnv:
         self.realised = None
         self._step_args = None
         self._stats = None
+        self._last = None
+        self._last_stats = None
+        self.last_episode = None
         nat.check(L.finenv_stock_init(self._h, int(day), self._stream()), self._h, "init")
 
     # ------------------------------------------------------------------ plumbing
@@ -165,6 +171,25 @@ class VecStockTradingEnv:
             self.term_obs = torch.zeros(self.num_envs, self.state_dim, dtype=torch.float32,
                                         device=self.device)
         return self.term_obs
+
+    def enable_last_episode(self):
+        """Attach a last-episode block (finenv_stock_set_last_episode): from now on the step that
+        reports done latches the finished episode's summary -- before an auto-reset replaces the
+        state -- into a caller-owned f64 [FINENV_STOCK_LAST_FIELDS, E] device tensor, returned here
+        and viewed by name in ``self.last_episode``.  ``count`` starts at 0 and every other field
+        at NaN.  Idempotent: a second call returns the same tensor.  The block's pointer is a
+        step-kernel argument, so a step captured into a graph writes the block only if it was
+        enabled before the capture."""
+        torch = _torch()
+        if self._last is None:
+            last = torch.full((len(nat.STOCK_LAST_FIELDS), self.num_envs), float("nan"),
+                              dtype=torch.float64, device=self.device)
+            last[0].zero_()
+            nat.check(nat.lib().finenv_stock_set_last_episode(self._h, C.c_void_p(last.data_ptr())),
+                      self._h, "set_last_episode")
+            self._last = last
+            self.last_episode = {k: last[j] for j, k in enumerate(nat.STOCK_LAST_FIELDS)}
+        return self._last
 
     def hint_desynchronised(self, on=True):
         """Performance hint (results never depend on it): the envs of this batch sit on different
@@ -271,6 +296,28 @@ class VecStockTradingEnv:
         st = self.episode_stats()
         return (st[:, 1] / st[:, 0]).to(_torch().float32)
 
+    def last_episode_stats(self):
+        """episode_stats() columns of each env's last FINISHED episode -> f64 [E, 6] device tensor
+        (rows of envs that have not finished one yet are NaN).  Needs enable_last_episode()."""
+        torch = _torch()
+        if self._last is None:
+            raise nat.FinenvError("last_episode_stats: call enable_last_episode() first")
+        if self._last_stats is None:
+            self._last_stats = torch.zeros(self.num_envs, 6, dtype=torch.float64, device=self.device)
+        nat.check(nat.lib().finenv_stock_last_episode_stats(
+            self._h, C.c_void_p(self._last_stats.data_ptr()), self._stream()), self._h,
+            "last_episode_stats")
+        return self._last_stats
+
+    def last_episode_return(self):
+        """end_total_asset / begin_total_asset of each env's last finished episode, f32 [E] (NaN
+        where none has finished): what episode_return() reports for the current episode, for the
+        one an auto-reset has already replaced -- the quantity to gather across ranks."""
+        if self._last is None:
+            raise nat.FinenvError("last_episode_return: call enable_last_episode() first")
+        le = self.last_episode
+        return (le["end_asset"] / le["begin_asset"]).to(_torch().float32)
+
     def state_numpy(self):
         """Host copy of the per-env state (synchronises)."""
         out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
@@ -293,10 +340,18 @@ class SB3VecEnvAdapter:
 
     def __init__(self, env):
         """env: any of the batched envs of this package (they share the tensor protocol:
-        ``reset()``, ``step(a) -> (obs, reward, done, _)``, ``enable_terminal_obs()``)."""
+        ``reset()``, ``step(a) -> (obs, reward, done, _)``, ``enable_terminal_obs()``).  Envs with
+        a last-episode block (stock, portfolio) get it enabled here, and every done env's info then
+        carries ``"episode_summary"``: the reference's terminal printout (begin / end total asset,
+        total reward, cost, trades, Sharpe; NaN where it prints none) under its names.  (SB3's own
+        ``"episode"`` key is Monitor's sum of the scaled rewards, a different quantity.)"""
         self.env = env
         env.auto_reset = True
         env.enable_terminal_obs()
+        self._summary_keys = None
+        if hasattr(env, "enable_last_episode"):
+            env.enable_last_episode()
+            self._summary_keys = env.last_episode_keys
         self.num_envs = env.num_envs
         self.observation_space = env.observation_space
         self.action_space = env.action_space
@@ -322,9 +377,15 @@ class SB3VecEnvAdapter:
         infos = [{} for _ in range(self.num_envs)]
         if done_h.any():
             idx = np.nonzero(done_h)[0]
-            term = self.env.term_obs[torch.from_numpy(idx).to(self.env.device)].cpu().numpy()
+            idx_t = torch.from_numpy(idx).to(self.env.device)
+            term = self.env.term_obs[idx_t].cpu().numpy()
             for j, i in enumerate(idx):
                 infos[i]["terminal_observation"] = term[j]
+            if self._summary_keys is not None:
+                summ = self.env.last_episode_stats()[idx_t].cpu().numpy()
+                for j, i in enumerate(idx):
+                    infos[i]["episode_summary"] = {k: float(v) for k, v in
+                                                   zip(self._summary_keys, summ[j])}
         return obs_h, rew_h, done_h, infos
 
     def step(self, actions):

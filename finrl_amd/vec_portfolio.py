@@ -17,6 +17,8 @@ class VecStockPortfolioEnv:
 
     if_discrete = False
     env_name = "StockPortfolioEnv-MI355X"
+    # names of the last_episode_stats() columns, as the reference prints them (:141-153)
+    last_episode_keys = ("begin_total_asset", "end_total_asset", "sharpe")
 
     def __init__(self, panel: PortfolioPanel, num_envs: int, *, initial_amount=1_000_000,
                  auto_reset=True, device="cuda"):
@@ -55,6 +57,9 @@ class VecStockPortfolioEnv:
         self.done = torch.zeros(E, dtype=torch.uint8, device=dev)
         self.term_obs = None
         self.weights = None
+        self._last = None
+        self._last_stats = None
+        self.last_episode = None
 
     def _stream(self):
         import torch
@@ -80,6 +85,52 @@ class VecStockPortfolioEnv:
             self.weights = torch.zeros(self.num_envs, self.stock_dim, dtype=torch.float32,
                                        device=self.device)
         return self.weights
+
+    def enable_last_episode(self):
+        """Attach a last-episode block (finenv_portfolio_set_last_episode), f64
+        [FINENV_PORTFOLIO_LAST_FIELDS, E] on the device, viewed by name in ``self.last_episode``:
+        the terminal step latches begin / end value and the daily-return sums of the finished
+        episode before an auto-reset.  While attached, every step also keeps running return sums
+        (``run_sum`` / ``run_sumsq``); they start at 0 for envs on day 0 and at NaN for envs in mid
+        episode (whose earlier returns were not kept: that episode's Sharpe reads NaN).
+        Idempotent; as for the stock env, a captured step sees the block only if it was enabled
+        before the capture."""
+        import torch
+        if self._last is None:
+            last = torch.full((len(nat.PORTFOLIO_LAST_FIELDS), self.num_envs), float("nan"),
+                              dtype=torch.float64, device=self.device)
+            last[0].zero_()
+            fresh = self.state["day"] == 0
+            for k in ("run_sum", "run_sumsq"):
+                j = nat.PORTFOLIO_LAST_FIELDS.index(k)
+                last[j] = torch.where(fresh, torch.zeros_like(last[j]), last[j])
+            nat.check(nat.lib().finenv_portfolio_set_last_episode(self._h, C.c_void_p(last.data_ptr())),
+                      self._h, "set_last_episode", "portfolio")
+            self._last = last
+            self.last_episode = {k: last[j] for j, k in enumerate(nat.PORTFOLIO_LAST_FIELDS)}
+        return self._last
+
+    def last_episode_stats(self):
+        """{begin_total_asset, end_total_asset, sharpe} of each env's last finished episode -> f64
+        [E, 3] device tensor (NaN rows where none has finished).  Needs enable_last_episode()."""
+        import torch
+        if self._last is None:
+            raise nat.FinenvError("last_episode_stats: call enable_last_episode() first")
+        if self._last_stats is None:
+            self._last_stats = torch.zeros(self.num_envs, 3, dtype=torch.float64, device=self.device)
+        nat.check(nat.lib().finenv_portfolio_last_episode_stats(
+            self._h, C.c_void_p(self._last_stats.data_ptr()), self._stream()), self._h,
+            "last_episode_stats", "portfolio")
+        return self._last_stats
+
+    def last_episode_return(self):
+        """end / begin value of each env's last finished episode, f32 [E] (NaN where none has
+        finished); same shape and dtype as episode_return()."""
+        import torch
+        if self._last is None:
+            raise nat.FinenvError("last_episode_return: call enable_last_episode() first")
+        le = self.last_episode
+        return (le["end_value"] / le["begin_value"]).to(torch.float32)
 
     def reset(self, mask=None):
         import torch

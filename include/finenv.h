@@ -216,6 +216,35 @@ int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *
  *                   total_trades, sharpe (NaN if undefined)}. */
 int finenv_stock_episode_stats(finenv_stock *h, double *out, void *stream);
 
+/* Last-episode block: the summary of each env's most recently FINISHED episode, latched by the
+ * step kernel on the step that reports done -- before an auto-reset replaces the state -- so that
+ * it survives auto_reset != 0 (the reference prints it in the terminal step, :222-264, before
+ * DummyVecEnv resets).  Opt-in and caller-owned: double last[FINENV_STOCK_LAST_FIELDS][E], device
+ * memory, same [field][E] layout as the state blocks.  The library writes it only on done steps
+ * (one write, and one COUNT increment, per reported done: with auto_reset == 0 every further
+ * terminal step latches again, as the reference prints again); reset through the host does not
+ * touch it.  The caller initialises it (COUNT = 0).  Fields: */
+enum {
+    FINENV_SL_COUNT = 0,          /* episodes finished since the block was enabled            */
+    FINENV_SL_EPISODE,            /* self.episode of the finished episode                     */
+    FINENV_SL_BEGIN_ASSET,        /* asset_memory[0]                                          */
+    FINENV_SL_END_ASSET,          /* end_total_asset, :226-228                                */
+    FINENV_SL_COST,               /* self.cost                                                */
+    FINENV_SL_TRADES,             /* self.trades                                              */
+    FINENV_SL_RET_N,              /* day - start_day: daily returns of the episode            */
+    FINENV_SL_RET_SUM,            /* their sum (0 without track_stats)                        */
+    FINENV_SL_RET_SUMSQ,          /* sum of their squares (0 without track_stats)             */
+    FINENV_STOCK_LAST_FIELDS
+};
+/* Attach (or, with NULL, detach -- the default) a last-episode block.  The pointer is a step-kernel
+ * argument: a step captured into a graph sees the block bound at capture time. */
+int finenv_stock_set_last_episode(finenv_stock *h, double *last);
+/* The episode_stats columns for the latched episodes: out [E][6] f64 = {begin_total_asset,
+ * end_total_asset, total_reward, total_cost, total_trades, sharpe}; a row is all NaN while
+ * COUNT == 0.  Sharpe is evaluated from the latched sums by the same code as episode_stats.
+ * FINENV_ERR_INVALID when no block is attached. */
+int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream);
+
 /* =====================================================================================
  * StockPortfolioEnv (finrl/meta/env_portfolio_allocation/env_portfolio.py:15-261)
  *   actions [E][N] f32 (portfolio scores; softmax-normalised inside, :225-229)
@@ -263,6 +292,29 @@ int  finenv_portfolio_reset(finenv_portfolio *h, const uint8_t *mask, float *obs
 int  finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs, float *reward,
                            uint8_t *done, float *term_obs, float *weights_out,
                            int32_t auto_reset, void *stream);
+
+/* Last-episode block of the portfolio env (same contract as the stock env's):
+ * double last[FINENV_PORTFOLIO_LAST_FIELDS][E].  The state keeps no return history, so while a
+ * block is attached every non-terminal step also adds its portfolio_return (:183-185) to RUN_SUM /
+ * RUN_SUMSQ (16 B read + 16 B written per env); the terminal step latches them into RET_SUM /
+ * RET_SUMSQ, and both the auto-reset and a host reset clear them.  The caller initialises COUNT = 0
+ * and the running sums (0 for an env on day 0). */
+enum {
+    FINENV_PL_COUNT = 0,          /* episodes finished since the block was enabled            */
+    FINENV_PL_BEGIN_VALUE,        /* asset_memory[0] = initial_amount                         */
+    FINENV_PL_END_VALUE,          /* portfolio_value at the terminal step                     */
+    FINENV_PL_RET_N,              /* len(portfolio_return_memory) = day + 1 (its leading 0
+                                     included, :217)                                          */
+    FINENV_PL_RET_SUM,            /* sum of portfolio_return_memory                           */
+    FINENV_PL_RET_SUMSQ,          /* sum of its squares                                       */
+    FINENV_PL_RUN_SUM,            /* running sums of the episode in progress                  */
+    FINENV_PL_RUN_SUMSQ,
+    FINENV_PORTFOLIO_LAST_FIELDS
+};
+int  finenv_portfolio_set_last_episode(finenv_portfolio *h, double *last);
+/* out [E][3] f64 = {begin_total_asset, end_total_asset, sharpe} of the latched episodes (all NaN
+ * while COUNT == 0); FINENV_ERR_INVALID when no block is attached. */
+int  finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *stream);
 
 /* =====================================================================================
  * CryptoEnv (finrl/meta/env_cryptocurrency_trading/env_multiple_crypto.py:10-111)
