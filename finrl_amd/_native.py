@@ -262,12 +262,12 @@ def lib():
     L.finenv_stoploss_set_random_start.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
     L.finenv_cashpenalty_set_audit.argtypes = [C.c_void_p, C.c_void_p]
     L.finenv_stoploss_set_audit.argtypes = [C.c_void_p, C.c_void_p]
-    # Last-episode block.  Bound only where exported: tools/exp_ab_inproc.py loads a build of an
+    # Last-episode block, episode windows.  Bound only where exported: tools/exp_ab_inproc.py loads a build of an
     # earlier commit through this function beside the current one (tests/test_native_abi.py checks
     # that the current build exports every symbol the header declares).
     for name, n in (("finenv_stock_set_last_episode", 2), ("finenv_stock_last_episode_stats", 3),
                     ("finenv_portfolio_set_last_episode", 2),
-                    ("finenv_portfolio_last_episode_stats", 3)):
+                    ("finenv_portfolio_last_episode_stats", 3), ("finenv_stock_set_windows", 2)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
     if L.finenv_abi_version() != ABI_VERSION:

@@ -85,6 +85,7 @@ struct finenv_stock {
     uint32_t magicN;
     char err[256];
     double *last;         // finenv_stock_set_last_episode (appended: the layout above is unchanged)
+    int32_t *win;         // finenv_stock_set_windows (appended likewise)
 };
 
 namespace {
@@ -117,6 +118,7 @@ Params make_params(const finenv_stock *h)
     p.desync_hint = h->desync_hint;
     p.magicN = h->magicN;
     p.last = h->last;
+    p.win = h->win;
     return p;
 }
 
@@ -362,6 +364,13 @@ int finenv_stock_set_last_episode(finenv_stock *h, double *last)
 {
     if (!h) return FINENV_ERR_INVALID;
     h->last = last;
+    return FINENV_OK;
+}
+
+int finenv_stock_set_windows(finenv_stock *h, int32_t *win)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->win = win;
     return FINENV_OK;
 }
 

@@ -368,7 +368,10 @@ constexpr int kLdsStep = kR1 + kR2 + kR3 + kR4;   // dynamic LDS of the step ker
 // rows split in episode-end blocks.  Results never depend on it -- the plain instantiation takes the
 // generic per-env paths -- but every one of those paths compiled into the lock-step kernel cost the
 // headline 0.1-0.7 us (register allocation, code layout: same-box A/B in DESIGN.md 4.3).
-template <bool TURB, bool STATS, bool DES = false>
+// WIN: the instantiation for batches with per-env episode windows (Params::win != NULL): the terminal
+// test reads the env's window end, a reset goes back to its window start.  A template parameter for
+// the same reason: the no-window instantiations compile exactly as before.
+template <bool TURB, bool STATS, bool DES = false, bool WIN = false>
 __global__ void __launch_bounds__(kStepThreads, (kNPad <= 32) ? 2 : 1)
 stock_step_kernel(const Params p)
 {
@@ -415,11 +418,14 @@ stock_step_kernel(const Params p)
     // ---- both roles: which panel rows this step touches (needs only day / price_day) -----
     int day = SI(FINENV_SI_DAY);
     int pd = SI(FINENV_SI_PRICE_DAY);
-    const bool term = day >= T - 1;                                           // :221
+    const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
+    const bool term = day >= last_day;                                        // :221
     const bool do_reset = term && p.auto_reset != 0;
     const int pd_cur = pd;                            // row held in the current observation
     const int pd_next = term ? pd : day + 1;          // row after the step, before any reset
-    const int row_obs = do_reset ? (p.cfg.reset_quirk ? pd : 0) : pd_next;
+    int reset_row = 0;                                // the window start (once per episode)
+    if (WIN && !p.cfg.reset_quirk && __any(do_reset)) reset_row = win_start(p.win, e, T);
+    const int row_obs = do_reset ? (p.cfg.reset_quirk ? pd : reset_row) : pd_next;
     const unsigned long long valid_mask = __ballot(valid);
     const unsigned long long term_mask = __ballot(term && valid);
     const int kpatch = (2 * N) / kWave + 1;           // chunks holding cash/holdings columns
@@ -1106,13 +1112,13 @@ stock_step_kernel(const Params p)
                 }
                 // begin asset of the episode's first step: sequential order (:311-314)
                 end_carry = initial_asset_lds(cash, hcol, p.panel.close, (unsigned)(pd * N), N, false);
+                day = WIN ? win_start(p.win, e, T) : 0;                       // day 0 of the window
                 if (valid) {
                     SF(FINENV_SF_ASSET0) = a0;
                     SF(FINENV_SF_RET_SUM) = 0.0;
                     SF(FINENV_SF_RET_SUMSQ) = 0.0;
-                    SI(FINENV_SI_START_DAY) = 0;
+                    SI(FINENV_SI_START_DAY) = day;
                 }
-                day = 0;
                 turb = 0.0;
                 cost = 0.0;
                 trades = 0;
@@ -1196,7 +1202,7 @@ __global__ void __launch_bounds__(kWave *kAuxWaves) stock_aux_kernel(const Param
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x >> 6;
     float *lds = lds_all + wib * kLdsPerWave;
-    const int E = p.cfg.n_envs, N = p.cfg.n_tickers, D = p.D, P = p.obs_pitch;
+    const int E = p.cfg.n_envs, N = p.cfg.n_tickers, D = p.D, P = p.obs_pitch, T = p.cfg.n_days;
     const int e0 = (blockIdx.x * kAuxWaves + wib) * kWave;
     if (e0 >= E) return;
     const int nenv_w = min(kWave, E - e0);
@@ -1205,7 +1211,7 @@ __global__ void __launch_bounds__(kWave *kAuxWaves) stock_aux_kernel(const Param
 
     int hf[kNPad];
     double cash;
-    int pd;
+    int pd, start = 0;
     bool sel = valid;
     if (mode >= 2) {
         cash = SF(FINENV_SF_CASH);
@@ -1222,8 +1228,11 @@ __global__ void __launch_bounds__(kWave *kAuxWaves) stock_aux_kernel(const Param
         }
     } else {
         if (mode == 1 && p.mask != nullptr) sel = valid && p.mask[e] != 0;
-        if (mode == 0) pd = p.day0;
-        else pd = p.cfg.reset_quirk ? SI(FINENV_SI_PRICE_DAY) : 0;
+        // first day of the episode: day0 / 0, counted from the env's window start when windows are set
+        const int w0 = p.win != nullptr ? win_start(p.win, e, T) : 0;
+        start = mode == 0 ? min(w0 + p.day0, T - 1) : w0;
+        if (mode == 0) pd = start;
+        else pd = p.cfg.reset_quirk ? SI(FINENV_SI_PRICE_DAY) : start;
         cash = SF(FINENV_SF_CASH0);
 #pragma unroll
         for (int i = 0; i < kNPad; ++i) {
@@ -1245,8 +1254,8 @@ __global__ void __launch_bounds__(kWave *kAuxWaves) stock_aux_kernel(const Param
             SF(FINENV_SF_ASSET0) = a0;
             SF(FINENV_SF_RET_SUM) = 0.0;
             SF(FINENV_SF_RET_SUMSQ) = 0.0;
-            SI(FINENV_SI_START_DAY) = (mode == 0) ? p.day0 : 0;
-            SI(FINENV_SI_DAY) = (mode == 0) ? p.day0 : 0;
+            SI(FINENV_SI_START_DAY) = start;
+            SI(FINENV_SI_DAY) = start;
             SI(FINENV_SI_PRICE_DAY) = pd;
             SF(FINENV_SF_TURBULENCE) = 0.0;
             SF(FINENV_SF_COST) = 0.0;

@@ -20,7 +20,14 @@ int launch_step(const Params &p, int device, hipStream_t stream)
     const dim3 block(kStepThreads);
     constexpr size_t lds = sizeof(float) * np32::kLdsStep;
     (void)device;
-    if (p.desync_hint)      // envs may sit on different days: the instantiation with the per-env fast paths
+    // per-env windows (p.win): the DES form only.  A lock-step WIN instantiation was measured too: no
+    // faster on windows [0, T) (21.41 vs 21.36 us), and the build holding it ran the no-window headline
+    // 1 % slower in the in-process A/B against the parent (cause not isolated)
+    if (p.win != nullptr)
+        launch_rounds(p, &np32::stock_step_kernel<TURB, STATS, true, true>, lds, [&](const Params &q, int nb) {
+            hipLaunchKernelGGL((np32::stock_step_kernel<TURB, STATS, true, true>), dim3((unsigned)nb), block, lds, stream, q);
+        });
+    else if (p.desync_hint) // envs may sit on different days: the instantiation with the per-env fast paths
         launch_rounds(p, &np32::stock_step_kernel<TURB, STATS, true>, lds, [&](const Params &q, int nb) {
             hipLaunchKernelGGL((np32::stock_step_kernel<TURB, STATS, true>), dim3((unsigned)nb), block, lds, stream, q);
         });

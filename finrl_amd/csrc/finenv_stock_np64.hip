@@ -20,9 +20,15 @@ int launch_step(const Params &p, int device, hipStream_t stream)
     const dim3 block(kStepThreads);
     constexpr size_t lds = sizeof(float) * np64::kLdsStep;
     (void)device;
-    launch_rounds(p, &np64::stock_step_kernel<TURB, STATS>, lds, [&](const Params &q, int nb) {
-        hipLaunchKernelGGL((np64::stock_step_kernel<TURB, STATS>), dim3((unsigned)nb), block, lds, stream, q);
-    });
+    if (p.win != nullptr)   // per-env windows
+        launch_rounds(p, &np64::stock_step_kernel<TURB, STATS, false, true>, lds, [&](const Params &q, int nb) {
+            hipLaunchKernelGGL((np64::stock_step_kernel<TURB, STATS, false, true>), dim3((unsigned)nb), block, lds,
+                               stream, q);
+        });
+    else
+        launch_rounds(p, &np64::stock_step_kernel<TURB, STATS>, lds, [&](const Params &q, int nb) {
+            hipLaunchKernelGGL((np64::stock_step_kernel<TURB, STATS>), dim3((unsigned)nb), block, lds, stream, q);
+        });
     return 0;
 }
 }  // namespace

@@ -71,7 +71,8 @@ __device__ __forceinline__ void sort_keys_pruned(int (&k)[NT])
 #undef CE
 }
 
-template <bool TURB, bool STATS, int NT>
+// WIN: per-env episode windows (Params::win), as in stock_step_kernel
+template <bool TURB, bool STATS, int NT, bool WIN = false>
 __global__ void __launch_bounds__(kStepThreads, 2)
 stock_step_wide_kernel(const Params p)
 {
@@ -133,11 +134,14 @@ stock_step_wide_kernel(const Params p)
     // ---- both roles: which panel rows this step touches (needs only day / price_day) -----------
     int day = SI(FINENV_SI_DAY);
     int pd = SI(FINENV_SI_PRICE_DAY);
-    const bool term = day >= T - 1;                                           // :221
+    const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
+    const bool term = day >= last_day;                                        // :221
     const bool do_reset = term && p.auto_reset != 0;
     const int pd_cur = pd;                            // row held in the current observation
     const int pd_next = term ? pd : day + 1;          // row after the step, before any reset
-    const int row_obs = do_reset ? (p.cfg.reset_quirk ? pd : 0) : pd_next;
+    int reset_row = 0;                                // the window start (once per episode)
+    if (WIN && !p.cfg.reset_quirk && __any(do_reset)) reset_row = win_start(p.win, e, T);
+    const int row_obs = do_reset ? (p.cfg.reset_quirk ? pd : reset_row) : pd_next;
     const unsigned long long valid_mask = __ballot(valid);
     const unsigned long long term_mask = __ballot(term && valid);
     constexpr int kpatch = (2 * N) / kWave + 1;       // chunks holding cash/holdings columns
@@ -547,13 +551,13 @@ stock_step_wide_kernel(const Params p)
                                                     N, p.cfg.initial != 0, kHS);
                 end_carry = initial_asset_lds(cash, hcol, p.panel.close, (unsigned)(pd * N), N, false,
                                               kHS);
+                day = WIN ? win_start(p.win, e, T) : 0;                       // day 0 of the window
                 if (valid) {
                     SF(FINENV_SF_ASSET0) = a0;
                     SF(FINENV_SF_RET_SUM) = 0.0;
                     SF(FINENV_SF_RET_SUMSQ) = 0.0;
-                    SI(FINENV_SI_START_DAY) = 0;
+                    SI(FINENV_SI_START_DAY) = day;
                 }
-                day = 0;
                 turb = 0.0;
                 cost = 0.0;
                 trades = 0;

@@ -59,3 +59,44 @@ def df_to_array(df, tech_indicator_list, if_vix, price_col="adjcp"):
     tech[np.isnan(tech)] = 0
     tech[np.isinf(tech)] = 0
     return np.ascontiguousarray(price), tech, np.array(turb)
+
+
+def windows_from_dates(dates, starts, ends):
+    """Panel rows of ``data_split(df, start, end)`` for each (start, end) date pair -> (start, end)
+    int64 arrays, end exclusive: the rows whose date satisfies ``start <= date < end`` (the
+    ``windows=`` / ``set_windows`` argument of VecStockTradingEnv).  ``dates``: the panel's dates
+    (e.g. ``df.date``; sorted and deduplicated here, i.e. the factorize order of ``data_split``
+    over the full frame).  Dates compare as they do in the frame: strings lexically, numbers
+    numerically.  Raises ValueError on a pair that selects no row."""
+    days = np.unique(np.asarray(dates))
+    lo = np.searchsorted(days, np.asarray(starts), side="left")
+    hi = np.searchsorted(days, np.asarray(ends), side="left")
+    lo, hi = np.broadcast_arrays(np.atleast_1d(lo), np.atleast_1d(hi))
+    empty = hi <= lo
+    if empty.any():
+        k = int(np.argmax(empty))
+        raise ValueError(f"window {k} selects no panel day (start={np.ravel(starts)[k % np.size(starts)]!r}, "
+                         f"end={np.ravel(ends)[k % np.size(ends)]!r})")
+    return lo.astype(np.int64), hi.astype(np.int64)
+
+
+def random_windows(T, E, length, generator=None, device="cuda"):
+    """E random windows of ``length`` panel days (an int, or [E] lengths) in a panel of T days ->
+    (start, end) int32 [E] tensors on ``device``, start uniform over the positions the window fits
+    in (the cash-penalty env's random start, env_stocktrading_cashpenalty.py:135).  Only torch ops:
+    usable inside a captured graph, e.g. ``env.set_windows(*random_windows(...), mask=done)``.
+    ``generator``: a torch.Generator on ``device``."""
+    import torch
+    dev, E, T = torch.device(device), int(E), int(T)
+    if torch.is_tensor(length):
+        length = length.to(device=dev, dtype=torch.int64).expand(E)
+    else:
+        n = np.asarray(length, dtype=np.int64)
+        if ((n < 1) | (n > T)).any():
+            raise ValueError(f"window length must be in [1, {T}]")
+        length = torch.full((E,), int(n), dtype=torch.int64, device=dev) if n.ndim == 0 else \
+            torch.from_numpy(np.broadcast_to(n, (E,)).copy()).to(dev)
+    span = T - length + 1                              # start positions the window fits in
+    u = torch.rand(E, generator=generator, device=dev, dtype=torch.float64)
+    start = torch.minimum((u * span).to(torch.int64), span - 1)
+    return start.to(torch.int32), (start + length).to(torch.int32)

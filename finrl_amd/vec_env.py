@@ -51,6 +51,13 @@ class VecStockTradingEnv:
     day, initial``).  ``initial_amount`` / ``num_stock_shares`` may be per-env
     ([E] / [E, N]) which also covers the ``previous_state`` carry-over (:423-450).
     Costs are scalars, as in this fork (:118, :179).
+
+    ``windows=(start, end)`` gives every env its own episode window of panel rows ``[start, end)``
+    (one pair for all envs, or [E] arrays / tensors): env e then behaves like the reference env
+    built on ``data_split(df, dates[start[e]], dates[end[e]])`` -- K ensemble windows or random
+    training windows in ONE batch over one panel.  ``day`` counts from each window's start.
+    ``state["day"]`` stays the panel row; ``window_day()`` is the reference's ``self.day``.
+    See ``set_windows``.
     """
 
     if_discrete = False
@@ -64,7 +71,7 @@ class VecStockTradingEnv:
                  initial_amount=1_000_000, num_stock_shares=None, buy_cost_pct=1e-3,
                  sell_cost_pct=1e-3, reward_scaling=1e-4, turbulence_threshold=None,
                  day=0, initial=True, reset_quirk=True, track_stats=True, auto_reset=True,
-                 device="cuda", obs_pitch=None):
+                 device="cuda", obs_pitch=None, windows=None):
         torch = _torch()
         if not isinstance(buy_cost_pct, (int, float)) or not isinstance(sell_cost_pct, (int, float)):
             # the fork's own env raises TypeError on list costs
@@ -148,6 +155,15 @@ class VecStockTradingEnv:
         self._last = None
         self._last_stats = None
         self.last_episode = None
+        self.windows = None
+        self._day0 = int(day)
+        if windows is not None:
+            start, end = windows
+            s_np, t_np = self._check_windows(start, end)
+            if not 0 <= self._day0 < int((t_np - s_np).min()):
+                raise ValueError(f"day={day} does not fit the shortest window "
+                                 f"({int((t_np - s_np).min())} days)")
+            self.set_windows(s_np, t_np)
         nat.check(L.finenv_stock_init(self._h, int(day), self._stream()), self._h, "init")
 
     # ------------------------------------------------------------------ plumbing
@@ -191,10 +207,92 @@ class VecStockTradingEnv:
             self.last_episode = {k: last[j] for j, k in enumerate(nat.STOCK_LAST_FIELDS)}
         return self._last
 
+    def _check_windows(self, start, end):
+        """Host validation of (start, end) -> two int64 [E] arrays (ValueError when a window is empty
+        or leaves the panel)."""
+        torch = _torch()
+        E, T = self.num_envs, self.panel.T
+        out = []
+        for x, what in ((start, "start"), (end, "end")):
+            if torch.is_tensor(x):
+                x = x.detach().cpu().numpy()
+            a = np.asarray(x)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"windows: {what} must be integer panel rows")
+            try:
+                out.append(np.broadcast_to(a.astype(np.int64), (E,)))
+            except ValueError:
+                raise ValueError(f"windows: {what} must be one value or [{E}] values") from None
+        s, t = out
+        if (s < 0).any() or (t > T).any():
+            raise ValueError(f"windows must lie in [0, {T}] (the panel's rows)")
+        if (t <= s).any():
+            raise ValueError("windows must not be empty (start < end)")
+        return s, t
+
+    def set_windows(self, start, end=None, mask=None):
+        """Per-env episode windows [start, end) of panel rows (finenv_stock_set_windows);
+        ``set_windows(None)`` detaches them (every env runs the whole panel again).
+
+        The windows live in ``self.windows``, an int32 [2, E] device tensor (row 0 starts, row 1
+        ends) whose address the step kernel takes as an argument; this call copies into it in place.
+        The step kernel reads an env's END on every step and its START only when it resets the env,
+        so an edited end applies from the next step and an edited start at the env's next reset
+        (auto-reset or ``reset()``); nothing moves an env that is mid-episode.  To start the envs
+        that just finished on new windows: ``set_windows(s, t, mask=done)`` then ``reset(done)``
+        (INTEGRATION.md D).
+
+        Host values (ints, arrays) are validated (ValueError on empty or out-of-range windows).
+        Device tensors are copied without a host synchronisation, so windows can be redrawn with
+        torch ops -- ``mask`` (bool [E]) limits the update to those envs, e.g. the ones that just
+        reported ``done`` -- even inside a captured graph (the graph sees the block's contents as
+        they are at each replay).  Those are NOT validated: the kernel clamps every window into
+        the panel, so a bad one gives wrong results, never a fault.  Attach windows before capturing
+        a graph: a graph keeps the pointer it was captured with.  ``max_step`` follows the windows
+        passed here (the longest minus one), except device tensors passed during a capture."""
+        torch = _torch()
+        L = nat.lib()
+        if start is None:
+            nat.check(L.finenv_stock_set_windows(self._h, None), self._h, "set_windows")
+            self.windows = None
+            self.max_step = self.panel.T - 1
+            return None
+        if end is None:
+            raise ValueError("set_windows needs start and end")
+        on_device = all(torch.is_tensor(x) and x.device.type == "cuda" for x in (start, end))
+        if self.windows is None:
+            self.windows = torch.zeros(2, self.num_envs, dtype=torch.int32, device=self.device)
+            self.windows[1].fill_(self.panel.T)
+        new = torch.empty_like(self.windows)
+        if on_device:
+            new[0].copy_(start.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
+            new[1].copy_(end.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
+        else:
+            s_np, t_np = self._check_windows(start, end)
+            new.copy_(torch.from_numpy(np.stack([s_np, t_np]).astype(np.int32)))
+        if mask is not None:
+            m = mask.to(device=self.device, dtype=torch.bool) if torch.is_tensor(mask) else \
+                torch.from_numpy(np.asarray(mask, dtype=bool)).to(self.device)
+            new = torch.where(m, new, self.windows)
+        self.windows.copy_(new)
+        nat.check(L.finenv_stock_set_windows(self._h, C.c_void_p(self.windows.data_ptr())), self._h,
+                  "set_windows")
+        if not (on_device and torch.cuda.is_current_stream_capturing()):
+            self.max_step = int((self.windows[1] - self.windows[0]).max().item()) - 1
+        return self.windows
+
+    def window_day(self):
+        """The reference's ``self.day`` of every env (int32 [E] device tensor): ``state["day"]`` minus
+        the panel row its window started on when the episode began.  A reset sets ``start_day`` to
+        that row; the constructor's episode began ``day`` rows later.  Without windows it equals
+        ``state["day"]``."""
+        st = self.state
+        return st["day"] - st["start_day"] + self._day0 * (st["episode"] == 0).to(st["day"].dtype)
+
     def hint_desynchronised(self, on=True):
         """Performance hint (results never depend on it): the envs of this batch sit on different
-        days -- per-env start days, staggered episode ends.  Selects the step-kernel instantiation
-        tuned for per-env panel rows (finenv_stock_set_desync_hint)."""
+        days -- per-env start days, staggered episode ends, windows with different starts.  Selects
+        the step-kernel instantiation tuned for per-env panel rows (finenv_stock_set_desync_hint)."""
         nat.check(nat.lib().finenv_stock_set_desync_hint(self._h, int(bool(on))), self._h,
                   "set_desync_hint")
 
@@ -321,6 +419,7 @@ class VecStockTradingEnv:
     def state_numpy(self):
         """Host copy of the per-env state (synchronises)."""
         out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
+        out["window_day"] = self.window_day().cpu().numpy()
         out["shares"] = np.ascontiguousarray(out.pop("holdings").T)
         out["shares0"] = np.ascontiguousarray(out["shares0"].T)
         return out

@@ -125,7 +125,8 @@ enum {                            /* i32 block: int32 i32[FINENV_STOCK_I32_FIELD
                                      reset)                                              */
     FINENV_SI_TRADES,             /* self.trades                                         */
     FINENV_SI_EPISODE,            /* self.episode                                        */
-    FINENV_SI_START_DAY,          /* day the episode started on (init: day0, reset: 0);
+    FINENV_SI_START_DAY,          /* day the episode started on (init: day0, reset: 0;
+                                     with windows s_e + day0 / s_e);
                                      daily returns accumulated so far = day - start_day  */
     FINENV_STOCK_I32_FIELDS       /* followed by holdings[N][E] = state[1+N .. 1+2N) and
                                      shares0[N][E] = num_stock_shares / previous_state
@@ -244,6 +245,26 @@ int finenv_stock_set_last_episode(finenv_stock *h, double *last);
  * COUNT == 0.  Sharpe is evaluated from the latched sums by the same code as episode_stats.
  * FINENV_ERR_INVALID when no block is attached. */
 int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream);
+
+/* Per-env episode windows: many data_split(df, dates[s], dates[t]) frames (preprocessors.py:24-33)
+ * of ONE bound panel in one batch.  Opt-in and caller-owned: int32_t win[2][E], device memory;
+ * win[0][e] = s_e (first panel row of env e's frame), win[1][e] = t_e (end, exclusive), and env e
+ * then behaves like StockTradingEnv on that frame:
+ *   - terminal when FINENV_SI_DAY >= t_e - 1 (:221);
+ *   - a reset (host or auto) goes back to panel row s_e: FINENV_SI_DAY = FINENV_SI_START_DAY = s_e,
+ *     the observation row is s_e (or, with reset_quirk, the row the env holds);
+ *   - finenv_stock_init(day0) starts every env on row s_e + day0.
+ * FINENV_SI_DAY stays the panel row; the reference's self.day is FINENV_SI_DAY - s_e.
+ * Preconditions for a faithful result: 0 <= s_e < t_e <= n_days, and s_e + day0 < t_e at init.
+ * The kernels clamp both rows into [0, n_days) whatever the block holds: a bad window is a wrong
+ * answer, never an access outside the panel or the state.  Valid windows read no panel row
+ * outside [s_e, t_e).
+ * The pointer is a kernel argument (a graph captured after attaching sees later edits of the
+ * block's CONTENTS).  step() reads t_e on every step and s_e only when it resets an env, so an
+ * edited end applies from the next step and an edited start at the env's next reset.
+ * NULL detaches (the default: every env runs rows 0 .. n_days-1).  Handle-wide settings (initial
+ * amounts, costs) stay handle-wide. */
+int finenv_stock_set_windows(finenv_stock *h, int32_t *win);
 
 /* =====================================================================================
  * StockPortfolioEnv (finrl/meta/env_portfolio_allocation/env_portfolio.py:15-261)

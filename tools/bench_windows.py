@@ -1,0 +1,55 @@
+#!/usr/bin/env python3
+"""Step time of the batched stock env with per-env episode windows (VecStockTradingEnv(windows=...)),
+on bench.py's workload (same synthetic panel, actions and env settings), beside the same batch
+without windows in the same process.
+usage: python3 tools/bench_windows.py <case> [envs] [steps]
+  case: full      -- every env on the whole panel [0, T) (lock-step days, the WIN instantiation)
+        random63  -- random 63-day windows, hint_desynchronised(True)
+        n100      -- the N = 100 shape (turbulence p90) with random 63-day windows
+        none      -- no windows (bench.py's headline path), for reference
+        desync    -- no windows, bench.py --desync's per-env start days"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    case = sys.argv[1]
+    E = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
+    steps = int(sys.argv[3]) if len(sys.argv) > 3 else 500
+    import torch
+    import bench
+    from finrl_amd.data import random_windows
+    dev = torch.device("cuda", 0)
+    n100 = case == "n100"
+    args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=case == "desync",
+                              no_stats=False, env="stock", tickers=100 if n100 else 30,
+                              turbulence_pct=90.0 if n100 else None))()
+    w = bench.build_workload(args, torch, dev, 0)
+    env = w.env
+    T = env.panel.T
+    if case == "full":
+        env.set_windows(0, T)
+    elif case in ("random63", "n100"):
+        g = torch.Generator(device=dev).manual_seed(7)
+        env.set_windows(*random_windows(T, E, 63, generator=g, device=dev))
+        env.hint_desynchronised(True)
+    env.reset()
+    if getattr(w, "after_reset", None):
+        w.after_reset()
+    for i in range(300):
+        env.step(w.pool[i % len(w.pool)])
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(steps):
+        env.step(w.pool[i % len(w.pool)])
+    e1.record()
+    torch.cuda.synchronize()
+    print(f"{case} E={E} N={env.stock_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
+
+
+if __name__ == "__main__":
+    main()
