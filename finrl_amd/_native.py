@@ -267,7 +267,8 @@ def lib():
     # that the current build exports every symbol the header declares).
     for name, n in (("finenv_stock_set_last_episode", 2), ("finenv_stock_last_episode_stats", 3),
                     ("finenv_portfolio_set_last_episode", 2),
-                    ("finenv_portfolio_last_episode_stats", 3), ("finenv_stock_set_windows", 2)):
+                    ("finenv_portfolio_last_episode_stats", 3), ("finenv_stock_set_windows", 2),
+                    ("finenv_portfolio_set_windows", 2)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
     if L.finenv_abi_version() != ABI_VERSION:

@@ -48,6 +48,20 @@ __device__ __forceinline__ double sharpe_from_sums(int n, double s1, double s2)
     return sharpe;
 }
 
+// Per-env episode windows (finenv_stock_set_windows, finenv_portfolio_set_windows): int32 win[2][E],
+// env e runs panel rows [win[0][e], win[1][e]).  Whatever the block holds, both helpers return a panel
+// row in [0, T): a bad window gives a wrong answer, never an access outside the panel.
+__device__ __forceinline__ int win_start(const int32_t *win, int e, int T)
+{
+    return min(max(*at(win, (unsigned)e), 0), T - 1);
+}
+// the window's terminal day end - 1 (the reference's `day >= len(df.index.unique()) - 1` on the
+// data_split frame)
+__device__ __forceinline__ int win_last_day(const int32_t *win, int E, int e, int T)
+{
+    return min(max(*at(win, (unsigned)E + (unsigned)e), 1), T) - 1;
+}
+
 // Counter-based uniform draw in [0, hi): splitmix64 of (seed, env, episode), multiply-shift.
 __device__ __forceinline__ int draw_start(unsigned long long seed, int env, int episode, int hi)
 {

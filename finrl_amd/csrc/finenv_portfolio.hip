@@ -11,7 +11,9 @@
 //   * one 128-thread block per 64 envs: both waves stream observation rows (32 rows each)
 //     with 16-byte stores in row-major order; wave 0 also does the arithmetic and the state;
 //   * when all 64 envs sit on the same day (always, in lock-step batches) the template row
-//     lives in registers and the row loop holds no load.
+//     lives in registers and the row loop holds no load;
+//   * per-env episode windows (finenv_portfolio_set_windows) are the WIN instantiation of the step
+//     kernel: the terminal test reads the env's window end, a reset goes back to its window start.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,6 +51,7 @@ struct PfParams {
     uint32_t magicN;
     double *last;          // last-episode block [FINENV_PORTFOLIO_LAST_FIELDS][E] or NULL
     double *stats_out;     // last_episode_stats: [E][3]
+    const int32_t *win;    // per-env windows [2][E] (starts, ends) or NULL (finenv_portfolio_set_windows)
 };
 
 #define PF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
@@ -56,6 +59,9 @@ struct PfParams {
 #define PL(fld) (*at(p.last, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 
 // Stream rows [el_lo, el_hi) of the block's observation tile.  row_day: per-lane panel row.
+// ROW16: rows on different days take 16-byte loads and stores when D % 4 == 0 (the WIN step kernel, where
+// windows put the 64 envs of a block on different days; the other kernels compile as before).
+template <bool ROW16 = false>
 __device__ __forceinline__ void pf_write_rows(float *__restrict__ dst,
                                               const float *__restrict__ tmpl, int D, int e0,
                                               int el_lo, int el_hi, int row_day,
@@ -99,6 +105,18 @@ __device__ __forceinline__ void pf_write_rows(float *__restrict__ dst,
         }
         return;
     }
+    if (ROW16 && (D & 3) == 0) {
+        // per-row path with 16-byte template loads and stores (rows 16-B aligned as above)
+        const float4 *const tmpl4 = reinterpret_cast<const float4 *>(tmpl);
+        float4 *const base4 = reinterpret_cast<float4 *>(base);
+        for (int el = el_lo; el < el_hi; ++el) {
+            if (!((sel >> el) & 1ull)) continue;
+            const int rd = __builtin_amdgcn_readlane(row_day, el);
+            for (int c4 = lane; c4 < n4; c4 += kWave)
+                *at(base4, (unsigned)(el * n4 + c4)) = *at(tmpl4, (unsigned)(rd * n4 + c4));
+        }
+        return;
+    }
     // general path: per-row template loads (desynchronised days, odd D, masked rows)
     const int nchunk = (D + kWave - 1) / kWave;
     for (int el = el_lo; el < el_hi; ++el) {
@@ -111,6 +129,9 @@ __device__ __forceinline__ void pf_write_rows(float *__restrict__ dst,
     }
 }
 
+// WIN: the instantiation for batches with per-env episode windows (PfParams::win != NULL).  A template
+// parameter so that the no-window kernel compiles exactly as before.
+template <bool WIN = false>
 __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams p)
 {
     __shared__ float tile[kWave * kTileStride];
@@ -125,9 +146,12 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
 
     // both waves: which panel rows this step shows (needs only `day`)
     int day = PI(FINENV_PI_DAY);
-    const bool term = day >= T - 1;                                           // :127
+    const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
+    const bool term = day >= last_day;                                        // :127
     const int day_next = term ? day : day + 1;
-    const int row_obs = (term && p.auto_reset) ? 0 : day_next;               // reset(): day 0
+    int start = 0;                                    // the window start (terminal / reset path only)
+    if (WIN && __any(term)) start = win_start(p.win, e, T);
+    const int row_obs = (term && p.auto_reset) ? start : day_next;           // reset(): window day 0
     const unsigned long long valid_mask = __ballot(valid);
     const unsigned long long term_mask = __ballot(term && valid);
 
@@ -205,7 +229,7 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
             PL(FINENV_PL_COUNT) = PL(FINENV_PL_COUNT) + 1.0;
             PL(FINENV_PL_BEGIN_VALUE) = p.cfg.initial_amount;                 // asset_memory[0]
             PL(FINENV_PL_END_VALUE) = value;
-            PL(FINENV_PL_RET_N) = (double)(day + 1);    // the memory's leading 0 (:217) counts
+            PL(FINENV_PL_RET_N) = (double)(day - start + 1);   // the memory's leading 0 (:217) counts
             PL(FINENV_PL_RET_SUM) = PL(FINENV_PL_RUN_SUM);
             PL(FINENV_PL_RET_SUMSQ) = PL(FINENV_PL_RUN_SUMSQ);
             if (p.auto_reset) {
@@ -214,7 +238,7 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
             }
         }
         if (term && p.auto_reset) {                                           // :202-220
-            day = 0;
+            day = start;
             value = p.cfg.initial_amount;
         }
         if (valid) {
@@ -227,24 +251,25 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
     // both waves: observation rows (wave 0: rows [0,32), wave 1: rows [32,64))
     const int el_lo = wib * 32, el_hi = min(nenv_w, el_lo + 32);
     if (term_mask != 0ull && p.term_obs != nullptr)
-        pf_write_rows(p.term_obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, day_next, term_mask, lane);
-    pf_write_rows(p.obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, row_obs, valid_mask, lane);
+        pf_write_rows<WIN>(p.term_obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, day_next, term_mask, lane);
+    pf_write_rows<WIN>(p.obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, row_obs, valid_mask, lane);
 }
 
 __global__ void __launch_bounds__(kThreads) portfolio_reset_kernel(const PfParams p)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x >> 6;
-    const int E = p.cfg.n_envs, D = p.D;
+    const int E = p.cfg.n_envs, D = p.D, T = p.cfg.n_days;
     const int e0 = blockIdx.x * kWave;
     if (e0 >= E) return;
     const int nenv_w = min(kWave, E - e0);
     const bool valid = lane < nenv_w;
     const int e = valid ? e0 + lane : e0;
     const bool sel = valid && (p.mask == nullptr || p.mask[e] != 0);
+    const int start = p.win != nullptr ? win_start(p.win, e, T) : 0;        // day 0 of the window
     if (wib == 0 && sel) {
         PF(FINENV_PF_VALUE) = p.cfg.initial_amount;
-        PI(FINENV_PI_DAY) = 0;
+        PI(FINENV_PI_DAY) = start;
         if (p.last != nullptr) {
             PL(FINENV_PL_RUN_SUM) = 0.0;
             PL(FINENV_PL_RUN_SUMSQ) = 0.0;
@@ -252,7 +277,7 @@ __global__ void __launch_bounds__(kThreads) portfolio_reset_kernel(const PfParam
     }
     if (p.obs == nullptr) return;
     const int el_lo = wib * 32, el_hi = min(nenv_w, el_lo + 32);
-    pf_write_rows(p.obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, 0, __ballot(sel), lane);
+    pf_write_rows(p.obs, p.panel.obs_tmpl, D, e0, el_lo, el_hi, start, __ballot(sel), lane);
 }
 
 // {begin, end, Sharpe} of the latched episodes; NaN rows where none has finished yet.
@@ -283,6 +308,7 @@ struct finenv_portfolio {
     uint32_t magicN;
     char err[256];
     double *last;         // finenv_portfolio_set_last_episode (appended: the layout above is unchanged)
+    int32_t *win;         // finenv_portfolio_set_windows (appended likewise)
 };
 
 namespace {
@@ -310,6 +336,7 @@ PfParams pf_params(const finenv_portfolio *h)
     p.D = h->D;
     p.magicN = h->magicN;
     p.last = h->last;
+    p.win = h->win;
     return p;
 }
 }  // namespace
@@ -386,8 +413,12 @@ int finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs,
     p.term_obs = term_obs;
     p.weights = weights_out;
     p.auto_reset = auto_reset;
-    hipLaunchKernelGGL(portfolio_step_kernel, dim3((h->cfg.n_envs + kWave - 1) / kWave),
-                       dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (p.win != nullptr)     // per-env windows
+        hipLaunchKernelGGL(portfolio_step_kernel<true>, dim3((h->cfg.n_envs + kWave - 1) / kWave),
+                           dim3(kThreads), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(portfolio_step_kernel<false>, dim3((h->cfg.n_envs + kWave - 1) / kWave),
+                           dim3(kThreads), 0, (hipStream_t)stream, p);
     return pf_check(h, "portfolio_step");
 }
 
@@ -395,6 +426,13 @@ int finenv_portfolio_set_last_episode(finenv_portfolio *h, double *last)
 {
     if (!h) return FINENV_ERR_INVALID;
     h->last = last;
+    return FINENV_OK;
+}
+
+int finenv_portfolio_set_windows(finenv_portfolio *h, int32_t *win)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->win = win;
     return FINENV_OK;
 }
 

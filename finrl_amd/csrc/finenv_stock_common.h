@@ -152,19 +152,9 @@ __device__ __forceinline__ double *last_block()
     return *reinterpret_cast<double *const *>(ka + offsetof(Params, last));
 }
 
-// Per-env episode windows (finenv_stock_set_windows): env e runs panel days [start, end).  Whatever the
-// block holds, both helpers return a panel row in [0, T): a bad window gives a wrong answer, never an
-// access outside the panel.  The step kernels read the end every step (one coalesced 4-byte load beside
-// SI(DAY)) and the start only on their wave-uniform reset path.
-__device__ __forceinline__ int win_start(const int32_t *win, int e, int T)
-{
-    return min(max(*at(win, (unsigned)e), 0), T - 1);
-}
-// the window's terminal day end - 1 (:221 on the data_split frame)
-__device__ __forceinline__ int win_last_day(const int32_t *win, int E, int e, int T)
-{
-    return min(max(*at(win, (unsigned)E + (unsigned)e), 1), T) - 1;
-}
+// Per-env episode windows (finenv_stock_set_windows): win_start / win_last_day of finenv_dev.h.  The step
+// kernels read the end every step (one coalesced 4-byte load beside SI(DAY)) and the start only on their
+// wave-uniform reset path.
 
 __device__ __forceinline__ void ce(int &a, int &b)
 {

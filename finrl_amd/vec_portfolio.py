@@ -9,11 +9,25 @@ import numpy as np
 from . import _native as nat
 from .panel import PortfolioPanel
 from .spaces import Box
+from .vec_env import _EpisodeWindows
 
 
-class VecStockPortfolioEnv:
+class VecStockPortfolioEnv(_EpisodeWindows):
     """E parallel StockPortfolioEnv.  step(actions f32 [E,N]) -> (obs f32 [E, N+K, N] flattened
-    to [E, D], reward f32 [E] = new portfolio value (:196), done u8 [E], None)."""
+    to [E, D], reward f32 [E] = new portfolio value (:196), done u8 [E], None).
+
+    ``windows=(start, end)`` gives every env its own episode window of panel rows ``[start, end)``
+    (one pair for all envs, or [E] arrays / tensors): env e then behaves like the reference env
+    built on ``data_split(df, dates[start[e]], dates[end[e]])`` -- the tutorial's train and trade
+    slices, or random training windows, in ONE batch over one panel.  ``state["day"]`` stays the
+    panel row; ``window_day()`` is the reference's ``self.day``.  See ``set_windows``: as in
+    VecStockTradingEnv an edited start applies at the env's next reset.  The portfolio state keeps
+    no start day, so ``window_day()`` and the last-episode latch count from the start in
+    ``self.windows``: an episode whose start was edited before it ended, and that was not reset
+    since, is out of contract (``set_windows(s, t, mask=done)`` then ``reset(done)`` is exact).
+    """
+
+    _kind = "portfolio"
 
     if_discrete = False
     env_name = "StockPortfolioEnv-MI355X"
@@ -21,7 +35,7 @@ class VecStockPortfolioEnv:
     last_episode_keys = ("begin_total_asset", "end_total_asset", "sharpe")
 
     def __init__(self, panel: PortfolioPanel, num_envs: int, *, initial_amount=1_000_000,
-                 auto_reset=True, device="cuda"):
+                 auto_reset=True, device="cuda", windows=None):
         import torch
         self.panel = panel
         self.device = torch.device(device)
@@ -60,6 +74,10 @@ class VecStockPortfolioEnv:
         self._last = None
         self._last_stats = None
         self.last_episode = None
+        self.windows = None
+        if windows is not None:
+            self.set_windows(*self._check_windows(*windows))
+            self.state["day"].copy_(self.windows[0])       # the constructor's episode: day 0 of each window
 
     def _stream(self):
         import torch
@@ -100,7 +118,7 @@ class VecStockPortfolioEnv:
             last = torch.full((len(nat.PORTFOLIO_LAST_FIELDS), self.num_envs), float("nan"),
                               dtype=torch.float64, device=self.device)
             last[0].zero_()
-            fresh = self.state["day"] == 0
+            fresh = self.window_day() == 0
             for k in ("run_sum", "run_sumsq"):
                 j = nat.PORTFOLIO_LAST_FIELDS.index(k)
                 last[j] = torch.where(fresh, torch.zeros_like(last[j]), last[j])
@@ -131,6 +149,13 @@ class VecStockPortfolioEnv:
             raise nat.FinenvError("last_episode_return: call enable_last_episode() first")
         le = self.last_episode
         return (le["end_value"] / le["begin_value"]).to(torch.float32)
+
+    def window_day(self):
+        """The reference's ``self.day`` of every env (int32 [E] device tensor): ``state["day"]`` minus
+        the env's window start in ``self.windows`` (``state["day"]`` without windows)."""
+        if self.windows is None:
+            return self.state["day"].clone()
+        return self.state["day"] - self.windows[0]
 
     def reset(self, mask=None):
         import torch
@@ -167,4 +192,6 @@ class VecStockPortfolioEnv:
         return (self.state["value"] / float(self._cfg.initial_amount)).to(torch.float32)
 
     def state_numpy(self):
-        return {k: v.detach().cpu().numpy() for k, v in self.state.items()}
+        out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
+        out["window_day"] = self.window_day().cpu().numpy()
+        return out

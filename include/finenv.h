@@ -337,6 +337,29 @@ int  finenv_portfolio_set_last_episode(finenv_portfolio *h, double *last);
  * while COUNT == 0); FINENV_ERR_INVALID when no block is attached. */
 int  finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *stream);
 
+/* Per-env episode windows of the portfolio env (the contract of finenv_stock_set_windows):
+ * many data_split(df, dates[s], dates[t]) frames of ONE bound panel in one batch.  Opt-in and
+ * caller-owned: int32_t win[2][E], device memory; win[0][e] = s_e (first panel row of env e's
+ * frame), win[1][e] = t_e (end, exclusive), and env e then behaves like StockPortfolioEnv on that
+ * frame:
+ *   - terminal when FINENV_PI_DAY >= t_e - 1 (:127);
+ *   - a reset (host or auto, :202-220) goes back to panel row s_e: FINENV_PI_DAY = s_e and the
+ *     observation row is s_e.
+ * FINENV_PI_DAY stays the panel row; the reference's self.day is FINENV_PI_DAY - s_e.
+ * Last-episode block: FINENV_PL_RET_N = FINENV_PI_DAY - s_e + 1, with s_e read at the terminal
+ * step.  The state keeps no start day, so an edited start takes effect at that env's next reset;
+ * an episode whose start was edited before it ended and that was never reset is out of contract
+ * (set the new windows for the envs that just reported done, then reset them).
+ * Preconditions for a faithful result: 0 <= s_e < t_e <= n_days.  The kernels clamp both rows
+ * into [0, n_days) whatever the block holds: a bad window is a wrong answer, never an access
+ * outside the panel or the state.  Valid windows read no panel row outside [s_e, t_e).
+ * The pointer is a kernel argument: launches and graph replays see later edits of the block's
+ * CONTENTS, but a graph keeps the pointer it was captured with.  step() reads t_e on every step
+ * and s_e only when an env is terminal or reset, so an edited end applies from the next step and
+ * an edited start at the env's next reset.  Works before bind.  NULL detaches (the default: every
+ * env runs rows 0 .. n_days-1).  Returns FINENV_ERR_INVALID for a NULL handle. */
+int  finenv_portfolio_set_windows(finenv_portfolio *h, int32_t *win);
+
 /* =====================================================================================
  * CryptoEnv (finrl/meta/env_cryptocurrency_trading/env_multiple_crypto.py:10-111)
  *   actions [E][N] f32 in [-1,1], scaled per asset by the action normaliser (:63-65, :103-111)

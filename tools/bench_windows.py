@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
-"""Step time of the batched stock env with per-env episode windows (VecStockTradingEnv(windows=...)),
-on bench.py's workload (same synthetic panel, actions and env settings), beside the same batch
-without windows in the same process.
+"""Step time of the batched stock and portfolio envs with per-env episode windows
+(VecStockTradingEnv / VecStockPortfolioEnv(windows=...)), on bench.py's workloads (same synthetic
+panel, actions and env settings).
 usage: python3 tools/bench_windows.py <case> [envs] [steps]
   case: full      -- every env on the whole panel [0, T) (lock-step days, the WIN instantiation)
         random63  -- random 63-day windows, hint_desynchronised(True)
         n100      -- the N = 100 shape (turbulence p90) with random 63-day windows
         none      -- no windows (bench.py's headline path), for reference
-        desync    -- no windows, bench.py --desync's per-env start days"""
+        desync    -- no windows, bench.py --desync's per-env start days
+        pf-none, pf-full, pf-random63
+                  -- the same on bench.py --env portfolio's workload (DOW30 x 8)
+        pf-split  -- portfolio, envs alternating between a train window [0, 0.8 T) and a trade
+                     window [0.8 T, T) (the portfolio tutorial's two data_split frames)"""
 import os
 import sys
 
@@ -24,8 +28,10 @@ def main():
     from finrl_amd.data import random_windows
     dev = torch.device("cuda", 0)
     n100 = case == "n100"
+    pf = case.startswith("pf-")
+    case = case[3:] if pf else case
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=case == "desync",
-                              no_stats=False, env="stock", tickers=100 if n100 else 30,
+                              no_stats=False, env="portfolio" if pf else "stock", tickers=100 if n100 else 30,
                               turbulence_pct=90.0 if n100 else None))()
     w = bench.build_workload(args, torch, dev, 0)
     env = w.env
@@ -35,7 +41,12 @@ def main():
     elif case in ("random63", "n100"):
         g = torch.Generator(device=dev).manual_seed(7)
         env.set_windows(*random_windows(T, E, 63, generator=g, device=dev))
-        env.hint_desynchronised(True)
+        if not pf:
+            env.hint_desynchronised(True)
+    elif case == "split":
+        cut = int(0.8 * T)
+        train = torch.arange(E, device=dev) % 2 == 0
+        env.set_windows(torch.where(train, 0, cut), torch.where(train, cut, T))
     env.reset()
     if getattr(w, "after_reset", None):
         w.after_reset()
@@ -48,7 +59,8 @@ def main():
         env.step(w.pool[i % len(w.pool)])
     e1.record()
     torch.cuda.synchronize()
-    print(f"{case} E={E} N={env.stock_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
+    name = ("pf-" if pf else "") + case
+    print(f"{name} E={E} N={env.stock_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of two builds of libfinenv.so inside ONE process on ONE env: same handle, same device buffers
 (so the same physical placement), only the library that launches the step kernel alternates.
-usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|stocknp> [rounds]"""
+usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|portfolio-random63|stocknp> [rounds]
+  portfolio-random63: the portfolio env with random 63-day episode windows (VecStockPortfolioEnv.set_windows)"""
 import os
 import sys
 
@@ -35,6 +36,9 @@ def main():
         E = int(e_txt)
     if kind.startswith("crypto") and kind != "crypto":      # crypto32768 / crypto65536 / crypto131072 / crypto262144
         E = int(kind[6:])
+    windows63 = kind == "portfolio-random63"
+    if windows63:
+        kind = "portfolio"
     a = dict(env="crypto", tickers=30, turbulence_pct=None) if kind.startswith("crypto") else \
         dict(env="portfolio", tickers=30, turbulence_pct=None) if kind == "portfolio" else \
         dict(env="stocknp", tickers=30, turbulence_pct=None) if kind == "stocknp" else \
@@ -42,6 +46,11 @@ def main():
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=False, no_stats=False, **a))()
     w = bench.build_workload(args, torch, dev, 0)
     env = w.env
+    if windows63:
+        from finrl_amd.data import random_windows
+        g = torch.Generator(device=dev).manual_seed(7)
+        env.set_windows(*random_windows(env.panel.T, E, 63, generator=g, device=dev))
+        kind = "portfolio-random63"
     env.reset()
     for i in range(2000):
         env.step(w.pool[i % 8])
