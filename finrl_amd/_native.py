@@ -178,79 +178,44 @@ def lib():
     L.finenv_strerror.restype = C.c_char_p
     L.finenv_strerror.argtypes = [C.c_int]
     L.finenv_device_count.restype = C.c_int
-    L.finenv_stock_create.argtypes = [C.POINTER(StockConfig), C.POINTER(C.c_void_p)]
-    L.finenv_stock_destroy.argtypes = [C.c_void_p]
-    L.finenv_stock_destroy.restype = None
-    L.finenv_stock_last_error.argtypes = [C.c_void_p]
-    L.finenv_stock_last_error.restype = C.c_char_p
-    L.finenv_stock_obs_dim.argtypes = [C.c_void_p]
+    # entry points every kind has; each *_step is declared below (their signatures differ)
+    for kind, cfg, panel, state in (
+            ("stock", StockConfig, StockPanelPtrs, StockStatePtrs),
+            ("portfolio", PortfolioConfig, PortfolioPanelPtrs, PortfolioStatePtrs),
+            ("crypto", CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs),
+            ("stocknp", StockNpConfig, StockNpPanelPtrs, StockNpStatePtrs),
+            ("cashpenalty", CashPenaltyConfig, CashPenaltyPanelPtrs, CashPenaltyStatePtrs),
+            ("stoploss", StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs)):
+        create, destroy, last_error, obs_dim, bind, reset = (
+            getattr(L, f"finenv_{kind}_{name}")
+            for name in ("create", "destroy", "last_error", "obs_dim", "bind", "reset"))
+        create.argtypes = [C.POINTER(cfg), C.POINTER(C.c_void_p)]
+        destroy.argtypes = [C.c_void_p]
+        destroy.restype = None
+        last_error.argtypes = [C.c_void_p]
+        last_error.restype = C.c_char_p
+        obs_dim.argtypes = [C.c_void_p]
+        bind.argtypes = [C.c_void_p, C.POINTER(panel), C.POINTER(state)]
+        reset.argtypes = [C.c_void_p] * 4
     L.finenv_stock_set_obs_pitch.argtypes = [C.c_void_p, C.c_int32]
     L.finenv_stock_set_desync_hint.argtypes = [C.c_void_p, C.c_int32]
-    L.finenv_stock_bind.argtypes = [C.c_void_p, C.POINTER(StockPanelPtrs),
-                                    C.POINTER(StockStatePtrs)]
     L.finenv_stock_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_stock_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_stock_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_stock_refresh.argtypes = [C.c_void_p, C.c_void_p]
     L.finenv_stock_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.finenv_stock_episode_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.finenv_portfolio_create.argtypes = [C.POINTER(PortfolioConfig), C.POINTER(C.c_void_p)]
-    L.finenv_portfolio_destroy.argtypes = [C.c_void_p]
-    L.finenv_portfolio_destroy.restype = None
-    L.finenv_portfolio_last_error.argtypes = [C.c_void_p]
-    L.finenv_portfolio_last_error.restype = C.c_char_p
-    L.finenv_portfolio_obs_dim.argtypes = [C.c_void_p]
-    L.finenv_portfolio_bind.argtypes = [C.c_void_p, C.POINTER(PortfolioPanelPtrs),
-                                        C.POINTER(PortfolioStatePtrs)]
-    L.finenv_portfolio_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_portfolio_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p]
-    L.finenv_crypto_create.argtypes = [C.POINTER(CryptoConfig), C.POINTER(C.c_void_p)]
-    L.finenv_crypto_destroy.argtypes = [C.c_void_p]
-    L.finenv_crypto_destroy.restype = None
-    L.finenv_crypto_last_error.argtypes = [C.c_void_p]
-    L.finenv_crypto_last_error.restype = C.c_char_p
-    L.finenv_crypto_obs_dim.argtypes = [C.c_void_p]
-    L.finenv_crypto_bind.argtypes = [C.c_void_p, C.POINTER(CryptoPanelPtrs),
-                                     C.POINTER(CryptoStatePtrs)]
-    L.finenv_crypto_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_crypto_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_void_p]
     L.finenv_crypto_step_record.argtypes = [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 6
-    L.finenv_stocknp_create.argtypes = [C.POINTER(StockNpConfig), C.POINTER(C.c_void_p)]
-    L.finenv_stocknp_destroy.argtypes = [C.c_void_p]
-    L.finenv_stocknp_destroy.restype = None
-    L.finenv_stocknp_last_error.argtypes = [C.c_void_p]
-    L.finenv_stocknp_last_error.restype = C.c_char_p
-    L.finenv_stocknp_obs_dim.argtypes = [C.c_void_p]
     L.finenv_stocknp_set_obs_pitch.argtypes = [C.c_void_p, C.c_int32]
-    L.finenv_stocknp_bind.argtypes = [C.c_void_p, C.POINTER(StockNpPanelPtrs),
-                                      C.POINTER(StockNpStatePtrs)]
-    L.finenv_stocknp_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_stocknp_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_cashpenalty_create.argtypes = [C.POINTER(CashPenaltyConfig), C.POINTER(C.c_void_p)]
-    L.finenv_cashpenalty_destroy.argtypes = [C.c_void_p]
-    L.finenv_cashpenalty_destroy.restype = None
-    L.finenv_cashpenalty_last_error.argtypes = [C.c_void_p]
-    L.finenv_cashpenalty_last_error.restype = C.c_char_p
-    L.finenv_cashpenalty_obs_dim.argtypes = [C.c_void_p]
-    L.finenv_cashpenalty_bind.argtypes = [C.c_void_p, C.POINTER(CashPenaltyPanelPtrs),
-                                          C.POINTER(CashPenaltyStatePtrs)]
-    L.finenv_cashpenalty_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_cashpenalty_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_stoploss_create.argtypes = [C.POINTER(StopLossConfig), C.POINTER(C.c_void_p)]
-    L.finenv_stoploss_destroy.argtypes = [C.c_void_p]
-    L.finenv_stoploss_destroy.restype = None
-    L.finenv_stoploss_last_error.argtypes = [C.c_void_p]
-    L.finenv_stoploss_last_error.restype = C.c_char_p
-    L.finenv_stoploss_obs_dim.argtypes = [C.c_void_p]
-    L.finenv_stoploss_bind.argtypes = [C.c_void_p, C.POINTER(StopLossPanelPtrs),
-                                       C.POINTER(StopLossStatePtrs)]
-    L.finenv_stoploss_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.finenv_stoploss_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.finenv_riskpre_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]

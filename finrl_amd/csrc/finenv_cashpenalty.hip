@@ -22,8 +22,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <new>
-
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
@@ -511,35 +509,17 @@ cashpenalty_kernel(const CpParams p)
 
 }  // namespace
 
-struct finenv_cashpenalty {
+struct finenv_cashpenalty : finenv_host::Handle {
     int32_t rs_hi;
     unsigned long long rs_seed;
     double *audit;
-    int device;           // HIP device that owns the bound state block (-1 before bind)
     finenv_cashpenalty_config cfg;
     finenv_cashpenalty_panel panel;
     finenv_cashpenalty_state st;
-    int bound;
-    int D;
     uint32_t magicN;
-    char err[256];
 };
 
 namespace {
-int kp_fail(finenv_cashpenalty *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
-    return code;
-}
-int kp_check(finenv_cashpenalty *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 CpParams kp_params(const finenv_cashpenalty *h)
 {
     CpParams p;
@@ -572,13 +552,9 @@ int finenv_cashpenalty_create(const finenv_cashpenalty_config *cfg, finenv_cashp
     if ((FINENV_CASHPENALTY_F64_FIELDS + N) * E * 8 > lim || T * N * cfg->n_cols * 4 > lim ||
         T * N * 8 > lim || 64 * D * 4 > lim || E * N * 4 > lim)
         return FINENV_ERR_INVALID;
-    finenv_cashpenalty *h = new (std::nothrow) finenv_cashpenalty;
+    finenv_cashpenalty *h = finenv_host::new_handle<finenv_cashpenalty>(cfg, D);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = (int)D;
-    h->magicN = N >= 2 ? (uint32_t)(((1ull << 32) + N - 1) / (unsigned long long)N) : 0u;
+    h->magicN = finenv_host::magic_for(N);
     *out = h;
     return FINENV_OK;
 }
@@ -586,9 +562,9 @@ int finenv_cashpenalty_create(const finenv_cashpenalty_config *cfg, finenv_cashp
 void finenv_cashpenalty_destroy(finenv_cashpenalty *h) { delete h; }
 const char *finenv_cashpenalty_last_error(const finenv_cashpenalty *h)
 {
-    return h ? h->err : "null handle";
+    return finenv_host::last_error(h);
 }
-int finenv_cashpenalty_obs_dim(const finenv_cashpenalty *h) { return h ? h->D : FINENV_ERR_INVALID; }
+int finenv_cashpenalty_obs_dim(const finenv_cashpenalty *h) { return finenv_host::obs_dim(h); }
 
 int finenv_cashpenalty_bind(finenv_cashpenalty *h, const finenv_cashpenalty_panel *panel,
                             const finenv_cashpenalty_state *st)
@@ -596,12 +572,8 @@ int finenv_cashpenalty_bind(finenv_cashpenalty *h, const finenv_cashpenalty_pane
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->close || (!panel->info && h->cfg.n_cols > 0) ||
         (!panel->turb && h->cfg.use_turbulence) || !st->f64 || !st->i32)
-        return kp_fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_cashpenalty_set_random_start(finenv_cashpenalty *h, int32_t hi, uint64_t seed)
@@ -622,26 +594,24 @@ int finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit)
 int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *obs_out,
                              void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return kp_fail(h, FINENV_ERR_UNBOUND, "reset: bind first");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     CpParams p = kp_params(h);
     p.mask = mask;
     p.obs = obs_out;
     hipLaunchKernelGGL((cashpenalty_kernel<true, 0, false>), kp_grid(h->cfg.n_envs), dim3(kWave * kWaves),
                        0, (hipStream_t)stream, p);
-    return kp_check(h, "cashpenalty_reset");
+    return finenv_host::check_launch(h, "cashpenalty_reset");
 }
 
 int finenv_cashpenalty_step(finenv_cashpenalty *h, const float *actions, float *obs,
                             float *reward, uint8_t *done, float *term_obs, int32_t auto_reset,
                             void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return kp_fail(h, FINENV_ERR_UNBOUND, "step: bind first");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return kp_fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     CpParams p = kp_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -669,7 +639,7 @@ int finenv_cashpenalty_step(finenv_cashpenalty *h, const float *actions, float *
     else if (h->D <= kWave + 4 * kWave) CP_LAUNCH(2);
     else CP_LAUNCH(0);
 #undef CP_LAUNCH
-    return kp_check(h, "cashpenalty_step");
+    return finenv_host::check_launch(h, "cashpenalty_step");
 }
 
 }  // extern "C"

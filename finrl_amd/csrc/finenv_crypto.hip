@@ -22,8 +22,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
-
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
@@ -474,32 +472,14 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
 
 }  // namespace
 
-struct finenv_crypto {
-    int device;           // HIP device that owns the bound state block (-1 before bind)
+struct finenv_crypto : finenv_host::Handle {
     finenv_crypto_config cfg;
     finenv_crypto_panel panel;
     finenv_crypto_state st;
-    int bound;
-    int D;
     uint32_t magicN, magicW, magicH, magicD;
-    char err[256];
 };
 
 namespace {
-int cr_fail(finenv_crypto *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
-    return code;
-}
-int cr_check(finenv_crypto *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 CrParams cr_params(const finenv_crypto *h)
 {
     CrParams p;
@@ -513,10 +493,6 @@ CrParams cr_params(const finenv_crypto *h)
     p.magicH = h->magicH;
     p.magicD = h->magicD;
     return p;
-}
-uint32_t magic_for(long long n)
-{
-    return n >= 2 ? (uint32_t)(((1ull << 32) + n - 1) / (unsigned long long)n) : 0u;
 }
 constexpr int kSmallWaves = 2048;      // up to here: one env wave per block (spread over every CU)
 template <bool RESET_ONLY, int NP>
@@ -574,23 +550,19 @@ int finenv_crypto_create(const finenv_crypto_config *cfg, finenv_crypto **out)
     if (E * 8 * FINENV_CRYPTO_F64_FIELDS > lim || E * N * 4 > lim || T * N * 8 > lim ||
         T * W * 4 > lim || 64 * D * 4 > lim || D > 65535)
         return FINENV_ERR_INVALID;
-    finenv_crypto *h = new (std::nothrow) finenv_crypto;
+    finenv_crypto *h = finenv_host::new_handle<finenv_crypto>(cfg, D);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = (int)D;
-    h->magicN = magic_for(N);
-    h->magicW = magic_for(W);
-    h->magicH = magic_for(N + 1);
-    h->magicD = magic_for(D);
+    h->magicN = finenv_host::magic_for(N);
+    h->magicW = finenv_host::magic_for(W);
+    h->magicH = finenv_host::magic_for(N + 1);
+    h->magicD = finenv_host::magic_for(D);
     *out = h;
     return FINENV_OK;
 }
 
 void finenv_crypto_destroy(finenv_crypto *h) { delete h; }
-const char *finenv_crypto_last_error(const finenv_crypto *h) { return h ? h->err : "null handle"; }
-int finenv_crypto_obs_dim(const finenv_crypto *h) { return h ? h->D : FINENV_ERR_INVALID; }
+const char *finenv_crypto_last_error(const finenv_crypto *h) { return finenv_host::last_error(h); }
+int finenv_crypto_obs_dim(const finenv_crypto *h) { return finenv_host::obs_dim(h); }
 
 int finenv_crypto_bind(finenv_crypto *h, const finenv_crypto_panel *panel,
                        const finenv_crypto_state *st)
@@ -598,34 +570,28 @@ int finenv_crypto_bind(finenv_crypto *h, const finenv_crypto_panel *panel,
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->price || (!panel->tech_scaled && h->cfg.n_tech > 0) || !panel->norm || !st->f64 ||
         !st->i32 || !st->stocks)
-        return cr_fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_crypto_reset(finenv_crypto *h, const uint8_t *mask, float *obs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return cr_fail(h, FINENV_ERR_UNBOUND, "reset: bind first");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     CrParams p = cr_params(h);
     p.mask = mask;
     p.obs = obs_out;
     cr_launch<true>(p, (hipStream_t)stream);
-    return cr_check(h, "crypto_reset");
+    return finenv_host::check_launch(h, "crypto_reset");
 }
 
 int finenv_crypto_step(finenv_crypto *h, const float *actions, float *obs, float *reward,
                        uint8_t *done, float *term_obs, int32_t auto_reset, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return cr_fail(h, FINENV_ERR_UNBOUND, "step: bind first");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return cr_fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     CrParams p = cr_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -637,7 +603,7 @@ int finenv_crypto_step(finenv_crypto *h, const float *actions, float *obs, float
     p.dbg = g_finenv_dbg;
 #endif
     cr_launch<false>(p, (hipStream_t)stream);
-    return cr_check(h, "crypto_step");
+    return finenv_host::check_launch(h, "crypto_step");
 }
 
 int finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *obs, float *reward,
@@ -645,17 +611,16 @@ int finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *obs
                               const float *values, const float *log_probs, float *actions_out,
                               float *values_out, float *log_probs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return cr_fail(h, FINENV_ERR_UNBOUND, "step_record: bind first");
+    if (const int rc = finenv_host::ready(h, "step_record")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done || !values || !log_probs || !actions_out ||
         !values_out || !log_probs_out)
-        return cr_fail(h, FINENV_ERR_INVALID, "step_record: null pointer");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step_record: null pointer");
     const long long na = (long long)h->cfg.n_envs * h->cfg.n_assets, nv = h->cfg.n_envs;
     const uintptr_t bits = (uintptr_t)actions | (uintptr_t)values | (uintptr_t)log_probs |
                            (uintptr_t)actions_out | (uintptr_t)values_out | (uintptr_t)log_probs_out;
     if ((bits & 15) != 0 || (na & 3) != 0 || (nv & 3) != 0)
-        return cr_fail(h, FINENV_ERR_INVALID,
+        return finenv_host::fail(h, FINENV_ERR_INVALID,
                        "step_record: 16-byte aligned buffers and n_envs % 4 == 0 required "
                        "(use finenv_crypto_step + finenv_rollout_put otherwise)");
     CrParams p = cr_params(h);
@@ -674,7 +639,7 @@ int finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *obs
     p.dbg = g_finenv_dbg;
 #endif
     cr_launch<false>(p, (hipStream_t)stream);
-    return cr_check(h, "crypto_step_record");
+    return finenv_host::check_launch(h, "crypto_step_record");
 }
 
 }  // extern "C"

@@ -1,6 +1,12 @@
 // finenv_host.h -- host-side helpers shared by the C-ABI entry points.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <new>
+
+#include "finenv.h"
 
 namespace finenv_host {
 
@@ -34,5 +40,75 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+
+// The part every env handle shares: each struct finenv_<kind> derives from it and adds its own
+// cfg / panel / st and whatever else is its own.
+struct Handle {
+    int device;           // HIP device that owns the bound state block (-1 before bind)
+    int bound;
+    int D;                // observation width (floats)
+    char err[256];        // finenv_<kind>_last_error
+};
+
+inline int fail(Handle *h, int code, const char *msg)
+{
+    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
+    return code;
+}
+
+inline int check_launch(Handle *h, const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
+        return FINENV_ERR_HIP;
+    }
+    return FINENV_OK;
+}
+
+// Ready to launch: a null handle is FINENV_ERR_INVALID, an unbound one FINENV_ERR_UNBOUND with
+// "<what>: bind first".  The caller then takes a DeviceGuard(h->device).
+inline int ready(Handle *h, const char *what)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (!h->bound) {
+        snprintf(h->err, sizeof(h->err), "%s: bind first", what);
+        return FINENV_ERR_UNBOUND;
+    }
+    return FINENV_OK;
+}
+
+inline const char *last_error(const Handle *h) { return h ? h->err : "null handle"; }
+inline int obs_dim(const Handle *h) { return h ? h->D : FINENV_ERR_INVALID; }
+
+// A zeroed handle on no device with its config and observation width; nullptr when out of memory.
+template <class H>
+H *new_handle(const decltype(H::cfg) *cfg, long long D)
+{
+    H *h = new (std::nothrow) H();
+    if (h) {
+        h->device = -1;
+        h->cfg = *cfg;
+        h->D = (int)D;
+    }
+    return h;
+}
+
+// The end of every bind, once the pointers are checked: keep them, launch on the state's device.
+template <class H>
+int bind(H *h, const decltype(H::panel) *panel, const decltype(H::st) *st)
+{
+    h->panel = *panel;
+    h->st = *st;
+    h->device = pointer_device(st->f64);
+    h->bound = 1;
+    return FINENV_OK;
+}
+
+// magicN-style reciprocal: ceil(2^32 / n) for n >= 2 (exact f / n for f < 2^16), 0 for n < 2.
+inline uint32_t magic_for(long long n)
+{
+    return n >= 2 ? (uint32_t)(((1ull << 32) + n - 1) / (unsigned long long)n) : 0u;
+}
 
 }  // namespace finenv_host

@@ -20,8 +20,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <new>
-
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
@@ -298,34 +296,16 @@ __global__ void portfolio_last_stats_kernel(const PfParams p)
 
 }  // namespace
 
-struct finenv_portfolio {
-    int device;           // HIP device that owns the bound state block (-1 before bind)
+struct finenv_portfolio : finenv_host::Handle {
     finenv_portfolio_config cfg;
     finenv_portfolio_panel panel;
     finenv_portfolio_state st;
-    int bound;
-    int D;
     uint32_t magicN;
-    char err[256];
-    double *last;         // finenv_portfolio_set_last_episode (appended: the layout above is unchanged)
-    int32_t *win;         // finenv_portfolio_set_windows (appended likewise)
+    double *last;         // finenv_portfolio_set_last_episode
+    int32_t *win;         // finenv_portfolio_set_windows
 };
 
 namespace {
-int pf_fail(finenv_portfolio *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
-    return code;
-}
-int pf_check(finenv_portfolio *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 PfParams pf_params(const finenv_portfolio *h)
 {
     PfParams p;
@@ -355,56 +335,46 @@ int finenv_portfolio_create(const finenv_portfolio_config *cfg, finenv_portfolio
     if (E * 8 * FINENV_PORTFOLIO_F64_FIELDS > lim || T * D * 4 > lim || T * N * 8 > lim ||
         E * N * 4 > lim || 64 * D * 4 > lim)
         return FINENV_ERR_INVALID;
-    finenv_portfolio *h = new (std::nothrow) finenv_portfolio;
+    finenv_portfolio *h = finenv_host::new_handle<finenv_portfolio>(cfg, D);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = (int)D;
-    h->magicN = N >= 2 ? (uint32_t)(((1ull << 32) + N - 1) / (unsigned long long)N) : 0u;
+    h->magicN = finenv_host::magic_for(N);
     *out = h;
     return FINENV_OK;
 }
 
 void finenv_portfolio_destroy(finenv_portfolio *h) { delete h; }
-const char *finenv_portfolio_last_error(const finenv_portfolio *h) { return h ? h->err : "null handle"; }
-int finenv_portfolio_obs_dim(const finenv_portfolio *h) { return h ? h->D : FINENV_ERR_INVALID; }
+const char *finenv_portfolio_last_error(const finenv_portfolio *h) { return finenv_host::last_error(h); }
+int finenv_portfolio_obs_dim(const finenv_portfolio *h) { return finenv_host::obs_dim(h); }
 
 int finenv_portfolio_bind(finenv_portfolio *h, const finenv_portfolio_panel *panel,
                           const finenv_portfolio_state *st)
 {
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->gross_ret || !panel->obs_tmpl || !st->f64 || !st->i32)
-        return pf_fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_portfolio_reset(finenv_portfolio *h, const uint8_t *mask, float *obs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return pf_fail(h, FINENV_ERR_UNBOUND, "reset: bind first");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     PfParams p = pf_params(h);
     p.mask = mask;
     p.obs = obs_out;
     hipLaunchKernelGGL(portfolio_reset_kernel, dim3((h->cfg.n_envs + kWave - 1) / kWave),
                        dim3(kThreads), 0, (hipStream_t)stream, p);
-    return pf_check(h, "portfolio_reset");
+    return finenv_host::check_launch(h, "portfolio_reset");
 }
 
 int finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs, float *reward,
                           uint8_t *done, float *term_obs, float *weights_out,
                           int32_t auto_reset, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return pf_fail(h, FINENV_ERR_UNBOUND, "step: bind first");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return pf_fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     PfParams p = pf_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -419,7 +389,7 @@ int finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs,
     else
         hipLaunchKernelGGL(portfolio_step_kernel<false>, dim3((h->cfg.n_envs + kWave - 1) / kWave),
                            dim3(kThreads), 0, (hipStream_t)stream, p);
-    return pf_check(h, "portfolio_step");
+    return finenv_host::check_launch(h, "portfolio_step");
 }
 
 int finenv_portfolio_set_last_episode(finenv_portfolio *h, double *last)
@@ -439,14 +409,14 @@ int finenv_portfolio_set_windows(finenv_portfolio *h, int32_t *win)
 int finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->last) return pf_fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
-    if (!h->bound) return pf_fail(h, FINENV_ERR_UNBOUND, "last_episode_stats: bind first");
+    if (!h->last) return finenv_host::fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
+    if (const int rc = finenv_host::ready(h, "last_episode_stats")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     PfParams p = pf_params(h);
     p.stats_out = out;
     hipLaunchKernelGGL(portfolio_last_stats_kernel, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
-    return pf_check(h, "portfolio_last_episode_stats");
+    return finenv_host::check_launch(h, "portfolio_last_episode_stats");
 }
 
 }  // extern "C"

@@ -73,38 +73,18 @@ __global__ void stock_last_stats_kernel(const Params p)
 // =====================================================================================
 // Host side: handle, validation, launches.  No allocation on the device, no sync.
 // =====================================================================================
-struct finenv_stock {
-    int device;           // HIP device that owns the bound state block (-1 before bind)
+struct finenv_stock : finenv_host::Handle {
     finenv_stock_config cfg;
     finenv_stock_panel panel;
     finenv_stock_state st;
-    int bound;
-    int D;
     int obs_pitch;        // row pitch of the obs buffers handed to step / reset / observe (floats)
     int desync_hint;      // finenv_stock_set_desync_hint
     uint32_t magicN;
-    char err[256];
-    double *last;         // finenv_stock_set_last_episode (appended: the layout above is unchanged)
-    int32_t *win;         // finenv_stock_set_windows (appended likewise)
+    double *last;         // finenv_stock_set_last_episode
+    int32_t *win;         // finenv_stock_set_windows
 };
 
 namespace {
-
-int fail(finenv_stock *h, int code, const char *fmt, const char *detail = "")
-{
-    if (h) snprintf(h->err, sizeof(h->err), fmt, detail);
-    return code;
-}
-
-int check_launch(finenv_stock *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 
 Params make_params(const finenv_stock *h)
 {
@@ -218,25 +198,20 @@ int finenv_stock_create(const finenv_stock_config *cfg, finenv_stock **out)
             T * D * 4 > lim || T * N * 8 > lim || E * N * 4 > lim)
             return FINENV_ERR_INVALID;
     }
-    finenv_stock *h = new (std::nothrow) finenv_stock;
+    finenv_stock *h = finenv_host::new_handle<finenv_stock>(
+        cfg, 1 + 2 * cfg->n_tickers + cfg->n_tech * cfg->n_tickers);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = 1 + 2 * cfg->n_tickers + cfg->n_tech * cfg->n_tickers;
     h->obs_pitch = h->D;
-    h->magicN = cfg->n_tickers >= 2
-                    ? (uint32_t)(((1ull << 32) + cfg->n_tickers - 1) / (unsigned)cfg->n_tickers)
-                    : 0u;
+    h->magicN = finenv_host::magic_for(cfg->n_tickers);
     *out = h;
     return FINENV_OK;
 }
 
 void finenv_stock_destroy(finenv_stock *h) { delete h; }
 
-const char *finenv_stock_last_error(const finenv_stock *h) { return h ? h->err : "null handle"; }
+const char *finenv_stock_last_error(const finenv_stock *h) { return finenv_host::last_error(h); }
 
-int finenv_stock_obs_dim(const finenv_stock *h) { return h ? h->D : FINENV_ERR_INVALID; }
+int finenv_stock_obs_dim(const finenv_stock *h) { return finenv_host::obs_dim(h); }
 
 int finenv_stock_set_desync_hint(finenv_stock *h, int32_t on)
 {
@@ -250,7 +225,7 @@ int finenv_stock_set_obs_pitch(finenv_stock *h, int32_t pitch)
     if (!h) return FINENV_ERR_INVALID;
     if (pitch == 0) pitch = h->D;
     if (pitch < h->D || (long long)pitch * 64 * 4 > (1ll << 32) - 1)
-        return fail(h, FINENV_ERR_INVALID, "set_obs_pitch: pitch must be >= obs_dim");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_obs_pitch: pitch must be >= obs_dim");
     h->obs_pitch = pitch;
     return FINENV_OK;
 }
@@ -261,70 +236,63 @@ int finenv_stock_bind(finenv_stock *h, const finenv_stock_panel *panel,
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->close || !panel->obs_tmpl ||
         (h->cfg.use_turbulence && !panel->risk))
-        return fail(h, FINENV_ERR_INVALID, "bind: null panel pointer%s");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null panel pointer");
     if (!st->f64 || !st->i32)
-        return fail(h, FINENV_ERR_INVALID, "bind: null state pointer%s");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null state pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_stock_init(finenv_stock *h, int32_t day0, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "init: bind first%s");
+    if (const int rc = finenv_host::ready(h, "init")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
-    if (day0 < 0 || day0 >= h->cfg.n_days) return fail(h, FINENV_ERR_INVALID, "init: bad day0%s");
+    if (day0 < 0 || day0 >= h->cfg.n_days)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "init: bad day0");
     Params p = make_params(h);
     p.day0 = day0;
     launch_aux(h, p, 0, (hipStream_t)stream);
-    return check_launch(h, "stock_init");
+    return finenv_host::check_launch(h, "stock_init");
 }
 
 int finenv_stock_reset(finenv_stock *h, const uint8_t *mask, float *obs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "reset: bind first%s");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     p.mask = mask;
     p.obs = obs_out;
     launch_aux(h, p, 1, (hipStream_t)stream);
-    return check_launch(h, "stock_reset");
+    return finenv_host::check_launch(h, "stock_reset");
 }
 
 int finenv_stock_observe(finenv_stock *h, float *obs_out, void *stream)
 {
     if (!h || !obs_out) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "observe: bind first%s");
+    if (const int rc = finenv_host::ready(h, "observe")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     p.obs = obs_out;
     launch_aux(h, p, 2, (hipStream_t)stream);
-    return check_launch(h, "stock_observe");
+    return finenv_host::check_launch(h, "stock_observe");
 }
 
 int finenv_stock_refresh(finenv_stock *h, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "refresh: bind first%s");
+    if (const int rc = finenv_host::ready(h, "refresh")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     launch_aux(h, p, 3, (hipStream_t)stream);
-    return check_launch(h, "stock_refresh");
+    return finenv_host::check_launch(h, "stock_refresh");
 }
 
 int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *reward,
                       uint8_t *done, float *term_obs, int32_t *realised, int32_t auto_reset,
                       void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "step: bind first%s");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done%s");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     Params p = make_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -343,21 +311,21 @@ int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *
     const hipStream_t s = (hipStream_t)stream;
     const bool turb = h->cfg.use_turbulence != 0, stats = h->cfg.track_stats != 0;
     const int rc = launch_step(h, p, turb, stats, s);
-    if (rc) return fail(h, FINENV_ERR_HIP, "step: cannot raise the dynamic LDS limit%s");
-    return check_launch(h, "stock_step");
+    if (rc) return finenv_host::fail(h, FINENV_ERR_HIP, "step: cannot raise the dynamic LDS limit");
+    return finenv_host::check_launch(h, "stock_step");
 }
 
 int finenv_stock_episode_stats(finenv_stock *h, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "episode_stats: bind first%s");
+    if (const int rc = finenv_host::ready(h, "episode_stats")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     p.stats_out = out;
     const int E = h->cfg.n_envs;
     hipLaunchKernelGGL(stock_stats_kernel, dim3((E + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
-    return check_launch(h, "stock_episode_stats");
+    return finenv_host::check_launch(h, "stock_episode_stats");
 }
 
 int finenv_stock_set_last_episode(finenv_stock *h, double *last)
@@ -377,15 +345,16 @@ int finenv_stock_set_windows(finenv_stock *h, int32_t *win)
 int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->last) return fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set%s");
-    if (!h->bound) return fail(h, FINENV_ERR_UNBOUND, "last_episode_stats: bind first%s");
+    if (!h->last)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
+    if (const int rc = finenv_host::ready(h, "last_episode_stats")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     p.stats_out = out;
     const int E = h->cfg.n_envs;
     hipLaunchKernelGGL(stock_last_stats_kernel, dim3((E + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
-    return check_launch(h, "stock_last_episode_stats");
+    return finenv_host::check_launch(h, "stock_last_episode_stats");
 }
 
 }  // extern "C"

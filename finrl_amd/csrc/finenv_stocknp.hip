@@ -14,8 +14,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <new>
-
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
@@ -651,33 +649,15 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
 
 }  // namespace
 
-struct finenv_stocknp {
-    int device;           // HIP device that owns the bound state block (-1 before bind)
+struct finenv_stocknp : finenv_host::Handle {
     finenv_stocknp_config cfg;
     finenv_stocknp_panel panel;
     finenv_stocknp_state st;
-    int bound;
-    int D;
     int obs_pitch;        // row pitch of the obs buffers handed to step / reset (floats)
     uint32_t magicN;
-    char err[256];
 };
 
 namespace {
-int np_fail(finenv_stocknp *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
-    return code;
-}
-int np_check(finenv_stocknp *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 NpParams np_params(const finenv_stocknp *h)
 {
     NpParams p;
@@ -712,28 +692,24 @@ int finenv_stocknp_create(const finenv_stocknp_config *cfg, finenv_stocknp **out
     if (E * 8 * FINENV_STOCKNP_F64_FIELDS > lim || E * N * 12 > lim || T * D * 4 > lim ||
         64 * D * 4 > lim)
         return FINENV_ERR_INVALID;
-    finenv_stocknp *h = new (std::nothrow) finenv_stocknp;
+    finenv_stocknp *h = finenv_host::new_handle<finenv_stocknp>(cfg, D);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = (int)D;
     h->obs_pitch = (int)D;
-    h->magicN = N >= 2 ? (uint32_t)(((1ull << 32) + N - 1) / (unsigned long long)N) : 0u;
+    h->magicN = finenv_host::magic_for(N);
     *out = h;
     return FINENV_OK;
 }
 
 void finenv_stocknp_destroy(finenv_stocknp *h) { delete h; }
-const char *finenv_stocknp_last_error(const finenv_stocknp *h) { return h ? h->err : "null handle"; }
-int finenv_stocknp_obs_dim(const finenv_stocknp *h) { return h ? h->D : FINENV_ERR_INVALID; }
+const char *finenv_stocknp_last_error(const finenv_stocknp *h) { return finenv_host::last_error(h); }
+int finenv_stocknp_obs_dim(const finenv_stocknp *h) { return finenv_host::obs_dim(h); }
 
 int finenv_stocknp_set_obs_pitch(finenv_stocknp *h, int32_t pitch)
 {
     if (!h) return FINENV_ERR_INVALID;
     if (pitch == 0) pitch = h->D;
     if (pitch < h->D || (long long)pitch * 64 * 4 > (1ll << 32) - 1)
-        return np_fail(h, FINENV_ERR_INVALID, "set_obs_pitch: pitch must be >= obs_dim");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_obs_pitch: pitch must be >= obs_dim");
     h->obs_pitch = pitch;
     return FINENV_OK;
 }
@@ -743,35 +719,29 @@ int finenv_stocknp_bind(finenv_stocknp *h, const finenv_stocknp_panel *panel,
 {
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->price || !panel->obs_tmpl || !panel->turb_bool || !st->f64 || !st->i32 || !st->f32)
-        return np_fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_stocknp_reset(finenv_stocknp *h, const uint8_t *mask, float *obs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return np_fail(h, FINENV_ERR_UNBOUND, "reset: bind first");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     NpParams p = np_params(h);
     p.mask = mask;
     p.obs = obs_out;
     hipLaunchKernelGGL((stocknp_kernel<true>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
                        (hipStream_t)stream, p);
-    return np_check(h, "stocknp_reset");
+    return finenv_host::check_launch(h, "stocknp_reset");
 }
 
 int finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, float *reward,
                         uint8_t *done, float *term_obs, int32_t auto_reset, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return np_fail(h, FINENV_ERR_UNBOUND, "step: bind first");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return np_fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     NpParams p = np_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -788,7 +758,7 @@ int finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, flo
 #endif
     hipLaunchKernelGGL((stocknp_kernel<false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
                        (hipStream_t)stream, p);
-    return np_check(h, "stocknp_step");
+    return finenv_host::check_launch(h, "stocknp_step");
 }
 
 }  // extern "C"

@@ -28,8 +28,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <new>
-
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
@@ -913,35 +911,17 @@ stoploss_step2_kernel(const SlParams p)
 
 }  // namespace
 
-struct finenv_stoploss {
+struct finenv_stoploss : finenv_host::Handle {
     int32_t rs_hi;
     unsigned long long rs_seed;
     double *audit;
-    int device;           // HIP device that owns the bound state block (-1 before bind)
     finenv_stoploss_config cfg;
     finenv_stoploss_panel panel;
     finenv_stoploss_state st;
-    int bound;
-    int D;
     uint32_t magicN;
-    char err[256];
 };
 
 namespace {
-int sl_fail(finenv_stoploss *h, int code, const char *msg)
-{
-    if (h) snprintf(h->err, sizeof(h->err), "%s", msg);
-    return code;
-}
-int sl_check(finenv_stoploss *h, const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(h->err, sizeof(h->err), "%s: %s", what, hipGetErrorString(e));
-        return FINENV_ERR_HIP;
-    }
-    return FINENV_OK;
-}
 SlParams sl_params(const finenv_stoploss *h)
 {
     SlParams p;
@@ -978,13 +958,9 @@ int finenv_stoploss_create(const finenv_stoploss_config *cfg, finenv_stoploss **
     if ((FINENV_STOPLOSS_F64_FIELDS + FINENV_STOPLOSS_BOOKS * N) * E * 8 > lim ||
         T * N * cfg->n_cols * 4 > lim || T * N * 8 > lim || 64 * D * 4 > lim || E * N * 4 > lim)
         return FINENV_ERR_INVALID;
-    finenv_stoploss *h = new (std::nothrow) finenv_stoploss;
+    finenv_stoploss *h = finenv_host::new_handle<finenv_stoploss>(cfg, D);
     if (!h) return FINENV_ERR_NOMEM;
-    memset(h, 0, sizeof(*h));
-    h->device = -1;
-    h->cfg = *cfg;
-    h->D = (int)D;
-    h->magicN = N >= 2 ? (uint32_t)(((1ull << 32) + N - 1) / (unsigned long long)N) : 0u;
+    h->magicN = finenv_host::magic_for(N);
     *out = h;
     return FINENV_OK;
 }
@@ -992,9 +968,9 @@ int finenv_stoploss_create(const finenv_stoploss_config *cfg, finenv_stoploss **
 void finenv_stoploss_destroy(finenv_stoploss *h) { delete h; }
 const char *finenv_stoploss_last_error(const finenv_stoploss *h)
 {
-    return h ? h->err : "null handle";
+    return finenv_host::last_error(h);
 }
-int finenv_stoploss_obs_dim(const finenv_stoploss *h) { return h ? h->D : FINENV_ERR_INVALID; }
+int finenv_stoploss_obs_dim(const finenv_stoploss *h) { return finenv_host::obs_dim(h); }
 
 int finenv_stoploss_bind(finenv_stoploss *h, const finenv_stoploss_panel *panel,
                          const finenv_stoploss_state *st)
@@ -1002,12 +978,8 @@ int finenv_stoploss_bind(finenv_stoploss *h, const finenv_stoploss_panel *panel,
     if (!h || !panel || !st) return FINENV_ERR_INVALID;
     if (!panel->close || (!panel->info && h->cfg.n_cols > 0) ||
         (!panel->turb && h->cfg.use_turbulence) || !st->f64 || !st->i32)
-        return sl_fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    h->panel = *panel;
-    h->st = *st;
-    h->device = finenv_host::pointer_device(st->f64);
-    h->bound = 1;
-    return FINENV_OK;
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
 }
 
 int finenv_stoploss_set_random_start(finenv_stoploss *h, int32_t hi, uint64_t seed)
@@ -1027,25 +999,23 @@ int finenv_stoploss_set_audit(finenv_stoploss *h, double *audit)
 
 int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return sl_fail(h, FINENV_ERR_UNBOUND, "reset: bind first");
+    if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     SlParams p = sl_params(h);
     p.mask = mask;
     p.obs = obs_out;
     hipLaunchKernelGGL((stoploss_kernel<true>), sl_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
                        (hipStream_t)stream, p);
-    return sl_check(h, "stoploss_reset");
+    return finenv_host::check_launch(h, "stoploss_reset");
 }
 
 int finenv_stoploss_step(finenv_stoploss *h, const float *actions, float *obs, float *reward,
                          uint8_t *done, float *term_obs, int32_t auto_reset, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->bound) return sl_fail(h, FINENV_ERR_UNBOUND, "step: bind first");
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
-        return sl_fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
     SlParams p = sl_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -1073,7 +1043,7 @@ int finenv_stoploss_step(finenv_stoploss *h, const float *actions, float *obs, f
     else if (h->D <= kWave + 4 * kWave) SL_LAUNCH2(2);
     else hipLaunchKernelGGL((stoploss_kernel<false>), grid, block, 0, (hipStream_t)stream, p);
 #undef SL_LAUNCH2
-    return sl_check(h, "stoploss_step");
+    return finenv_host::check_launch(h, "stoploss_step");
 }
 
 }  // extern "C"

@@ -43,13 +43,9 @@ class GraphedSegment:
             v.copy_(snap[k])
 
     def _state_tensors(self):
-        env = self.env
-        out = {}
-        for name in ("_f64", "_i32", "_f32", "_state_f64", "_state_i32", "_stocks"):
-            t = getattr(env, name, None)
-            if t is not None:
-                out[name] = t
-        return out
+        """The env's state blocks (finrl_amd.vec_base.BatchedEnv: None where the kind has none)."""
+        blocks = ((k, getattr(self.env, k, None)) for k in ("_f64", "_i32", "_f32"))
+        return {k: t for k, t in blocks if t is not None}
 
     def _segment(self, policy):
         buf, env = self.buf, self.env

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native as nat
 from .spaces import Box
+from .vec_base import BatchedEnv
 
 
 def action_norm_vector(price0):
@@ -21,20 +22,22 @@ def action_norm_vector(price0):
     return np.asarray(out) * 10000
 
 
-class VecCryptoEnv:
+class VecCryptoEnv(BatchedEnv):
     """E parallel CryptoEnv.  Constructor mirrors the reference: ``config`` holds
     ``price_array`` [T,N] and ``tech_array`` [T,W] (float64)."""
 
     env_name = "MulticryptoEnv-MI355X"
     if_discrete = False
     target_return = 10
+    _kind = "crypto"
+    _panel_cls, _state_cls = nat.CryptoPanelPtrs, nat.CryptoStatePtrs
+    _layout = {"f64": (nat.CRYPTO_F64_FIELDS, ()), "i32": (nat.CRYPTO_I32_FIELDS, ()),
+               "f32": ((), ("stocks",))}
 
     def __init__(self, config, num_envs, *, lookback=1, initial_capital=1e6, buy_cost_pct=1e-3,
                  sell_cost_pct=1e-3, gamma=0.99, auto_reset=True, device="cuda"):
         import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FinenvError("finrl_amd has no CPU path: device must be a HIP GPU")
+        self._set_device(device)
         self.price_array = np.ascontiguousarray(config["price_array"], dtype=np.float64)
         self.tech_array = np.ascontiguousarray(config["tech_array"], dtype=np.float64)
         T, N = self.price_array.shape
@@ -52,66 +55,21 @@ class VecCryptoEnv:
         self.action_norm_vector = action_norm_vector(self.price_array[0])
         self.observation_space = Box(-3000, 3000, (self.obs_dim,), np.float32)
         self.action_space = Box(-1, 1, (N,), np.float32)
-        L = nat.lib()
-        self._cfg = nat.CryptoConfig(E, N, W, T, lookback, 0, float(initial_capital),
-                                     float(buy_cost_pct), float(sell_cost_pct), float(gamma))
-        self._h = C.c_void_p()
-        nat.check(L.finenv_crypto_create(C.byref(self._cfg), C.byref(self._h)), None,
-                  "finenv_crypto_create")
+        self._open(nat.CryptoConfig(E, N, W, T, lookback, 0, float(initial_capital),
+                                    float(buy_cost_pct), float(sell_cost_pct), float(gamma)))
         dev = self.device
         self._price = torch.from_numpy(self.price_array).to(dev)
         self._tech = torch.from_numpy((self.tech_array * 2 ** -15).astype(np.float32)).to(dev)
         self._norm = torch.from_numpy(np.ascontiguousarray(self.action_norm_vector)).to(dev)
-        self._f64 = torch.zeros(len(nat.CRYPTO_F64_FIELDS), E, dtype=torch.float64, device=dev)
-        self._i32 = torch.zeros(len(nat.CRYPTO_I32_FIELDS), E, dtype=torch.int32, device=dev)
-        self._stocks = torch.zeros(N, E, dtype=torch.float32, device=dev)
-        self.state = {k: self._f64[j] for j, k in enumerate(nat.CRYPTO_F64_FIELDS)}
-        self.state.update({k: self._i32[j] for j, k in enumerate(nat.CRYPTO_I32_FIELDS)})
-        self.state["stocks"] = self._stocks
+        self._alloc_state(E, N)
         self.state["cash"].fill_(float(initial_capital))                         # __init__ :26-35
         self.state["total_asset"].fill_(float(initial_capital))
         self.state["time"].fill_(lookback - 1)
-        pp = nat.CryptoPanelPtrs(self._price.data_ptr(), self._tech.data_ptr(),
-                                 self._norm.data_ptr())
-        sp = nat.CryptoStatePtrs(self._f64.data_ptr(), self._i32.data_ptr(),
-                                 self._stocks.data_ptr())
-        nat.check(L.finenv_crypto_bind(self._h, C.byref(pp), C.byref(sp)), self._h, "bind",
-                  "crypto")
-        self.obs = torch.zeros(E, self.obs_dim, dtype=torch.float32, device=dev)
-        self.reward = torch.zeros(E, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(E, dtype=torch.uint8, device=dev)
-        self.term_obs = None
-
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                nat.lib().finenv_crypto_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._bind(self._price, self._tech, self._norm)
+        self._alloc_outputs(E, self.obs_dim)
 
     def close(self):
         pass
-
-    def enable_terminal_obs(self):
-        import torch
-        if self.term_obs is None:
-            self.term_obs = torch.zeros_like(self.obs)
-        return self.term_obs
-
-    def reset(self, mask=None):
-        import torch
-        mptr = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mptr = C.c_void_p(mask.data_ptr())
-        nat.check(nat.lib().finenv_crypto_reset(self._h, mptr, C.c_void_p(self.obs.data_ptr()),
-                                                self._stream()), self._h, "reset", "crypto")
-        return self.obs
 
     supports_record = True      # step(..., record=...) stores the policy's outputs in the same launch
 
@@ -122,46 +80,28 @@ class VecCryptoEnv:
         record=(values, log_probs, actions_out, values_out, log_probs_out): also copy this step's
         policy outputs into the rollout tensors, in the same launch (finenv_crypto_step_record;
         contiguous float32, 16-byte aligned, E % 4 == 0 -- else use RolloutBuffer.put)."""
+        if record is None:
+            return super().step(actions, out)
         import torch
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or \
-                actions.device != self.obs.device:
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        actions = self._actions(actions)
         obs, rew, done = out if out is not None else (self.obs, self.reward, self.done)
-        if record is not None:
-            v, lp, a_out, v_out, lp_out = record
-            for t_ in (v, lp, a_out, v_out, lp_out):
-                if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != self.obs.device:
-                    raise ValueError("record tensors must be contiguous float32 on the env's device")
-            if a_out.numel() != actions.numel() or v.numel() != self.num_envs or \
-                    lp.numel() != self.num_envs or v_out.numel() != self.num_envs or \
-                    lp_out.numel() != self.num_envs:
-                raise ValueError("record: expected values / log_probs [E] and actions_out [E, N]")
-            nat.check(nat.lib().finenv_crypto_step_record(
-                self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-                C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-                C.c_void_p(self.term_obs.data_ptr()) if self.term_obs is not None else None,
-                int(self.auto_reset), C.c_void_p(v.data_ptr()), C.c_void_p(lp.data_ptr()),
-                C.c_void_p(a_out.data_ptr()), C.c_void_p(v_out.data_ptr()),
-                C.c_void_p(lp_out.data_ptr()), self._stream()), self._h, "step_record", "crypto")
-            return obs, rew, done, None
-        nat.check(nat.lib().finenv_crypto_step(
-            self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-            C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-            C.c_void_p(self.term_obs.data_ptr()) if self.term_obs is not None else None,
-            int(self.auto_reset), self._stream()), self._h, "step", "crypto")
+        v, lp, a_out, v_out, lp_out = record
+        for t_ in (v, lp, a_out, v_out, lp_out):
+            if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != self.obs.device:
+                raise ValueError("record tensors must be contiguous float32 on the env's device")
+        if a_out.numel() != actions.numel() or v.numel() != self.num_envs or \
+                lp.numel() != self.num_envs or v_out.numel() != self.num_envs or \
+                lp_out.numel() != self.num_envs:
+            raise ValueError("record: expected values / log_probs [E] and actions_out [E, N]")
+        self._call("step_record", C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
+                   C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
+                   C.c_void_p(self.term_obs.data_ptr()) if self.term_obs is not None else None,
+                   int(self.auto_reset), C.c_void_p(v.data_ptr()), C.c_void_p(lp.data_ptr()),
+                   C.c_void_p(a_out.data_ptr()), C.c_void_p(v_out.data_ptr()),
+                   C.c_void_p(lp_out.data_ptr()), self._stream())
         return obs, rew, done, None
-
-    def as_sb3_vec_env(self):
-        """stable-baselines3 VecEnv-shaped view (numpy in / out, auto-reset, terminal_observation)."""
-        from .vec_env import SB3VecEnvAdapter
-        return SB3VecEnvAdapter(self)
 
     def episode_return(self):
         """total_asset / initial cash of each env's last finished episode (:89), f32."""
         import torch
         return self.state["episode_return"].to(torch.float32)
-
-    def state_numpy(self):
-        out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
-        out["stocks"] = np.ascontiguousarray(out["stocks"].T)
-        return out

@@ -12,13 +12,13 @@ only owns the torch tensors that back the state and hands their pointers over.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _native as nat
 from .panel import StockPanel
 from .spaces import Box
+from .vec_base import BatchedEnv
 
 
 def _torch():
@@ -26,34 +26,19 @@ def _torch():
     return torch
 
 
-def _checked_out_pitch(out, obs, reward, done):
-    """Validate step(out=(obs, reward, done)) against the env's own output tensors and return the row
-    pitch (floats) of out[0].  The kernel writes float32 rows of D columns `pitch` floats apart."""
-    o, r, d = out
-    E, D = obs.shape
-    for t, ref, what in ((o, obs, "out[0]"), (r, reward, "out[1]"), (d, done, "out[2]")):
-        if t.dtype != ref.dtype or t.device != ref.device or tuple(t.shape) != tuple(ref.shape):
-            raise ValueError(f"{what} must be {tuple(ref.shape)} {ref.dtype} on {ref.device}")
-    if o.stride(-1) != 1 or not r.is_contiguous() or not d.is_contiguous():
-        raise ValueError("out[0] needs unit column stride; out[1] / out[2] must be contiguous")
-    if E == 1:                  # (torch reports an arbitrary row stride for a single row)
-        return D
-    if o.stride(0) < D:
-        raise ValueError("out[0]: rows overlap (row stride smaller than the observation dimension)")
-    return o.stride(0)
+class _EpisodeWindows(BatchedEnv):
+    """Per-env episode windows and the last-episode latch of a panel-driven batch: the host side
+    shared by VecStockTradingEnv and VecStockPortfolioEnv (``num_envs``, ``panel.T`` and
+    ``max_step`` are theirs).  ``_last_fields`` is the kind's last-episode block layout,
+    ``_last_ratio`` its (begin, end) fields and ``last_episode_keys`` the last_episode_stats()
+    columns."""
 
-
-class _EpisodeWindows:
-    """Per-env episode windows of a panel-driven batch: the host side shared by VecStockTradingEnv and
-    VecStockPortfolioEnv (``num_envs``, ``panel.T``, ``device`` and ``max_step`` are theirs).
-    ``_kind`` names the C ABI family whose ``finenv_<kind>_set_windows`` takes the block."""
-
-    _kind = "stock"
     windows = None
+    _last = _last_stats = last_episode = None
+    _last_fields, _last_ratio, last_episode_keys = (), ("", ""), ()
 
     def _attach_windows(self, ptr):
-        nat.check(getattr(nat.lib(), f"finenv_{self._kind}_set_windows")(self._h, ptr), self._h,
-                  "set_windows", self._kind)
+        self._call("set_windows", ptr)
 
     def _check_windows(self, start, end):
         """Host validation of (start, end) -> two int64 [E] arrays (ValueError when a window is empty
@@ -127,6 +112,49 @@ class _EpisodeWindows:
             self.max_step = int((self.windows[1] - self.windows[0]).max().item()) - 1
         return self.windows
 
+    def _init_last(self, last):
+        """Hook: edit a new last-episode block before it is attached."""
+
+    def enable_last_episode(self):
+        """Attach a last-episode block (finenv_<kind>_set_last_episode): from now on the step that
+        reports done latches the finished episode's summary -- before an auto-reset replaces the
+        state -- into a caller-owned f64 [_last_fields, E] device tensor, returned here and viewed
+        by name in ``self.last_episode``.  ``count`` starts at 0 and every other field at NaN.
+        Idempotent: a second call returns the same tensor.  The block's pointer is a step-kernel
+        argument, so a step captured into a graph writes the block only if it was enabled before
+        the capture."""
+        torch = _torch()
+        if self._last is None:
+            last = torch.full((len(self._last_fields), self.num_envs), float("nan"),
+                              dtype=torch.float64, device=self.device)
+            last[0].zero_()
+            self._init_last(last)
+            self._call("set_last_episode", C.c_void_p(last.data_ptr()))
+            self._last = last
+            self.last_episode = {k: last[j] for j, k in enumerate(self._last_fields)}
+        return self._last
+
+    def last_episode_stats(self):
+        """``last_episode_keys`` of each env's last FINISHED episode -> f64 [E, len(keys)] device
+        tensor (rows of envs that have not finished one yet are NaN).  Needs enable_last_episode()."""
+        torch = _torch()
+        if self._last is None:
+            raise nat.FinenvError("last_episode_stats: call enable_last_episode() first")
+        if self._last_stats is None:
+            self._last_stats = torch.zeros(self.num_envs, len(self.last_episode_keys),
+                                           dtype=torch.float64, device=self.device)
+        self._call("last_episode_stats", C.c_void_p(self._last_stats.data_ptr()), self._stream())
+        return self._last_stats
+
+    def last_episode_return(self):
+        """end / begin total asset of each env's last finished episode, f32 [E] (NaN where none has
+        finished): what episode_return() reports for the current episode, for the one an auto-reset
+        has already replaced -- the quantity to gather across ranks."""
+        if self._last is None:
+            raise nat.FinenvError("last_episode_return: call enable_last_episode() first")
+        begin, end = self._last_ratio
+        return (self.last_episode[end] / self.last_episode[begin]).to(_torch().float32)
+
 
 class VecStockTradingEnv(_EpisodeWindows):
     """E parallel copies of the reference ``StockTradingEnv`` (env_stocktrading.py:19-552).
@@ -152,6 +180,19 @@ class VecStockTradingEnv(_EpisodeWindows):
     last_episode_keys = ("begin_total_asset", "end_total_asset", "total_reward", "total_cost",
                          "total_trades", "sharpe")
 
+    _kind = "stock"
+    _panel_cls, _state_cls = nat.StockPanelPtrs, nat.StockStatePtrs
+    # two [field][E] blocks (include/finenv.h); holdings and shares0 are [N][E] books of the i32 one
+    _layout = {"f64": (nat.STOCK_F64_FIELDS, ()),
+               "i32": (nat.STOCK_I32_FIELDS, ("holdings", "shares0"))}
+    _step_extras = ("term_obs", "realised")
+    _pitched = True
+    _last_fields, _last_ratio = nat.STOCK_LAST_FIELDS, ("begin_asset", "end_asset")
+    _stats = None
+    # the stock env's own names of its two state blocks, kept for code that reads them
+    _state_f64 = property(lambda self: self._f64)
+    _state_i32 = property(lambda self: self._i32)
+
     def __init__(self, panel: StockPanel, num_envs: int, *, hmax=100,
                  initial_amount=1_000_000, num_stock_shares=None, buy_cost_pct=1e-3,
                  sell_cost_pct=1e-3, reward_scaling=1e-4, turbulence_threshold=None,
@@ -162,9 +203,7 @@ class VecStockTradingEnv(_EpisodeWindows):
             # the fork's own env raises TypeError on list costs
             raise TypeError("buy_cost_pct / sell_cost_pct must be scalars in this fork")
         self.panel = panel
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FinenvError("finrl_amd has no CPU path: device must be a HIP GPU")
+        self._set_device(device)
         E, N, K, T = int(num_envs), panel.N, panel.K, panel.T
         self.num_envs = self.env_num = E
         self.stock_dim = self.action_dim = N
@@ -177,70 +216,25 @@ class VecStockTradingEnv(_EpisodeWindows):
         self.observation_space = Box(-np.inf, np.inf, (panel.D,), np.float32)
         self.action_space = Box(-1.0, 1.0, (N,), np.float32)
 
-        self._cfg = nat.StockConfig(
+        self._open(nat.StockConfig(
             E, N, K, T, self.hmax, int(turbulence_threshold is not None), int(bool(reset_quirk)),
             int(bool(initial)), int(bool(track_stats)),
             int(N == 1),      # one ticker in the frame: the reference's single-stock branches (:415-422)
             float(buy_cost_pct),
             float(sell_cost_pct), float(reward_scaling),
-            float(turbulence_threshold) if turbulence_threshold is not None else 0.0)
-        L = nat.lib()
-        self._h = C.c_void_p()
-        nat.check(L.finenv_stock_create(C.byref(self._cfg), C.byref(self._h)), None,
-                  "finenv_stock_create")
-
-        dev = self.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
+            float(turbulence_threshold) if turbulence_threshold is not None else 0.0))
         cash0 = np.broadcast_to(np.asarray(initial_amount, dtype=np.float64), (E,))
         if num_stock_shares is None:
             num_stock_shares = np.zeros(N, dtype=np.int64)
         sh0 = np.broadcast_to(np.asarray(num_stock_shares, dtype=np.int64), (E, N))
-        # two [field][E] blocks (include/finenv.h); self.state holds named views into them
-        nf, ni = len(nat.STOCK_F64_FIELDS), len(nat.STOCK_I32_FIELDS)
-        self._state_f64 = torch.zeros(nf, E, **f64)
-        self._state_i32 = torch.zeros(ni + 2 * N, E, **i32)
-        self.state = {k: self._state_f64[j] for j, k in enumerate(nat.STOCK_F64_FIELDS)}
-        self.state.update({k: self._state_i32[j] for j, k in enumerate(nat.STOCK_I32_FIELDS)})
-        self.state["holdings"] = self._state_i32[ni:ni + N]
-        self.state["shares0"] = self._state_i32[ni + N:ni + 2 * N]
+        self._alloc_state(E, N)
         self.state["cash0"].copy_(torch.from_numpy(np.array(cash0, dtype=np.float64)))
         self.state["shares0"].copy_(torch.from_numpy(np.ascontiguousarray(sh0.T).astype(np.int32)))
-        self._panel_t = panel.to_device(dev)
-        pp = nat.StockPanelPtrs(*(self._panel_t[k].data_ptr()
-                                  for k in ("close", "obs_tmpl", "risk")))
-        sp = nat.StockStatePtrs(self._state_f64.data_ptr(), self._state_i32.data_ptr())
-        nat.check(L.finenv_stock_bind(self._h, C.byref(pp), C.byref(sp)), self._h, "bind")
-
-        # Observation rows: `obs` is a [E, D] view of a buffer whose rows start on 64-byte boundaries
-        # (pitch = D rounded up to 16 floats) unless obs_pitch="packed" / an explicit pitch is given:
-        # packed rows of 4*D bytes share their first and last 64-byte segment with a neighbour row
-        # written microseconds apart -- two partial HBM writes instead of one.
-        # Values and shape are the reference's; only the row stride differs (obs.stride(0)).
-        if obs_pitch is None:
-            obs_pitch = os.environ.get("FINENV_OBS_PITCH", "aligned")
-        if obs_pitch == "aligned":
-            pitch = (panel.D + 15) // 16 * 16
-        elif obs_pitch == "packed":
-            pitch = panel.D
-        else:
-            pitch = int(obs_pitch)
-            if pitch < panel.D:
-                raise ValueError("obs_pitch must be >= the observation dimension")
-        self._obs_buf = torch.zeros(E, pitch, dtype=torch.float32, device=dev)
-        self.obs = self._obs_buf[:, :panel.D]
-        self._pitch = self._pitch_set = pitch
-        nat.check(L.finenv_stock_set_obs_pitch(self._h, pitch), self._h, "set_obs_pitch")
-        self.reward = torch.zeros(E, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(E, dtype=torch.uint8, device=dev)
-        self.term_obs = None
-        self.realised = None
-        self._step_args = None
-        self._stats = None
-        self._last = None
-        self._last_stats = None
-        self.last_episode = None
-        self.windows = None
+        self._panel_t = panel.to_device(self.device)
+        self._bind(*(self._panel_t[k] for k in ("close", "obs_tmpl", "risk")))
+        # obs rows start on 64-byte boundaries unless obs_pitch="packed" / an explicit pitch is
+        # given (vec_base.obs_pitch_for)
+        self._alloc_outputs(E, panel.D, obs_pitch)
         self._day0 = int(day)
         if windows is not None:
             start, end = windows
@@ -249,48 +243,9 @@ class VecStockTradingEnv(_EpisodeWindows):
                 raise ValueError(f"day={day} does not fit the shortest window "
                                  f"({int((t_np - s_np).min())} days)")
             self.set_windows(s_np, t_np)
-        nat.check(L.finenv_stock_init(self._h, int(day), self._stream()), self._h, "init")
+        self._call("init", int(day), self._stream())
 
-    # ------------------------------------------------------------------ plumbing
-    def _stream(self):
-        torch = _torch()
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                nat.lib().finenv_stock_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    close = __del__
-
-    def enable_terminal_obs(self):
-        torch = _torch()
-        if self.term_obs is None:
-            self.term_obs = torch.zeros(self.num_envs, self.state_dim, dtype=torch.float32,
-                                        device=self.device)
-        return self.term_obs
-
-    def enable_last_episode(self):
-        """Attach a last-episode block (finenv_stock_set_last_episode): from now on the step that
-        reports done latches the finished episode's summary -- before an auto-reset replaces the
-        state -- into a caller-owned f64 [FINENV_STOCK_LAST_FIELDS, E] device tensor, returned here
-        and viewed by name in ``self.last_episode``.  ``count`` starts at 0 and every other field
-        at NaN.  Idempotent: a second call returns the same tensor.  The block's pointer is a
-        step-kernel argument, so a step captured into a graph writes the block only if it was
-        enabled before the capture."""
-        torch = _torch()
-        if self._last is None:
-            last = torch.full((len(nat.STOCK_LAST_FIELDS), self.num_envs), float("nan"),
-                              dtype=torch.float64, device=self.device)
-            last[0].zero_()
-            nat.check(nat.lib().finenv_stock_set_last_episode(self._h, C.c_void_p(last.data_ptr())),
-                      self._h, "set_last_episode")
-            self._last = last
-            self.last_episode = {k: last[j] for j, k in enumerate(nat.STOCK_LAST_FIELDS)}
-        return self._last
+    close = BatchedEnv.__del__
 
     def window_day(self):
         """The reference's ``self.day`` of every env (int32 [E] device tensor): ``state["day"]`` minus
@@ -304,87 +259,24 @@ class VecStockTradingEnv(_EpisodeWindows):
         """Performance hint (results never depend on it): the envs of this batch sit on different
         days -- per-env start days, staggered episode ends, windows with different starts.  Selects
         the step-kernel instantiation tuned for per-env panel rows (finenv_stock_set_desync_hint)."""
-        nat.check(nat.lib().finenv_stock_set_desync_hint(self._h, int(bool(on))), self._h,
-                  "set_desync_hint")
-
-    def _use_pitch(self, pitch):
-        if pitch != self._pitch_set:
-            nat.check(nat.lib().finenv_stock_set_obs_pitch(self._h, int(pitch)), self._h,
-                      "set_obs_pitch")
-            self._pitch_set = pitch
+        self._call("set_desync_hint", int(bool(on)))
 
     def enable_realised(self):
-        torch = _torch()
-        if self.realised is None:
-            self.realised = torch.zeros(self.num_envs, self.stock_dim, dtype=torch.int32,
-                                        device=self.device)
-        return self.realised
+        return self._enable_output("realised", self.stock_dim, _torch().int32)
 
     # ------------------------------------------------------------------ env protocol
-    def reset(self, mask=None):
-        """reset() (:359-393) for all envs (or mask[e] != 0) -> obs [E, D] f32 (device)."""
-        L = nat.lib()
-        mptr = None
-        if mask is not None:
-            torch = _torch()
-            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mptr = C.c_void_p(mask.data_ptr())
-        self._use_pitch(self._pitch)
-        nat.check(L.finenv_stock_reset(self._h, mptr, C.c_void_p(self.obs.data_ptr()),
-                                       self._stream()), self._h, "reset")
-        return self.obs
-
+    # reset() (:359-393) and step() (:220-357) are BatchedEnv's
     def refresh(self):
         """Call after editing ``state["cash"]`` / ``state["holdings"]`` / ``state["price_day"]`` in
         place: re-evaluates the carried begin asset (``state["begin_asset"]``) that ``step`` uses
         for the next reward instead of recomputing it (finenv_stock_refresh)."""
-        nat.check(nat.lib().finenv_stock_refresh(self._h, self._stream()), self._h, "refresh")
+        self._call("refresh", self._stream())
 
     def observe(self):
         """render() (:395-396): current observation without stepping."""
         self._use_pitch(self._pitch)
-        nat.check(nat.lib().finenv_stock_observe(self._h, C.c_void_p(self.obs.data_ptr()),
-                                                 self._stream()), self._h, "observe")
+        self._call("observe", C.c_void_p(self.obs.data_ptr()), self._stream())
         return self.obs
-
-    def step(self, actions, out=None):
-        """One step() (:220-357) for every env, asynchronously on the current stream.
-
-        actions: float32 [E, N] CUDA tensor.  Returns (obs, reward, done, info) where the
-        first three are views of persistent device tensors, overwritten by the next call
-        (clone them to keep).  No host synchronisation happens here.
-        out = (obs [E, D] f32, reward [E] f32, done [E] u8): write there instead (rollout
-        buffers: the kernel writes straight into slice t, no staging copy).
-        """
-        torch = _torch()
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or \
-                actions.device != self.obs.device or \
-                tuple(actions.shape) != (self.num_envs, self.stock_dim):
-            actions = actions.to(device=self.device, dtype=torch.float32).reshape(
-                self.num_envs, self.stock_dim).contiguous()
-        # the pointers of the persistent output tensors are cached (the Python side of a launch
-        # costs more than half of the ~13 us a step call takes on the host)
-        key = (self.term_obs is not None, self.realised is not None)
-        if self._step_args is None or self._step_args[0] != key:
-            self._step_args = (key, nat.lib().finenv_stock_step, (
-                C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
-                C.c_void_p(self.done.data_ptr()),
-                C.c_void_p(self.term_obs.data_ptr()) if self.term_obs is not None else None,
-                C.c_void_p(self.realised.data_ptr()) if self.realised is not None else None))
-        _, fn, outs = self._step_args
-        ret = (self.obs, self.reward, self.done)
-        if out is not None:
-            ret = out
-            self._use_pitch(_checked_out_pitch(out, self.obs, self.reward, self.done))
-            outs = (C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
-                    C.c_void_p(out[2].data_ptr())) + outs[3:]
-        elif self._pitch_set != self._pitch:
-            self._use_pitch(self._pitch)
-        rc = fn(self._h, C.c_void_p(actions.data_ptr()), *outs, int(self.auto_reset),
-                self._stream())
-        if rc:
-            nat.check(rc, self._h, "step")
-        return ret[0], ret[1], ret[2], None
 
     # ------------------------------------------------------------------ introspection
     def episode_stats(self):
@@ -393,8 +285,7 @@ class VecStockTradingEnv(_EpisodeWindows):
         torch = _torch()
         if self._stats is None:
             self._stats = torch.zeros(self.num_envs, 6, dtype=torch.float64, device=self.device)
-        nat.check(nat.lib().finenv_stock_episode_stats(
-            self._h, C.c_void_p(self._stats.data_ptr()), self._stream()), self._h, "stats")
+        self._call("episode_stats", C.c_void_p(self._stats.data_ptr()), self._stream(), what="stats")
         return self._stats
 
     def total_asset(self):
@@ -405,38 +296,12 @@ class VecStockTradingEnv(_EpisodeWindows):
         st = self.episode_stats()
         return (st[:, 1] / st[:, 0]).to(_torch().float32)
 
-    def last_episode_stats(self):
-        """episode_stats() columns of each env's last FINISHED episode -> f64 [E, 6] device tensor
-        (rows of envs that have not finished one yet are NaN).  Needs enable_last_episode()."""
-        torch = _torch()
-        if self._last is None:
-            raise nat.FinenvError("last_episode_stats: call enable_last_episode() first")
-        if self._last_stats is None:
-            self._last_stats = torch.zeros(self.num_envs, 6, dtype=torch.float64, device=self.device)
-        nat.check(nat.lib().finenv_stock_last_episode_stats(
-            self._h, C.c_void_p(self._last_stats.data_ptr()), self._stream()), self._h,
-            "last_episode_stats")
-        return self._last_stats
-
-    def last_episode_return(self):
-        """end_total_asset / begin_total_asset of each env's last finished episode, f32 [E] (NaN
-        where none has finished): what episode_return() reports for the current episode, for the
-        one an auto-reset has already replaced -- the quantity to gather across ranks."""
-        if self._last is None:
-            raise nat.FinenvError("last_episode_return: call enable_last_episode() first")
-        le = self.last_episode
-        return (le["end_asset"] / le["begin_asset"]).to(_torch().float32)
-
     def state_numpy(self):
         """Host copy of the per-env state (synchronises)."""
-        out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
+        out = super().state_numpy()
         out["window_day"] = self.window_day().cpu().numpy()
-        out["shares"] = np.ascontiguousarray(out.pop("holdings").T)
-        out["shares0"] = np.ascontiguousarray(out["shares0"].T)
+        out["shares"] = out.pop("holdings")
         return out
-
-    def as_sb3_vec_env(self):
-        return SB3VecEnvAdapter(self)
 
 
 class SB3VecEnvAdapter:

@@ -3,13 +3,11 @@
 one HIP launch per step through the C ABI (finenv_stocknp_*)."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-
 import numpy as np
 
 from . import _native as nat
 from .spaces import Box
+from .vec_base import BatchedEnv
 
 TAG_PY, TAG_F32, TAG_F64 = 0, 1, 2
 
@@ -28,22 +26,25 @@ def derive_arrays(price_array, tech_array, turbulence_array, turbulence_thresh=9
     return price, tech, turb_ary, turb_bool
 
 
-class VecStockTradingEnvNP:
+class VecStockTradingEnvNP(BatchedEnv):
     """E parallel copies; constructor mirrors the reference (``config`` dict with
     price_array / tech_array / turbulence_array / if_train)."""
 
     env_name = "StockEnv-MI355X"
     if_discrete = False
     target_return = 10.0
+    _kind = "stocknp"
+    _panel_cls, _state_cls = nat.StockNpPanelPtrs, nat.StockNpStatePtrs
+    _layout = {"f64": (nat.STOCKNP_F64_FIELDS, ()), "i32": (nat.STOCKNP_I32_FIELDS, ()),
+               "f32": ((), ("stocks", "cool_down", "stocks0"))}
+    _pitched = True
 
     def __init__(self, config, num_envs, *, gamma=0.99, turbulence_thresh=99, min_stock_rate=0.1,
                  max_stock=1e2, initial_capital=1e6, buy_cost_pct=1e-3, sell_cost_pct=1e-3,
                  reward_scaling=2 ** -11, initial_stocks=None, auto_reset=True, device="cuda",
                  seed=0, obs_amount_floor=0.0, obs_pitch=None):
         import torch
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise nat.FinenvError("finrl_amd has no CPU path: device must be a HIP GPU")
+        self._set_device(device)
         price, tech, turb_ary, turb_bool = derive_arrays(
             config["price_array"], config["tech_array"], config["turbulence_array"],
             turbulence_thresh)
@@ -65,13 +66,9 @@ class VecStockTradingEnvNP:
             np.asarray(initial_stocks, np.float32)
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(seed)
-        L = nat.lib()
-        self._cfg = nat.StockNpConfig(E, N, W, T, int(max_stock * min_stock_rate), 0,
-                                      float(max_stock), float(buy_cost_pct), float(sell_cost_pct),
-                                      float(reward_scaling), float(gamma), float(obs_amount_floor))
-        self._h = C.c_void_p()
-        nat.check(L.finenv_stocknp_create(C.byref(self._cfg), C.byref(self._h)), None,
-                  "finenv_stocknp_create")
+        self._open(nat.StockNpConfig(E, N, W, T, int(max_stock * min_stock_rate), 0,
+                                     float(max_stock), float(buy_cost_pct), float(sell_cost_pct),
+                                     float(reward_scaling), float(gamma), float(obs_amount_floor)))
         D = self.state_dim
         tmpl = np.zeros((T, D), np.float32)
         tmpl[:, 1] = turb_ary
@@ -82,35 +79,11 @@ class VecStockTradingEnvNP:
         self._price = torch.from_numpy(np.ascontiguousarray(price)).to(dev)
         self._tmpl = torch.from_numpy(tmpl).to(dev)
         self._tbool = torch.from_numpy(np.ascontiguousarray(turb_bool)).to(dev)
-        self._f64 = torch.zeros(len(nat.STOCKNP_F64_FIELDS), E, dtype=torch.float64, device=dev)
-        self._i32 = torch.zeros(len(nat.STOCKNP_I32_FIELDS), E, dtype=torch.int32, device=dev)
-        self._f32 = torch.zeros(3 * N, E, dtype=torch.float32, device=dev)
-        self.state = {k: self._f64[j] for j, k in enumerate(nat.STOCKNP_F64_FIELDS)}
-        self.state.update({k: self._i32[j] for j, k in enumerate(nat.STOCKNP_I32_FIELDS)})
-        self.state["stocks"] = self._f32[0:N]
-        self.state["cool_down"] = self._f32[N:2 * N]
-        self.state["stocks0"] = self._f32[2 * N:3 * N]
+        self._alloc_state(E, N)
         self.set_start_state(self.initial_stocks, float(initial_capital), TAG_PY)
-        pp = nat.StockNpPanelPtrs(self._price.data_ptr(), self._tmpl.data_ptr(),
-                                  self._tbool.data_ptr())
-        sp = nat.StockNpStatePtrs(self._f64.data_ptr(), self._i32.data_ptr(),
-                                  self._f32.data_ptr())
-        nat.check(L.finenv_stocknp_bind(self._h, C.byref(pp), C.byref(sp)), self._h, "bind",
-                  "stocknp")
-        # obs: [E, D] view of a buffer whose rows start on 64-byte boundaries (see
-        # VecStockTradingEnv: packed rows share 64-byte segments that are then written twice)
-        if obs_pitch is None:
-            obs_pitch = os.environ.get("FINENV_OBS_PITCH", "aligned")
-        pitch = (D + 15) // 16 * 16 if obs_pitch == "aligned" else (D if obs_pitch == "packed" else int(obs_pitch))
-        if pitch < D:
-            raise ValueError("obs_pitch must be >= the observation dimension")
-        self._obs_buf = torch.zeros(E, pitch, dtype=torch.float32, device=dev)
-        self.obs = self._obs_buf[:, :D]
-        self._pitch = self._pitch_set = pitch
-        nat.check(L.finenv_stocknp_set_obs_pitch(self._h, pitch), self._h, "set_obs_pitch", "stocknp")
-        self.reward = torch.zeros(E, dtype=torch.float32, device=dev)
-        self.done = torch.zeros(E, dtype=torch.uint8, device=dev)
-        self.term_obs = None
+        self._bind(self._price, self._tmpl, self._tbool)
+        # obs: [E, D] view of a buffer whose rows start on 64-byte boundaries (vec_base.obs_pitch_for)
+        self._alloc_outputs(E, D, obs_pitch)
 
     def set_start_state(self, stocks0, amount0, amount0_tag):
         """Per-env state that reset() restores: stocks0 [N] or [E,N], amount0 scalar or [E],
@@ -137,66 +110,9 @@ class VecStockTradingEnvNP:
         self.state["amount0"].copy_(amount.to(torch.float64))
         self.state["amount0_tag"].fill_(TAG_F32)
 
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                nat.lib().finenv_stocknp_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def enable_terminal_obs(self):
-        import torch
-        if self.term_obs is None:
-            self.term_obs = torch.zeros(self.num_envs, self.obs.shape[1], dtype=torch.float32,
-                                        device=self.device)
-        return self.term_obs
-
-    def _use_pitch(self, pitch):
-        if pitch != self._pitch_set:
-            nat.check(nat.lib().finenv_stocknp_set_obs_pitch(self._h, int(pitch)), self._h,
-                      "set_obs_pitch", "stocknp")
-            self._pitch_set = pitch
-
-    def reset(self, mask=None):
-        import torch
+    def _before_reset(self):
         if self.if_train:
             self._draw_train_start()
-        mptr = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            mptr = C.c_void_p(mask.data_ptr())
-        self._use_pitch(self._pitch)
-        nat.check(nat.lib().finenv_stocknp_reset(self._h, mptr, C.c_void_p(self.obs.data_ptr()),
-                                                 self._stream()), self._h, "reset", "stocknp")
-        return self.obs
-
-    def step(self, actions, out=None):
-        import torch
-        if actions.dtype != torch.float32 or not actions.is_contiguous() or \
-                actions.device != self.obs.device:
-            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        obs, rew, done = out if out is not None else (self.obs, self.reward, self.done)
-        if out is not None:
-            from .vec_env import _checked_out_pitch
-            self._use_pitch(_checked_out_pitch(out, self.obs, self.reward, self.done))
-        else:
-            self._use_pitch(self._pitch)
-        nat.check(nat.lib().finenv_stocknp_step(
-            self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(obs.data_ptr()),
-            C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()),
-            C.c_void_p(self.term_obs.data_ptr()) if self.term_obs is not None else None,
-            int(self.auto_reset), self._stream()), self._h, "step", "stocknp")
-        return obs, rew, done, None
-
-    def as_sb3_vec_env(self):
-        """stable-baselines3 VecEnv-shaped view (numpy in / out, auto-reset, terminal_observation)."""
-        from .vec_env import SB3VecEnvAdapter
-        return SB3VecEnvAdapter(self)
 
     def episode_return(self):
         """total_asset / initial_total_asset of each env's last finished episode (:145), f32."""
@@ -204,9 +120,7 @@ class VecStockTradingEnvNP:
         return self.state["episode_return"].to(torch.float32)
 
     def state_numpy(self):
-        out = {k: v.detach().cpu().numpy() for k, v in self.state.items()}
-        for k in ("stocks", "cool_down", "stocks0"):
-            out[k] = np.ascontiguousarray(out[k].T)
+        out = super().state_numpy()
         t = out["tags"]
         out["amount_tag"], out["ta_tag"], out["g_tag"] = t & 3, (t >> 2) & 3, (t >> 4) & 3
         out["reward_tag"] = (t >> 8) & 3

@@ -88,3 +88,60 @@ def test_product_never_imports_oracle():
     for line in bench.splitlines():          # every oracle import of bench.py sits in a cpu_baseline leg
         if "from oracle" in line or "import oracle" in line:
             assert line.startswith("    "), line
+
+
+# One valid config per handle kind, the obs_dim it gives, and the entry points that launch work
+# (name, argument count after the handle).  The host contract below holds for every kind alike.
+def _kind_cases():
+    from finrl_amd import _native as nat
+    cash = (64, 4, 3, 50, 0, 1, 0, 0, 10.0, 3e-3, 3e-3, 1e6, 0.1, 0.0)
+    return {
+        "stock": (nat.StockConfig(64, 30, 8, 100, 100, 0, 1, 1, 1, 0, 1e-3, 1e-3, 1e-4, 0.0),
+                  nat.StockPanelPtrs, 301,
+                  (("init", 2), ("reset", 3), ("observe", 2), ("refresh", 1), ("step", 8),
+                   ("episode_stats", 2), ("last_episode_stats", 2))),
+        "portfolio": (nat.PortfolioConfig(64, 5, 4, 50, 1e6), nat.PortfolioPanelPtrs, 45,
+                      (("reset", 3), ("step", 8), ("last_episode_stats", 2))),
+        "crypto": (nat.CryptoConfig(64, 3, 4, 50, 2, 0, 1e6, 1e-3, 1e-3, 0.99),
+                   nat.CryptoPanelPtrs, 12, (("reset", 3), ("step", 7), ("step_record", 12))),
+        "stocknp": (nat.StockNpConfig(64, 5, 7, 50, 10, 0, 100.0, 1e-3, 1e-3, 2 ** -11, 0.99, 0.0),
+                    nat.StockNpPanelPtrs, 25, (("reset", 3), ("step", 7))),
+        "cashpenalty": (nat.CashPenaltyConfig(*cash), nat.CashPenaltyPanelPtrs, 17,
+                        (("reset", 3), ("step", 7))),
+        "stoploss": (nat.StopLossConfig(*cash, 0.9, 1.2), nat.StopLossPanelPtrs, 17,
+                     (("reset", 3), ("step", 7))),
+    }
+
+
+@pytest.mark.parametrize("kind", ["stock", "portfolio", "crypto", "stocknp", "cashpenalty", "stoploss"])
+def test_host_contract_every_kind(L, kind):
+    """Null handles, create / obs_dim, launches before bind and bind with a null state pointer give
+    the same codes and messages in every env's C ABI (no GPU needed: nothing here launches)."""
+    cfg, panel_cls, D, launches = _kind_cases()[kind]
+    fn = lambda name: getattr(L, f"finenv_{kind}_{name}")          # noqa: E731
+
+    def launch(name, h):        # a private function object: the library's own argtypes stay as declared
+        f = L[f"finenv_{kind}_{name}"]
+        nargs = dict(launches)[name]
+        f.argtypes = [C.c_void_p] * (1 + nargs)
+        return f(h, *([None] * nargs))
+
+    assert fn("last_error")(None) == b"null handle"
+    assert fn("obs_dim")(None) == -1
+    for name, _ in launches:
+        assert launch(name, None) == -1, name
+    h = C.c_void_p()
+    assert fn("create")(C.byref(cfg), C.byref(h)) == 0
+    try:
+        assert h.value and fn("obs_dim")(h) == D
+        assert fn("last_error")(h) == b""
+        for name in ("reset", "step"):
+            assert launch(name, h) == -2, name
+            assert b"bind first" in fn("last_error")(h), name
+            assert fn("last_error")(h).startswith(name.encode() + b": "), name
+        panel = panel_cls()
+        assert fn("bind")(h, C.byref(panel), None) == -1
+        assert fn("bind")(None, C.byref(panel), None) == -1
+        assert launch("step", h) == -2                                   # still unbound
+    finally:
+        fn("destroy")(h)

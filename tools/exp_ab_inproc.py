@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """A/B of two builds of libfinenv.so inside ONE process on ONE env: same handle, same device buffers
-(so the same physical placement), only the library that launches the step kernel alternates.
+(so the same physical placement), only the library that launches the step kernel alternates.  The
+handle is created by the base build, so both builds must share the layout of the finenv_<kind> handle
+structs (variants of one source tree always do).
 usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|portfolio-random63|stocknp> [rounds]
   portfolio-random63: the portfolio env with random 63-day episode windows (VecStockPortfolioEnv.set_windows)"""
 import os
@@ -63,8 +65,7 @@ def main():
                     os.environ.pop(v2.split("=")[0], None)
             if envs.get(name):
                 os.environ[envs[name].split("=")[0]] = envs[name].split("=")[1]
-            if hasattr(env, "_step_args"):
-                env._step_args = None            # cached function pointer of the previous library
+            env._step_args = None                # BatchedEnv.step caches the previous library's function
             for i in range(100):
                 env.step(w.pool[i % 8])
             torch.cuda.synchronize()
