@@ -285,7 +285,7 @@ int finenv_riskpre_returns(const double *close, double *returns, int32_t n_days,
 int finenv_riskpre_turbulence(const double *returns, double *quad, double *turbulence,
                               int32_t n_days, int32_t n_assets, int32_t window, void *stream)
 {
-    if (!returns || !quad || !turbulence || n_assets < 2 ||
+    if (!returns || !quad || !turbulence || n_assets < 1 ||
         n_assets > FINENV_RISKPRE_MAX_ASSETS || window < 3 || n_days < window)
         return FINENV_ERR_INVALID;
     const finenv_host::DeviceGuard guard(finenv_host::pointer_device(returns));

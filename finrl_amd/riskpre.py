@@ -31,11 +31,13 @@ def _dev_close(close, device):
         raise nat.FinenvError("finrl_amd has no CPU path: device must be a HIP GPU")
     if isinstance(close, torch.Tensor):
         t = close.to(device=dev, dtype=torch.float64).contiguous()
+        finite = bool(torch.isfinite(t).all())
     else:
         a = np.ascontiguousarray(close, dtype=np.float64)
-        if not np.isfinite(a).all():
-            raise nat.FinenvError("close contains NaN/inf")
+        finite = bool(np.isfinite(a).all())
         t = torch.from_numpy(a).to(dev)
+    if not finite:
+        raise nat.FinenvError("close contains NaN/inf")
     if t.dim() != 2:
         raise nat.FinenvError("close must be [T, N]")
     return t

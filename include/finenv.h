@@ -663,7 +663,8 @@ int finenv_riskpre_returns(const double *close, double *returns, int32_t n_days,
 /* FeatureEngineer.calculate_turbulence (preprocessors.py:215-267): turbulence[t] for all T days
  * (0 for t < window and for the first two positive values, :247-257).  quad: [T] f64 scratch
  * (the unfiltered quadratic forms, :244-246).  Needs n_days >= window (the reference raises
- * otherwise, :260-266) and 2 <= n_assets <= FINENV_RISKPRE_MAX_ASSETS. */
+ * otherwise, :260-266) and 1 <= n_assets <= FINENV_RISKPRE_MAX_ASSETS (one asset: the 1 x 1
+ * covariance, x^2 / var, or 0 where the window's variance is 0, as np.linalg.pinv gives). */
 int finenv_riskpre_turbulence(const double *returns, double *quad, double *turbulence,
                               int32_t n_days, int32_t n_assets, int32_t window, void *stream);
 /* cov_list of the portfolio-allocation tutorial

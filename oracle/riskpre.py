@@ -38,7 +38,8 @@ def turbulence_quadratic_forms(close, window=252):
         hist = r[i - window:i]                                   # :229-232
         lead = int(np.isnan(hist).sum(axis=0).min())             # :234-236
         hist = hist[lead:]
-        cov = np.cov(hist.T, ddof=1)                             # pandas .cov() fast path, :238
+        cov = np.atleast_2d(np.cov(hist.T, ddof=1))              # pandas .cov() fast path, :238
+                                                                 # (1 x 1 for one ticker)
         cur = r[i] - np.mean(hist, axis=0)                       # :239-241
         out[i] = cur.dot(np.linalg.pinv(cov)).dot(cur)           # :244-246
     return out
@@ -70,5 +71,5 @@ def rolling_covariance(close, lookback=252):
     T, N = r.shape
     out = np.empty((max(T - lookback, 0), N, N))
     for i in range(lookback, T):
-        out[i - lookback] = np.cov(r[i - lookback + 1:i + 1].T, ddof=1)
+        out[i - lookback] = np.atleast_2d(np.cov(r[i - lookback + 1:i + 1].T, ddof=1))
     return out

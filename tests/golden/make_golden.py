@@ -756,6 +756,8 @@ RISKPRE_SCENARIOS = {
     "dow30": dict(seed=81, T=300, N=30),
     "small": dict(seed=82, T=280, N=6, sigma=0.02),
     "wide": dict(seed=83, T=262, N=100, common=0.8),
+    # one ticker: 1 x 1 covariance, pinv = 1 / var
+    "n1": dict(seed=84, T=270, N=1),
 }
 
 
