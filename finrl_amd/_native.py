@@ -60,6 +60,17 @@ class StockStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p)]
 
 
+class StockHistoryPtrs(C.Structure):
+    """finenv_stock_history: the episode-history tensors of finenv_stock_set_history."""
+    _fields_ = [("asset", C.c_void_p), ("row", C.c_void_p), ("actions", C.c_void_p),
+                ("len", C.c_void_p), ("flags", C.c_void_p), ("capacity", C.c_int32)]
+
+
+HIST_COMPLETE, HIST_OVERFLOW = 1, 2          # FINENV_HIST_*: bits of the history's flags
+# columns of finenv_stock_history_metrics (FINENV_HM_*)
+STOCK_HISTORY_METRICS = ("n_returns", "cumulative_return", "mean", "std", "sharpe", "max_drawdown")
+
+
 class PortfolioConfig(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("n_tickers", C.c_int32), ("n_tech", C.c_int32),
                 ("n_days", C.c_int32), ("initial_amount", C.c_double)]
@@ -236,6 +247,10 @@ def lib():
                     ("finenv_portfolio_set_windows", 2)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
+    if hasattr(L, "finenv_stock_set_history"):       # episode history (same rule)
+        L.finenv_stock_set_history.argtypes = [C.c_void_p, C.POINTER(StockHistoryPtrs)]
+        L.finenv_stock_history_arm.argtypes = [C.c_void_p] * 3
+        L.finenv_stock_history_metrics.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]

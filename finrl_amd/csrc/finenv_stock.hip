@@ -27,16 +27,45 @@
 
 namespace {
 
+// end_total_asset of env e from its state in memory (:226-228, :344-347): cash + sum_i close * shares,
+// summed sequentially from ticker 0 on the prices of the current observation.  `p` is any argument
+// struct with the state blocks in p.st (the SF / SI / HOLD accessors).  One lane owns the env, so the N
+// (price, shares) pairs are loaded kAssetBatch at a time before the first add of the batch: a rolled
+// load / wait / add loop exposes one memory round trip per ticker (the callers run one wave per SIMD).
+constexpr int kAssetBatch = 16;
+template <typename P>
+__device__ __forceinline__ double end_total_asset(const P &p, const double *close, int E, int N, int e)
+{
+    const double *prow = close + (size_t)SI(FINENV_SI_PRICE_DAY) * N;
+    double s = 0.0;
+    for (int i0 = 0; i0 < N; i0 += kAssetBatch) {
+        double pr[kAssetBatch];
+        int hd[kAssetBatch];
+#pragma unroll
+        for (int j = 0; j < kAssetBatch; ++j) {
+            const int i = min(i0 + j, N - 1);
+            pr[j] = prow[i];
+            hd[j] = HOLD(i);
+        }
+#pragma unroll
+        for (int j = 0; j < kAssetBatch; ++j) {
+            pin(pr[j]);
+            pin(hd[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kAssetBatch; ++j)
+            if (i0 + j < N) s = s + fabs(pr[j]) * (double)hd[j];   // sign bit = flag
+    }
+    return SF(FINENV_SF_CASH) + s;
+}
+
 // Terminal summary :226-264 from current state: one lane per env.
 __global__ void stock_stats_kernel(const Params p)
 {
     const int E = p.cfg.n_envs, N = p.cfg.n_tickers;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    const double *prow = p.panel.close + (size_t)SI(FINENV_SI_PRICE_DAY) * N;
-    double s = 0.0;
-    for (int i = 0; i < N; ++i) s = s + fabs(prow[i]) * (double)HOLD(i);   // sign bit = flag
-    const double end = SF(FINENV_SF_CASH) + s;
+    const double end = end_total_asset(p, p.panel.close, E, N, e);
     const double a0 = SF(FINENV_SF_ASSET0);
     double *out = p.stats_out + (size_t)e * 6;
     out[0] = a0;
@@ -68,6 +97,147 @@ __global__ void stock_last_stats_kernel(const Params p)
     out[5] = sharpe_from_sums((int)SL(FINENV_SL_RET_N), SL(FINENV_SL_RET_SUM), SL(FINENV_SL_RET_SUMSQ));
 }
 
+// -------------------------------------------------------------------------------------
+// Episode history (finenv_stock_set_history): asset_memory / date_memory / actions_memory of every
+// env's current episode, kept on the device.  Three small kernels with their own argument struct; they
+// ride behind the step / init / reset kernels as separate launches on the same stream and read the
+// state those left in memory.  Time-major layout ([k][E], actions [k][E][N]): a lock-step batch writes
+// whole contiguous rows.
+// -------------------------------------------------------------------------------------
+struct HistoryArgs {
+    finenv_stock_history h;
+    finenv_stock_state st;
+    const double *close;          // panel closes [T][N]
+    const uint8_t *done;          // record: this step's done [E]
+    const int32_t *realised;      // record: this step's realised trades [E][N] (NULL without actions)
+    const uint8_t *mask;          // arm: envs to arm, or NULL = all
+    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
+    double annualization;
+    int32_t E, N;
+    uint32_t magicN;              // ceil(2^32 / N) for N >= 2
+};
+
+constexpr int kHistThreads = 256;     // envs per block of the record kernel
+constexpr int kHistBatch = 16;        // dwords of `realised` each lane has in flight
+
+// After a step.  Block b owns envs [256 b, 256 b + 256): each lane first decides for its own env whether
+// entry k = len[e] is written, publishes k in LDS, then the whole block copies the block's [nenv][N]
+// tile of `realised` flat (consecutive lanes = consecutive dwords of both the source and, where
+// neighbouring envs share k, the destination), and each lane writes its env's two scalar columns.
+// len[e] is read before the barrier and written after it by the lane that owns it.
+__global__ __launch_bounds__(kHistThreads) void stock_history_record_kernel(const HistoryArgs p)
+{
+    __shared__ int ks[kHistThreads];
+    const int E = p.E, N = p.N, cap = p.h.capacity;
+    const int e0 = blockIdx.x * kHistThreads;
+    const int e = e0 + (int)threadIdx.x;
+    int k = 0;                                        // 0 = this env writes no entry on this step
+    if (e < E) {
+        const int len = p.h.len[e], fl = p.h.flags[e];
+        if (!(fl & FINENV_HIST_COMPLETE) && len >= 1) {
+            if (p.done[e]) p.h.flags[e] = fl | FINENV_HIST_COMPLETE;      // :222-301 appends nothing
+            else if (len >= cap) p.h.flags[e] = fl | FINENV_HIST_OVERFLOW;
+            else k = len;
+        }
+    }
+    ks[threadIdx.x] = k;
+    __syncthreads();
+    if (p.h.actions != nullptr) {
+        const int nenv = min(kHistThreads, E - e0);
+        const int total = nenv * N;                   // <= 256 * 128: magicN is exact below 2^16
+        const int32_t *src = p.realised + (size_t)e0 * N;
+        for (int f0 = 0; f0 < total; f0 += kHistBatch * kHistThreads) {      // loads first, then stores
+            int v[kHistBatch];
+#pragma unroll
+            for (int j = 0; j < kHistBatch; ++j) {
+                const int f = f0 + j * kHistThreads + (int)threadIdx.x;
+                v[j] = src[f < total ? f : total - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < kHistBatch; ++j) pin(v[j]);
+#pragma unroll
+            for (int j = 0; j < kHistBatch; ++j) {
+                const int f = f0 + j * kHistThreads + (int)threadIdx.x;
+                if (f < total) {
+                    const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
+                    const int kk = ks[el];
+                    if (kk >= 1) p.h.actions[((size_t)(kk - 1) * E + e0) * N + f] = v[j];
+                }
+            }
+        }
+    }
+    if (k >= 1) {
+        p.h.asset[(size_t)k * E + e] = end_total_asset(p, p.close, E, N, e);
+        p.h.row[(size_t)k * E + e] = SI(FINENV_SI_DAY);                    // _get_date() after :335-336
+        p.h.len[e] = k + 1;
+    }
+}
+
+// What __init__ (:85-97) / reset() (:359-393) leave in asset_memory / date_memory, for the envs of the
+// mask: one entry.  At the start of an episode that entry is asset_memory[0] as init / reset evaluated
+// it (FINENV_SF_ASSET0: the reference sums it in another order than a step does, and with
+// initial == 0 it is the previous total asset); armed mid-episode, the record starts at the current
+// total asset.
+__global__ void stock_history_arm_kernel(const HistoryArgs p)
+{
+    const int E = p.E, N = p.N;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || (p.mask != nullptr && p.mask[e] == 0)) return;
+    p.h.asset[e] = SI(FINENV_SI_DAY) == SI(FINENV_SI_START_DAY) ? SF(FINENV_SF_ASSET0)
+                                                                : end_total_asset(p, p.close, E, N, e);
+    p.h.row[e] = SI(FINENV_SI_DAY);
+    p.h.len[e] = 1;
+    p.h.flags[e] = 0;
+}
+
+// Backtest figures of each env's recorded series: one lane per env, a time loop strided by E (the
+// accesses of a wave are contiguous at every k), fp64, two sequential passes for mean / std as pandas
+// takes them (pct_change, .mean(), .std() with ddof = 1).
+__global__ void stock_history_metrics_kernel(const HistoryArgs p)
+{
+    const int E = p.E;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double *out = p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS;
+    const double nan = __builtin_nan("");
+    const int len = min(p.h.len[e], p.h.capacity);
+    if (len < 1) {
+        for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
+        return;
+    }
+    const double *a = p.h.asset + e;
+    const double first = a[0];
+    const int n = len - 1;
+    double prev = first, peak = first, sum = 0.0, mdd = 0.0;       // asset[0] / asset[0] - 1 == 0
+    for (int k = 1; k < len; ++k) {
+        const double v = a[(size_t)k * E];
+        sum = sum + (v / prev - 1.0);
+        peak = v > peak ? v : peak;
+        const double dd = v / peak - 1.0;
+        mdd = dd < mdd ? dd : mdd;
+        prev = v;
+    }
+    const double mean = n >= 1 ? sum / (double)n : nan;
+    double sd = nan;
+    if (n >= 2) {
+        double ss = 0.0;
+        prev = first;
+        for (int k = 1; k < len; ++k) {
+            const double v = a[(size_t)k * E];
+            const double d = (v / prev - 1.0) - mean;
+            ss = ss + d * d;
+            prev = v;
+        }
+        sd = sqrt(ss / (double)(n - 1));
+    }
+    out[FINENV_HM_N_RETURNS] = (double)n;
+    out[FINENV_HM_CUMULATIVE_RETURN] = prev / first - 1.0;
+    out[FINENV_HM_MEAN] = mean;
+    out[FINENV_HM_STD] = sd;
+    out[FINENV_HM_SHARPE] = (n >= 2 && sd != 0.0) ? p.annualization * mean / sd : nan;
+    out[FINENV_HM_MAX_DRAWDOWN] = mdd;
+}
+
 }  // namespace
 
 // =====================================================================================
@@ -82,6 +252,8 @@ struct finenv_stock : finenv_host::Handle {
     uint32_t magicN;
     double *last;         // finenv_stock_set_last_episode
     int32_t *win;         // finenv_stock_set_windows
+    int has_hist;         // finenv_stock_set_history
+    finenv_stock_history hist;
 };
 
 namespace {
@@ -117,6 +289,27 @@ int launch_step(finenv_stock *h, const Params &p, bool turb, bool stats, hipStre
     if (h->cfg.n_tickers <= 32) return finenv_stock_impl::launch_step_np32(p, turb, stats, h->device, stream);
     if (h->cfg.n_tickers <= 64) return finenv_stock_impl::launch_step_np64(p, turb, stats, h->device, stream);
     return finenv_stock_impl::launch_step_np128(p, turb, stats, h->device, stream);
+}
+
+HistoryArgs make_history_args(const finenv_stock *h)
+{
+    HistoryArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h->hist;
+    a.st = h->st;
+    a.close = h->panel.close;
+    a.E = h->cfg.n_envs;
+    a.N = h->cfg.n_tickers;
+    a.magicN = h->magicN;
+    return a;
+}
+
+// init / reset (re)start episodes: the reference's __init__ / reset() start the memories afresh
+void launch_history_arm(const finenv_stock *h, const uint8_t *mask, hipStream_t stream)
+{
+    HistoryArgs a = make_history_args(h);
+    a.mask = mask;
+    hipLaunchKernelGGL(stock_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
 }
 
 }  // namespace
@@ -251,6 +444,7 @@ int finenv_stock_init(finenv_stock *h, int32_t day0, void *stream)
     Params p = make_params(h);
     p.day0 = day0;
     launch_aux(h, p, 0, (hipStream_t)stream);
+    if (h->has_hist) launch_history_arm(h, nullptr, (hipStream_t)stream);
     return finenv_host::check_launch(h, "stock_init");
 }
 
@@ -262,6 +456,7 @@ int finenv_stock_reset(finenv_stock *h, const uint8_t *mask, float *obs_out, voi
     p.mask = mask;
     p.obs = obs_out;
     launch_aux(h, p, 1, (hipStream_t)stream);
+    if (h->has_hist) launch_history_arm(h, mask, (hipStream_t)stream);
     return finenv_host::check_launch(h, "stock_reset");
 }
 
@@ -293,6 +488,9 @@ int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
         return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+    if (h->has_hist && h->hist.actions && !realised)
+        return finenv_host::fail(h, FINENV_ERR_INVALID,
+                                 "step: the attached history records actions and needs `realised`");
     Params p = make_params(h);
     p.actions = actions;
     p.obs = obs;
@@ -312,6 +510,13 @@ int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *
     const bool turb = h->cfg.use_turbulence != 0, stats = h->cfg.track_stats != 0;
     const int rc = launch_step(h, p, turb, stats, s);
     if (rc) return finenv_host::fail(h, FINENV_ERR_HIP, "step: cannot raise the dynamic LDS limit");
+    if (h->has_hist) {      // behind the step kernel (its last round): reads done, realised and the new state
+        HistoryArgs a = make_history_args(h);
+        a.done = done;
+        a.realised = realised;
+        hipLaunchKernelGGL(stock_history_record_kernel, dim3((a.E + kHistThreads - 1) / kHistThreads),
+                           dim3(kHistThreads), 0, s, a);
+    }
     return finenv_host::check_launch(h, "stock_step");
 }
 
@@ -355,6 +560,49 @@ int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream)
     hipLaunchKernelGGL(stock_last_stats_kernel, dim3((E + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "stock_last_episode_stats");
+}
+
+int finenv_stock_set_history(finenv_stock *h, const finenv_stock_history *hist)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (!hist) {
+        h->has_hist = 0;
+        memset(&h->hist, 0, sizeof(h->hist));
+        return FINENV_OK;
+    }
+    if (!hist->asset || !hist->row || !hist->len || !hist->flags)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: null asset/row/len/flags");
+    if (hist->capacity < 2)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
+    h->hist = *hist;
+    h->has_hist = 1;
+    return FINENV_OK;
+}
+
+int finenv_stock_history_arm(finenv_stock *h, const uint8_t *mask, void *stream)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (!h->has_hist)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_arm: no history attached");
+    if (const int rc = finenv_host::ready(h, "history_arm")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    launch_history_arm(h, mask, (hipStream_t)stream);
+    return finenv_host::check_launch(h, "stock_history_arm");
+}
+
+int finenv_stock_history_metrics(finenv_stock *h, double annualization, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (!h->has_hist)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_metrics: no history attached");
+    if (const int rc = finenv_host::ready(h, "history_metrics")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    HistoryArgs a = make_history_args(h);
+    a.out = out;
+    a.annualization = annualization;
+    hipLaunchKernelGGL(stock_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return finenv_host::check_launch(h, "stock_history_metrics");
 }
 
 }  // extern "C"

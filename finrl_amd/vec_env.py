@@ -189,6 +189,7 @@ class VecStockTradingEnv(_EpisodeWindows):
     _pitched = True
     _last_fields, _last_ratio = nat.STOCK_LAST_FIELDS, ("begin_asset", "end_asset")
     _stats = None
+    history = None              # enable_history()
     # the stock env's own names of its two state blocks, kept for code that reads them
     _state_f64 = property(lambda self: self._f64)
     _state_i32 = property(lambda self: self._i32)
@@ -263,6 +264,55 @@ class VecStockTradingEnv(_EpisodeWindows):
 
     def enable_realised(self):
         return self._enable_output("realised", self.stock_dim, _torch().int32)
+
+    def enable_history(self, capacity=None, actions=True):
+        """Record every env's episode on the device: the reference's ``asset_memory``,
+        ``date_memory`` and (with ``actions``) ``actions_memory`` (:85-97, :332, :348-349), written by
+        one small kernel behind each step -- no ``state_numpy()`` per step, no host loop, and it sits
+        in a captured graph.  Returns the ``finrl_amd.history.EpisodeHistory`` (also
+        ``self.history``); idempotent like ``enable_last_episode``: a second call returns the same
+        object whatever its arguments.
+
+        ``capacity``: entries per env, by default the longest episode in panel rows (``T``, or the
+        longest window).  Every env is armed from its current state; ``reset(mask)`` re-arms the envs
+        it resets, an auto-reset does not (the finished record stays readable), see EpisodeHistory.
+        With ``actions`` the ``realised`` step output is enabled too.
+
+        Memory: ``E * (12 * capacity + 8) + 4 * E * N * (capacity - 1)`` bytes.  63-day windows at
+        65,536 x DOW30 are 0.05 GB without and 0.54 GB with actions; a full 2,893-day episode at that
+        batch is 2.3 GB without and 25 GB with, which is why ``actions`` is optional.
+
+        Enable it before capturing a graph (the tensors' addresses are launch arguments).  A
+        ``GraphedSegment`` restores only the env's state blocks after its warm-up steps, so a history
+        enabled before the segment is built has recorded the warm-up: build the segment, then
+        ``history.arm()``."""
+        if self.history is None:
+            from .history import EpisodeHistory
+            self.history = EpisodeHistory(
+                self, self.max_step + 1 if capacity is None else capacity, actions)
+        return self.history
+
+    def _history(self, what):
+        if self.history is None:
+            raise nat.FinenvError(f"{what}: call enable_history() first")
+        return self.history
+
+    def _env_indices(self, indices):
+        if indices is None:
+            return list(range(self.num_envs))
+        if isinstance(indices, (int, np.integer)):
+            return [int(indices)]
+        return [int(i) for i in indices]
+
+    def save_asset_memory(self, indices=None):
+        """The reference's save_asset_memory() frames (:517-525), one per selected env (all by
+        default).  Needs enable_history()."""
+        return self._history("save_asset_memory").save_asset_memory(self._env_indices(indices))
+
+    def save_action_memory(self, indices=None):
+        """The reference's save_action_memory() frames (:527-543), one per selected env (all by
+        default).  Needs enable_history() with actions."""
+        return self._history("save_action_memory").save_action_memory(self._env_indices(indices))
 
     # ------------------------------------------------------------------ env protocol
     # reset() (:359-393) and step() (:220-357) are BatchedEnv's

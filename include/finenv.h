@@ -266,6 +266,69 @@ int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream);
  * amounts, costs) stay handle-wide. */
 int finenv_stock_set_windows(finenv_stock *h, int32_t *win);
 
+/* Episode history: asset_memory, date_memory and actions_memory (:85-97, :332, :348-349) of every
+ * env's CURRENT episode, recorded on the device -- what save_asset_memory() / save_action_memory()
+ * (:517-543), the account_value_*.csv of the terminal branch (:230-292) and get_validation_sharpe
+ * read.  Opt-in and caller-owned device memory, time-major:
+ *   asset[k][e]      the k-th entry of env e's asset_memory (fp64, the value the reference appends)
+ *   row[k][e]        the panel row whose date is the k-th entry of its date_memory
+ *   actions[k][e][:] the k-th entry of its actions_memory: the `realised` row of that step
+ *   len[e]           entries recorded so far (actions: len[e] - 1); 0 = not armed, nothing is recorded
+ *   flags[e]         FINENV_HIST_COMPLETE: the episode has reported done, the record is final;
+ *                    FINENV_HIST_OVERFLOW: a step found len[e] == capacity and recorded nothing
+ * While a history is attached, finenv_stock_step launches one more small kernel behind the step kernel
+ * on the same stream (the step kernels themselves do not know about it).  Per env, by its own counter:
+ *   - not armed (len == 0) or complete: nothing;
+ *   - the step reported done: COMPLETE is set and nothing else is written -- the terminal branch
+ *     appends to no memory (:222-301) -- whatever auto_reset is;
+ *   - else entry k = len[e]: asset[k][e] = end_total_asset (:344-347), row[k][e] = FINENV_SI_DAY,
+ *     actions[k-1][e][:] = realised[e][:], len[e] = k + 1; with k == capacity nothing is written and
+ *     OVERFLOW is set.  No entry at or past `capacity` (actions: capacity - 1) is ever written.
+ * Arming an env writes entry 0 -- what __init__ / reset() leave in the memories: asset_memory[0]
+ * (FINENV_SF_ASSET0; with initial == 0 the previous total asset, :372-378) when the env stands at the
+ * start of an episode, else its current total asset; its current FINENV_SI_DAY -- sets len[e] = 1 and
+ * clears flags[e].  finenv_stock_init arms every env and finenv_stock_reset the envs it resets (the
+ * reference's reset() wipes the lists).  An auto-reset inside step does NOT arm: the finished
+ * episode's record stays readable and the env is not recorded again until a host reset or
+ * finenv_stock_history_arm.  (DRL_prediction pulls the memories one step before the end because
+ * DummyVecEnv's reset destroys them; here they survive it.)
+ * The struct's pointers are LAUNCH ARGUMENTS: a step captured into a graph records only if the
+ * history was attached before the capture, and into the tensors attached then.  With
+ * actions != NULL, finenv_stock_step needs realised != NULL (FINENV_ERR_INVALID otherwise).
+ * Memory: E * (12 * capacity + 8) + 4 * E * N * (capacity - 1) bytes. */
+enum {
+    FINENV_HIST_COMPLETE = 1,
+    FINENV_HIST_OVERFLOW = 2
+};
+typedef struct finenv_stock_history {
+    double  *asset;     /* [capacity][E]        asset_memory                              */
+    int32_t *row;       /* [capacity][E]        panel row of date_memory                  */
+    int32_t *actions;   /* [capacity-1][E][N]   actions_memory (realised), or NULL        */
+    int32_t *len;       /* [E] entries recorded for the env's episode; 0 = not armed      */
+    int32_t *flags;     /* [E] bit 0 complete, bit 1 overflow                             */
+    int32_t  capacity;  /* >= 2                                                           */
+} finenv_stock_history;
+/* Attach a history (the struct is copied), or detach with NULL (the default).  Allowed before bind.
+ * Attaching arms nothing: zero len / flags, then finenv_stock_init / _reset / _history_arm. */
+int finenv_stock_set_history(finenv_stock *h, const finenv_stock_history *hist);
+/* Arm every env, or those with mask[e] != 0 (device u8[E]), from its current state. */
+int finenv_stock_history_arm(finenv_stock *h, const uint8_t *mask, void *stream);
+/* Backtest figures of the recorded series: out [E][FINENV_STOCK_HISTORY_METRICS] f64, columns below;
+ * daily returns r_k = asset[k] / asset[k-1] - 1, mean and std (ddof = 1) in two sequential passes as
+ * pandas takes them.  sharpe = annualization * mean / std, NaN with fewer than two returns or
+ * std == 0: annualization = sqrt(252) is the terminal printout (:243-251), sqrt(4) is
+ * get_validation_sharpe.  Rows of unarmed envs are NaN. */
+enum {
+    FINENV_HM_N_RETURNS = 0,      /* len - 1                                                  */
+    FINENV_HM_CUMULATIVE_RETURN,  /* asset[len-1] / asset[0] - 1                              */
+    FINENV_HM_MEAN,               /* mean of the daily returns (NaN without one)              */
+    FINENV_HM_STD,                /* their std, ddof = 1 (NaN with fewer than two)            */
+    FINENV_HM_SHARPE,
+    FINENV_HM_MAX_DRAWDOWN,       /* min_k (asset[k] / max_{j<=k} asset[j] - 1), <= 0         */
+    FINENV_STOCK_HISTORY_METRICS
+};
+int finenv_stock_history_metrics(finenv_stock *h, double annualization, double *out, void *stream);
+
 /* =====================================================================================
  * StockPortfolioEnv (finrl/meta/env_portfolio_allocation/env_portfolio.py:15-261)
  *   actions [E][N] f32 (portfolio scores; softmax-normalised inside, :225-229)
