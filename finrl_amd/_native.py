@@ -91,6 +91,17 @@ class PortfolioStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p)]
 
 
+class PortfolioHistoryPtrs(C.Structure):
+    """finenv_portfolio_history: the episode-history tensors of finenv_portfolio_set_history."""
+    _fields_ = [("value", C.c_void_p), ("ret", C.c_void_p), ("row", C.c_void_p),
+                ("weights", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
+                ("capacity", C.c_int32)]
+
+
+# columns of finenv_portfolio_history_metrics: the FINENV_HM_* indices (n_returns counts the leading 0)
+PORTFOLIO_HISTORY_METRICS = STOCK_HISTORY_METRICS
+
+
 class CryptoConfig(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("n_assets", C.c_int32), ("n_tech", C.c_int32),
                 ("n_steps", C.c_int32), ("lookback", C.c_int32), ("reserved0", C.c_int32),
@@ -251,6 +262,10 @@ def lib():
         L.finenv_stock_set_history.argtypes = [C.c_void_p, C.POINTER(StockHistoryPtrs)]
         L.finenv_stock_history_arm.argtypes = [C.c_void_p] * 3
         L.finenv_stock_history_metrics.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    if hasattr(L, "finenv_portfolio_set_history"):
+        L.finenv_portfolio_set_history.argtypes = [C.c_void_p, C.POINTER(PortfolioHistoryPtrs)]
+        L.finenv_portfolio_history_arm.argtypes = [C.c_void_p] * 3
+        L.finenv_portfolio_history_metrics.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]

@@ -13,7 +13,12 @@
 //   * when all 64 envs sit on the same day (always, in lock-step batches) the template row
 //     lives in registers and the row loop holds no load;
 //   * per-env episode windows (finenv_portfolio_set_windows) are the WIN instantiation of the step
-//     kernel: the terminal test reads the env's window end, a reset goes back to its window start.
+//     kernel: the terminal test reads the env's window end, a reset goes back to its window start;
+//   * the episode history (finenv_portfolio_set_history) is the HIST instantiation: portfolio_return
+//     lives in a register of wave 0 and nowhere else, so the record is taken there -- value, return
+//     and row by the lane that owns the env, the block's [64][N] weights flat out of the LDS tile
+//     (time-major layout: one contiguous run when the block's envs share their entry index).  Wave 1
+//     does not take part.  Arming and the metrics are two small kernels off the step path.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +55,7 @@ struct PfParams {
     double *last;          // last-episode block [FINENV_PORTFOLIO_LAST_FIELDS][E] or NULL
     double *stats_out;     // last_episode_stats: [E][3]
     const int32_t *win;    // per-env windows [2][E] (starts, ends) or NULL (finenv_portfolio_set_windows)
+    finenv_portfolio_history hist;   // HIST step kernel only (last: the older fields keep their offsets)
 };
 
 #define PF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
@@ -129,7 +135,11 @@ __device__ __forceinline__ void pf_write_rows(float *__restrict__ dst,
 
 // WIN: the instantiation for batches with per-env episode windows (PfParams::win != NULL).  A template
 // parameter so that the no-window kernel compiles exactly as before.
-template <bool WIN = false>
+// HIST: the recording instantiation (PfParams::hist attached, finenv_portfolio_set_history; the rule is
+// in include/finenv.h).  Wave 0 reads the env's counter and flags beside `day`, writes the env's
+// value / return / row where it stores the state, and copies the block's weights out of the LDS tile
+// after its own weight loop: no barrier is added, wave 1 goes straight to its observation rows.
+template <bool WIN = false, bool HIST = false>
 __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams p)
 {
     __shared__ float tile[kWave * kTileStride];
@@ -144,6 +154,12 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
 
     // both waves: which panel rows this step shows (needs only `day`)
     int day = PI(FINENV_PI_DAY);
+    // HIST, wave 0: the env's entry counter and flags, in flight together with `day`
+    int hlen = 0, hfl = 0;
+    if (HIST && wib == 0 && valid) {
+        hlen = *at(p.hist.len, (unsigned)e);
+        hfl = *at(p.hist.flags, (unsigned)e);
+    }
     const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
     const bool term = day >= last_day;                                        // :127
     const int day_next = term ? day : day + 1;
@@ -168,6 +184,11 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
         double value = PF(FINENV_PF_VALUE);
         double last_reward = PF(FINENV_PF_LAST_REWARD);
         float *row = tile + lane * kTileStride;
+        // HIST: the entry this env records on this step (-1: none).  An armed env (len >= 1; only
+        // valid lanes loaded one) whose episode is in progress records unless the step is terminal
+        // or the record is full; those two set a flag further down.
+        const bool hlive = HIST && hlen >= 1 && !(hfl & FINENV_HIST_COMPLETE);
+        const int hk = (hlive && !term && hlen < p.hist.capacity) ? hlen : -1;
         if (!term) {
             // softmax in float32 (:225-229): exp, NumPy pairwise sum order, divide
             float r8[8];
@@ -218,6 +239,47 @@ __global__ void __launch_bounds__(kThreads) portfolio_step_kernel(const PfParams
             }
             if (p.weights != nullptr && valid)
                 for (int i = 0; i < N; ++i) *at(p.weights, (unsigned)(e * N + i)) = row[i];
+            if (HIST && hk >= 0) {     // :190-193; the time-major slabs are indexed in 64 bits
+                const size_t o = (size_t)hk * (size_t)E + (size_t)e;
+                p.hist.value[o] = value;
+                p.hist.ret[o] = ret;
+                p.hist.row[o] = day_next;
+                *at(p.hist.len, (unsigned)e) = hk + 1;
+            }
+        }
+        if (HIST) {
+            if (hlive && hk < 0) {     // terminal: the record is final; else it is full
+                const int nfl = hfl | (term ? FINENV_HIST_COMPLETE : FINENV_HIST_OVERFLOW);
+                if (nfl != hfl) *at(p.hist.flags, (unsigned)e) = nfl;   // (an overflowed env: set once)
+            }
+            const unsigned long long rec = __ballot(hk >= 0);
+            if (p.hist.weights != nullptr && rec != 0ull) {
+                // actions_memory (:168): the recording envs' rows of the tile hold this step's weights
+                // (written by this wave, read back by this wave: no workgroup barrier).  Flat copy,
+                // consecutive lanes on consecutive dwords of the block's [nenv][N] slab of weights[k].
+                wave_sync();
+                const int k0 = __builtin_amdgcn_readlane(hk, __builtin_ctzll(rec));
+                const int total = nenv_w * N;                 // <= 64 * 64: magicN is exact
+                if (rec == valid_mask && __all(!valid || hk == k0)) {
+                    // one k for the whole block (always, in a lock-step batch): one contiguous run
+                    float *const dst = p.hist.weights + ((size_t)k0 * (size_t)E + (size_t)e0) * (size_t)N;
+                    for (int f = lane; f < total; f += kWave) {
+                        const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
+                        *at(dst, (unsigned)f) = tile[el * kTileStride + (f - el * N)];
+                    }
+                } else {
+                    // k differs inside the block (or some envs do not record): each element goes to
+                    // its own env's entry; still flat within every env's row
+                    for (int f0 = 0; f0 < total; f0 += kWave) {
+                        const int f = min(f0 + lane, total - 1);
+                        const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
+                        const int kk = __shfl(hk, el);        // every lane takes part
+                        if (f0 + lane < total && kk >= 0)
+                            p.hist.weights[((size_t)kk * (size_t)E + (size_t)e0) * (size_t)N + (size_t)f] =
+                                tile[el * kTileStride + (f - el * N)];
+                    }
+                }
+            }
         }
         if (valid) {
             *at(p.reward, (unsigned)e) = (float)last_reward;
@@ -294,6 +356,92 @@ __global__ void portfolio_last_stats_kernel(const PfParams p)
     out[2] = sharpe_from_sums((int)PL(FINENV_PL_RET_N), PL(FINENV_PL_RET_SUM), PL(FINENV_PL_RET_SUMSQ));
 }
 
+// -------------------------------------------------------------------------------------
+// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
+// instantiation of the step kernel above).
+// -------------------------------------------------------------------------------------
+struct PfHistArgs {
+    finenv_portfolio_history h;
+    finenv_portfolio_state st;
+    const uint8_t *mask;          // arm: envs to arm, or NULL = all
+    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
+    double annualization;
+    int32_t E, N;
+    uint32_t magicN;              // ceil(2^32 / N) for N >= 2
+};
+
+constexpr int kArmThreads = 256;      // envs per block of the arm kernel
+
+// What __init__ (:116-123) / reset() (:202-220) leave in the four memories, for the envs of the mask:
+// one entry.  value[0] is the env's current portfolio value (the initial amount at the start of an
+// episode), ret[0] = 0, row[0] its current panel row, weights[0] the equal-weight row; the block writes
+// its [nenv][N] slab of weights[0] flat.
+__global__ __launch_bounds__(kArmThreads) void portfolio_history_arm_kernel(const PfHistArgs p)
+{
+    const int E = p.E, N = p.N;
+    const int e0 = blockIdx.x * kArmThreads;
+    const int e = e0 + (int)threadIdx.x;
+    if (e < E && (p.mask == nullptr || p.mask[e] != 0)) {
+        p.h.value[e] = PF(FINENV_PF_VALUE);
+        p.h.ret[e] = 0.0;
+        p.h.row[e] = PI(FINENV_PI_DAY);
+        p.h.len[e] = 1;
+        p.h.flags[e] = 0;
+    }
+    if (p.h.weights == nullptr || e0 >= E) return;
+    const int total = min(kArmThreads, E - e0) * N;     // <= 256 * 64: magicN is exact below 2^16
+    const float w0 = (float)(1.0 / (double)N);
+    for (int f = (int)threadIdx.x; f < total; f += kArmThreads) {
+        const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
+        if (p.mask == nullptr || p.mask[e0 + el] != 0) p.h.weights[(size_t)e0 * N + f] = w0;
+    }
+}
+
+// Backtest figures of each env's recorded series: one lane per env, a time loop strided by E (the
+// accesses of a wave are contiguous at every k), fp64.  Mean / std over the RECORDED returns, leading 0
+// included, in two sequential passes as the terminal branch's pandas calls take them (:145-152, std
+// with ddof = 1); drawdown and cumulative return over the values.
+__global__ void portfolio_history_metrics_kernel(const PfHistArgs p)
+{
+    const int E = p.E;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    double *out = p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS;
+    const double nan = __builtin_nan("");
+    const int len = min(p.h.len[e], p.h.capacity);
+    if (len < 1) {
+        for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
+        return;
+    }
+    const double *v = p.h.value + e, *r = p.h.ret + e;
+    const double first = v[0];
+    double lastv = first, peak = first, sum = 0.0, mdd = 0.0;
+    for (int k = 0; k < len; ++k) {
+        const double x = v[(size_t)k * E];
+        sum = sum + r[(size_t)k * E];
+        peak = x > peak ? x : peak;
+        const double dd = x / peak - 1.0;
+        mdd = dd < mdd ? dd : mdd;
+        lastv = x;
+    }
+    const double mean = sum / (double)len;
+    double sd = nan;
+    if (len >= 2) {
+        double ss = 0.0;
+        for (int k = 0; k < len; ++k) {
+            const double d = r[(size_t)k * E] - mean;
+            ss = ss + d * d;
+        }
+        sd = sqrt(ss / (double)(len - 1));
+    }
+    out[FINENV_HM_N_RETURNS] = (double)len;
+    out[FINENV_HM_CUMULATIVE_RETURN] = lastv / first - 1.0;
+    out[FINENV_HM_MEAN] = mean;
+    out[FINENV_HM_STD] = sd;
+    out[FINENV_HM_SHARPE] = (len >= 2 && sd != 0.0) ? p.annualization * mean / sd : nan;
+    out[FINENV_HM_MAX_DRAWDOWN] = mdd;
+}
+
 }  // namespace
 
 struct finenv_portfolio : finenv_host::Handle {
@@ -303,6 +451,8 @@ struct finenv_portfolio : finenv_host::Handle {
     uint32_t magicN;
     double *last;         // finenv_portfolio_set_last_episode
     int32_t *win;         // finenv_portfolio_set_windows
+    int has_hist;         // finenv_portfolio_set_history
+    finenv_portfolio_history hist;
 };
 
 namespace {
@@ -317,7 +467,36 @@ PfParams pf_params(const finenv_portfolio *h)
     p.magicN = h->magicN;
     p.last = h->last;
     p.win = h->win;
+    if (h->has_hist) p.hist = h->hist;
     return p;
+}
+
+PfHistArgs pf_hist_args(const finenv_portfolio *h)
+{
+    PfHistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h->hist;
+    a.st = h->st;
+    a.E = h->cfg.n_envs;
+    a.N = h->cfg.n_tickers;
+    a.magicN = h->magicN;
+    return a;
+}
+
+// reset (re)starts episodes: the reference's reset() starts the memories afresh
+void launch_history_arm(const finenv_portfolio *h, const uint8_t *mask, hipStream_t stream)
+{
+    PfHistArgs a = pf_hist_args(h);
+    a.mask = mask;
+    hipLaunchKernelGGL(portfolio_history_arm_kernel, dim3((a.E + kArmThreads - 1) / kArmThreads),
+                       dim3(kArmThreads), 0, stream, a);
+}
+
+template <bool WIN, bool HIST>
+void launch_step(const finenv_portfolio *h, const PfParams &p, hipStream_t stream)
+{
+    hipLaunchKernelGGL((portfolio_step_kernel<WIN, HIST>), dim3((h->cfg.n_envs + kWave - 1) / kWave),
+                       dim3(kThreads), 0, stream, p);
 }
 }  // namespace
 
@@ -364,6 +543,7 @@ int finenv_portfolio_reset(finenv_portfolio *h, const uint8_t *mask, float *obs_
     p.obs = obs_out;
     hipLaunchKernelGGL(portfolio_reset_kernel, dim3((h->cfg.n_envs + kWave - 1) / kWave),
                        dim3(kThreads), 0, (hipStream_t)stream, p);
+    if (h->has_hist) launch_history_arm(h, mask, (hipStream_t)stream);   // behind the reset: reads its state
     return finenv_host::check_launch(h, "portfolio_reset");
 }
 
@@ -383,12 +563,14 @@ int finenv_portfolio_step(finenv_portfolio *h, const float *actions, float *obs,
     p.term_obs = term_obs;
     p.weights = weights_out;
     p.auto_reset = auto_reset;
-    if (p.win != nullptr)     // per-env windows
-        hipLaunchKernelGGL(portfolio_step_kernel<true>, dim3((h->cfg.n_envs + kWave - 1) / kWave),
-                           dim3(kThreads), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(portfolio_step_kernel<false>, dim3((h->cfg.n_envs + kWave - 1) / kWave),
-                           dim3(kThreads), 0, (hipStream_t)stream, p);
+    const hipStream_t s = (hipStream_t)stream;
+    if (p.win != nullptr) {   // per-env windows
+        if (h->has_hist) launch_step<true, true>(h, p, s);
+        else launch_step<true, false>(h, p, s);
+    } else {
+        if (h->has_hist) launch_step<false, true>(h, p, s);
+        else launch_step<false, false>(h, p, s);
+    }
     return finenv_host::check_launch(h, "portfolio_step");
 }
 
@@ -417,6 +599,49 @@ int finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *
     hipLaunchKernelGGL(portfolio_last_stats_kernel, dim3((h->cfg.n_envs + 255) / 256), dim3(256), 0,
                        (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "portfolio_last_episode_stats");
+}
+
+int finenv_portfolio_set_history(finenv_portfolio *h, const finenv_portfolio_history *hist)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (!hist) {
+        h->has_hist = 0;
+        memset(&h->hist, 0, sizeof(h->hist));
+        return FINENV_OK;
+    }
+    if (!hist->value || !hist->ret || !hist->row || !hist->len || !hist->flags)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: null value/ret/row/len/flags");
+    if (hist->capacity < 2)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
+    h->hist = *hist;
+    h->has_hist = 1;
+    return FINENV_OK;
+}
+
+int finenv_portfolio_history_arm(finenv_portfolio *h, const uint8_t *mask, void *stream)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (!h->has_hist)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_arm: no history attached");
+    if (const int rc = finenv_host::ready(h, "history_arm")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    launch_history_arm(h, mask, (hipStream_t)stream);
+    return finenv_host::check_launch(h, "portfolio_history_arm");
+}
+
+int finenv_portfolio_history_metrics(finenv_portfolio *h, double annualization, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (!h->has_hist)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_metrics: no history attached");
+    if (const int rc = finenv_host::ready(h, "history_metrics")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    PfHistArgs a = pf_hist_args(h);
+    a.out = out;
+    a.annualization = annualization;
+    hipLaunchKernelGGL(portfolio_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return finenv_host::check_launch(h, "portfolio_history_metrics");
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ class _EpisodeWindows(BatchedEnv):
     columns."""
 
     windows = None
+    history = None              # enable_history() of the subclass
     _last = _last_stats = last_episode = None
     _last_fields, _last_ratio, last_episode_keys = (), ("", ""), ()
 
@@ -112,6 +113,19 @@ class _EpisodeWindows(BatchedEnv):
             self.max_step = int((self.windows[1] - self.windows[0]).max().item()) - 1
         return self.windows
 
+    def _history(self, what):
+        """The episode history (enable_history() of the subclass), or FinenvError."""
+        if self.history is None:
+            raise nat.FinenvError(f"{what}: call enable_history() first")
+        return self.history
+
+    def _env_indices(self, indices):
+        if indices is None:
+            return list(range(self.num_envs))
+        if isinstance(indices, (int, np.integer)):
+            return [int(indices)]
+        return [int(i) for i in indices]
+
     def _init_last(self, last):
         """Hook: edit a new last-episode block before it is attached."""
 
@@ -189,7 +203,6 @@ class VecStockTradingEnv(_EpisodeWindows):
     _pitched = True
     _last_fields, _last_ratio = nat.STOCK_LAST_FIELDS, ("begin_asset", "end_asset")
     _stats = None
-    history = None              # enable_history()
     # the stock env's own names of its two state blocks, kept for code that reads them
     _state_f64 = property(lambda self: self._f64)
     _state_i32 = property(lambda self: self._i32)
@@ -291,18 +304,6 @@ class VecStockTradingEnv(_EpisodeWindows):
             self.history = EpisodeHistory(
                 self, self.max_step + 1 if capacity is None else capacity, actions)
         return self.history
-
-    def _history(self, what):
-        if self.history is None:
-            raise nat.FinenvError(f"{what}: call enable_history() first")
-        return self.history
-
-    def _env_indices(self, indices):
-        if indices is None:
-            return list(range(self.num_envs))
-        if isinstance(indices, (int, np.integer)):
-            return [int(indices)]
-        return [int(i) for i in indices]
 
     def save_asset_memory(self, indices=None):
         """The reference's save_asset_memory() frames (:517-525), one per selected env (all by

@@ -62,6 +62,44 @@ class VecStockPortfolioEnv(_EpisodeWindows):
         import torch
         return self._enable_output("weights", self.stock_dim, torch.float32)
 
+    def enable_history(self, capacity=None, weights=True):
+        """Record every env's episode on the device: the reference's ``asset_memory``,
+        ``portfolio_return_memory``, ``date_memory`` and (with ``weights``) ``actions_memory``
+        (:118-123, :168, :190-193), written by the step kernel itself -- no ``state_numpy()`` /
+        ``weights.cpu()`` per step, no host loop, and it sits in a captured graph.  Returns the
+        ``finrl_amd.history.PortfolioEpisodeHistory`` (also ``self.history``); idempotent: a second call
+        returns the same object whatever its arguments.
+
+        ``capacity``: entries per env, by default the longest episode in panel rows (``max_step + 1``:
+        ``T``, or the longest window) AS IT IS AT THIS CALL: windows made longer (or detached) by a
+        later ``set_windows`` do not grow the tensors, and the longer episodes then end with
+        ``overflow`` set and their first ``capacity`` days recorded -- pass ``capacity`` for the longest
+        window to come.  Every env is armed from its current state; ``reset(mask)`` re-arms the envs
+        it resets, an auto-reset does not (the finished record stays readable).
+
+        Memory: ``E * (20 * capacity + 8) + 4 * E * N * capacity`` bytes.  63-day windows at
+        65,536 x DOW30 are 0.08 GB without and 0.58 GB with weights; a full 2,893-day episode at that
+        batch is 3.8 GB without and 26.5 GB with, which is why ``weights`` is optional.
+
+        Enable it before capturing a graph (the tensors' addresses are launch arguments)."""
+        if self.history is None:
+            from .history import PortfolioEpisodeHistory
+            self.history = PortfolioEpisodeHistory(
+                self, self.max_step + 1 if capacity is None else capacity, weights)
+        return self.history
+
+    def save_asset_memory(self, indices=None):
+        """The reference's save_asset_memory() frames ``{date, daily_return}`` (:231-239), one per
+        selected env (all by default).  Always a list, also for a single index (as
+        VecStockTradingEnv does; ``self.history.save_asset_memory(e)`` gives the bare frame).  Needs
+        enable_history()."""
+        return self._history("save_asset_memory").save_asset_memory(self._env_indices(indices))
+
+    def save_action_memory(self, indices=None):
+        """The reference's save_action_memory() frames (:241-252), one per selected env (all by
+        default; always a list).  Needs enable_history() with weights."""
+        return self._history("save_action_memory").save_action_memory(self._env_indices(indices))
+
     def _init_last(self, last):
         """While a last-episode block is attached, every step also keeps running return sums
         (``run_sum`` / ``run_sumsq``); they start at 0 for envs on day 0 and at NaN for envs in mid

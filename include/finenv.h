@@ -423,6 +423,65 @@ int  finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void 
  * env runs rows 0 .. n_days-1).  Returns FINENV_ERR_INVALID for a NULL handle. */
 int  finenv_portfolio_set_windows(finenv_portfolio *h, int32_t *win);
 
+/* Episode history of the portfolio env: asset_memory, portfolio_return_memory, date_memory and
+ * actions_memory (:118-123, :168, :190-193) of every env's CURRENT episode, recorded on the device --
+ * what save_asset_memory() / save_action_memory() (:231-252), DRL_prediction's two frames and the
+ * terminal Sharpe (:145-153) read.  Opt-in and caller-owned device memory, time-major; all four
+ * memories have the same length (actions_memory starts with the equal-weight row, :122):
+ *   value[k][e]      the k-th entry of env e's asset_memory (fp64: the value the step stores to
+ *                    FINENV_PF_VALUE)
+ *   ret[k][e]        the k-th entry of its portfolio_return_memory (fp64: the step's own
+ *                    portfolio_return, :183-185; entry 0 is the leading 0 of :121)
+ *   row[k][e]        the panel row whose date is the k-th entry of its date_memory
+ *   weights[k][e][:] the k-th entry of its actions_memory: the f32 softmax weights of that step
+ *   len[e]           entries recorded so far; 0 = not armed, nothing is recorded
+ *   flags[e]         FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW, as in the stock env's history
+ * portfolio_return is not in the state (the step folds it into the value and drops it), so the record
+ * is taken INSIDE the step kernel: while a history is attached finenv_portfolio_step launches the
+ * recording instantiation of its kernel, no second launch.  Per env, by its own counter:
+ *   - not armed (len == 0) or complete: nothing;
+ *   - the step is terminal for the env: COMPLETE is set and nothing else is written -- the terminal
+ *     branch appends to no list (:130-156) -- whatever auto_reset is;
+ *   - else entry k = len[e]: value[k][e] = the new portfolio_value (:193), ret[k][e] = this step's
+ *     portfolio_return (:191), row[k][e] = the panel row the env moved to (:192), weights[k][e][:] =
+ *     this step's softmax weights (:168), len[e] = k + 1; with k == capacity nothing is written and
+ *     OVERFLOW is set.  No entry at or past `capacity` is ever written, in any tensor.
+ * Arming an env writes entry 0 -- what __init__ / reset() leave in the memories: value[0][e] = its
+ * current FINENV_PF_VALUE (the initial amount at the start of an episode), ret[0][e] = 0, row[0][e] =
+ * its current FINENV_PI_DAY, weights[0][e][:] = (float)(1.0 / N) -- sets len[e] = 1 and clears
+ * flags[e].  finenv_portfolio_reset arms the envs it resets (the reference's reset() wipes the lists,
+ * :202-220).  An auto-reset inside step does NOT arm: the finished episode's record stays readable
+ * and the env is not recorded again until a host reset or finenv_portfolio_history_arm.
+ * (DRL_prediction pulls the memories one step before the end because DummyVecEnv's reset destroys
+ * them; here they survive it.)
+ * The struct's pointers are LAUNCH ARGUMENTS: a step captured into a graph records only if the
+ * history was attached before the capture, and into the tensors attached then.
+ * Memory: E * (20 * capacity + 8) + 4 * E * N * capacity bytes. */
+typedef struct finenv_portfolio_history {
+    double  *value;     /* [capacity][E]     asset_memory                                  */
+    double  *ret;       /* [capacity][E]     portfolio_return_memory                       */
+    int32_t *row;       /* [capacity][E]     panel row of date_memory                      */
+    float   *weights;   /* [capacity][E][N]  actions_memory (softmax weights), or NULL     */
+    int32_t *len;       /* [E] entries recorded for the env's episode; 0 = not armed       */
+    int32_t *flags;     /* [E] FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW                  */
+    int32_t  capacity;  /* >= 2                                                            */
+} finenv_portfolio_history;
+/* Attach a history (the struct is copied), or detach with NULL (the default).  Allowed before bind.
+ * Attaching arms nothing: zero len / flags, then finenv_portfolio_reset / _history_arm. */
+int  finenv_portfolio_set_history(finenv_portfolio *h, const finenv_portfolio_history *hist);
+/* Arm every env, or those with mask[e] != 0 (device u8[E]), from its current state. */
+int  finenv_portfolio_history_arm(finenv_portfolio *h, const uint8_t *mask, void *stream);
+/* Backtest figures of the recorded series: out [E][FINENV_STOCK_HISTORY_METRICS] f64, the FINENV_HM_*
+ * columns, taken over the RECORDED returns ret[0 .. len-1] -- portfolio_return_memory with its leading
+ * 0, what the terminal branch takes (:145-152) -- not over value ratios:
+ *   N_RETURNS = len.  This differs from the stock env's len - 1 by that leading 0 (the convention
+ *   of FINENV_PL_RET_N); CUMULATIVE_RETURN = value[len-1] / value[0] - 1; MEAN, STD (ddof = 1, NaN
+ *   with fewer than two entries) in two sequential passes as pandas takes them; SHARPE =
+ *   annualization * mean / std, NaN with fewer than two entries or std == 0 (the reference prints
+ *   none then); MAX_DRAWDOWN over value.  Rows of unarmed envs are NaN. */
+int  finenv_portfolio_history_metrics(finenv_portfolio *h, double annualization, double *out,
+                                      void *stream);
+
 /* =====================================================================================
  * CryptoEnv (finrl/meta/env_cryptocurrency_trading/env_multiple_crypto.py:10-111)
  *   actions [E][N] f32 in [-1,1], scaled per asset by the action normaliser (:63-65, :103-111)
