@@ -258,14 +258,12 @@ def lib():
                     ("finenv_portfolio_set_windows", 2)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
-    if hasattr(L, "finenv_stock_set_history"):       # episode history (same rule)
-        L.finenv_stock_set_history.argtypes = [C.c_void_p, C.POINTER(StockHistoryPtrs)]
-        L.finenv_stock_history_arm.argtypes = [C.c_void_p] * 3
-        L.finenv_stock_history_metrics.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
-    if hasattr(L, "finenv_portfolio_set_history"):
-        L.finenv_portfolio_set_history.argtypes = [C.c_void_p, C.POINTER(PortfolioHistoryPtrs)]
-        L.finenv_portfolio_history_arm.argtypes = [C.c_void_p] * 3
-        L.finenv_portfolio_history_metrics.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs)):
+        if hasattr(L, f"finenv_{kind}_set_history"):       # episode history (same rule)
+            getattr(L, f"finenv_{kind}_set_history").argtypes = [C.c_void_p, C.POINTER(ptrs)]
+            getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3
+            getattr(L, f"finenv_{kind}_history_metrics").argtypes = [C.c_void_p, C.c_double,
+                                                                     C.c_void_p, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]

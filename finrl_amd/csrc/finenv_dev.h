@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include "finenv.h"
+
 namespace {
 
 constexpr int kWaveSize = 64;
@@ -46,6 +48,50 @@ __device__ __forceinline__ double sharpe_from_sums(int n, double s1, double s2)
         if (var > 0.0) sharpe = sqrt(252.0) * mean / sqrt(var);
     }
     return sharpe;
+}
+
+// Backtest figures of one env's recorded series (finenv_{stock,portfolio}_history_metrics) -> the
+// FINENV_HM_* columns of `out`.  v: the env's values, entry k at v[k * E], `len` of them (clamped to the
+// capacity by the caller; < 1 = not armed: a NaN row).  Entries k0 .. len - 1 carry a daily return,
+// ret(k), so n = len - k0 returns.  One lane per env, the time loop strided by E (a wave's accesses are
+// contiguous at every k), fp64; mean and std in two sequential passes as pandas takes them (.mean(),
+// .std() with ddof = 1); peak, drawdown and the cumulative return over the values.
+template <typename Ret>
+__device__ __forceinline__ void series_metrics(const double *v, int E, int len, int k0,
+                                               double annualization, double *out, Ret ret)
+{
+    const double nan = __builtin_nan("");
+    if (len < 1) {
+        for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
+        return;
+    }
+    const double first = v[0];
+    const int n = len - k0;
+    double last = first, peak = first, sum = 0.0, mdd = 0.0;
+    for (int k = k0; k < len; ++k) {
+        const double x = v[(size_t)k * E];
+        sum = sum + ret(k);
+        peak = x > peak ? x : peak;
+        const double dd = x / peak - 1.0;
+        mdd = dd < mdd ? dd : mdd;
+        last = x;
+    }
+    const double mean = n >= 1 ? sum / (double)n : nan;
+    double sd = nan;
+    if (n >= 2) {
+        double ss = 0.0;
+        for (int k = k0; k < len; ++k) {
+            const double d = ret(k) - mean;
+            ss = ss + d * d;
+        }
+        sd = sqrt(ss / (double)(n - 1));
+    }
+    out[FINENV_HM_N_RETURNS] = (double)n;
+    out[FINENV_HM_CUMULATIVE_RETURN] = last / first - 1.0;
+    out[FINENV_HM_MEAN] = mean;
+    out[FINENV_HM_STD] = sd;
+    out[FINENV_HM_SHARPE] = (n >= 2 && sd != 0.0) ? annualization * mean / sd : nan;
+    out[FINENV_HM_MAX_DRAWDOWN] = mdd;
 }
 
 // Per-env episode windows (finenv_stock_set_windows, finenv_portfolio_set_windows): int32 win[2][E],

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <new>
 
@@ -75,6 +76,48 @@ inline int ready(Handle *h, const char *what)
         snprintf(h->err, sizeof(h->err), "%s: bind first", what);
         return FINENV_ERR_UNBOUND;
     }
+    return FINENV_OK;
+}
+
+// ready() for an entry point that works on an optional block of a non-null handle: a block that is not
+// attached is FINENV_ERR_INVALID with "<what>: <missing>", and that is checked before the binding.
+inline int ready_block(Handle *h, bool attached, const char *what, const char *missing)
+{
+    if (attached) return ready(h, what);
+    snprintf(h->err, sizeof(h->err), "%s: %s", what, missing);
+    return FINENV_ERR_INVALID;
+}
+
+// The two optional blocks of the stock and portfolio handles (members `has_hist`, `last`): null handle,
+// then ready_block().
+template <class H>
+int ready_history(H *h, const char *what)
+{
+    return h ? ready_block(h, h->has_hist != 0, what, "no history attached") : FINENV_ERR_INVALID;
+}
+
+template <class H>
+int ready_last_episode(H *h, const char *what)
+{
+    return h ? ready_block(h, h->last != nullptr, what, "no last-episode block set") : FINENV_ERR_INVALID;
+}
+
+// finenv_<kind>_set_history behind the handle check: NULL detaches and zeroes the stored struct.
+// `missing` is the kind's complaint about its own mandatory pointers (nullptr: all there); a refused
+// struct leaves the attached one as it was.
+template <class Hist>
+int set_history(Handle *h, Hist &stored, int &has_hist, const Hist *hist, const char *missing)
+{
+    if (!hist) {
+        has_hist = 0;
+        memset(&stored, 0, sizeof(stored));
+        return FINENV_OK;
+    }
+    if (missing) return fail(h, FINENV_ERR_INVALID, missing);
+    if (hist->capacity < 2)
+        return fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
+    stored = *hist;
+    has_hist = 1;
     return FINENV_OK;
 }
 

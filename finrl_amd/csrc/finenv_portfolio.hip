@@ -397,49 +397,18 @@ __global__ __launch_bounds__(kArmThreads) void portfolio_history_arm_kernel(cons
     }
 }
 
-// Backtest figures of each env's recorded series: one lane per env, a time loop strided by E (the
-// accesses of a wave are contiguous at every k), fp64.  Mean / std over the RECORDED returns, leading 0
-// included, in two sequential passes as the terminal branch's pandas calls take them (:145-152, std
-// with ddof = 1); drawdown and cumulative return over the values.
+// Backtest figures of each env's recorded series (series_metrics, finenv_dev.h).  The daily returns are
+// the RECORDED ones, leading 0 included, as the terminal branch's pandas calls take them (:145-152): every
+// entry carries one, so n_returns is len.
 __global__ void portfolio_history_metrics_kernel(const PfHistArgs p)
 {
     const int E = p.E;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    double *out = p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS;
-    const double nan = __builtin_nan("");
-    const int len = min(p.h.len[e], p.h.capacity);
-    if (len < 1) {
-        for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
-        return;
-    }
-    const double *v = p.h.value + e, *r = p.h.ret + e;
-    const double first = v[0];
-    double lastv = first, peak = first, sum = 0.0, mdd = 0.0;
-    for (int k = 0; k < len; ++k) {
-        const double x = v[(size_t)k * E];
-        sum = sum + r[(size_t)k * E];
-        peak = x > peak ? x : peak;
-        const double dd = x / peak - 1.0;
-        mdd = dd < mdd ? dd : mdd;
-        lastv = x;
-    }
-    const double mean = sum / (double)len;
-    double sd = nan;
-    if (len >= 2) {
-        double ss = 0.0;
-        for (int k = 0; k < len; ++k) {
-            const double d = r[(size_t)k * E] - mean;
-            ss = ss + d * d;
-        }
-        sd = sqrt(ss / (double)(len - 1));
-    }
-    out[FINENV_HM_N_RETURNS] = (double)len;
-    out[FINENV_HM_CUMULATIVE_RETURN] = lastv / first - 1.0;
-    out[FINENV_HM_MEAN] = mean;
-    out[FINENV_HM_STD] = sd;
-    out[FINENV_HM_SHARPE] = (len >= 2 && sd != 0.0) ? p.annualization * mean / sd : nan;
-    out[FINENV_HM_MAX_DRAWDOWN] = mdd;
+    const double *r = p.h.ret + e;
+    series_metrics(p.h.value + e, E, min(p.h.len[e], p.h.capacity), 0, p.annualization,
+                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
+                   [=](int k) { return r[(size_t)k * E]; });
 }
 
 }  // namespace
@@ -591,8 +560,7 @@ int finenv_portfolio_set_windows(finenv_portfolio *h, int32_t *win)
 int finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->last) return finenv_host::fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
-    if (const int rc = finenv_host::ready(h, "last_episode_stats")) return rc;
+    if (const int rc = finenv_host::ready_last_episode(h, "last_episode_stats")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     PfParams p = pf_params(h);
     p.stats_out = out;
@@ -604,26 +572,14 @@ int finenv_portfolio_last_episode_stats(finenv_portfolio *h, double *out, void *
 int finenv_portfolio_set_history(finenv_portfolio *h, const finenv_portfolio_history *hist)
 {
     if (!h) return FINENV_ERR_INVALID;
-    if (!hist) {
-        h->has_hist = 0;
-        memset(&h->hist, 0, sizeof(h->hist));
-        return FINENV_OK;
-    }
-    if (!hist->value || !hist->ret || !hist->row || !hist->len || !hist->flags)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: null value/ret/row/len/flags");
-    if (hist->capacity < 2)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
-    h->hist = *hist;
-    h->has_hist = 1;
-    return FINENV_OK;
+    const bool missing = hist && (!hist->value || !hist->ret || !hist->row || !hist->len || !hist->flags);
+    return finenv_host::set_history(h, h->hist, h->has_hist, hist,
+                                    missing ? "set_history: null value/ret/row/len/flags" : nullptr);
 }
 
 int finenv_portfolio_history_arm(finenv_portfolio *h, const uint8_t *mask, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->has_hist)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_arm: no history attached");
-    if (const int rc = finenv_host::ready(h, "history_arm")) return rc;
+    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     launch_history_arm(h, mask, (hipStream_t)stream);
     return finenv_host::check_launch(h, "portfolio_history_arm");
@@ -632,9 +588,7 @@ int finenv_portfolio_history_arm(finenv_portfolio *h, const uint8_t *mask, void 
 int finenv_portfolio_history_metrics(finenv_portfolio *h, double annualization, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->has_hist)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_metrics: no history attached");
-    if (const int rc = finenv_host::ready(h, "history_metrics")) return rc;
+    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     PfHistArgs a = pf_hist_args(h);
     a.out = out;

@@ -190,52 +190,17 @@ __global__ void stock_history_arm_kernel(const HistoryArgs p)
     p.h.flags[e] = 0;
 }
 
-// Backtest figures of each env's recorded series: one lane per env, a time loop strided by E (the
-// accesses of a wave are contiguous at every k), fp64, two sequential passes for mean / std as pandas
-// takes them (pct_change, .mean(), .std() with ddof = 1).
+// Backtest figures of each env's recorded series (series_metrics, finenv_dev.h).  The daily returns are
+// asset_memory.pct_change(): entry 0 carries none, so n_returns is len - 1.
 __global__ void stock_history_metrics_kernel(const HistoryArgs p)
 {
     const int E = p.E;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    double *out = p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS;
-    const double nan = __builtin_nan("");
-    const int len = min(p.h.len[e], p.h.capacity);
-    if (len < 1) {
-        for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
-        return;
-    }
     const double *a = p.h.asset + e;
-    const double first = a[0];
-    const int n = len - 1;
-    double prev = first, peak = first, sum = 0.0, mdd = 0.0;       // asset[0] / asset[0] - 1 == 0
-    for (int k = 1; k < len; ++k) {
-        const double v = a[(size_t)k * E];
-        sum = sum + (v / prev - 1.0);
-        peak = v > peak ? v : peak;
-        const double dd = v / peak - 1.0;
-        mdd = dd < mdd ? dd : mdd;
-        prev = v;
-    }
-    const double mean = n >= 1 ? sum / (double)n : nan;
-    double sd = nan;
-    if (n >= 2) {
-        double ss = 0.0;
-        prev = first;
-        for (int k = 1; k < len; ++k) {
-            const double v = a[(size_t)k * E];
-            const double d = (v / prev - 1.0) - mean;
-            ss = ss + d * d;
-            prev = v;
-        }
-        sd = sqrt(ss / (double)(n - 1));
-    }
-    out[FINENV_HM_N_RETURNS] = (double)n;
-    out[FINENV_HM_CUMULATIVE_RETURN] = prev / first - 1.0;
-    out[FINENV_HM_MEAN] = mean;
-    out[FINENV_HM_STD] = sd;
-    out[FINENV_HM_SHARPE] = (n >= 2 && sd != 0.0) ? p.annualization * mean / sd : nan;
-    out[FINENV_HM_MAX_DRAWDOWN] = mdd;
+    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
+                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
+                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
 }
 
 }  // namespace
@@ -550,9 +515,7 @@ int finenv_stock_set_windows(finenv_stock *h, int32_t *win)
 int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->last)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "last_episode_stats: no last-episode block set");
-    if (const int rc = finenv_host::ready(h, "last_episode_stats")) return rc;
+    if (const int rc = finenv_host::ready_last_episode(h, "last_episode_stats")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     Params p = make_params(h);
     p.stats_out = out;
@@ -565,26 +528,14 @@ int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream)
 int finenv_stock_set_history(finenv_stock *h, const finenv_stock_history *hist)
 {
     if (!h) return FINENV_ERR_INVALID;
-    if (!hist) {
-        h->has_hist = 0;
-        memset(&h->hist, 0, sizeof(h->hist));
-        return FINENV_OK;
-    }
-    if (!hist->asset || !hist->row || !hist->len || !hist->flags)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: null asset/row/len/flags");
-    if (hist->capacity < 2)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
-    h->hist = *hist;
-    h->has_hist = 1;
-    return FINENV_OK;
+    const bool missing = hist && (!hist->asset || !hist->row || !hist->len || !hist->flags);
+    return finenv_host::set_history(h, h->hist, h->has_hist, hist,
+                                    missing ? "set_history: null asset/row/len/flags" : nullptr);
 }
 
 int finenv_stock_history_arm(finenv_stock *h, const uint8_t *mask, void *stream)
 {
-    if (!h) return FINENV_ERR_INVALID;
-    if (!h->has_hist)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_arm: no history attached");
-    if (const int rc = finenv_host::ready(h, "history_arm")) return rc;
+    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     launch_history_arm(h, mask, (hipStream_t)stream);
     return finenv_host::check_launch(h, "stock_history_arm");
@@ -593,9 +544,7 @@ int finenv_stock_history_arm(finenv_stock *h, const uint8_t *mask, void *stream)
 int finenv_stock_history_metrics(finenv_stock *h, double annualization, double *out, void *stream)
 {
     if (!h || !out) return FINENV_ERR_INVALID;
-    if (!h->has_hist)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "history_metrics: no history attached");
-    if (const int rc = finenv_host::ready(h, "history_metrics")) return rc;
+    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
     HistoryArgs a = make_history_args(h);
     a.out = out;

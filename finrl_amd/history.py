@@ -107,15 +107,42 @@ def portfolio_action_memory_frame(dates, tickers, weights, row, length):
 
 
 # ---------------------------------------------------------------------- the device side
-def _env_list(e):
-    """(single?, [env, ...]) of an env selection: one index, or a sequence of them."""
-    one = isinstance(e, (int, np.integer))
-    return one, ([int(e)] if one else [int(x) for x in e])
-
-
 class _Record:
-    """What the two device-resident records share: the flag views and the masked arm call (``env``,
-    ``flags`` are the subclass's)."""
+    """A device-resident episode record: what ``EpisodeHistory`` and ``PortfolioEpisodeHistory`` are made
+    of.  A subclass declares its data:
+      ``_ptrs_cls``    the ctypes struct of finenv_<kind>_set_history (one pointer per tensor, capacity)
+      ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]
+      ``_per_ticker``  (name, dtype, rows short of capacity): the optional tensor [capacity - short, E, N]
+      ``metric_keys``  the columns of ``metrics()``
+    """
+
+    def __init__(self, env, capacity, per_ticker=True):
+        torch = _torch()
+        E, N, dev = env.num_envs, env.stock_dim, env.device
+        capacity = int(capacity)
+        if capacity < 2:
+            raise ValueError("history capacity must be >= 2")
+        self.env, self.capacity = env, capacity
+        for name, dtype in self._series:
+            setattr(self, name, torch.zeros(capacity, E, dtype=getattr(torch, dtype), device=dev))
+        name, dtype, short = self._per_ticker
+        setattr(self, name, torch.zeros(capacity - short, E, N, dtype=getattr(torch, dtype), device=dev)
+                if per_ticker else None)
+        self.length = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.flags = torch.zeros(E, dtype=torch.int32, device=dev)
+        self._metrics = None
+        self._ptrs = self._ptrs_cls(*(None if t is None else t.data_ptr() for t in self._tensors()),
+                                    capacity)
+        env._call("set_history", C.byref(self._ptrs))
+        self.arm()
+
+    def _tensors(self):
+        """The tensors in the pointer struct's field order (None: the per-ticker one, disabled)."""
+        return [getattr(self, "length" if f == "len" else f) for f, _ in self._ptrs_cls._fields_[:-1]]
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self._tensors() if t is not None)
 
     @property
     def complete(self):
@@ -128,7 +155,10 @@ class _Record:
         missing."""
         return (self.flags & nat.HIST_OVERFLOW) != 0
 
-    def _arm(self, mask):
+    def arm(self, mask=None):
+        """Start a new record for every env, or those with mask[e] != 0, from its CURRENT state: one
+        entry (the class docstring says what it holds), flags cleared (finenv_<kind>_history_arm).  No
+        host synchronisation."""
         mptr = None
         if mask is not None:
             torch = _torch()
@@ -137,6 +167,50 @@ class _Record:
             mask = mask.to(device=self.env.device, dtype=torch.uint8).contiguous()
             mptr = C.c_void_p(mask.data_ptr())
         self.env._call("history_arm", mptr, self.env._stream())
+
+    def metrics(self, annualization=252 ** 0.5):
+        """Backtest figures of the recorded series -> f64 [E, 6] device tensor, columns ``metric_keys``
+        (n_returns, cumulative_return, mean, std, sharpe, max_drawdown); finenv_<kind>_history_metrics.
+        ``252 ** 0.5`` gives the env's terminal printout (env_stocktrading.py:243-251,
+        env_portfolio.py:145-152), ``4 ** 0.5`` get_validation_sharpe's figure.  The stock env's returns
+        are ``asset.pct_change()``, so ``n_returns`` is ``length - 1``; the portfolio env's are the
+        recorded ones with their leading 0, so it is ``length``.  Sharpe is NaN with fewer than two
+        returns or zero std; rows of unarmed envs are NaN.  The tensor is reused by the next call."""
+        if self._metrics is None:
+            self._metrics = _torch().zeros(self.env.num_envs, len(self.metric_keys),
+                                           dtype=_torch().float64, device=self.env.device)
+        self.env._call("history_metrics", float(annualization), C.c_void_p(self._metrics.data_ptr()),
+                       self.env._stream())
+        return self._metrics
+
+    def metrics_dict(self, annualization=252 ** 0.5):
+        """``metrics()`` as ``{name: f64 [E] device tensor}``."""
+        m = self.metrics(annualization)
+        return {k: m[:, j] for j, k in enumerate(self.metric_keys)}
+
+    # ------------------------------------------------------------------ frames
+    def _host(self, envs, names):
+        """Host copies of the selected envs' columns, ``{"length": ..., name: ...}``: one device-to-host
+        copy per tensor."""
+        torch = _torch()
+        idx = torch.as_tensor(envs, dtype=torch.int64, device=self.env.device)
+        out = {"length": self.length.index_select(0, idx).cpu().numpy()}
+        for k in names:
+            t = getattr(self, k)
+            if t is None:
+                raise nat.FinenvError(f"this history was enabled with {k}=False")
+            out[k] = t.index_select(1, idx).cpu().numpy()
+        return out
+
+    def _frames(self, e, build, *names, tickers=False):
+        """``e`` -> host columns -> frame(s): ``build(dates, [tickers,] *columns, length)`` for one env
+        index (a frame) or a sequence of them (a list of frames)."""
+        one = isinstance(e, (int, np.integer))
+        envs = [int(e)] if one else [int(x) for x in e]
+        h, panel = self._host(envs, names), self.env.panel
+        head = (panel.dates, panel.tickers) if tickers else (panel.dates,)
+        out = [build(*head, *(h[k][:, j] for k in names), h["length"][j]) for j in range(len(envs))]
+        return out[0] if one else out
 
 
 class EpisodeHistory(_Record):
@@ -151,63 +225,19 @@ class EpisodeHistory(_Record):
 
     A record starts when its env is armed -- by the constructor's init, by ``env.reset(mask)`` for the
     envs it resets, or by ``arm(mask)`` from the env's current state -- and ends on the step that
-    reports ``done`` (``complete``).  An auto-reset inside ``step`` does not arm: the finished
-    episode stays readable until the next host reset or ``arm``.  The pointers are launch arguments, so
-    a captured graph records only if the history was enabled before the capture.
+    reports ``done`` (``complete``).  Its first entry is asset_memory[0] at the start of an episode,
+    else the current total asset, and the current date.  An auto-reset inside ``step`` does not arm: the
+    finished episode stays readable until the next host reset or ``arm``.  The pointers are launch
+    arguments, so a captured graph records only if the history was enabled before the capture.
     """
 
+    _ptrs_cls, metric_keys = nat.StockHistoryPtrs, METRIC_KEYS
+    _series, _per_ticker = (("asset", "float64"), ("row", "int32")), ("actions", "int32", 1)
+
     def __init__(self, env, capacity, actions=True):
-        torch = _torch()
-        E, N = env.num_envs, env.stock_dim
-        capacity = int(capacity)
-        if capacity < 2:
-            raise ValueError("history capacity must be >= 2")
-        self.env, self.capacity = env, capacity
-        dev = env.device
-        self.asset = torch.zeros(capacity, E, dtype=torch.float64, device=dev)
-        self.row = torch.zeros(capacity, E, dtype=torch.int32, device=dev)
-        self.actions = torch.zeros(capacity - 1, E, N, dtype=torch.int32, device=dev) if actions else None
-        self.length = torch.zeros(E, dtype=torch.int32, device=dev)
-        self.flags = torch.zeros(E, dtype=torch.int32, device=dev)
-        self._metrics = None
+        super().__init__(env, capacity, actions)
         if actions:
             env.enable_realised()
-        self._ptrs = nat.StockHistoryPtrs(
-            self.asset.data_ptr(), self.row.data_ptr(),
-            self.actions.data_ptr() if actions else None,
-            self.length.data_ptr(), self.flags.data_ptr(), capacity)
-        env._call("set_history", C.byref(self._ptrs))
-        self.arm()
-
-    @property
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in
-                   (self.asset, self.row, self.actions, self.length, self.flags) if t is not None)
-
-    def arm(self, mask=None):
-        """Start a new record for every env, or those with mask[e] != 0, from its CURRENT state: one
-        entry (asset_memory[0] at the start of an episode, else the current total asset; the current
-        date), flags cleared (finenv_stock_history_arm).  No host synchronisation."""
-        self._arm(mask)
-
-    def metrics(self, annualization=252 ** 0.5):
-        """Backtest figures of the recorded series -> f64 [E, 6] device tensor, columns ``METRIC_KEYS``
-        (n_returns, cumulative_return, mean, std, sharpe, max_drawdown); finenv_stock_history_metrics.
-        ``252 ** 0.5`` gives the env's terminal printout (:243-251), ``4 ** 0.5``
-        get_validation_sharpe's figure.  Sharpe is NaN with fewer than two returns or zero std; rows of
-        unarmed envs are NaN.  The tensor is reused by the next call."""
-        torch = _torch()
-        if self._metrics is None:
-            self._metrics = torch.zeros(self.env.num_envs, len(METRIC_KEYS), dtype=torch.float64,
-                                        device=self.env.device)
-        self.env._call("history_metrics", float(annualization), C.c_void_p(self._metrics.data_ptr()),
-                       self.env._stream())
-        return self._metrics
-
-    def metrics_dict(self, annualization=252 ** 0.5):
-        """``metrics()`` as ``{name: f64 [E] device tensor}``."""
-        m = self.metrics(annualization)
-        return {k: m[:, j] for j, k in enumerate(METRIC_KEYS)}
 
     def validation_sharpe(self):
         """get_validation_sharpe (models.py:214-230) of every env's record -> host f64 [E]: ``inf`` /
@@ -215,44 +245,18 @@ class EpisodeHistory(_Record):
         m = self.metrics(4 ** 0.5).cpu().numpy()
         return validation_sharpe_from(m[:, METRIC_KEYS.index("mean")], m[:, METRIC_KEYS.index("std")])
 
-    # ------------------------------------------------------------------ frames
-    def _host(self, envs, with_actions):
-        """Host copies of the selected envs' columns: one device-to-host copy per tensor."""
-        torch = _torch()
-        idx = torch.as_tensor(envs, dtype=torch.int64, device=self.env.device)
-        length = self.length.index_select(0, idx).cpu().numpy()
-        asset = self.asset.index_select(1, idx).cpu().numpy()
-        row = self.row.index_select(1, idx).cpu().numpy()
-        acts = None
-        if with_actions:
-            if self.actions is None:
-                raise nat.FinenvError("this history was enabled with actions=False")
-            acts = self.actions.index_select(1, idx).cpu().numpy()
-        return length, asset, row, acts
-
-    def _frames(self, e, build, with_actions=False):
-        one, envs = _env_list(e)
-        length, asset, row, acts = self._host(envs, with_actions)
-        out = [build(j, int(length[j]), asset, row, acts) for j in range(len(envs))]
-        return out[0] if one else out
-
     def save_asset_memory(self, e):
         """The reference's save_asset_memory() frame of env ``e`` (a list of frames for a list of
         envs)."""
-        dates = self.env.panel.dates
-        return self._frames(e, lambda j, n, a, r, _: asset_memory_frame(dates, a[:, j], r[:, j], n))
+        return self._frames(e, asset_memory_frame, "asset", "row")
 
     def save_action_memory(self, e):
         """The reference's save_action_memory() frame of env ``e`` (a list for a list of envs)."""
-        dates, tickers = self.env.panel.dates, self.env.panel.tickers
-        return self._frames(
-            e, lambda j, n, a, r, acts: action_memory_frame(dates, tickers, acts[:, j], r[:, j], n),
-            with_actions=True)
+        return self._frames(e, action_memory_frame, "actions", "row", tickers=True)
 
     def account_value_frame(self, e):
         """The frame behind account_value_*.csv of env ``e`` (a list for a list of envs)."""
-        dates = self.env.panel.dates
-        return self._frames(e, lambda j, n, a, r, _: account_value_frame(dates, a[:, j], r[:, j], n))
+        return self._frames(e, account_value_frame, "asset", "row")
 
 
 class PortfolioEpisodeHistory(_Record):
@@ -270,90 +274,23 @@ class PortfolioEpisodeHistory(_Record):
       ``flags``    i32 [E]               bit 0 complete, bit 1 overflow (``complete`` / ``overflow``)
 
     Armed by the constructor (from the env's current state), by ``env.reset(mask)`` for the envs it
-    resets and by ``arm(mask)``; final on the step that reports ``done``.  An auto-reset inside ``step``
-    does not arm.  The pointers are launch arguments: enable the history before capturing a graph.
+    resets and by ``arm(mask)``; final on the step that reports ``done``.  The first entry is the current
+    portfolio value, return 0, the current date and weights 1/N.  An auto-reset inside ``step`` does not
+    arm.  The pointers are launch arguments: enable the history before capturing a graph.
     """
 
+    _ptrs_cls, metric_keys = nat.PortfolioHistoryPtrs, PORTFOLIO_METRIC_KEYS
+    _series = (("value", "float64"), ("ret", "float64"), ("row", "int32"))
+    _per_ticker = ("weights", "float32", 0)
+
     def __init__(self, env, capacity, weights=True):
-        torch = _torch()
-        E, N = env.num_envs, env.stock_dim
-        capacity = int(capacity)
-        if capacity < 2:
-            raise ValueError("history capacity must be >= 2")
-        self.env, self.capacity = env, capacity
-        dev = env.device
-        self.value = torch.zeros(capacity, E, dtype=torch.float64, device=dev)
-        self.ret = torch.zeros(capacity, E, dtype=torch.float64, device=dev)
-        self.row = torch.zeros(capacity, E, dtype=torch.int32, device=dev)
-        self.weights = torch.zeros(capacity, E, N, dtype=torch.float32, device=dev) if weights else None
-        self.length = torch.zeros(E, dtype=torch.int32, device=dev)
-        self.flags = torch.zeros(E, dtype=torch.int32, device=dev)
-        self._metrics = None
-        self._ptrs = nat.PortfolioHistoryPtrs(
-            self.value.data_ptr(), self.ret.data_ptr(), self.row.data_ptr(),
-            self.weights.data_ptr() if weights else None,
-            self.length.data_ptr(), self.flags.data_ptr(), capacity)
-        env._call("set_history", C.byref(self._ptrs))
-        self.arm()
-
-    @property
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in
-                   (self.value, self.ret, self.row, self.weights, self.length, self.flags)
-                   if t is not None)
-
-    def arm(self, mask=None):
-        """Start a new record for every env, or those with mask[e] != 0, from its CURRENT state: one
-        entry (the current portfolio value, return 0, the current date, weights 1/N), flags cleared
-        (finenv_portfolio_history_arm).  No host synchronisation."""
-        self._arm(mask)
-
-    def metrics(self, annualization=252 ** 0.5):
-        """Backtest figures of the recorded series -> f64 [E, 6] device tensor, columns
-        ``PORTFOLIO_METRIC_KEYS`` (finenv_portfolio_history_metrics): mean / std / Sharpe over the
-        recorded returns with their leading 0, as the env's terminal printout takes them (:145-152),
-        so ``n_returns`` is ``length`` (one more than the stock env's convention).  Sharpe is NaN with
-        fewer than two entries or zero std; rows of unarmed envs are NaN.  Reused by the next call."""
-        torch = _torch()
-        if self._metrics is None:
-            self._metrics = torch.zeros(self.env.num_envs, len(PORTFOLIO_METRIC_KEYS),
-                                        dtype=torch.float64, device=self.env.device)
-        self.env._call("history_metrics", float(annualization), C.c_void_p(self._metrics.data_ptr()),
-                       self.env._stream())
-        return self._metrics
-
-    def metrics_dict(self, annualization=252 ** 0.5):
-        """``metrics()`` as ``{name: f64 [E] device tensor}``."""
-        m = self.metrics(annualization)
-        return {k: m[:, j] for j, k in enumerate(PORTFOLIO_METRIC_KEYS)}
-
-    # ------------------------------------------------------------------ frames
-    def _host(self, envs, names):
-        """Host copies of the selected envs' columns: one device-to-host copy per tensor."""
-        torch = _torch()
-        idx = torch.as_tensor(envs, dtype=torch.int64, device=self.env.device)
-        out = {"length": self.length.index_select(0, idx).cpu().numpy()}
-        for k in names:
-            t = getattr(self, k)
-            if t is None:
-                raise nat.FinenvError("this history was enabled with weights=False")
-            out[k] = t.index_select(1, idx).cpu().numpy()
-        return out
+        super().__init__(env, capacity, weights)
 
     def save_asset_memory(self, e):
         """The reference's save_asset_memory() frame ``{date, daily_return}`` of env ``e`` (a list of
         frames for a list of envs)."""
-        one, envs = _env_list(e)
-        h, dates = self._host(envs, ("ret", "row")), self.env.panel.dates
-        out = [portfolio_asset_memory_frame(dates, h["ret"][:, j], h["row"][:, j], h["length"][j])
-               for j in range(len(envs))]
-        return out[0] if one else out
+        return self._frames(e, portfolio_asset_memory_frame, "ret", "row")
 
     def save_action_memory(self, e):
         """The reference's save_action_memory() frame of env ``e`` (a list for a list of envs)."""
-        one, envs = _env_list(e)
-        h = self._host(envs, ("weights", "row"))
-        dates, tickers = self.env.panel.dates, self.env.panel.tickers
-        out = [portfolio_action_memory_frame(dates, tickers, h["weights"][:, j], h["row"][:, j],
-                                             h["length"][j]) for j in range(len(envs))]
-        return out[0] if one else out
+        return self._frames(e, portfolio_action_memory_frame, "weights", "row", tickers=True)

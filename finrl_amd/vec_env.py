@@ -26,6 +26,16 @@ def _torch():
     return torch
 
 
+def _indices(env, indices):
+    """SB3 ``VecEnv._get_indices`` over ``env.num_envs``: None -> all envs, int -> [int], else the
+    iterable."""
+    if indices is None:
+        return list(range(env.num_envs))
+    if isinstance(indices, (int, np.integer)):
+        return [int(indices)]
+    return [int(i) for i in indices]
+
+
 class _EpisodeWindows(BatchedEnv):
     """Per-env episode windows and the last-episode latch of a panel-driven batch: the host side
     shared by VecStockTradingEnv and VecStockPortfolioEnv (``num_envs``, ``panel.T`` and
@@ -119,12 +129,18 @@ class _EpisodeWindows(BatchedEnv):
             raise nat.FinenvError(f"{what}: call enable_history() first")
         return self.history
 
-    def _env_indices(self, indices):
-        if indices is None:
-            return list(range(self.num_envs))
-        if isinstance(indices, (int, np.integer)):
-            return [int(indices)]
-        return [int(i) for i in indices]
+    def save_asset_memory(self, indices=None):
+        """The reference's save_asset_memory() frames (env_stocktrading.py:517-525; for the portfolio env
+        ``{date, daily_return}``, env_portfolio.py:231-239), one per selected env (all by default).
+        Always a list, also for a single index (``self.history.save_asset_memory(e)`` gives the bare
+        frame).  Needs enable_history()."""
+        return self._history("save_asset_memory").save_asset_memory(_indices(self, indices))
+
+    def save_action_memory(self, indices=None):
+        """The reference's save_action_memory() frames (env_stocktrading.py:527-543,
+        env_portfolio.py:241-252), one per selected env (all by default; always a list).  Needs
+        enable_history() with actions / weights."""
+        return self._history("save_action_memory").save_action_memory(_indices(self, indices))
 
     def _init_last(self, last):
         """Hook: edit a new last-episode block before it is attached."""
@@ -305,16 +321,6 @@ class VecStockTradingEnv(_EpisodeWindows):
                 self, self.max_step + 1 if capacity is None else capacity, actions)
         return self.history
 
-    def save_asset_memory(self, indices=None):
-        """The reference's save_asset_memory() frames (:517-525), one per selected env (all by
-        default).  Needs enable_history()."""
-        return self._history("save_asset_memory").save_asset_memory(self._env_indices(indices))
-
-    def save_action_memory(self, indices=None):
-        """The reference's save_action_memory() frames (:527-543), one per selected env (all by
-        default).  Needs enable_history() with actions."""
-        return self._history("save_action_memory").save_action_memory(self._env_indices(indices))
-
     # ------------------------------------------------------------------ env protocol
     # reset() (:359-393) and step() (:220-357) are BatchedEnv's
     def refresh(self):
@@ -428,20 +434,12 @@ class SB3VecEnvAdapter:
         obs = self.env.observe() if hasattr(self.env, "observe") else self.env.obs
         return obs.cpu().numpy()
 
-    def _indices(self, indices):
-        """SB3 ``VecEnv._get_indices``: None -> all envs, int -> [int], else the iterable."""
-        if indices is None:
-            return list(range(self.num_envs))
-        if isinstance(indices, (int, np.integer)):
-            return [int(indices)]
-        return [int(i) for i in indices]
-
     def env_is_wrapped(self, wrapper_class, indices=None):
-        return [False] * len(self._indices(indices))
+        return [False] * len(_indices(self, indices))
 
     def get_attr(self, attr_name, indices=None):
         v = getattr(self.env, attr_name)
-        return [v] * len(self._indices(indices))
+        return [v] * len(_indices(self, indices))
 
     def set_attr(self, attr_name, value, indices=None):
         setattr(self.env, attr_name, value)
@@ -451,7 +449,7 @@ class SB3VecEnvAdapter:
         agents/stablebaselines3/models.py:120-121).  The batch is one object, so the method
         runs once and its result is repeated per selected env."""
         r = getattr(self.env, method_name)(*method_args, **method_kwargs)
-        return [r] * len(self._indices(indices))
+        return [r] * len(_indices(self, indices))
 
 
 class SingleEnvVecAdapter:

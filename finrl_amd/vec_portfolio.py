@@ -88,18 +88,6 @@ class VecStockPortfolioEnv(_EpisodeWindows):
                 self, self.max_step + 1 if capacity is None else capacity, weights)
         return self.history
 
-    def save_asset_memory(self, indices=None):
-        """The reference's save_asset_memory() frames ``{date, daily_return}`` (:231-239), one per
-        selected env (all by default).  Always a list, also for a single index (as
-        VecStockTradingEnv does; ``self.history.save_asset_memory(e)`` gives the bare frame).  Needs
-        enable_history()."""
-        return self._history("save_asset_memory").save_asset_memory(self._env_indices(indices))
-
-    def save_action_memory(self, indices=None):
-        """The reference's save_action_memory() frames (:241-252), one per selected env (all by
-        default; always a list).  Needs enable_history() with weights."""
-        return self._history("save_action_memory").save_action_memory(self._env_indices(indices))
-
     def _init_last(self, last):
         """While a last-episode block is attached, every step also keeps running return sums
         (``run_sum`` / ``run_sumsq``); they start at 0 for envs on day 0 and at NaN for envs in mid

@@ -1,24 +1,28 @@
 #!/usr/bin/env python3
-"""Cost of the stock env's episode history (VecStockTradingEnv.enable_history) on bench.py's headline
-workload: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows.  ONE process, ONE env; the
-variants alternate inside every round, each timed with HIP events over steps that all record:
+"""Cost of the episode history (enable_history) of the batched stock or portfolio env on bench.py's
+workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows.  ONE process, ONE
+env; the variants alternate inside every round, each timed with HIP events over steps that all record:
   a  history detached (the step path of a build without the feature)
-  b  history attached, actions=False        (+12 B written per env and step)
-  c  history attached, actions=True         (+12 + 4N B; the step kernel also writes `realised`)
-  d  history detached, one state_numpy() after every step: the host copy the history replaces
-usage: python3 tools/bench_history.py <lockstep|desync> [--variants a,b,c,d] [--rounds R] [--envs E]
-                                      [--json PATH]
+  b  history attached without the per-ticker tensor (actions=False / weights=False)
+       stock +12 B written per env and step; portfolio +20 B written, 8 B read
+  c  history attached with it: stock +12 + 4N B (the step kernel also writes `realised`);
+       portfolio +20 + 4N B written
+  d  history detached, the host copy the history replaces after every step: one state_numpy()
+     (portfolio: and one weights.cpu())
+usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio] [--variants a,b,c,d]
+                                      [--rounds R] [--envs E] [--json PATH]
   lockstep  every env on the window [0, 63): one record row per step, written contiguously
-  desync    random 63-day windows, hint_desynchronised(True), and a random half of the envs restarted
-            31 steps after the others: neighbouring envs sit on different panel rows AND on different
-            record rows
+  desync    random 63-day windows (stock: with hint_desynchronised(True)) and a random half of the envs
+            restarted 31 steps after the others: neighbouring envs sit on different panel rows AND on
+            different record rows
 A round of a variant is: reset (arms every record), [desync: 31 steps, reset of a random half],
 then the timed steps -- 62 (lockstep) or 31 (desync), none of them terminal, so every env records on
-every timed step.  Rounds default to what gives at least 200 timed steps per variant.
+every timed step (asserted).  Rounds default to what gives at least 200 timed steps per variant.
 FINENV_LIB=<libfinenv.so of another build> times that build; one without the history entry points
-can run variant a only (that is how the parent commit is measured with this same script).
+can run variant a only (that is how a commit before the feature is measured with this same script).
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/bench_history.py lockstep --variants c` the
-kernel stats give stock_history_record_kernel's own time; record_bytes() below is what it moves."""
+kernel stats give stock_history_record_kernel's own time (record_bytes() below is what it moves);
+with `--env portfolio`, the recording instantiation's of the step kernel."""
 import argparse
 import ctypes as C
 import json
@@ -41,6 +45,7 @@ def record_bytes(N, actions):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("case", choices=("lockstep", "desync"))
+    ap.add_argument("--env", choices=("stock", "portfolio"), default="stock")
     ap.add_argument("--variants", default="a,b,c,d")
     ap.add_argument("--rounds", type=int, default=0)
     ap.add_argument("--envs", type=int, default=65536)
@@ -56,17 +61,19 @@ def main():
     dev = torch.device("cuda", 0)
     E = o.envs
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=False, no_stats=False,
-                              env="stock", tickers=30, turbulence_pct=None))()
+                              env=o.env, tickers=30, turbulence_pct=None))()
     w = bench.build_workload(args, torch, dev, 0)
     env, N = w.env, w.env.stock_dim
-    has_api = hasattr(nat.lib(), "finenv_stock_set_history")
+    stock = o.env == "stock"
+    has_api = hasattr(nat.lib(), f"finenv_{o.env}_set_history")
     if not has_api and variants != ["a"]:
-        sys.exit("bench_history: this libfinenv.so has no episode history; it can run --variants a only")
+        sys.exit(f"bench_history: this libfinenv.so has no {o.env} history; it can run --variants a only")
     desync = o.case == "desync"
     gen = torch.Generator(device=dev).manual_seed(7)
     if desync:
         env.set_windows(*random_windows(env.panel.T, E, WINDOW, generator=gen, device=dev))
-        env.hint_desynchronised(True)
+        if stock:
+            env.hint_desynchronised(True)
     else:
         env.set_windows(0, WINDOW)
     timed = 31 if desync else WINDOW - 1
@@ -75,16 +82,22 @@ def main():
 
     hists = {}
     if has_api:
-        from finrl_amd.history import EpisodeHistory
-        for v, acts in (("b", False), ("c", True)):
+        from finrl_amd.history import EpisodeHistory, PortfolioEpisodeHistory
+        for v, per_ticker in (("b", False), ("c", True)):
             if v in variants:
-                hists[v] = EpisodeHistory(env, WINDOW, actions=acts)
-    realised = env.realised                     # enabled by variant c's history; passed to its steps only
+                hists[v] = EpisodeHistory(env, WINDOW, actions=per_ticker) if stock else \
+                    PortfolioEpisodeHistory(env, WINDOW, weights=per_ticker)
+    # the step's optional per-ticker output: stock `realised`, enabled by variant c's history and passed
+    # to its steps only; portfolio `weights`, variant d's host copy
+    extra, extra_v = ("realised", "c") if stock else ("weights", "d")
+    if not stock and "d" in variants:
+        env.enable_weights()
+    extra_out = getattr(env, extra)
 
     def select(v):
         if has_api:
             env._call("set_history", C.byref(hists[v]._ptrs) if v in hists else None)
-        env.realised = realised if v == "c" else None
+        setattr(env, extra, extra_out if v == extra_v else None)
         env._step_args = None                   # BatchedEnv.step caches the output pointers
 
     def one_round(v, record):
@@ -102,6 +115,8 @@ def main():
             env.step(w.pool[(i + j) % len(w.pool)])
             if v == "d":
                 env.state_numpy()
+                if not stock:
+                    env.weights.cpu()
         e1.record()
         torch.cuda.synchronize()
         if record:
@@ -123,8 +138,11 @@ def main():
         t = sorted(times[v])
         res["us_per_step"][v] = round(t[len(t) // 2], 2)
         res["rounds_us"][v] = [round(x, 2) for x in times[v]]
-    res["added_bytes_per_env_step"] = {"b": 12, "c": 12 + 4 * N}
-    res["record_kernel_bytes_per_env_step"] = {"b": record_bytes(N, False), "c": record_bytes(N, True)}
+    if stock:
+        res["added_bytes_per_env_step"] = {"b": 12, "c": 12 + 4 * N}
+        res["record_kernel_bytes_per_env_step"] = {"b": record_bytes(N, False), "c": record_bytes(N, True)}
+    else:
+        res["added_bytes_written_per_env_step"] = {"b": 20, "c": 20 + 4 * N}
     line = json.dumps(res)
     print(line, flush=True)
     if o.json:
