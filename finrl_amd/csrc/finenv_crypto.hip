@@ -64,6 +64,9 @@ struct CrParams {
     const float *rec_src[3];      // actions (== actions), values, log-probs
     float *rec_dst[3];
     unsigned long long *dbg;      // FINENV_DIAG builds only: [wave][16] s_memrealtime stamps
+    // finenv_crypto_set_windows (the WIN instantiations; NULL otherwise)
+    int32_t *win;                 // [4][E]: pending start / end, active start / end
+    const double *norm_rows;      // [T][N]: the action normaliser of every panel row
 };
 
 #ifdef FINENV_DIAG
@@ -82,6 +85,14 @@ struct CrParams {
 #define CF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define CI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define STK(i) (*at(p.st.stocks, (unsigned)(i) * (unsigned)E + (unsigned)e))
+#define WINROW(r) (*at(p.win, (unsigned)(r) * (unsigned)E + (unsigned)e))
+
+// WIN: a panel row whose lookback rows all lie in the panel, whatever the time counter holds (a bad
+// window block is a wrong answer, never an access outside the panel)
+__device__ __forceinline__ int cr_row(int t, const finenv_crypto_config &cfg)
+{
+    return min(max(t, cfg.lookback - 1), cfg.n_steps - 1);
+}
 
 // rows[el*stride + 0] = f32(cash * 2^-18), rows[el*stride + 1 + i] = stocks_i * 2^-3   (:93)
 // columns >= 1 + N: tech_scaled[(t_el - l) * W + j]                              (:94-97)
@@ -114,7 +125,15 @@ __device__ __forceinline__ void cr_write_rows(float *__restrict__ dst, const CrP
 // its write-back at the end of the step, the streamer leaves as soon as its stores are issued.
 // (At 32,768 envs the env waves occupy half the chip's SIMDs and the step is one serial chain: assembling
 // and writing the whole rows was its last 2 us.)
-template <bool RESET_ONLY, int kWaves, int NP, bool TWO = false>
+// WIN: per-env episode windows (finenv_crypto_set_windows).  Env e runs the ACTIVE window [s_e, t_e) =
+// win[2][e], win[3][e]: done at time == t_e - lookback - 1, actions normalised by norm_rows[s_e]; a
+// reset (host or auto) first copies the PENDING window win[0][e], win[1][e] into the active rows and
+// restarts at its s_e + lookback - 1.  The active rows do not depend on `time`: they are loaded in
+// round trip 1 right behind the time counter, the normaliser row (which depends on s_e) goes out
+// with the price row in round trip 2 -- it is first needed after the action tile's transposition.
+// The streamer still reads nothing but LDS: the env wave publishes the row each env will SHOW (its
+// new time, or on an auto-reset its pending start row) instead of the raw time counter.
+template <bool RESET_ONLY, int kWaves, int NP, bool TWO = false, bool WIN = false>
 __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_kernel(const CrParams p)
 {
     constexpr int kRowW = NP + 1;                            // odd row stride of the LDS rows (dwords)
@@ -158,7 +177,8 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         const int max_step_s = p.cfg.n_steps - p.cfg.lookback - 1;           // :24
         const int time_s = tpub[lane];                                        // time + 1, :60
         const bool done_s = time_s == max_step_s;                             // :80
-        const int trow = (done_s && p.auto_reset) ? p.cfg.lookback - 1 : time_s;
+        // (WIN: the env wave has resolved and clamped the row, see the publish below)
+        const int trow = WIN ? time_s : ((done_s && p.auto_reset) ? p.cfg.lookback - 1 : time_s);
         const int W = p.cfg.n_tech;
         const bool act = lane < n_ind;
         const int c2 = act ? lane : 0;
@@ -191,7 +211,15 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
 
     if (RESET_ONLY) {                                       // reset(), :48-57
         const bool sel = valid && (p.mask == nullptr || p.mask[e] != 0);
-        const int t = p.cfg.lookback - 1;
+        int t = p.cfg.lookback - 1;
+        if (WIN) {                                          // pending -> active, restart on its start row
+            const int ps = WINROW(0), pt = WINROW(1);
+            t = min(max(ps, 0), p.cfg.n_steps - 1) + p.cfg.lookback - 1;
+            if (sel) {
+                WINROW(2) = ps;
+                WINROW(3) = pt;
+            }
+        }
         if (sel) {
             CI(FINENV_CI_TIME) = t;
             CF(FINENV_CF_CASH) = p.cfg.initial_cash;
@@ -202,7 +230,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         row[0] = (float)(p.cfg.initial_cash * 0x1p-18);
         for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
         wave_sync();
-        cr_write_rows(p.obs, p, e0, nenv_w, t, __ballot(sel), rows, kRowW, lane);
+        cr_write_rows(p.obs, p, e0, nenv_w, WIN ? cr_row(t, p.cfg) : t, __ballot(sel), rows, kRowW, lane);
         return;
     }
 
@@ -210,6 +238,11 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     // ---- round trip 1: everything that does not depend on `time`; the time counter first (loads
     // return in order: it is the one value the next round trip -- and the streamer -- wait for) ------
     const int time = CI(FINENV_CI_TIME) + 1;                                  // :60
+    int w_start = 0, w_last = 0;                            // WIN: active start row, end - 1
+    if (WIN) {
+        w_start = win_start(p.win + 2 * (size_t)E, e, p.cfg.n_steps);
+        w_last = win_last_day(p.win + 2 * (size_t)E, E, e, p.cfg.n_steps);
+    }
     double cash = CF(FINENV_CF_CASH);
     const double prev_asset = CF(FINENV_CF_TOTAL_ASSET);
     double gamma_ret = CF(FINENV_CF_GAMMA_RETURN);
@@ -218,7 +251,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         sv[i] = STK(min(i, N - 1));
-        nrm[i] = p.panel.norm[min(i, N - 1)];
+        if (!WIN) nrm[i] = p.panel.norm[min(i, N - 1)];
     }
     // action tile [nenv_w][N]: coalesced read (NP loads cover 64 x N values), transposed through LDS
     // once the second round trip is on its way
@@ -230,26 +263,42 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         const int f = j * kWave + lane;
         av[j] = *at(a_src, (unsigned)(f < a_total ? f : a_total - 1));
     }
+    // WIN: the row this env shows after the step -- its new time, or where an auto-reset restarts it
+    // (the pending start is read only in a step in which an env of the wave ends its episode)
+    int t_show = time;
+    if (WIN) {
+        const bool done_w = time == w_last - p.cfg.lookback;                  // :24, :80 on [s_e, t_e)
+        if (p.auto_reset && __any(done_w && valid)) {
+            const int ps = win_start(p.win, e, p.cfg.n_steps);
+            if (done_w) t_show = ps + p.cfg.lookback - 1;                      // :27, :49
+        }
+    }
     if (TWO) {
-        tpub[lane] = time;
+        tpub[lane] = WIN ? cr_row(t_show, p.cfg) : time;
         lds_barrier();                    // the streamer takes the time counters from here
     }
     CSTAMP(1);
-    const int max_step = p.cfg.n_steps - p.cfg.lookback - 1;                  // :24
+    const int max_step = WIN ? w_last - p.cfg.lookback : p.cfg.n_steps - p.cfg.lookback - 1;   // :24
     const bool done = time == max_step;                                       // :80
 
     // ---- round trip 2: the price row of the new time step (registers: sells, buys, asset sum) and
     // the indicator values of the observation row, issued together ---------------------------
-    const unsigned pb = (unsigned)(time * N);
+    const int trd = WIN ? cr_row(time, p.cfg) : time;       // the panel row read
+    const unsigned pb = (unsigned)(trd * N);
     double prc[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) prc[i] = *at(p.panel.price, pb + (unsigned)min(i, N - 1));
+    if (WIN) {                                              // the normaliser of the window's first row
+        const unsigned nb = (unsigned)(w_start * N);
+#pragma unroll
+        for (int i = 0; i < NP; ++i) nrm[i] = *at(p.norm_rows, nb + (unsigned)min(i, N - 1));
+    }
     const int D = p.D, W = p.cfg.n_tech;
     const int nchunk = (D + kWave - 1) / kWave;
-    const int t_first = __builtin_amdgcn_readfirstlane(time);
+    const int t_first = __builtin_amdgcn_readfirstlane(trd);
     // fast path of the observation write: every env of the wave shows the same row (lock-step and
     // nobody resets in this step) and the row fits kObsChunks chunks
-    const bool fast_obs = nchunk <= kObsChunks && __all(time == t_first) &&
+    const bool fast_obs = nchunk <= kObsChunks && __all(trd == t_first) &&
                           !(p.auto_reset && __any(done && valid));
     float tt[kObsChunks];
     int tsel[kObsChunks];
@@ -391,11 +440,16 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     double cash_out = cash, asset_out = next;
     if (done_mask != 0ull) {
         if (p.term_obs != nullptr)
-            cr_write_rows(p.term_obs, p, e0, nenv_w, time, done_mask, rows, kRowW, lane);
+            cr_write_rows(p.term_obs, p, e0, nenv_w, trd, done_mask, rows, kRowW, lane);
         if (p.auto_reset) {                                                   // reset(), :48-57
             wave_sync();
             if (done) {
-                t_row = p.cfg.lookback - 1;
+                t_row = WIN ? t_show : p.cfg.lookback - 1;
+                if (WIN && valid) {                                           // pending -> active
+                    const int ps = WINROW(0), pt = WINROW(1);
+                    WINROW(2) = ps;
+                    WINROW(3) = pt;
+                }
                 cash_out = p.cfg.initial_cash;
                 asset_out = p.cfg.initial_cash;
                 row[0] = (float)(p.cfg.initial_cash * 0x1p-18);
@@ -459,7 +513,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
             }
         }
     } else {
-        cr_write_rows(p.obs, p, e0, nenv_w, t_row, valid_mask, rows, kRowW, lane);
+        cr_write_rows(p.obs, p, e0, nenv_w, WIN ? cr_row(t_row, p.cfg) : t_row, valid_mask, rows, kRowW, lane);
     }
     CSTAMP(7);
     if (valid) {
@@ -477,6 +531,8 @@ struct finenv_crypto : finenv_host::Handle {
     finenv_crypto_panel panel;
     finenv_crypto_state st;
     uint32_t magicN, magicW, magicH, magicD;
+    int32_t *win;                 // finenv_crypto_set_windows
+    const double *norm_rows;
 };
 
 namespace {
@@ -492,10 +548,12 @@ CrParams cr_params(const finenv_crypto *h)
     p.magicW = h->magicW;
     p.magicH = h->magicH;
     p.magicD = h->magicD;
+    p.win = h->win;
+    p.norm_rows = h->norm_rows;
     return p;
 }
 constexpr int kSmallWaves = 2048;      // up to here: one env wave per block (spread over every CU)
-template <bool RESET_ONLY, int NP>
+template <bool RESET_ONLY, int NP, bool WIN>
 void cr_launch_np(const CrParams &p, hipStream_t stream)
 {
     const int waves = (p.cfg.n_envs + kWave - 1) / kWave;
@@ -509,10 +567,10 @@ void cr_launch_np(const CrParams &p, hipStream_t stream)
         const int rec_blocks = n4 > 0 ? min(512, (n4 + kWave * 16 - 1) / (kWave * 16)) : 0;
         q.env_blocks = n4 > 0 ? waves : 0;
         if (RESET_ONLY)
-            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, false>), dim3((unsigned)(waves + rec_blocks)),
+            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, false, WIN>), dim3((unsigned)(waves + rec_blocks)),
                                dim3(kWave), lds1, stream, q);
         else        // trader + streamer wave per 64 envs
-            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, true>), dim3((unsigned)(waves + rec_blocks)),
+            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, true, WIN>), dim3((unsigned)(waves + rec_blocks)),
                                dim3(2 * kWave), lds1, stream, q);
     } else {
         const int blocks = (waves + 3) / 4;
@@ -521,18 +579,24 @@ void cr_launch_np(const CrParams &p, hipStream_t stream)
         // Large batches are bandwidth-, not latency-bound: no streamer waves (a streamer is a wave of
         // the same kernel and would hold a full wave's registers: half the env waves' residency), the
         // env wave writes whole rows in the block form.
-        hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 4, NP, false>), dim3((unsigned)(blocks + rec_blocks)),
+        hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 4, NP, false, WIN>), dim3((unsigned)(blocks + rec_blocks)),
                            dim3(kWave * 4), 4 * lds1, stream, q);
     }
+}
+template <bool RESET_ONLY, bool WIN>
+void cr_launch_win(const CrParams &p, hipStream_t stream)
+{
+    if (RESET_ONLY) cr_launch_np<RESET_ONLY, 32, WIN>(p, stream);      // (no per-asset registers: one build)
+    else if (p.cfg.n_assets <= 8) cr_launch_np<RESET_ONLY, 8, WIN>(p, stream);
+    else if (p.cfg.n_assets <= 12) cr_launch_np<RESET_ONLY, 12, WIN>(p, stream);
+    else if (p.cfg.n_assets <= 16) cr_launch_np<RESET_ONLY, 16, WIN>(p, stream);
+    else cr_launch_np<RESET_ONLY, 32, WIN>(p, stream);
 }
 template <bool RESET_ONLY>
 void cr_launch(const CrParams &p, hipStream_t stream)
 {
-    if (RESET_ONLY) cr_launch_np<RESET_ONLY, 32>(p, stream);      // (no per-asset registers: one build)
-    else if (p.cfg.n_assets <= 8) cr_launch_np<RESET_ONLY, 8>(p, stream);
-    else if (p.cfg.n_assets <= 12) cr_launch_np<RESET_ONLY, 12>(p, stream);
-    else if (p.cfg.n_assets <= 16) cr_launch_np<RESET_ONLY, 16>(p, stream);
-    else cr_launch_np<RESET_ONLY, 32>(p, stream);
+    if (p.win != nullptr) cr_launch_win<RESET_ONLY, true>(p, stream);   // a window block is attached
+    else cr_launch_win<RESET_ONLY, false>(p, stream);
 }
 }  // namespace
 
@@ -572,6 +636,17 @@ int finenv_crypto_bind(finenv_crypto *h, const finenv_crypto_panel *panel,
         !st->i32 || !st->stocks)
         return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
     return finenv_host::bind(h, panel, st);
+}
+
+int finenv_crypto_set_windows(finenv_crypto *h, int32_t *win, const double *norm_rows)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    if (win != nullptr && norm_rows == nullptr)
+        return finenv_host::fail(h, FINENV_ERR_INVALID,
+                                 "set_windows: a window block needs the normaliser table (norm_rows)");
+    h->win = win;
+    h->norm_rows = win != nullptr ? norm_rows : nullptr;
+    return FINENV_OK;
 }
 
 int finenv_crypto_reset(finenv_crypto *h, const uint8_t *mask, float *obs_out, void *stream)

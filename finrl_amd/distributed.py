@@ -25,12 +25,14 @@ def shard_range(global_envs: int, rank: int, world: int):
 
 
 # constructor arguments that may be given per env ([E] / [E, N]) and are then sliced per rank
+# (and ``windows``, a pair of them: see shard_env_kwargs)
 _PER_ENV_KWARGS = ("initial_amount", "num_stock_shares", "initial_capital", "initial_stocks")
 
 
 def shard_env_kwargs(global_envs: int, rank: int, world: int, **kw):
-    """Slice per-env constructor arguments (e.g. initial_amount [E], num_stock_shares [E, N]) down
-    to this rank's envs; scalars / per-ticker vectors pass through unchanged."""
+    """Slice per-env constructor arguments (e.g. initial_amount [E], num_stock_shares [E, N], the
+    two halves of windows=(start [E], end [E])) down to this rank's envs; scalars / per-ticker
+    vectors pass through unchanged."""
     lo, hi = shard_range(global_envs, rank, world)
     out = dict(kw)
     for name in _PER_ENV_KWARGS:
@@ -38,6 +40,12 @@ def shard_env_kwargs(global_envs: int, rank: int, world: int, **kw):
         if v is not None and np.ndim(v) >= 1 and len(v) == global_envs and \
                 (np.ndim(v) == 2 or name in ("initial_amount", "initial_capital")):
             out[name] = np.asarray(v)[lo:hi]
+    if kw.get("windows") is not None:
+        # windows=(start, end): per-env [E] arrays / tensors (host or device) are sliced, one row
+        # for all envs passes through
+        out["windows"] = tuple(
+            x[lo:hi] if getattr(x, "ndim", 0) == 1 and len(x) == global_envs else x
+            for x in kw["windows"])
     return hi - lo, out
 
 

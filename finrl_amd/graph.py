@@ -43,8 +43,11 @@ class GraphedSegment:
             v.copy_(snap[k])
 
     def _state_tensors(self):
-        """The env's state blocks (finrl_amd.vec_base.BatchedEnv: None where the kind has none)."""
-        blocks = ((k, getattr(self.env, k, None)) for k in ("_f64", "_i32", "_f32"))
+        """The env's state blocks (finrl_amd.vec_base.BatchedEnv: None where the kind has none) and
+        its episode-window blocks, which a reset inside the warm-up (VecCryptoEnv: pending -> active)
+        or a policy that redraws windows writes."""
+        blocks = ((k, getattr(self.env, k, None))
+                  for k in ("_f64", "_i32", "_f32", "windows", "active_windows"))
         return {k: t for k, t in blocks if t is not None}
 
     def _segment(self, policy):

@@ -227,3 +227,111 @@ class BatchedEnv:
         for k in self._books:
             out[k] = np.ascontiguousarray(out[k].T)
         return out
+
+
+class WindowedEnv(BatchedEnv):
+    """Per-env episode windows over one shared panel: the host side of ``finenv_<kind>_set_windows``,
+    shared by VecStockTradingEnv, VecStockPortfolioEnv and VecCryptoEnv (``num_envs`` and
+    ``max_step`` are theirs).  What differs between the kinds is named by four hooks:
+    ``_window_rows`` (the panel's row count), ``_window_min`` (the shortest window that makes an
+    episode), ``_window_max_step`` (``max_step`` of the longest window) and ``_new_window_block``
+    (the device block the kernel reads; ``self.windows`` is its [2, E] start / end view)."""
+
+    windows = None
+    _window_min = 1
+
+    @property
+    def _window_rows(self):
+        return self.panel.T
+
+    def _window_max_step(self, longest):
+        return longest - 1
+
+    def _new_window_block(self):
+        """Allocate the block the kernel reads -> its [2, E] view of starts and ends, every env on
+        the whole panel."""
+        win = _torch().zeros(2, self.num_envs, dtype=_torch().int32, device=self.device)
+        win[1].fill_(self._window_rows)
+        return win
+
+    def _attach_windows(self, ptr):
+        self._call("set_windows", ptr)
+
+    def _check_window_starts(self, start):
+        """Hook: kind-specific host validation of the start rows (int64 [E])."""
+
+    def _check_windows(self, start, end):
+        """Host validation of (start, end) -> two int64 [E] arrays (ValueError when a window is too
+        short to make an episode or leaves the panel)."""
+        torch = _torch()
+        E, T = self.num_envs, self._window_rows
+        out = []
+        for x, what in ((start, "start"), (end, "end")):
+            if torch.is_tensor(x):
+                x = x.detach().cpu().numpy()
+            a = np.asarray(x)
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"windows: {what} must be integer panel rows")
+            try:
+                out.append(np.broadcast_to(a.astype(np.int64), (E,)))
+            except ValueError:
+                raise ValueError(f"windows: {what} must be one value or [{E}] values") from None
+        s, t = out
+        if (s < 0).any() or (t > T).any():
+            raise ValueError(f"windows must lie in [0, {T}] (the panel's rows)")
+        if (t <= s).any():
+            raise ValueError("windows must not be empty (start < end)")
+        if (t - s < self._window_min).any():
+            raise ValueError(f"windows must span at least {self._window_min} panel rows")
+        self._check_window_starts(s)
+        return s, t
+
+    def set_windows(self, start, end=None, mask=None):
+        """Per-env episode windows [start, end) of panel rows (finenv_<kind>_set_windows);
+        ``set_windows(None)`` detaches them (every env runs the whole panel again).
+
+        The windows live in ``self.windows``, an int32 [2, E] device tensor (row 0 starts, row 1
+        ends) whose address the step kernel takes as an argument; this call copies into it in place.
+        The stock and portfolio step kernels read an env's END on every step and its START only when
+        they reset the env, so an edited end applies from the next step and an edited start at the
+        env's next reset (auto-reset or ``reset()``); nothing moves an env that is mid-episode.  To
+        start the envs that just finished on new windows: ``set_windows(s, t, mask=done)`` then
+        ``reset(done)``.  (VecCryptoEnv takes both at the env's next reset: see
+        its own ``set_windows``.)
+
+        Host values (ints, arrays) are validated (ValueError on empty or out-of-range windows).
+        Device tensors are copied without a host synchronisation, so windows can be redrawn with
+        torch ops -- ``mask`` (bool [E]) limits the update to those envs, e.g. the ones that just
+        reported ``done`` -- even inside a captured graph (the graph sees the block's contents as
+        they are at each replay).  Those are NOT validated: the kernel clamps every window into
+        the panel, so a bad one gives wrong results, never a fault.  Attach windows before capturing
+        a graph: a graph keeps the pointer it was captured with.  ``max_step`` follows the windows
+        passed here (that of the longest), except device tensors passed during a capture."""
+        torch = _torch()
+        if start is None:
+            self._attach_windows(None)
+            self.windows = None
+            self.max_step = self._window_max_step(self._window_rows)
+            return None
+        if end is None:
+            raise ValueError("set_windows needs start and end")
+        on_device = all(torch.is_tensor(x) and x.device.type == "cuda" for x in (start, end))
+        if self.windows is None:
+            self.windows = self._new_window_block()
+        new = torch.empty_like(self.windows)
+        if on_device:
+            new[0].copy_(start.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
+            new[1].copy_(end.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
+        else:
+            s_np, t_np = self._check_windows(start, end)
+            new.copy_(torch.from_numpy(np.stack([s_np, t_np]).astype(np.int32)))
+        if mask is not None:
+            m = mask.to(device=self.device, dtype=torch.bool) if torch.is_tensor(mask) else \
+                torch.from_numpy(np.asarray(mask, dtype=bool)).to(self.device)
+            new = torch.where(m, new, self.windows)
+        self.windows.copy_(new)
+        self._attach_windows(C.c_void_p(self.windows.data_ptr()))
+        if not (on_device and torch.cuda.is_current_stream_capturing()):
+            self.max_step = self._window_max_step(
+                int((self.windows[1] - self.windows[0]).max().item()))
+        return self.windows

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _native as nat
 from .spaces import Box
-from .vec_base import BatchedEnv
+from .vec_base import WindowedEnv
 
 
 def action_norm_vector(price0):
@@ -22,9 +22,42 @@ def action_norm_vector(price0):
     return np.asarray(out) * 10000
 
 
-class VecCryptoEnv(BatchedEnv):
+def action_norm_table(price_array):
+    """``action_norm_vector`` of every row of ``price_array`` [T, N] -> f64 [T, N]: the table the
+    windowed step kernel indexes by an env's window start (finenv_crypto_set_windows).  Row r
+    equals ``action_norm_vector(price_array[r])`` bit for bit: the exponent is taken by the same
+    ``math.floor(math.log(price, 10))`` -- NOT ``np.log10``, which floors 1000.0 to 3 where
+    ``math.log(1000.0, 10)`` gives 2.9999999999999996 -- and the scale by the same Python
+    expression of that exponent.  A row with a price that is not positive and finite is all NaN,
+    with no exception: the reference raises on such a first row, and an env whose window starts
+    there makes no trades.  T * N calls of ``math.log``: about half a second for a month of
+    one-minute bars of ten pairs (43,200 x 10); built once per env."""
+    price = np.asarray(price_array, dtype=np.float64)
+    out = np.full(price.shape, np.nan)
+    scale = {}                                  # exponent -> 1 / 10 ** x * 10000, evaluated as above
+    ok = (np.isfinite(price) & (price > 0)).all(axis=1)
+    for r in np.flatnonzero(ok):
+        row = out[r]
+        for i, p in enumerate(price[r].tolist()):
+            x = math.floor(math.log(p, 10))
+            v = scale.get(x)
+            if v is None:
+                v = scale[x] = (np.asarray([1 / ((10) ** x)]) * 10000)[0]
+            row[i] = v
+    return out
+
+
+class VecCryptoEnv(WindowedEnv):
     """E parallel CryptoEnv.  Constructor mirrors the reference: ``config`` holds
-    ``price_array`` [T,N] and ``tech_array`` [T,W] (float64)."""
+    ``price_array`` [T,N] and ``tech_array`` [T,W] (float64).
+
+    ``windows=(start, end)`` gives every env its own episode window of panel rows ``[start, end)``
+    (one pair for all envs, or [E] arrays / tensors): env e then equals the reference env built on
+    ``{'price_array': price_array[s:t], 'tech_array': tech_array[s:t]}`` -- the tutorial's train and
+    test slices, or random training windows, in ONE batch over one panel -- including its action
+    normaliser, which the reference derives from the first row of the array it is given.
+    ``state["time"]`` stays the panel row; ``window_time()`` is the reference's ``self.time``.
+    See ``set_windows``."""
 
     env_name = "MulticryptoEnv-MI355X"
     if_discrete = False
@@ -35,7 +68,7 @@ class VecCryptoEnv(BatchedEnv):
                "f32": ((), ("stocks",))}
 
     def __init__(self, config, num_envs, *, lookback=1, initial_capital=1e6, buy_cost_pct=1e-3,
-                 sell_cost_pct=1e-3, gamma=0.99, auto_reset=True, device="cuda"):
+                 sell_cost_pct=1e-3, gamma=0.99, auto_reset=True, device="cuda", windows=None):
         import torch
         self._set_device(device)
         self.price_array = np.ascontiguousarray(config["price_array"], dtype=np.float64)
@@ -52,7 +85,12 @@ class VecCryptoEnv(BatchedEnv):
         self.gamma = gamma
         self.initial_cash = initial_capital
         self.auto_reset = bool(auto_reset)
-        self.action_norm_vector = action_norm_vector(self.price_array[0])
+        self._window_min = lookback + 2                   # the n_steps rule of finenv_crypto_create
+        self._norm_table = self._norm_rows = None
+        # (the handle-wide normaliser is that of panel row 0, where the reference raises on a price
+        #  <= 0; with windows nobody need start there, and row 0 of the table says the same or NaN)
+        self.action_norm_vector = action_norm_vector(self.price_array[0]) if windows is None \
+            else self.norm_table()[0].copy()
         self.observation_space = Box(-3000, 3000, (self.obs_dim,), np.float32)
         self.action_space = Box(-1, 1, (N,), np.float32)
         self._open(nat.CryptoConfig(E, N, W, T, lookback, 0, float(initial_capital),
@@ -67,6 +105,78 @@ class VecCryptoEnv(BatchedEnv):
         self.state["time"].fill_(lookback - 1)
         self._bind(self._price, self._tech, self._norm)
         self._alloc_outputs(E, self.obs_dim)
+        if windows is not None:                       # the constructor's episode: each on its own window
+            self.set_windows(*self._check_windows(*windows))
+            self.active_windows.copy_(self.windows)
+            self.state["time"].copy_(self.windows[0] + (lookback - 1))
+
+    # ------------------------------------------------------------------ episode windows
+    active_windows = None
+    _window_rows = property(lambda self: self.price_array.shape[0])
+
+    def _window_max_step(self, longest):
+        return longest - self.lookback - 1                                       # :24
+
+    def norm_table(self):
+        """``action_norm_table(price_array)``, f64 [T, N] on the host; built on first use."""
+        if self._norm_table is None:
+            self._norm_table = action_norm_table(self.price_array)
+        return self._norm_table
+
+    def _new_window_block(self):
+        """int32 [4, E]: rows 0, 1 the pending windows (``self.windows``, what the caller edits),
+        rows 2, 3 the active ones (``self.active_windows``, kernel-owned).  Both start on the whole
+        panel, which is what an env without windows is running."""
+        import torch
+        block = torch.zeros(4, self.num_envs, dtype=torch.int32, device=self.device)
+        block[1::2].fill_(self._window_rows)
+        self.active_windows = block[2:]
+        return block[:2]
+
+    def _attach_windows(self, ptr):
+        import torch
+        if ptr is not None and self._norm_rows is None:
+            self._norm_rows = torch.from_numpy(self.norm_table()).to(self.device)
+        self._call("set_windows", ptr,
+                   C.c_void_p(self._norm_rows.data_ptr()) if ptr is not None else None)
+
+    def _check_window_starts(self, start):
+        bad = np.isnan(self.norm_table()[start, 0])
+        if bad.any():
+            raise ValueError(f"windows: start row {int(start[np.argmax(bad)])} holds a price <= 0 "
+                             "(the reference's action normaliser raises there)")
+
+    def set_windows(self, start, end=None, mask=None):
+        """Per-env episode windows [start, end) of panel rows (finenv_crypto_set_windows), with the
+        arguments, validation and device-tensor rules of ``WindowedEnv.set_windows``; a window
+        needs ``lookback + 2`` rows and a start row whose prices are all positive (host values are
+        checked for both).  ``set_windows(None)`` detaches.
+
+        ``self.windows`` holds the PENDING windows: an env takes its pair at its next reset
+        (``reset()`` or the auto-reset inside ``step``) and runs the whole episode on it -- start,
+        end and the action normaliser of the start row -- whatever is written here meanwhile; the
+        running episodes' windows are in ``self.active_windows`` (kernel-owned, read-only for the
+        caller).  So windows can be redrawn for the envs that just finished with torch ops alone,
+        also inside a captured graph, with no reset launch::
+
+            obs, rew, done, _ = env.step(actions)          # auto-reset: took the pending windows
+            env.set_windows(*random_windows(T, E, L, device=dev), mask=done)   # for the one after
+
+        As in the reference's ``reset()``, ``gamma_return`` and ``episode_return`` survive a reset:
+        for "a fresh env object on a new slice" zero ``state["gamma_return"]`` of those envs.
+        Attaching windows to a running batch leaves every env on the whole panel until its next
+        reset.  ``max_step`` is that of the longest pending window."""
+        out = super().set_windows(start, end, mask)
+        if out is None:
+            self.active_windows = None
+        return out
+
+    def window_time(self):
+        """The reference's ``self.time`` of every env (int32 [E] device tensor): ``state["time"]``
+        minus the start row of the window its episode runs on."""
+        if self.active_windows is None:
+            return self.state["time"].clone()
+        return self.state["time"] - self.active_windows[0]
 
     def close(self):
         pass

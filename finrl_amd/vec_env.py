@@ -18,7 +18,7 @@ import numpy as np
 from . import _native as nat
 from .panel import StockPanel
 from .spaces import Box
-from .vec_base import BatchedEnv
+from .vec_base import BatchedEnv, WindowedEnv
 
 
 def _torch():
@@ -36,92 +36,16 @@ def _indices(env, indices):
     return [int(i) for i in indices]
 
 
-class _EpisodeWindows(BatchedEnv):
-    """Per-env episode windows and the last-episode latch of a panel-driven batch: the host side
-    shared by VecStockTradingEnv and VecStockPortfolioEnv (``num_envs``, ``panel.T`` and
-    ``max_step`` are theirs).  ``_last_fields`` is the kind's last-episode block layout,
-    ``_last_ratio`` its (begin, end) fields and ``last_episode_keys`` the last_episode_stats()
-    columns."""
+class _EpisodeWindows(WindowedEnv):
+    """Per-env episode windows (vec_base.WindowedEnv) and the last-episode latch of a panel-driven
+    batch: the host side shared by VecStockTradingEnv and VecStockPortfolioEnv (``num_envs``,
+    ``panel.T`` and ``max_step`` are theirs).  ``_last_fields`` is the kind's last-episode block
+    layout, ``_last_ratio`` its (begin, end) fields and ``last_episode_keys`` the
+    last_episode_stats() columns."""
 
-    windows = None
     history = None              # enable_history() of the subclass
     _last = _last_stats = last_episode = None
     _last_fields, _last_ratio, last_episode_keys = (), ("", ""), ()
-
-    def _attach_windows(self, ptr):
-        self._call("set_windows", ptr)
-
-    def _check_windows(self, start, end):
-        """Host validation of (start, end) -> two int64 [E] arrays (ValueError when a window is empty
-        or leaves the panel)."""
-        torch = _torch()
-        E, T = self.num_envs, self.panel.T
-        out = []
-        for x, what in ((start, "start"), (end, "end")):
-            if torch.is_tensor(x):
-                x = x.detach().cpu().numpy()
-            a = np.asarray(x)
-            if a.dtype.kind not in "iu":
-                raise ValueError(f"windows: {what} must be integer panel rows")
-            try:
-                out.append(np.broadcast_to(a.astype(np.int64), (E,)))
-            except ValueError:
-                raise ValueError(f"windows: {what} must be one value or [{E}] values") from None
-        s, t = out
-        if (s < 0).any() or (t > T).any():
-            raise ValueError(f"windows must lie in [0, {T}] (the panel's rows)")
-        if (t <= s).any():
-            raise ValueError("windows must not be empty (start < end)")
-        return s, t
-
-    def set_windows(self, start, end=None, mask=None):
-        """Per-env episode windows [start, end) of panel rows (finenv_{stock,portfolio}_set_windows);
-        ``set_windows(None)`` detaches them (every env runs the whole panel again).
-
-        The windows live in ``self.windows``, an int32 [2, E] device tensor (row 0 starts, row 1
-        ends) whose address the step kernel takes as an argument; this call copies into it in place.
-        The step kernel reads an env's END on every step and its START only when it resets the env,
-        so an edited end applies from the next step and an edited start at the env's next reset
-        (auto-reset or ``reset()``); nothing moves an env that is mid-episode.  To start the envs
-        that just finished on new windows: ``set_windows(s, t, mask=done)`` then ``reset(done)``
-        (INTEGRATION.md D).
-
-        Host values (ints, arrays) are validated (ValueError on empty or out-of-range windows).
-        Device tensors are copied without a host synchronisation, so windows can be redrawn with
-        torch ops -- ``mask`` (bool [E]) limits the update to those envs, e.g. the ones that just
-        reported ``done`` -- even inside a captured graph (the graph sees the block's contents as
-        they are at each replay).  Those are NOT validated: the kernel clamps every window into
-        the panel, so a bad one gives wrong results, never a fault.  Attach windows before capturing
-        a graph: a graph keeps the pointer it was captured with.  ``max_step`` follows the windows
-        passed here (the longest minus one), except device tensors passed during a capture."""
-        torch = _torch()
-        if start is None:
-            self._attach_windows(None)
-            self.windows = None
-            self.max_step = self.panel.T - 1
-            return None
-        if end is None:
-            raise ValueError("set_windows needs start and end")
-        on_device = all(torch.is_tensor(x) and x.device.type == "cuda" for x in (start, end))
-        if self.windows is None:
-            self.windows = torch.zeros(2, self.num_envs, dtype=torch.int32, device=self.device)
-            self.windows[1].fill_(self.panel.T)
-        new = torch.empty_like(self.windows)
-        if on_device:
-            new[0].copy_(start.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
-            new[1].copy_(end.to(device=self.device, dtype=torch.int32).expand(self.num_envs))
-        else:
-            s_np, t_np = self._check_windows(start, end)
-            new.copy_(torch.from_numpy(np.stack([s_np, t_np]).astype(np.int32)))
-        if mask is not None:
-            m = mask.to(device=self.device, dtype=torch.bool) if torch.is_tensor(mask) else \
-                torch.from_numpy(np.asarray(mask, dtype=bool)).to(self.device)
-            new = torch.where(m, new, self.windows)
-        self.windows.copy_(new)
-        self._attach_windows(C.c_void_p(self.windows.data_ptr()))
-        if not (on_device and torch.cuda.is_current_stream_capturing()):
-            self.max_step = int((self.windows[1] - self.windows[0]).max().item()) - 1
-        return self.windows
 
     def _history(self, what):
         """The episode history (enable_history() of the subclass), or FinenvError."""

@@ -544,6 +544,46 @@ int  finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *ob
                                const float *values, const float *log_probs, float *actions_out,
                                float *values_out, float *log_probs_out, void *stream);
 
+/* Per-env episode windows of the crypto env: many CryptoEnv instances built on slices
+ * {'price_array': price[s:t], 'tech_array': tech[s:t]} of ONE bound panel in one batch (the
+ * tutorial's train / test split, random-window training).  Env e on window [s_e, t_e) equals the
+ * reference env on that slice; FINENV_CI_TIME stays the PANEL row (the reference's self.time is
+ * FINENV_CI_TIME - s_e).  In panel rows:
+ *   - a reset (finenv_crypto_reset or the auto-reset inside step) sets time = s_e + lookback - 1
+ *     (:27, :49);
+ *   - done when the incremented time equals t_e - lookback - 1 (:24, :80);
+ *   - observation row l reads tech[time - l] as always; with a valid window no row outside
+ *     [s_e, t_e) is read, and rows t_e - lookback .. t_e - 1 are never visited (as in the reference);
+ *   - actions are scaled by the normaliser of row s_e, norm_rows[s_e][:] -- the reference derives
+ *     action_norm_vector from price_array[0] of the array it was given (:103-111).
+ * Only what the reference's reset() resets is reset: FINENV_CF_GAMMA_RETURN and _EPISODE_RETURN
+ * survive (:48-57); a caller who wants "a fresh env object on a new slice" zeroes GAMMA_RETURN of
+ * those envs.  A window needs t_e - s_e >= lookback + 2 (the n_steps rule of finenv_crypto_create).
+ *
+ * win: caller-owned device block int32_t [4][E], or NULL to detach (the default: every env runs
+ * the whole panel with finenv_crypto_panel.norm).
+ *   rows 0, 1  the PENDING window (s_e, t_e): the caller writes them whenever it likes, the env
+ *              takes them at its next reset;
+ *   rows 2, 3  the ACTIVE window of the running episode: written only by the reset paths
+ *              (finenv_crypto_reset and the auto-reset inside step, which copy rows 0, 1 of the
+ *              envs they reset), read by step.  Initialise them to the window of the episode in
+ *              progress, or reset every env once after attaching.
+ * Unlike the [2][E] blocks of the stock and portfolio envs: the crypto state has no start field
+ * and the start stays live for the whole episode (it selects the normaliser), so an edit must
+ * not reach a running episode.  With the two extra rows, redrawing the windows of the envs that
+ * just reported done needs no reset launch: their auto-reset has already taken the windows that
+ * were pending, the redraw is taken at the one after.
+ * norm_rows: device f64 [n_steps][n_assets], one action normaliser per panel row; required while
+ * win is non-NULL (FINENV_ERR_INVALID otherwise).  Rows whose prices are all positive hold
+ * action_norm_vector(price[row]); a row with a price <= 0 holds NaN (the reference raises there):
+ * a window that starts on such a row is out of contract and makes no trades.
+ * The kernels clamp window rows and the rows they read into the panel whatever the block and the
+ * time counter hold: bad device-side content is a wrong answer, never an access outside the panel.
+ * Both pointers are kernel arguments: launches and graph replays see later edits of the block's
+ * CONTENTS, a graph keeps the pointers it was captured with.  Works before bind.  Returns
+ * FINENV_ERR_INVALID for a NULL handle. */
+int finenv_crypto_set_windows(finenv_crypto *h, int32_t *win, const double *norm_rows);
+
 /* =====================================================================================
  * Rollout helper (caller side of the path): generalized advantage estimation
  * over device-resident rollout tensors [n_steps][E], time-reverse scan, one lane per env.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Step time of the batched stock and portfolio envs with per-env episode windows
-(VecStockTradingEnv / VecStockPortfolioEnv(windows=...)), on bench.py's workloads (same synthetic
-panel, actions and env settings).
+"""Step time of the batched stock, portfolio and crypto envs with per-env episode windows
+(VecStockTradingEnv / VecStockPortfolioEnv / VecCryptoEnv(windows=...)), on bench.py's workloads
+(same synthetic panel, actions and env settings).
 usage: python3 tools/bench_windows.py <case> [envs] [steps]
   case: full      -- every env on the whole panel [0, T) (lock-step days, the WIN instantiation)
         random63  -- random 63-day windows, hint_desynchronised(True)
@@ -11,7 +11,11 @@ usage: python3 tools/bench_windows.py <case> [envs] [steps]
         pf-none, pf-full, pf-random63
                   -- the same on bench.py --env portfolio's workload (DOW30 x 8)
         pf-split  -- portfolio, envs alternating between a train window [0, 0.8 T) and a trade
-                     window [0.8 T, T) (the portfolio tutorial's two data_split frames)"""
+                     window [0.8 T, T) (the portfolio tutorial's two data_split frames)
+        cr-none, cr-full, cr-split
+                  -- the same on bench.py --env crypto's workload (10 pairs, one-minute bars)
+        cr-random<L>
+                  -- crypto, random windows of L rows (e.g. cr-random1440: one day of minutes)"""
 import os
 import sys
 
@@ -28,15 +32,18 @@ def main():
     from finrl_amd.data import random_windows
     dev = torch.device("cuda", 0)
     n100 = case == "n100"
-    pf = case.startswith("pf-")
-    case = case[3:] if pf else case
+    pf, cr = case.startswith("pf-"), case.startswith("cr-")
+    case = case[3:] if pf or cr else case
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=case == "desync",
-                              no_stats=False, env="portfolio" if pf else "stock", tickers=100 if n100 else 30,
+                              no_stats=False, env="portfolio" if pf else "crypto" if cr else "stock", tickers=100 if n100 else 30,
                               turbulence_pct=90.0 if n100 else None))()
     w = bench.build_workload(args, torch, dev, 0)
     env = w.env
-    T = env.panel.T
-    if case == "full":
+    T = env.price_array.shape[0] if cr else env.panel.T
+    if cr and case.startswith("random"):
+        g = torch.Generator(device=dev).manual_seed(7)
+        env.set_windows(*random_windows(T, E, int(case[len("random"):]), generator=g, device=dev))
+    elif case == "full":
         env.set_windows(0, T)
     elif case in ("random63", "n100"):
         g = torch.Generator(device=dev).manual_seed(7)
@@ -59,8 +66,8 @@ def main():
         env.step(w.pool[i % len(w.pool)])
     e1.record()
     torch.cuda.synchronize()
-    name = ("pf-" if pf else "") + case
-    print(f"{name} E={E} N={env.stock_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
+    name = ("pf-" if pf else "cr-" if cr else "") + case
+    print(f"{name} E={E} N={env.action_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
 
 
 if __name__ == "__main__":
