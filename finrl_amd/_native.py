@@ -121,6 +121,17 @@ class CryptoStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p), ("stocks", C.c_void_p)]
 
 
+class CryptoHistoryPtrs(C.Structure):
+    """finenv_crypto_history: the episode-history tensors of finenv_crypto_set_history."""
+    _fields_ = [("asset", C.c_void_p), ("holdings", C.c_void_p), ("stocks", C.c_void_p),
+                ("start", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
+                ("capacity", C.c_int32)]
+
+
+# columns of finenv_crypto_history_metrics: the FINENV_HM_* indices, n_returns = len - 1 as in the stock env
+CRYPTO_HISTORY_METRICS = STOCK_HISTORY_METRICS
+
+
 class StockNpConfig(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("n_tickers", C.c_int32), ("n_techw", C.c_int32),
                 ("n_days", C.c_int32), ("min_action", C.c_int32), ("reserved0", C.c_int32),
@@ -258,7 +269,8 @@ def lib():
                     ("finenv_portfolio_set_windows", 2), ("finenv_crypto_set_windows", 3)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
-    for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs)):
+    for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs),
+                       ("crypto", CryptoHistoryPtrs)):
         if hasattr(L, f"finenv_{kind}_set_history"):       # episode history (same rule)
             getattr(L, f"finenv_{kind}_set_history").argtypes = [C.c_void_p, C.POINTER(ptrs)]
             getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3

@@ -68,6 +68,16 @@ struct CrParams {
     int32_t *win;                 // [4][E]: pending start / end, active start / end
     const double *norm_rows;      // [T][N]: the action normaliser of every panel row
 };
+// The argument of the HIST step kernels: the history behind the last older field, which all keep their
+// kernel-argument offsets.  A struct of its own, not a member of CrParams: a longer argument moves the
+// hidden launch arguments that follow it, the scalar loads of the block size then pair up differently,
+// and every non-recording step kernel came out with another register allocation and schedule.  This
+// way those kernels take the argument they always took and compile to the same code.
+struct CrParamsHist : CrParams {
+    finenv_crypto_history hist;
+};
+template <bool HIST>
+using CrArgs = typename std::conditional<HIST, CrParamsHist, CrParams>::type;
 
 #ifdef FINENV_DIAG
 #define CSTAMP(k)                                                                           \
@@ -113,6 +123,28 @@ __device__ __forceinline__ void cr_write_rows(float *__restrict__ dst, const CrP
         [=](int col) { return col < 1 + N ? col : -1; });
 }
 
+// `double sum` = np.sum(stocks * price_array[time]) (:82) in NumPy's pairwise order over the holdings sv[NP]
+// and the price row prc[NP], statically indexed (guards are wave-uniform).  ONE text for the step and
+// for the history's arm kernel, so the order of the additions is the same by construction -- and a
+// macro, not a function: behind a (force-inlined) call the non-recording step kernels came out with
+// another schedule than the statements in place, which is what they must stay.
+#define CR_HOLDINGS_SUM(sum, sv, prc, N, NP)                                                  \
+    auto prod = [&](int i) { return (double)sv[i] * prc[i]; };                                \
+    double sum = 0.0;                                                                         \
+    if (N < 8) {                                                                              \
+        _Pragma("unroll") for (int i = 0; i < 7; ++i)                                         \
+            if (i < N) sum += prod(i);                                                        \
+    } else {                                                                                  \
+        double r8[8];                                                                         \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) r8[j] = prod(j);                        \
+        const int full = N - (N & 7);                                                         \
+        _Pragma("unroll") for (int i = 8; i < NP; ++i)                                        \
+            if (i < full) r8[i & 7] += prod(i);                                               \
+        sum = ((r8[0] + r8[1]) + (r8[2] + r8[3])) + ((r8[4] + r8[5]) + (r8[6] + r8[7]));      \
+        _Pragma("unroll") for (int i = 8; i < NP; ++i)                                        \
+            if (i >= full && i < N) sum += prod(i);                                           \
+    }
+
 // NP = asset count padded to 8 / 12 / 16 / 32: the per-asset state lives in statically indexed
 // registers, so the unrolled loops are compiled per padded width (N = 10 runs the 12-wide build:
 // <= 128 VGPRs, four env waves per SIMD -- every wave of a 262,144-env batch is resident at once).
@@ -133,8 +165,13 @@ __device__ __forceinline__ void cr_write_rows(float *__restrict__ dst, const CrP
 // with the price row in round trip 2 -- it is first needed after the action tile's transposition.
 // The streamer still reads nothing but LDS: the env wave publishes the row each env will SHOW (its
 // new time, or on an auto-reset its pending start row) instead of the raw time counter.
-template <bool RESET_ONLY, int kWaves, int NP, bool TWO = false, bool WIN = false>
-__global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_kernel(const CrParams p)
+// HIST: the recording instantiation (CrParamsHist::hist attached, finenv_crypto_set_history; the rule is
+// in include/finenv.h).  What it records -- the new total asset, the holdings sum, the post-trade
+// holdings -- exists only in this kernel's registers.  It adds no round trip: the env's entry counter
+// and flags depend on nothing and are loaded in round trip 1 right behind the time counter, the
+// record stores go out with the state write-back, and nothing is loaded to decide what to store.
+template <bool RESET_ONLY, int kWaves, int NP, bool TWO = false, bool WIN = false, bool HIST = false>
+__global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_kernel(const CrArgs<HIST> p)
 {
     constexpr int kRowW = NP + 1;                            // odd row stride of the LDS rows (dwords)
     extern __shared__ __attribute__((aligned(16))) float lds_all[];   // kWaves * lds_per_wave(NP)
@@ -238,6 +275,11 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     // ---- round trip 1: everything that does not depend on `time`; the time counter first (loads
     // return in order: it is the one value the next round trip -- and the streamer -- wait for) ------
     const int time = CI(FINENV_CI_TIME) + 1;                                  // :60
+    int hlen = 0, hfl = 0;                                  // HIST: the env's entry counter and flags
+    if constexpr (HIST) {
+        hlen = *at(p.hist.len, (unsigned)e);
+        hfl = *at(p.hist.flags, (unsigned)e);
+    }
     int w_start = 0, w_last = 0;                            // WIN: active start row, end - 1
     if (WIN) {
         w_start = win_start(p.win + 2 * (size_t)E, e, p.cfg.n_steps);
@@ -381,26 +423,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     }
     CSTAMP(4);
     // ---- total asset: cash + np.sum(stocks * price) (NumPy pairwise order), :82 -----------
-    // (statically indexed over the NP registers; guards are wave-uniform)
-    auto prod = [&](int i) { return (double)sv[i] * prc[i]; };
-    double sum = 0.0;
-    if (N < 8) {
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-            if (i < N) sum += prod(i);
-    } else {
-        double r8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r8[j] = prod(j);
-        const int full = N - (N & 7);
-#pragma unroll
-        for (int i = 8; i < NP; ++i)
-            if (i < full) r8[i & 7] += prod(i);
-        sum = ((r8[0] + r8[1]) + (r8[2] + r8[3])) + ((r8[4] + r8[5]) + (r8[6] + r8[7]));
-#pragma unroll
-        for (int i = 8; i < NP; ++i)
-            if (i >= full && i < N) sum += prod(i);
-    }
+    CR_HOLDINGS_SUM(sum, sv, prc, N, NP)
     const double next = cash + sum;
     double reward = (next - prev_asset) * 0x1p-16;                            // :83
     gamma_ret = gamma_ret * p.cfg.gamma + reward;                             // :85
@@ -432,6 +455,29 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         CF(FINENV_CF_LAST_REWARD) = reward;
         CF(FINENV_CF_GAMMA_RETURN) = gamma_ret;
         if (done) CF(FINENV_CF_EPISODE_RETURN) = next / p.cfg.initial_cash;   // :89
+    }
+    if constexpr (HIST) {
+        // entry hlen of an armed, unfinished record (the terminal step included: this env trades and
+        // revalues on it); the time-major slabs are indexed in 64 bits
+        if (valid && hlen >= 1 && !(hfl & FINENV_HIST_COMPLETE)) {
+            const bool room = hlen < p.hist.capacity;
+            if (room) {
+                const size_t o = (size_t)hlen * (size_t)E + (size_t)e;
+                p.hist.asset[o] = next;
+                p.hist.holdings[o] = sum;
+                if (p.hist.stocks != nullptr) {
+                    float *const hs = p.hist.stocks + (size_t)hlen * (size_t)N * (size_t)E + (size_t)e;
+#pragma unroll
+                    for (int i = 0; i < NP; ++i) {
+                        if (i >= N) continue;
+                        hs[(size_t)i * (size_t)E] = sv[i];   // (before an auto-reset zeroes them)
+                    }
+                }
+                *at(p.hist.len, (unsigned)e) = hlen + 1;
+            }
+            const int nfl = hfl | (room ? 0 : FINENV_HIST_OVERFLOW) | (done ? FINENV_HIST_COMPLETE : 0);
+            if (nfl != hfl) *at(p.hist.flags, (unsigned)e) = nfl;   // (an overflowed env: set once)
+        }
     }
     wave_sync();
     const unsigned long long valid_mask = __ballot(valid);
@@ -524,6 +570,65 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     CSTAMP(8);
 }
 
+// -------------------------------------------------------------------------------------
+// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
+// instantiation of the step kernel above).
+// -------------------------------------------------------------------------------------
+struct CrHistArgs {
+    finenv_crypto_history h;
+    finenv_crypto_state st;
+    const double *price;          // [T][N]
+    const uint8_t *mask;          // arm: envs to arm, or NULL = all
+    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
+    double annualization;
+    int32_t E, N, T;
+};
+
+// Entry 0 of the envs of the mask, from their current state: total_asset, the holdings sum over the
+// state's stocks and price[time] (CR_HOLDINGS_SUM: the step's own order of additions; 0.0 at the start of
+// an episode), the holdings, and the panel row the env stands on.  One lane per env; the 32-wide form
+// of the sum adds the same terms in the same order as every narrower build.
+__global__ __launch_bounds__(256) void crypto_history_arm_kernel(const CrHistArgs p)
+{
+    constexpr int NP = FINENV_CRYPTO_MAX_ASSETS;
+    const int E = p.E, N = p.N;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || (p.mask != nullptr && p.mask[e] == 0)) return;
+    const int time = CI(FINENV_CI_TIME);
+    const unsigned pb = (unsigned)(min(max(time, 0), p.T - 1) * N);     // (a panel row, whatever it holds)
+    float sv[NP];
+    double prc[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        sv[i] = STK(min(i, N - 1));
+        prc[i] = *at(p.price, pb + (unsigned)min(i, N - 1));
+    }
+    CR_HOLDINGS_SUM(sum, sv, prc, N, NP)
+    p.h.asset[e] = CF(FINENV_CF_TOTAL_ASSET);
+    p.h.holdings[e] = sum;
+    if (p.h.stocks != nullptr) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i)
+            if (i < N) p.h.stocks[(size_t)i * (size_t)E + (size_t)e] = sv[i];
+    }
+    p.h.start[e] = time;
+    p.h.len[e] = 1;
+    p.h.flags[e] = 0;
+}
+
+// Backtest figures of each env's recorded account values (series_metrics, finenv_dev.h): the returns
+// are asset[k] / asset[k-1] - 1, entry 0 carries none, so n_returns is len - 1 (the stock env's rule).
+__global__ void crypto_history_metrics_kernel(const CrHistArgs p)
+{
+    const int E = p.E;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double *a = p.h.asset + e;
+    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
+                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
+                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
+}
+
 }  // namespace
 
 struct finenv_crypto : finenv_host::Handle {
@@ -533,6 +638,8 @@ struct finenv_crypto : finenv_host::Handle {
     uint32_t magicN, magicW, magicH, magicD;
     int32_t *win;                 // finenv_crypto_set_windows
     const double *norm_rows;
+    int has_hist;                 // finenv_crypto_set_history
+    finenv_crypto_history hist;
 };
 
 namespace {
@@ -552,12 +659,33 @@ CrParams cr_params(const finenv_crypto *h)
     p.norm_rows = h->norm_rows;
     return p;
 }
+CrHistArgs cr_hist_args(const finenv_crypto *h)
+{
+    CrHistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h->hist;
+    a.st = h->st;
+    a.price = h->panel.price;
+    a.E = h->cfg.n_envs;
+    a.N = h->cfg.n_assets;
+    a.T = h->cfg.n_steps;
+    return a;
+}
+
+// reset (re)starts episodes: the records of the envs it resets start afresh
+void launch_history_arm(const finenv_crypto *h, const uint8_t *mask, hipStream_t stream)
+{
+    CrHistArgs a = cr_hist_args(h);
+    a.mask = mask;
+    hipLaunchKernelGGL(crypto_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
+}
+
 constexpr int kSmallWaves = 2048;      // up to here: one env wave per block (spread over every CU)
-template <bool RESET_ONLY, int NP, bool WIN>
-void cr_launch_np(const CrParams &p, hipStream_t stream)
+template <bool RESET_ONLY, int NP, bool WIN, bool HIST>
+void cr_launch_np(const CrArgs<HIST> &p, hipStream_t stream)
 {
     const int waves = (p.cfg.n_envs + kWave - 1) / kWave;
-    CrParams q = p;
+    CrArgs<HIST> q = p;
     const int n4 = p.rec_na4 + 2 * p.rec_nv4;            // record work (0: plain step)
     const size_t lds1 = sizeof(float) * lds_per_wave(NP);
     // (regime boundary checked in one process, same buffers: with streamers 9.05 / 11.0 / 12.7 us at
@@ -566,11 +694,11 @@ void cr_launch_np(const CrParams &p, hipStream_t stream)
     if (waves <= small_waves) {
         const int rec_blocks = n4 > 0 ? min(512, (n4 + kWave * 16 - 1) / (kWave * 16)) : 0;
         q.env_blocks = n4 > 0 ? waves : 0;
-        if (RESET_ONLY)
-            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, false, WIN>), dim3((unsigned)(waves + rec_blocks)),
-                               dim3(kWave), lds1, stream, q);
+        if (RESET_ONLY)     // (never records)
+            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, false, WIN, false>), dim3((unsigned)(waves + rec_blocks)),
+                               dim3(kWave), lds1, stream, static_cast<const CrParams &>(q));
         else        // trader + streamer wave per 64 envs
-            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, true, WIN>), dim3((unsigned)(waves + rec_blocks)),
+            hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 1, NP, true, WIN, HIST>), dim3((unsigned)(waves + rec_blocks)),
                                dim3(2 * kWave), lds1, stream, q);
     } else {
         const int blocks = (waves + 3) / 4;
@@ -579,24 +707,36 @@ void cr_launch_np(const CrParams &p, hipStream_t stream)
         // Large batches are bandwidth-, not latency-bound: no streamer waves (a streamer is a wave of
         // the same kernel and would hold a full wave's registers: half the env waves' residency), the
         // env wave writes whole rows in the block form.
-        hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 4, NP, false, WIN>), dim3((unsigned)(blocks + rec_blocks)),
+        hipLaunchKernelGGL((crypto_kernel<RESET_ONLY, 4, NP, false, WIN, HIST>), dim3((unsigned)(blocks + rec_blocks)),
                            dim3(kWave * 4), 4 * lds1, stream, q);
     }
 }
-template <bool RESET_ONLY, bool WIN>
-void cr_launch_win(const CrParams &p, hipStream_t stream)
+template <bool RESET_ONLY, bool WIN, bool HIST>
+void cr_launch_win(const CrArgs<HIST> &p, hipStream_t stream)
 {
-    if (RESET_ONLY) cr_launch_np<RESET_ONLY, 32, WIN>(p, stream);      // (no per-asset registers: one build)
-    else if (p.cfg.n_assets <= 8) cr_launch_np<RESET_ONLY, 8, WIN>(p, stream);
-    else if (p.cfg.n_assets <= 12) cr_launch_np<RESET_ONLY, 12, WIN>(p, stream);
-    else if (p.cfg.n_assets <= 16) cr_launch_np<RESET_ONLY, 16, WIN>(p, stream);
-    else cr_launch_np<RESET_ONLY, 32, WIN>(p, stream);
+    if (RESET_ONLY) cr_launch_np<RESET_ONLY, 32, WIN, HIST>(p, stream);   // (no per-asset registers: one build)
+    else if (p.cfg.n_assets <= 8) cr_launch_np<RESET_ONLY, 8, WIN, HIST>(p, stream);
+    else if (p.cfg.n_assets <= 12) cr_launch_np<RESET_ONLY, 12, WIN, HIST>(p, stream);
+    else if (p.cfg.n_assets <= 16) cr_launch_np<RESET_ONLY, 16, WIN, HIST>(p, stream);
+    else cr_launch_np<RESET_ONLY, 32, WIN, HIST>(p, stream);
 }
-template <bool RESET_ONLY>
-void cr_launch(const CrParams &p, hipStream_t stream)
+template <bool RESET_ONLY, bool HIST = false>
+void cr_launch(const CrArgs<HIST> &p, hipStream_t stream)
 {
-    if (p.win != nullptr) cr_launch_win<RESET_ONLY, true>(p, stream);   // a window block is attached
-    else cr_launch_win<RESET_ONLY, false>(p, stream);
+    if (p.win != nullptr) cr_launch_win<RESET_ONLY, true, HIST>(p, stream);   // a window block is attached
+    else cr_launch_win<RESET_ONLY, false, HIST>(p, stream);
+}
+// a step: the recording instantiation while a history is attached
+void cr_launch_step(const finenv_crypto *h, const CrParams &p, hipStream_t stream)
+{
+    if (h->has_hist) {
+        CrParamsHist q;
+        static_cast<CrParams &>(q) = p;
+        q.hist = h->hist;
+        cr_launch<false, true>(q, stream);
+    } else {
+        cr_launch<false>(p, stream);
+    }
 }
 }  // namespace
 
@@ -657,6 +797,7 @@ int finenv_crypto_reset(finenv_crypto *h, const uint8_t *mask, float *obs_out, v
     p.mask = mask;
     p.obs = obs_out;
     cr_launch<true>(p, (hipStream_t)stream);
+    if (h->has_hist) launch_history_arm(h, mask, (hipStream_t)stream);   // behind the reset: reads its state
     return finenv_host::check_launch(h, "crypto_reset");
 }
 
@@ -677,7 +818,7 @@ int finenv_crypto_step(finenv_crypto *h, const float *actions, float *obs, float
 #ifdef FINENV_DIAG
     p.dbg = g_finenv_dbg;
 #endif
-    cr_launch<false>(p, (hipStream_t)stream);
+    cr_launch_step(h, p, (hipStream_t)stream);
     return finenv_host::check_launch(h, "crypto_step");
 }
 
@@ -713,8 +854,38 @@ int finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *obs
 #ifdef FINENV_DIAG
     p.dbg = g_finenv_dbg;
 #endif
-    cr_launch<false>(p, (hipStream_t)stream);
+    cr_launch_step(h, p, (hipStream_t)stream);
     return finenv_host::check_launch(h, "crypto_step_record");
+}
+
+int finenv_crypto_set_history(finenv_crypto *h, const finenv_crypto_history *hist)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    const bool missing = hist && (!hist->asset || !hist->holdings || !hist->start || !hist->len ||
+                                  !hist->flags);
+    return finenv_host::set_history(h, h->hist, h->has_hist, hist,
+                                    missing ? "set_history: null asset/holdings/start/len/flags" : nullptr);
+}
+
+int finenv_crypto_history_arm(finenv_crypto *h, const uint8_t *mask, void *stream)
+{
+    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    launch_history_arm(h, mask, (hipStream_t)stream);
+    return finenv_host::check_launch(h, "crypto_history_arm");
+}
+
+int finenv_crypto_history_metrics(finenv_crypto *h, double annualization, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    CrHistArgs a = cr_hist_args(h);
+    a.out = out;
+    a.annualization = annualization;
+    hipLaunchKernelGGL(crypto_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return finenv_host::check_launch(h, "crypto_history_metrics");
 }
 
 }  // extern "C"

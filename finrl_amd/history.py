@@ -6,7 +6,9 @@ device-to-host copy per tensor.
 
 The frame builders at the top work on host arrays (time-major, as the device holds them) and need
 no GPU; ``EpisodeHistory`` owns the device tensors and is what
-``VecStockTradingEnv.enable_history()`` returns.
+``VecStockTradingEnv.enable_history()`` returns.  ``PortfolioEpisodeHistory`` and
+``CryptoEpisodeHistory`` are the same for the portfolio and the crypto env, whose step kernels write
+the record themselves.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ from . import _native as nat
 
 METRIC_KEYS = nat.STOCK_HISTORY_METRICS
 PORTFOLIO_METRIC_KEYS = nat.PORTFOLIO_HISTORY_METRICS
+CRYPTO_METRIC_KEYS = nat.CRYPTO_HISTORY_METRICS
 
 
 def _torch():
@@ -106,19 +109,52 @@ def portfolio_action_memory_frame(dates, tickers, weights, row, length):
     return df_actions
 
 
+def crypto_account_values(asset, length):
+    """The true account value of one crypto env's recorded episode: ``total_asset`` after every step
+    (env_multiple_crypto.py:82-84), entry 0 the value the episode started with -> f64 [length]."""
+    return np.array(np.asarray(asset, dtype=np.float64)[:int(length)])
+
+
+def crypto_episode_total_assets(holdings, length, initial_total_asset):
+    """The list DRLAgent.DRL_prediction_load_from_file returns (agents/stablebaselines3/models.py:146-156)
+    from one env's recorded ``holdings`` column, as Python floats: ``[initial_total_asset]`` and then
+    ``initial_total_asset + holdings[k]`` per step.  The reference adds the value of the holdings to
+    ``initial_total_asset`` where the remaining cash belongs (models.py:152-155), so this is not the
+    account value (``crypto_account_values``) once anything was bought; it is reproduced as it is."""
+    init = float(initial_total_asset)
+    h = np.asarray(holdings, dtype=np.float64)[1:max(int(length), 1)]
+    return [init] + [init + float(x) for x in h]
+
+
+def crypto_positions(stocks, length):
+    """One crypto env's holdings after every recorded entry -> f32 [length, N] (``stocks``: [>= length, N])."""
+    return np.array(np.asarray(stocks, dtype=np.float32)[:int(length)])
+
+
+def crypto_rows(start, length):
+    """The panel row of every recorded entry of one crypto env: ``start + arange(length)`` (the env
+    moves one row per step), for indexing the caller's own timestamps."""
+    return int(start) + np.arange(int(length), dtype=np.int64)
+
+
 # ---------------------------------------------------------------------- the device side
 class _Record:
-    """A device-resident episode record: what ``EpisodeHistory`` and ``PortfolioEpisodeHistory`` are made
-    of.  A subclass declares its data:
+    """A device-resident episode record: what ``EpisodeHistory``, ``PortfolioEpisodeHistory`` and
+    ``CryptoEpisodeHistory`` are made of.  A subclass declares its data:
       ``_ptrs_cls``    the ctypes struct of finenv_<kind>_set_history (one pointer per tensor, capacity)
       ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]
       ``_per_ticker``  (name, dtype, rows short of capacity): the optional tensor [capacity - short, E, N]
+      ``_env_last``    that tensor is [capacity - short, N, E] instead (the env is the fastest index)
+      ``_per_env``     ((name, dtype), ...): the tensors [E] beside ``length`` and ``flags``
+      ``_assets``      the env attribute that holds N
       ``metric_keys``  the columns of ``metrics()``
     """
 
+    _env_last, _per_env, _assets = False, (), "stock_dim"
+
     def __init__(self, env, capacity, per_ticker=True):
         torch = _torch()
-        E, N, dev = env.num_envs, env.stock_dim, env.device
+        E, N, dev = env.num_envs, getattr(env, self._assets), env.device
         capacity = int(capacity)
         if capacity < 2:
             raise ValueError("history capacity must be >= 2")
@@ -126,8 +162,11 @@ class _Record:
         for name, dtype in self._series:
             setattr(self, name, torch.zeros(capacity, E, dtype=getattr(torch, dtype), device=dev))
         name, dtype, short = self._per_ticker
-        setattr(self, name, torch.zeros(capacity - short, E, N, dtype=getattr(torch, dtype), device=dev)
+        shape = (capacity - short, N, E) if self._env_last else (capacity - short, E, N)
+        setattr(self, name, torch.zeros(*shape, dtype=getattr(torch, dtype), device=dev)
                 if per_ticker else None)
+        for name, dtype in self._per_env:
+            setattr(self, name, torch.zeros(E, dtype=getattr(torch, dtype), device=dev))
         self.length = torch.zeros(E, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(E, dtype=torch.int32, device=dev)
         self._metrics = None
@@ -191,25 +230,37 @@ class _Record:
     # ------------------------------------------------------------------ frames
     def _host(self, envs, names):
         """Host copies of the selected envs' columns, ``{"length": ..., name: ...}``: one device-to-host
-        copy per tensor."""
+        copy per tensor.  Time-major with the env second ([entries, n] and [entries, n, N]), whatever
+        the device layout is; the per-env tensors are [n]."""
         torch = _torch()
         idx = torch.as_tensor(envs, dtype=torch.int64, device=self.env.device)
         out = {"length": self.length.index_select(0, idx).cpu().numpy()}
+        per_env = [name for name, _ in self._per_env]
         for k in names:
             t = getattr(self, k)
             if t is None:
                 raise nat.FinenvError(f"this history was enabled with {k}=False")
-            out[k] = t.index_select(1, idx).cpu().numpy()
+            if k in per_env:
+                out[k] = t.index_select(0, idx).cpu().numpy()
+            elif self._env_last and k == self._per_ticker[0]:
+                out[k] = t.index_select(2, idx).cpu().numpy().transpose(0, 2, 1)
+            else:
+                out[k] = t.index_select(1, idx).cpu().numpy()
         return out
 
-    def _frames(self, e, build, *names, tickers=False):
-        """``e`` -> host columns -> frame(s): ``build(dates, [tickers,] *columns, length)`` for one env
+    def _frames(self, e, build, *names, tickers=False, dates=True):
+        """``e`` -> host columns -> frame(s): ``build([dates, [tickers,]] *columns, length)`` for one env
         index (a frame) or a sequence of them (a list of frames)."""
         one = isinstance(e, (int, np.integer))
         envs = [int(e)] if one else [int(x) for x in e]
-        h, panel = self._host(envs, names), self.env.panel
-        head = (panel.dates, panel.tickers) if tickers else (panel.dates,)
-        out = [build(*head, *(h[k][:, j] for k in names), h["length"][j]) for j in range(len(envs))]
+        h = self._host(envs, names)
+        head = ()
+        if dates:
+            panel = self.env.panel
+            head = (panel.dates, panel.tickers) if tickers else (panel.dates,)
+        per_env = [name for name, _ in self._per_env]
+        out = [build(*head, *(h[k][j] if k in per_env else h[k][:, j] for k in names), h["length"][j])
+               for j in range(len(envs))]
         return out[0] if one else out
 
 
@@ -294,3 +345,59 @@ class PortfolioEpisodeHistory(_Record):
     def save_action_memory(self, e):
         """The reference's save_action_memory() frame of env ``e`` (a list for a list of envs)."""
         return self._frames(e, portfolio_action_memory_frame, "weights", "row", tickers=True)
+
+
+class CryptoEpisodeHistory(_Record):
+    """Device-resident episode record of a ``VecCryptoEnv`` (``env.enable_history()``): the account value
+    of every env's episode, one entry per step, written by the step kernel itself
+    (finenv_crypto_set_history, include/finenv.h) -- what DRLAgent.DRL_prediction_load_from_file
+    (agents/stablebaselines3/models.py:144-162) returns for the one env it runs.
+
+    Tensors (time-major; entries at or past ``length[e]`` are unspecified):
+      ``asset``     f64 [capacity, E]     total_asset after the step (env_multiple_crypto.py:82-84)
+      ``holdings``  f64 [capacity, E]     np.sum(stocks * price_array[time]) of that step (:82)
+      ``stocks``    f32 [capacity, N, E]  holdings after the step (the state's [N, E] layout), or None
+      ``start``     i32 [E]               panel row of entry 0; entry k is panel row ``start + k``
+      ``length``    i32 [E]               entries recorded; 0 = not armed
+      ``flags``     i32 [E]               bit 0 complete, bit 1 overflow (``complete`` / ``overflow``)
+
+    Armed by the constructor (from the env's current state), by ``env.reset(mask)`` for the envs it
+    resets and by ``arm(mask)``; entry 0 is the current total asset, the value of the current holdings
+    (``initial_cash`` and 0.0 at the start of an episode) and the current holdings.  The terminal step is
+    recorded -- this env trades on it -- and makes the record final.  An auto-reset inside ``step`` does
+    not arm: the finished episode stays readable until the next host reset or ``arm``.  The pointers are
+    launch arguments: enable the history before capturing a graph.
+    """
+
+    _ptrs_cls, metric_keys = nat.CryptoHistoryPtrs, CRYPTO_METRIC_KEYS
+    _series = (("asset", "float64"), ("holdings", "float64"))
+    _per_ticker, _env_last = ("stocks", "float32", 0), True
+    _per_env, _assets = (("start", "int32"),), "crypto_num"
+
+    def __init__(self, env, capacity, stocks=True):
+        super().__init__(env, capacity, stocks)
+
+    def account_values(self, e):
+        """The true account value of env ``e``'s recorded episode, ``asset[:length]`` -> f64 array (a list
+        of arrays for a sequence of envs)."""
+        return self._frames(e, crypto_account_values, "asset", dates=False)
+
+    def episode_total_assets(self, e, initial_total_asset=None):
+        """The list DRL_prediction_load_from_file returns for env ``e`` (a list of lists for a sequence of
+        envs), as Python floats: ``[initial_total_asset] + [initial_total_asset + holdings[k]]``.  The
+        reference adds the holdings' value to ``initial_total_asset`` where the cash belongs
+        (models.py:152-155); this reproduces its list, ``account_values`` gives the true curve.
+        ``initial_total_asset`` defaults to the env's ``initial_cash``."""
+        init = self.env.initial_cash if initial_total_asset is None else initial_total_asset
+        return self._frames(e, lambda holdings, n: crypto_episode_total_assets(holdings, n, init),
+                            "holdings", dates=False)
+
+    def positions(self, e):
+        """The holdings after every recorded entry of env ``e`` -> f32 [length, N] (a list for a sequence
+        of envs); needs ``stocks=True``."""
+        return self._frames(e, crypto_positions, "stocks", dates=False)
+
+    def rows(self, e):
+        """The panel rows of env ``e``'s entries, ``start + arange(length)`` (a list for a sequence of
+        envs): index your own timestamps with them."""
+        return self._frames(e, crypto_rows, "start", dates=False)

@@ -211,6 +211,35 @@ class VecCryptoEnv(WindowedEnv):
                    C.c_void_p(lp_out.data_ptr()), self._stream())
         return obs, rew, done, None
 
+    history = None              # enable_history()
+
+    def enable_history(self, capacity=None, stocks=True):
+        """Record every env's episode on the device: ``total_asset`` and the value of the holdings
+        after every step and (with ``stocks``) the holdings themselves, written by the step kernel
+        itself (finenv_crypto_set_history) -- no ``state_numpy()`` per step, no host loop, and it sits
+        in a captured graph.  Returns the ``finrl_amd.history.CryptoEpisodeHistory`` (also
+        ``self.history``), whose ``episode_total_assets(e)`` is the list the reference's
+        DRL_prediction_load_from_file returns and ``account_values(e)`` the true equity curve;
+        idempotent: a second call returns the same object whatever its arguments.
+
+        ``capacity``: entries per env, by default the longest episode (``max_step - lookback + 2``
+        entries: the armed one and one per step; ``L - 2 * lookback + 1`` for the longest pending
+        window of ``L`` rows) AS IT IS AT THIS CALL: windows made longer by a later ``set_windows`` do
+        not grow the tensors, and the longer episodes then end with ``overflow`` set and their first
+        ``capacity`` entries recorded -- pass ``capacity`` for the longest window to come.  Every env
+        is armed from its current state; ``reset(mask)`` re-arms the envs it resets, an auto-reset
+        does not (the finished record stays readable).
+
+        Memory: ``E * (16 * capacity + 12) + 4 * E * N * capacity`` bytes: 262,144 envs on 1,440-row
+        windows of 10 pairs are 6 GB without and 21 GB with ``stocks``, which is why it is optional.
+
+        Enable it before capturing a graph (the tensors' addresses are launch arguments)."""
+        if self.history is None:
+            from .history import CryptoEpisodeHistory
+            self.history = CryptoEpisodeHistory(
+                self, self.max_step - self.lookback + 2 if capacity is None else capacity, stocks)
+        return self.history
+
     def episode_return(self):
         """total_asset / initial cash of each env's last finished episode (:89), f32."""
         import torch

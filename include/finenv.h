@@ -584,6 +584,70 @@ int  finenv_crypto_step_record(finenv_crypto *h, const float *actions, float *ob
  * FINENV_ERR_INVALID for a NULL handle. */
 int finenv_crypto_set_windows(finenv_crypto *h, int32_t *win, const double *norm_rows);
 
+/* Episode history of the crypto env: the account value of every env's CURRENT episode, one entry
+ * per step, recorded on the device -- what DRLAgent.DRL_prediction_load_from_file
+ * (agents/stablebaselines3/models.py:144-162) returns as episode_total_assets.  Opt-in and
+ * caller-owned device memory, time-major:
+ *   asset[k][e]      total_asset after the step (:82, :84): the step's own cash + sum, fp64
+ *   holdings[k][e]   np.sum(stocks * price_array[time]) of that step (:82), NumPy's pairwise order:
+ *                    the term the prediction loop builds its list from -- it appends
+ *                    initial_total_asset + (price_array[time] * stocks).sum() (models.py:152-156),
+ *                    not total_asset.  With both columns the true account value and the
+ *                    reference's list can each be reproduced bit for bit.
+ *   stocks[k][i][e]  holdings of asset i after the step (f32), or not recorded (NULL)
+ *   start[e]         panel row of entry 0; entry k belongs to panel row start[e] + k
+ *   len[e]           entries recorded so far; 0 = not armed, nothing is recorded
+ *   flags[e]         FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW, as in the stock env's history
+ * Three choices differ from the portfolio env's struct:
+ *   - no per-entry row: this env has no date_memory and its time counter advances by exactly one
+ *     panel row per step, windows included, so one start row per env says everything (4 B per env
+ *     and step saved);
+ *   - holdings is recorded beside asset (above);
+ *   - stocks is [capacity][N][E], the layout of the state's stocks tensor: a lane of the step kernel
+ *     is an env, so every store of a wave is one contiguous 256 B ([E][N] would be strided here).
+ * The holdings sum lives only in the step's registers, so the record is taken INSIDE the step
+ * kernel: while a history is attached finenv_crypto_step / _step_record launch the recording
+ * instantiation of their kernel, no second launch and no further dependent load.  Per env, by its
+ * own counter:
+ *   - not armed (len == 0) or complete: nothing;
+ *   - else entry k = len[e]: asset[k][e] = the new total_asset, holdings[k][e] = the holdings sum,
+ *     stocks[k][i][e] = the post-trade holdings (on a terminal step: before an auto-reset zeroes
+ *     them), len[e] = k + 1; with k == capacity nothing is written and OVERFLOW is set.  No entry
+ *     at or past `capacity` is ever written, in any tensor;
+ *   - the terminal step IS recorded -- unlike the stock and portfolio envs this env trades and
+ *     revalues on its last step (:59-90 has no terminal branch) -- and then sets COMPLETE, whatever
+ *     auto_reset is (also when that step overflowed).
+ * Arming an env writes entry 0 from its current state: asset[0][e] = FINENV_CF_TOTAL_ASSET,
+ * holdings[0][e] = the same pairwise sum over the state's stocks and price[time] (exactly 0.0 at
+ * the start of an episode, where asset[0] is exactly initial_cash), stocks[0][:][e] = the state's
+ * holdings, start[e] = FINENV_CI_TIME; it sets len[e] = 1 and clears flags[e].
+ * finenv_crypto_reset arms the envs it resets, behind the reset (with windows: on their new
+ * active window).  An auto-reset inside step does NOT arm: the finished episode's record stays
+ * readable and the env is not recorded again until a host reset or finenv_crypto_history_arm.
+ * The struct's pointers are LAUNCH ARGUMENTS: a step captured into a graph records only if the
+ * history was attached before the capture, and into the tensors attached then.
+ * Memory: E * (16 * capacity + 12) + 4 * E * N * capacity bytes (262,144 envs on 1,440-row windows
+ * of 10 pairs: 6 GB without stocks, 21 GB with -- which is why stocks is optional). */
+typedef struct finenv_crypto_history {
+    double  *asset;     /* [capacity][E]     total_asset after the step (:82, :84)                   */
+    double  *holdings;  /* [capacity][E]     np.sum(stocks * price_array[time]) of that step (:82)  */
+    float   *stocks;    /* [capacity][N][E]  holdings after the step, or NULL                        */
+    int32_t *start;     /* [E] panel row of entry 0; entry k is panel row start[e] + k               */
+    int32_t *len;       /* [E] entries recorded; 0 = not armed                                       */
+    int32_t *flags;     /* [E] FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW                            */
+    int32_t  capacity;  /* >= 2                                                                      */
+} finenv_crypto_history;
+/* Attach a history (the struct is copied), or detach with NULL (the default).  Allowed before bind.
+ * Attaching arms nothing: zero len / flags, then finenv_crypto_reset / _history_arm. */
+int finenv_crypto_set_history(finenv_crypto *h, const finenv_crypto_history *hist);
+/* Arm every env, or those with mask[e] != 0 (device u8[E]), from its current state. */
+int finenv_crypto_history_arm(finenv_crypto *h, const uint8_t *mask, void *stream);
+/* Backtest figures of the recorded account values: out [E][FINENV_STOCK_HISTORY_METRICS] f64, the
+ * FINENV_HM_* columns with the stock env's convention: returns asset[k] / asset[k-1] - 1 for
+ * k = 1 .. len-1, N_RETURNS = len - 1.  `annualization` is the caller's (one-minute bars have no
+ * fixed year).  Rows of unarmed envs are NaN. */
+int finenv_crypto_history_metrics(finenv_crypto *h, double annualization, double *out, void *stream);
+
 /* =====================================================================================
  * Rollout helper (caller side of the path): generalized advantage estimation
  * over device-resident rollout tensors [n_steps][E], time-reverse scan, one lane per env.

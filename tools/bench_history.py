@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
-"""Cost of the episode history (enable_history) of the batched stock or portfolio env on bench.py's
-workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows.  ONE process, ONE
+"""Cost of the episode history (enable_history) of the batched stock, portfolio or crypto env on
+bench.py's workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows (crypto:
+10 pairs x 40 indicator columns, 1,440-row windows, --envs 32768 / 65536 / 262144).  ONE process, ONE
 env; the variants alternate inside every round, each timed with HIP events over steps that all record:
   a  history detached (the step path of a build without the feature)
   b  history attached without the per-ticker tensor (actions=False / weights=False)
-       stock +12 B written per env and step; portfolio +20 B written, 8 B read
+       stock +12 B written per env and step; portfolio +20 B written, 8 B read; crypto +16 B
+       written, 8 B read
   c  history attached with it: stock +12 + 4N B (the step kernel also writes `realised`);
-       portfolio +20 + 4N B written
+       portfolio +20 + 4N B written; crypto +16 + 4N B written
   d  history detached, the host copy the history replaces after every step: one state_numpy()
      (portfolio: and one weights.cpu())
-usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio] [--variants a,b,c,d]
-                                      [--rounds R] [--envs E] [--json PATH]
+usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio|crypto]
+                                      [--variants a,b,c,d] [--rounds R] [--envs E] [--json PATH]
   lockstep  every env on the window [0, 63): one record row per step, written contiguously
   desync    random 63-day windows (stock: with hint_desynchronised(True)) and a random half of the envs
             restarted 31 steps after the others: neighbouring envs sit on different panel rows AND on
@@ -18,11 +20,13 @@ usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio] 
 A round of a variant is: reset (arms every record), [desync: 31 steps, reset of a random half],
 then the timed steps -- 62 (lockstep) or 31 (desync), none of them terminal, so every env records on
 every timed step (asserted).  Rounds default to what gives at least 200 timed steps per variant.
+--env crypto: windows of 1,440 rows, 64 timed steps per round in both cases (a record of 100 entries per
+env, not of the whole window: 262,144 envs x 100 x (16 + 4N) B is 1.5 GB).
 FINENV_LIB=<libfinenv.so of another build> times that build; one without the history entry points
 can run variant a only (that is how a commit before the feature is measured with this same script).
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/bench_history.py lockstep --variants c` the
 kernel stats give stock_history_record_kernel's own time (record_bytes() below is what it moves);
-with `--env portfolio`, the recording instantiation's of the step kernel."""
+with `--env portfolio` / `--env crypto`, the recording instantiation's of the step kernel."""
 import argparse
 import ctypes as C
 import json
@@ -33,6 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 WINDOW = 63
+CRYPTO_WINDOW, CRYPTO_TIMED, CRYPTO_CAPACITY = 1440, 64, 100
 
 
 def record_bytes(N, actions):
@@ -45,7 +50,7 @@ def record_bytes(N, actions):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("case", choices=("lockstep", "desync"))
-    ap.add_argument("--env", choices=("stock", "portfolio"), default="stock")
+    ap.add_argument("--env", choices=("stock", "portfolio", "crypto"), default="stock")
     ap.add_argument("--variants", default="a,b,c,d")
     ap.add_argument("--rounds", type=int, default=0)
     ap.add_argument("--envs", type=int, default=65536)
@@ -63,41 +68,46 @@ def main():
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=False, no_stats=False,
                               env=o.env, tickers=30, turbulence_pct=None))()
     w = bench.build_workload(args, torch, dev, 0)
-    env, N = w.env, w.env.stock_dim
-    stock = o.env == "stock"
+    stock, crypto = o.env == "stock", o.env == "crypto"
+    env, N = w.env, w.env.crypto_num if crypto else w.env.stock_dim
+    window = CRYPTO_WINDOW if crypto else WINDOW
+    rows = env.price_array.shape[0] if crypto else env.panel.T
     has_api = hasattr(nat.lib(), f"finenv_{o.env}_set_history")
     if not has_api and variants != ["a"]:
         sys.exit(f"bench_history: this libfinenv.so has no {o.env} history; it can run --variants a only")
     desync = o.case == "desync"
     gen = torch.Generator(device=dev).manual_seed(7)
     if desync:
-        env.set_windows(*random_windows(env.panel.T, E, WINDOW, generator=gen, device=dev))
+        env.set_windows(*random_windows(rows, E, window, generator=gen, device=dev))
         if stock:
             env.hint_desynchronised(True)
     else:
-        env.set_windows(0, WINDOW)
-    timed = 31 if desync else WINDOW - 1
+        env.set_windows(0, window)
+    timed = CRYPTO_TIMED if crypto else (31 if desync else WINDOW - 1)
     rounds = o.rounds or -(-200 // timed)
     half = (torch.rand(E, generator=gen, device=dev) < 0.5).to(torch.uint8)
 
     hists = {}
     if has_api:
-        from finrl_amd.history import EpisodeHistory, PortfolioEpisodeHistory
+        from finrl_amd import history as H
         for v, per_ticker in (("b", False), ("c", True)):
             if v in variants:
-                hists[v] = EpisodeHistory(env, WINDOW, actions=per_ticker) if stock else \
-                    PortfolioEpisodeHistory(env, WINDOW, weights=per_ticker)
+                hists[v] = H.EpisodeHistory(env, WINDOW, actions=per_ticker) if stock else \
+                    H.CryptoEpisodeHistory(env, CRYPTO_CAPACITY, stocks=per_ticker) if crypto else \
+                    H.PortfolioEpisodeHistory(env, WINDOW, weights=per_ticker)
     # the step's optional per-ticker output: stock `realised`, enabled by variant c's history and passed
     # to its steps only; portfolio `weights`, variant d's host copy
+    # (the crypto step has no such output)
     extra, extra_v = ("realised", "c") if stock else ("weights", "d")
-    if not stock and "d" in variants:
+    if o.env == "portfolio" and "d" in variants:
         env.enable_weights()
-    extra_out = getattr(env, extra)
+    extra_out = getattr(env, extra, None)
 
     def select(v):
         if has_api:
             env._call("set_history", C.byref(hists[v]._ptrs) if v in hists else None)
-        setattr(env, extra, extra_out if v == extra_v else None)
+        if not crypto:
+            setattr(env, extra, extra_out if v == extra_v else None)
         env._step_args = None                   # BatchedEnv.step caches the output pointers
 
     def one_round(v, record):
@@ -115,7 +125,7 @@ def main():
             env.step(w.pool[(i + j) % len(w.pool)])
             if v == "d":
                 env.state_numpy()
-                if not stock:
+                if o.env == "portfolio":
                     env.weights.cpu()
         e1.record()
         torch.cuda.synchronize()
@@ -132,7 +142,7 @@ def main():
     for r in range(rounds):
         for v in variants:
             one_round(v, True)
-    res = dict(case=o.case, envs=E, tickers=N, window=WINDOW, timed_steps_per_variant=timed * rounds,
+    res = dict(case=o.case, env=o.env, envs=E, tickers=N, window=window, timed_steps_per_variant=timed * rounds,
                lib=os.path.abspath(nat.LIB_PATH), us_per_step={}, rounds_us={})
     for v in variants:
         t = sorted(times[v])
@@ -141,6 +151,9 @@ def main():
     if stock:
         res["added_bytes_per_env_step"] = {"b": 12, "c": 12 + 4 * N}
         res["record_kernel_bytes_per_env_step"] = {"b": record_bytes(N, False), "c": record_bytes(N, True)}
+    elif crypto:
+        res["added_bytes_written_per_env_step"] = {"b": 16, "c": 16 + 4 * N}
+        res["added_bytes_read_per_env_step"] = {"b": 8, "c": 8}
     else:
         res["added_bytes_written_per_env_step"] = {"b": 20, "c": 20 + 4 * N}
     line = json.dumps(res)
