@@ -242,7 +242,10 @@ cashpenalty_kernel(const CpParams p)
         typedef f4 f4u __attribute__((aligned(4)));
         const int nq = (p.D - kWave + 3) >> 2;                 // quads per row (<= 64)
         const bool qa = NCH > 1 && lane < nq;
-        const int qstart = qa ? min(kWave + 4 * lane, p.D - 4) : kWave;   // (> N: market data only)
+        // (> N: market data only.  Lanes past the last quad load it once more and store nothing: every lane
+        //  loads, and a quad starting at column 64 of a row narrower than 68 ends past the row -- on the
+        //  panel's last date, past the end of panel.info)
+        const int qstart = min(kWave + 4 * lane, p.D - 4);
         auto quad_src = [&](int de) {
             return reinterpret_cast<const f4u *>(reinterpret_cast<const char *>(p.panel.info) +
                                                  (size_t)((unsigned)(de * W + qstart - 1 - N) * 4u));

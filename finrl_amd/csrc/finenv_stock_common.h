@@ -37,7 +37,7 @@ struct Params {
     int32_t day0;
     uint32_t magicN;      // ceil(2^32 / N) for N >= 2 (exact f / N for f < 2^16)
     int32_t block_base;   // first 64-env group of this launch (batches larger than one resident round of
-                          // blocks are stepped as several launches: launch_rounds below)
+                          // blocks are stepped as several launches: launch_step_rounds below)
     int32_t diag;         // FINENV_DIAG builds only: phase-skip bitmask (timing experiments)
     unsigned long long *dbg;   // FINENV_DIAG builds only: [block][role][16] s_memrealtime stamps
     double *last;         // last-episode block [FINENV_STOCK_LAST_FIELDS][E] or NULL
@@ -49,9 +49,6 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kStepThreads = 2 * kWave;
-#ifndef FINENV_TRADE_UNROLL
-#define FINENV_TRADE_UNROLL 2     // unroll factor of the rolled sell / buy loops (tuning switch)
-#endif
 
 using finenv_stock_impl::Params;
 
@@ -61,10 +58,24 @@ using finenv_stock_impl::Params;
 // other blocks' stores -- and the per-env cost rises by a third (DOW30: 65,536 envs 0.64 of the
 // roofline, 262,144 envs 0.47; profiles/r03_placement.md).  So a large batch is stepped as
 // ceil(blocks / round) launches of equal size on the caller's stream, each one resident round or less.
-// `fn(q, nblocks)` launches nblocks blocks with q.block_base set.
-template <typename Kernel, typename Launch>
-inline void launch_rounds(const Params &p, Kernel kernel, size_t lds_bytes, Launch fn)
+// `Kernel` is a template VALUE: the occupancy figure and the LDS opt-in below are cached per kernel, which
+// is what they depend on (every stock_step_kernel<...> has the same function type).
+// Returns 0, or -1 when the dynamic-LDS limit could not be raised.
+template <auto Kernel>
+int launch_step_rounds(const Params &p, size_t lds_bytes, int device, hipStream_t stream)
 {
+    // > 64 KiB of dynamic LDS needs an explicit opt-in, once per device (a process may hold handles on
+    // several GPUs)
+    if (lds_bytes > 64 * 1024) {
+        static unsigned long long attr_set_mask = 0ull;
+        const int dev = device >= 0 && device < 64 ? device : 0;
+        if (!((attr_set_mask >> dev) & 1ull)) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes) != hipSuccess)
+                return -1;
+            attr_set_mask |= 1ull << dev;
+        }
+    }
     static int cus = 0;
     if (cus == 0) {
         int dev = 0;
@@ -72,27 +83,28 @@ inline void launch_rounds(const Params &p, Kernel kernel, size_t lds_bytes, Laun
         cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
                prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     }
-    static int per_cu = 0;                       // (one static per kernel instantiation)
+    static int per_cu = 0;
     if (per_cu == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kernel), kStepThreads,
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(Kernel), kStepThreads,
                                                          lds_bytes) != hipSuccess || nb < 1)
             nb = 1;
         per_cu = nb;
     }
+    // one 128-thread block per 64 envs
     const int blocks = (p.cfg.n_envs + kWave - 1) / kWave;
     const int round = per_cu * cus;
+    const int k = (blocks + round - 1) / round;                    // launches
+    const int chunk = k > 1 ? (blocks + k - 1) / k : blocks;
     Params q = p;
-    if (blocks <= round) {
-        q.block_base = 0;
-        fn(q, blocks);
-        return;
-    }
-    const int k = (blocks + round - 1) / round, chunk = (blocks + k - 1) / k;
-    for (int b = 0; b < blocks; b += chunk) {
+    int b = 0;
+    do {
         q.block_base = b;
-        fn(q, blocks - b < chunk ? blocks - b : chunk);
-    }
+        const int nb = blocks - b < chunk ? blocks - b : chunk;
+        hipLaunchKernelGGL(Kernel, dim3((unsigned)nb), dim3(kStepThreads), lds_bytes, stream, q);
+        b += chunk;
+    } while (b < blocks);
+    return 0;
 }
 
 #ifdef FINENV_DIAG

@@ -1,12 +1,18 @@
 // finenv_stock_kernels.inc -- the stock step / aux kernels, compiled once per padded ticker count
-// (included by finenv_stock.hip inside namespaces np32 / np128 with FINENV_NP, FINENV_LOG2NP and
-// FINENV_SORTNET defined).  See finenv_stock.hip for the design notes.
+// (included by finenv_stock_width.inc inside namespace np32 / np64 / np128 with FINENV_NP,
+// FINENV_LOG2NP and FINENV_SORTNET defined).  See finenv_stock.hip for the design notes.
 
-// ---- geometry of this variant (FINENV_NP = padded ticker count: 32 or 128) -------------------
+// ---- geometry of this variant (FINENV_NP = padded ticker count: 32, 64 or 128) ---------------
 constexpr int kNPad = FINENV_NP;
 constexpr int kLog2NPad = FINENV_LOG2NP;
+// THE width predicate.  32-wide build (DOW30, the headline): holdings, keys and prices of every ticker
+// fit in VGPRs, so the trader stages everything itself ("solo": the streamer depends on nothing but the
+// day index and starts streaming ~3 us earlier; an "early release" barrier variant was slower) and
+// trades on rank-ordered registers.  Wide builds (64, 128): rolled loops over LDS-resident data, the
+// streamer stages holdings and compact price rows for the trader.
+constexpr bool kWide = kNPad > 32;
 constexpr int kRow = kNPad + 1;                         // LDS row stride in dwords (odd)
-constexpr int kAuxWaves = (kNPad <= 32) ? 4 : 1;        // waves per block of the aux kernel
+constexpr int kAuxWaves = kWide ? 1 : 4;                // waves per block of the aux kernel
 constexpr int kLdsPerWave = kWave * kRow;               // >= kNPad * kWave
 constexpr int kAMax = 1 << (30 - kLog2NPad);            // |scaled action| clamp (key packing)
 static_assert((1 << kLog2NPad) == kNPad, "NP must be a power of two");
@@ -314,50 +320,20 @@ __device__ __forceinline__ void write_obs_rows(float *__restrict__ dst,
 // one VALU instruction per ~4 cycles (fp64 ~8) whatever the dependencies, so the trader's
 // time is its instruction count; the streamer shares the SIMD and keeps HBM writing
 // meanwhile (measured: DESIGN.md "stock_step").
+// The observation chunk(s) holding cash / holdings are written after the hand-off barrier, half the
+// rows by the streamer (it has finished streaming by then) and half by the trader, which goes on to
+// the state write-back.  Measured against the trader writing them alone: 21.5 vs 21.8 us (32-wide),
+// and the 128-wide trader is the critical path by far.  This and every alternative named below was a
+// compile-time switch once; each was measured in a same-box A/B (DESIGN.md 4.1-4.3) and then removed.
+// A new experiment is a `make variant` build run through tools/exp_ab_inproc.py.
 // -------------------------------------------------------------------------------------
-// Tuning switches (see tools/sweep_stock.py --variants; defaults = measured best)
-// Who writes the observation chunk(s) holding cash / holdings: the streamer after the hand-off
-// barrier (true; it has finished streaming by then and the trader goes on to the state
-// write-back) or the trader itself (false).  Measured: 21.5 vs 21.8 us (32-wide), and the
-// 128-wide trader is the critical path by far.
-#ifndef FINENV_HANDOFF
-#define FINENV_HANDOFF 1
-#endif
-constexpr bool kHandOff = FINENV_HANDOFF != 0;
-// Switches of the desynchronised-batch instantiation (DES = true; each measured on its own in a
-// same-box A/B, DESIGN.md 4.3): row-wise price gather, staging barrier, head rows split in
-// episode-end blocks, 16-byte row copies (chunks per batch; 1 = dword form), parked head chunks.
-#ifndef FINENV_ROW_GATHER
-#define FINENV_ROW_GATHER 1
-#endif
-#ifndef FINENV_DESYNC_BARRIER
-#define FINENV_DESYNC_BARRIER 1
-#endif
-#ifndef FINENV_SPLIT_TERM
-#define FINENV_SPLIT_TERM 1
-#endif
-#ifndef FINENV_DESYNC_X4
-#define FINENV_DESYNC_X4 4
-#endif
-#ifndef FINENV_DESYNC_PARK
-#define FINENV_DESYNC_PARK 1
-#endif
-// Solo staging (32-wide variant): the trader stages the whole action tile and the price row
-// itself, so the streamer depends on nothing but the day index and starts streaming ~3 us
-// earlier (measured: DESIGN.md history; an "early release" barrier variant was slower).
-#ifndef FINENV_SOLO_STAGING
-#define FINENV_SOLO_STAGING 1
-#endif
-constexpr bool kSolo = FINENV_SOLO_STAGING != 0 && kNPad <= 32;
-constexpr int kPriceRole = kSolo ? 0 : 1;          // who stages the price row
 constexpr int kR1 = kWave * kRow;                 // dwords: act tile / holdings / obs rows
 // Price staging.  32-wide variant: f64 [ticker][lane] (per-env day, conflict-free dynamic gather).
-// 128-wide variant: that would be 64 KB and pin the kernel to one block per CU, so it stages ONE
-// f64 row [ticker] when the block's 64 envs share the price day (always, in lock-step batches) and
-// gathers from the L1-resident panel row otherwise.
-constexpr bool kCompactPrices = kNPad > 32;
+// Wide variants: that would be 64 KB and pin the kernel to one block per CU, so they stage compact
+// prices -- ONE f64 row [ticker] when the block's 64 envs share the price day (always, in lock-step
+// batches) -- and gather from the L1-resident panel row otherwise.
 constexpr int kPStride = kWave + 1;              // f64 price rows gathered per env: odd stride (transposed writes)
-constexpr int kR2 = kCompactPrices ? kNPad * 4 : kNPad * kPStride * 2;   // dwords (compact: current + next row)
+constexpr int kR2 = kWide ? kNPad * 4 : kNPad * kPStride * 2;   // dwords (compact: current + next row)
 constexpr int kR3 = kWave * kRow;                 // dwords: sorted keys [rank][lane] / obs rows
 constexpr int kHeadMax = (2 * kNPad) / kWave + 1; // observation chunks holding cash / holdings
 constexpr int kR4 = kHeadMax * kWave;             // dwords: their template values (head_park)
@@ -372,7 +348,7 @@ constexpr int kLdsStep = kR1 + kR2 + kR3 + kR4;   // dynamic LDS of the step ker
 // test reads the env's window end, a reset goes back to its window start.  A template parameter for
 // the same reason: the no-window instantiations compile exactly as before.
 template <bool TURB, bool STATS, bool DES = false, bool WIN = false>
-__global__ void __launch_bounds__(kStepThreads, (kNPad <= 32) ? 2 : 1)
+__global__ void __launch_bounds__(kStepThreads, kWide ? 1 : 2)
 stock_step_kernel(const Params p)
 {
     extern __shared__ __attribute__((aligned(16))) float lds_all[];   // kR1 + kR2 + kR3 dwords
@@ -385,9 +361,9 @@ stock_step_kernel(const Params p)
     float *rows = lds_all + kR1 + kR2;                          // later: obs rows [env][kRow]
     float *ldshead = lds_all + kR1 + kR2 + kR3;                 // head-chunk template values
     // Action tile [env][kRow]: in R1 for the 32-wide variant (holdings move there from registers
-    // once the keys are built); in R3 for the 128-wide one, whose holdings are staged straight
+    // once the keys are built); in R3 for the wide ones, whose holdings are staged straight
     // into R1 by the streamer (R3 is free until the sorted keys are parked).
-    float *tile = kNPad > 32 ? rows : lds_all;
+    float *tile = kWide ? rows : lds_all;
 
     const int E = p.cfg.n_envs, N = p.cfg.n_tickers, D = p.D, T = p.cfg.n_days;
     const int P = p.obs_pitch;                            // row pitch of p.obs in floats (>= D)
@@ -401,17 +377,17 @@ stock_step_kernel(const Params p)
 #ifdef FINENV_DIAG
     if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 14] = __builtin_amdgcn_s_memtime();
 #endif
-    // ---- both waves: their half of the action tile [nenv_w][N] f32, issued before anything else
-    // (16-B coalesced loads; chunk `it` belongs to wave it & 1) -------------------------------
+    // ---- the action tile [nenv_w][N] f32, issued before anything else (16-B coalesced loads): all of
+    // it in the trader (32-wide), or half per wave (wide: chunk `it` belongs to wave it & 1) ------
     const float *__restrict__ act_src = p.actions + (size_t)e0 * N;          // 16-B aligned
     const int act_total = nenv_w * N;
     const int act_n4 = act_total >> 2;
-    constexpr int kTileLoads = kSolo ? kNPad / 4 : kNPad / 8;   // float4 loads per lane
+    constexpr int kTileLoads = kWide ? kNPad / 8 : kNPad / 4;   // float4 loads per lane
     float4 av[kTileLoads];
-    if (!kSolo || role == 0) {
+    if (kWide || role == 0) {
 #pragma unroll
         for (int j = 0; j < kTileLoads; ++j) {
-            const int idx4 = (kSolo ? j : 2 * j + role) * kWave + lane;
+            const int idx4 = (kWide ? 2 * j + role : j) * kWave + lane;
             av[j] = reinterpret_cast<const float4 *>(act_src)[(idx4 < act_n4 && !DIAG(8)) ? idx4 : 0];
         }
     }
@@ -435,22 +411,21 @@ stock_step_kernel(const Params p)
         return col == 0 ? 0 : ((hidx >= 0 && hidx < N) ? 1 + hidx : -1);
     };
     const int pd_first = __builtin_amdgcn_readfirstlane(pd_cur);
-    const bool uniform_pd = kCompactPrices && __all(pd_cur == pd_first);   // same in both waves
+    const bool uniform_pd = kWide && __all(pd_cur == pd_first);   // same in both waves
     // 32-wide variant, lock-step days: ONE shared price row at the start of the price region
     // (lane i < 32 loads ticker i: one coalesced load instead of 32 wave-uniform ones -- the
     // trader's staging is paced by the number of loads it has in flight under the streamers'
     // store traffic).  Reads go through ldsp[idx * pmul + padd] in either layout.
-    const bool shared_row = kSolo && !kCompactPrices && __all(pd_cur == pd_first);
+    const bool shared_row = !kWide && __all(pd_cur == pd_first);
     const bool desync_days = !__all(pd_cur == pd_first);
-    const bool gather_rows = DES && FINENV_ROW_GATHER && !kCompactPrices && desync_days;
+    const bool gather_rows = DES && !kWide && desync_days;   // row-wise price gather by the streamer (below)
     // Desynchronised days, one head chunk: every env's head chunk comes from its own panel row.  Loading
     // those rows after the hand-off means loads behind a full queue of stores (a ~3 us wait before the
     // first head row can go out).  The streamer -- idle until the staging barrier -- fetches all 64
     // rows' head chunks at the start (16-byte loads, 4 rows per instruction), keeps them while it
     // streams, and parks them in the (by then dead) price region after the hand-off barrier; one more
     // barrier, then both waves write their 32 head rows from LDS.
-    const bool park_heads = DES && FINENV_DESYNC_PARK && !kCompactPrices && kHandOff && desync_days &&
-                            kpatch == 1 && D >= kWave;
+    const bool park_heads = gather_rows && kpatch == 1 && D >= kWave;
     typedef float hf4 __attribute__((ext_vector_type(4)));
     typedef hf4 hf4u __attribute__((aligned(4)));
     // head rows [el_lo, el_hi) from the parked templates + the (cash, holdings) image in LDS
@@ -473,7 +448,7 @@ stock_step_kernel(const Params p)
     };
     const int pmul = shared_row ? 1 : (gather_rows ? kPStride : kWave), padd = shared_row ? 0 : lane;
     const int pn_first = __builtin_amdgcn_readfirstlane(pd_next);
-    const bool uniform_next = kCompactPrices && __all(pd_next == pn_first);
+    const bool uniform_next = kWide && __all(pd_next == pn_first);
     STAMP(1);
 
     // values the trader loads before the barrier (declared here: one barrier call site)
@@ -481,8 +456,7 @@ stock_step_kernel(const Params p)
     double st_mean = 0.0, st_m2 = 0.0;
     int trades = 0;
     bool first_step = false;                      // first step of this env's episode (STATS)
-    constexpr bool kWide = kNPad > 32;            // NASDAQ-100 variant: rolled loops, fewer VGPRs
-    int hreg[kWide ? 1 : kNPad];
+    int hreg[kWide ? 1 : kNPad];                  // (wide variants: rolled loops, fewer VGPRs)
 
     if (role == 0) {
         // ---- trader, part 1: every global load it will ever need, issued up front ----------
@@ -499,7 +473,7 @@ stock_step_kernel(const Params p)
         }
         if (!kWide) {
 #pragma unroll
-            for (int i = 0; i < (kWide ? 1 : kNPad); ++i) {
+            for (int i = 0; i < kNPad; ++i) {
                 // padded slots hold 0 shares: they then add exactly +0.0 to the begin / end asset
                 // sums (prices are finite), which saves a select pair per slot in both loops
                 const int hv = HOLD(i < N ? i : 0);
@@ -509,11 +483,11 @@ stock_step_kernel(const Params p)
     }
     // (desynchronised instantiation: the STREAMER gathers the 64 price rows -- it idles until the
     //  staging barrier anyway -- and the trader's staging is its own tile / state loads again)
-    if (role == (gather_rows ? 1 : kPriceRole)) {
+    if (role == ((kWide || gather_rows) ? 1 : 0)) {
         // template values of the head chunks for the end of the step (see head_plan)
         float head_tt[kHeadMax];
-        if (kHandOff && !park_heads) head_fetch(head_tt, p.panel.obs_tmpl, D, ro_first, lane, kpatch);
-        // ---- stage the current price row in LDS (streamer; the trader when kSolo) --------------
+        if (!park_heads) head_fetch(head_tt, p.panel.obs_tmpl, D, ro_first, lane, kpatch);
+        // ---- stage the current price row in LDS (streamer; the trader in the 32-wide build) -----
         // The day's "untradable" flag of each ticker (first indicator == 1.0, :105/:174) rides
         // in the SIGN BIT of the panel's closes (packed on the host; prices are >= 0 by contract):
         // the trade loops need no mask registers and no bit lookup, the staging no second load.
@@ -543,7 +517,7 @@ stock_step_kernel(const Params p)
                 for (int j = 0; j < kWave; ++j)
                     if (lane < kNPad) ldsp[lane * kPStride + j] = pv[j];
             }
-        } else if (!kCompactPrices) {
+        } else if (!kWide) {
             for (int base = 0; base < kNPad; base += 32) {   // 32 loads in flight per batch
                 double pv[32];
 #pragma unroll
@@ -581,22 +555,21 @@ stock_step_kernel(const Params p)
 #pragma unroll
             for (int i = 0; i < kNPad; ++i) ldsh[i * kWave + lane] = (i < N) ? hv[i] : 0;
         }
-        if (kHandOff && !park_heads) head_park(ldshead, head_tt, lane);
+        if (!park_heads) head_park(ldshead, head_tt, lane);
     }
-    // Desynchronised instantiation: the staging barrier sits HERE for the trader -- its global loads
-    // have landed, which is all the streamer has to wait for (the tile transposition below is the
-    // trader's own LDS work: 2 us the streamer would otherwise idle through).
-    const bool early_barrier = gather_rows && FINENV_DESYNC_BARRIER && kSolo;
-    if (early_barrier && role == 0) {
+    // Desynchronised days (gather_rows): the staging barrier sits HERE for the trader -- its global
+    // loads have landed, which is all the streamer has to wait for (the tile transposition below is
+    // the trader's own LDS work: 2 us the streamer would otherwise idle through).
+    if (gather_rows && role == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();
     }
     // ---- transpose the action tile into LDS rows (stride 33): half per wave, or all of it in the
-    // trader when kSolo -------------------------------------------------------------------------
-    if (!kSolo || role == 0) {
+    // trader (32-wide) --------------------------------------------------------------------------
+    if (kWide || role == 0) {
 #pragma unroll
     for (int j = 0; j < kTileLoads; ++j) {
-        const int idx4 = (kSolo ? j : 2 * j + role) * kWave + lane;
+        const int idx4 = (kWide ? 2 * j + role : j) * kWave + lane;
         if (idx4 < act_n4) {
             const float c[4] = {av[j].x, av[j].y, av[j].z, av[j].w};
 #pragma unroll
@@ -608,7 +581,7 @@ stock_step_kernel(const Params p)
         }
     }
     }
-    if (role == (kSolo ? 0 : 1))
+    if (role == (kWide ? 1 : 0))
         for (int f = 4 * act_n4 + lane; f < act_total; f += kWave) {          // < 4 leftover floats
             const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
             tile[el * kRow + (f - el * N)] = *at(act_src, (unsigned)f);
@@ -629,10 +602,11 @@ stock_step_kernel(const Params p)
     // Desynchronised days: the trader's staging loads (64 price rows) would otherwise queue behind
     // four streamers' row traffic in the CU's memory pipeline and return when the streaming is
     // over (timeline: staged at 16 us instead of 5, the whole trade serialised behind it).  The
-    // streamer waits here until they have landed.
-    if (early_barrier) {
+    // streamer waits here until they have landed (the trader met this barrier above).  Otherwise the
+    // 32-wide trader staged for itself alone, and the wide builds' waves staged for each other.
+    if (gather_rows) {
         if (role == 1) lds_barrier(); else wave_sync();
-    } else if (kSolo && !(gather_rows && FINENV_DESYNC_BARRIER)) {
+    } else if (!kWide) {
         wave_sync();
     } else {
         lds_barrier();
@@ -645,43 +619,42 @@ stock_step_kernel(const Params p)
             if (term_mask != 0ull && p.term_obs != nullptr)
                 write_obs_rows(p.term_obs, p.panel.obs_tmpl, D, D, N, e0, nenv_w, pd_cur,
                                term_mask, lds, lane, kpatch);
-            write_obs_rows<(DES ? FINENV_DESYNC_X4 : 1)>(p.obs, p.panel.obs_tmpl, D, P, N, e0, nenv_w, row_obs, valid_mask, lds,
+            // desynchronised instantiation: 16-byte row copies, this many chunks per batch (1 = dword form)
+            constexpr int kDesyncCh = 4;
+            write_obs_rows<(DES ? kDesyncCh : 1)>(p.obs, p.panel.obs_tmpl, D, P, N, e0, nenv_w, row_obs, valid_mask, lds,
                               lane, kpatch);
         }
         STAMP(4);
-        // ---- streamer, part 3 (kHandOff only): once the trader has published the (cash,
-        // holdings) rows in LDS, write the chunk(s) that contain them; the trader goes on to its
-        // state write-back.
-        if (kHandOff) {
-            lds_barrier();
-            if (park_heads) {
-                float *const park = reinterpret_cast<float *>(ldsp);     // (prices are dead by now)
-                const int q = lane & 15, rs = lane >> 4;
+        // ---- streamer, part 3: once the trader has published the (cash, holdings) rows in LDS,
+        // write the chunk(s) that contain them; the trader goes on to its state write-back.
+        lds_barrier();
+        if (park_heads) {
+            float *const park = reinterpret_cast<float *>(ldsp);     // (prices are dead by now)
+            const int q = lane & 15, rs = lane >> 4;
 #pragma unroll
-                for (int u = 0; u < 16; ++u)
-                    *reinterpret_cast<hf4 *>(park + (4 * u + rs) * kWave + 4 * q) = ht[u];
-                lds_barrier();
-                if (!DIAG(1)) head_rows_parked(park, rows, kWave / 2, kWave);
-            } else
-            // (episode-end blocks of a desynchronised batch too -- every step has some, and they set
-            //  the kernel's duration; rows are final at the barrier.  With lock-step days the trader
-            //  keeps them: making the split unconditional cost the headline path 1.3 us)
-            if (!DIAG(1) && (term_mask == 0ull || (DES && FINENV_SPLIT_TERM && desync_days))) {
-                // rows[el * kRow + w] holds cash (w = 0) and holdings (w = 1 + ticker)
-                HeadPlan<kHeadMax> hp;
-                head_plan(hp, ldshead, D, row_obs, ro_first, valid_mask, lane, kpatch, head_widx);
-                if (hp.uniform)      // rows 32..63 here, rows 0..31 in the trader
-                    head_store(hp, p.obs, D, P, e0, nenv_w, valid_mask, lane, kWave / 2, kWave,
-                               [rows](int el, int w) { return rows[el * kRow + w]; });
-                else
-                    write_obs_rows(p.obs, p.panel.obs_tmpl, D, P, N, e0, nenv_w, row_obs, valid_mask,
-                                   rows, lane, 0, kpatch, kWave / 2, kWave);
-            }
-            STAMP(5);
-            if (valid) {                           // holdings write-back (final after the barrier)
+            for (int u = 0; u < 16; ++u)
+                *reinterpret_cast<hf4 *>(park + (4 * u + rs) * kWave + 4 * q) = ht[u];
+            lds_barrier();
+            if (!DIAG(1)) head_rows_parked(park, rows, kWave / 2, kWave);
+        } else
+        // (episode-end blocks of a desynchronised batch too -- every step has some, and they set
+        //  the kernel's duration; rows are final at the barrier.  With lock-step days the trader
+        //  keeps them: making the split unconditional cost the headline path 1.3 us)
+        if (!DIAG(1) && (term_mask == 0ull || (DES && desync_days))) {
+            // rows[el * kRow + w] holds cash (w = 0) and holdings (w = 1 + ticker)
+            HeadPlan<kHeadMax> hp;
+            head_plan(hp, ldshead, D, row_obs, ro_first, valid_mask, lane, kpatch, head_widx);
+            if (hp.uniform)      // rows 32..63 here, rows 0..31 in the trader
+                head_store(hp, p.obs, D, P, e0, nenv_w, valid_mask, lane, kWave / 2, kWave,
+                           [rows](int el, int w) { return rows[el * kRow + w]; });
+            else
+                write_obs_rows(p.obs, p.panel.obs_tmpl, D, P, N, e0, nenv_w, row_obs, valid_mask,
+                               rows, lane, 0, kpatch, kWave / 2, kWave);
+        }
+        STAMP(5);
+        if (valid) {                           // holdings write-back (final after the barrier)
 #pragma unroll 8
-                for (int i = 0; i < N; ++i) HOLD(i) = ldsh[i * kWave + lane];
-            }
+            for (int i = 0; i < N; ++i) HOLD(i) = ldsh[i * kWave + lane];
         }
         return;
     }
@@ -689,7 +662,7 @@ stock_step_kernel(const Params p)
     // =========================== trader wave only below ===================================
     // 32-wide variant: the trader is the critical path; its instructions win issue arbitration
     // against the streamer wave sharing the SIMD (measured -0.2 us; nothing at 128 wide)
-    if (kNPad <= 32) __builtin_amdgcn_s_setprio(3);
+    if (!kWide) __builtin_amdgcn_s_setprio(3);
     // Code-size note: only the key build, the begin-asset sum and the sorting network are
     // unrolled (they need statically indexed VGPRs).  Everything after the sort is a rolled,
     // software-pipelined loop over LDS-resident data: the fully unrolled form was ~55 KB of
@@ -716,7 +689,7 @@ stock_step_kernel(const Params p)
 
     // signed price of ticker idx for this env (sign bit = untradable flag)
     auto price_signed = [&](int idx) -> double {
-        if (!kCompactPrices) return ldsp[idx * pmul + padd];
+        if (!kWide) return ldsp[idx * pmul + padd];
         if (uniform_pd) return ldsp[idx];
         return *at(p.panel.close, (unsigned)(pd_cur * N + min(idx, N - 1)));
     };
@@ -729,7 +702,7 @@ stock_step_kernel(const Params p)
     double s = 0.0;
     if (!kWide) {
 #pragma unroll
-        for (int i = 0; i < (kWide ? 1 : kNPad); ++i) ldsh[i * kWave + lane] = hreg[i];
+        for (int i = 0; i < kNPad; ++i) ldsh[i * kWave + lane] = hreg[i];
     }
     STAMP(4);
 
@@ -739,8 +712,7 @@ stock_step_kernel(const Params p)
     const double one_m_cs = 1 - c_s, one_p_cb = 1 + c_b;
     const int *kcol = ldsk + lane;                 // this env's sorted keys, stride kWave
     int *hcol = ldsh + lane;                       // this env's holdings by ticker, stride kWave
-    constexpr bool kPrefetchNext = kNPad <= 32;    // 2 VGPRs per ticker: only when they fit
-    double nreg[kPrefetchNext ? kNPad : 1];
+    double nreg[kWide ? 1 : kNPad];                // next-row prices, 2 VGPRs per ticker: only where they fit
 
     if (!kWide) {
         // ======================= 32-wide variant: rank-ordered registers ========================
@@ -806,11 +778,9 @@ stock_step_kernel(const Params p)
         // the loads fly during the buy loop; the fence keeps hipcc from hoisting 64 more live
         // VGPRs above the sell pass
         asm volatile("" ::: "memory");
-        if (kPrefetchNext) {
 #pragma unroll
-            for (int i = 0; i < (kPrefetchNext ? kNPad : 1); ++i)
-                nreg[i] = *at(p.panel.close, (unsigned)(pd_next * N + (i < N ? i : 0)));
-        }
+        for (int i = 0; i < kNPad; ++i)
+            nreg[i] = *at(p.panel.close, (unsigned)(pd_next * N + (i < N ? i : 0)));
         // ---- buys: largest first (:319, :328-330, _buy_stock :171-213) -------------------------
         // Serial through cash: q = min(a, cash // unit), cash -= p*q*(1+c_b).  Keys and prices are
         // read by RANK (static stride, three ranks ahead); unit price and its refined reciprocal
@@ -869,7 +839,7 @@ stock_step_kernel(const Params p)
     for (int r = 0; r < kNPad; ++r) ldsk[r * kWave + lane] = keys[r];
     STAMP(5);
 
-    if (kWide && uniform_pd) {
+    if (uniform_pd) {
         // ---- lock-step days (one shared price row in LDS): the rank-ordered form of the 32-wide
         // variant in register chunks.  Keys of a chunk are read back by rank (static stride),
         // their (price, holdings) gathered with the whole chunk's LDS loads in flight, and the
@@ -968,7 +938,7 @@ stock_step_kernel(const Params p)
         int h0 = hcol[(key0 & (kNPad - 1)) * kWave];
         double q0p = price_signed(key0 & (kNPad - 1));
         int n_sold = 0;
-#pragma unroll FINENV_TRADE_UNROLL
+#pragma unroll 2
         for (int r = 0; r < kNPad; ++r) {
             if (!__any(key0 < 0)) break;               // sorted: no sells beyond this rank
             const int key2 = kcol[min(r + 2, kNPad - 1) * kWave];
@@ -1003,7 +973,7 @@ stock_step_kernel(const Params p)
         double p0 = price_signed(key0 & (kNPad - 1));
         double u0 = p0 * one_p_cb;                                            // :179
         double x0 = refined_rcp(u0);
-#pragma unroll FINENV_TRADE_UNROLL
+#pragma unroll 2
         for (int r = kNPad - 1; r >= 0; --r) {
             if (!__any(key0 >= kNPad)) break;          // sorted: no buys (a >= 1) below this rank
             const int key2 = kcol[max(r - 2, 0) * kWave];
@@ -1043,9 +1013,9 @@ stock_step_kernel(const Params p)
     s = 0.0;
     if (!kWide) {
 #pragma unroll
-        for (int i = 0; i < (kWide ? 1 : kNPad); ++i) {
+        for (int i = 0; i < kNPad; ++i) {
             const int h = hcol[i * kWave];
-            s = s + fabs(nreg[kPrefetchNext ? i : 0]) * (double)h;     // padded slots: h == 0
+            s = s + fabs(nreg[i]) * (double)h;     // padded slots: h == 0
             rows[lane * kRow + 1 + i] = (float)h;   // slots > N: padding, never read
         }
     } else {
@@ -1131,10 +1101,10 @@ stock_step_kernel(const Params p)
     // ---- the observation chunk(s) holding cash / holdings (:342 / :453-478): after this barrier
     // (rows are final) the streamer writes rows 32..63 and the trader rows 0..31 (its template loads
     // go out before its state stores) ---------------------------------------------------------------
-    if (kHandOff) lds_barrier(); else wave_sync();
+    lds_barrier();
     if (park_heads) lds_barrier();            // the streamer has parked every row's head chunk
     HeadPlan<kHeadMax> hpt;
-    const bool split_head = kHandOff && (term_mask == 0ull || (DES && FINENV_SPLIT_TERM && desync_days));
+    const bool split_head = term_mask == 0ull || (DES && desync_days);
     if (split_head && !park_heads)
         head_plan(hpt, ldshead, D, row_obs, ro_first, valid_mask, lane, kpatch, head_widx);
     if (!DIAG(1) && !split_head && !park_heads)
@@ -1170,10 +1140,6 @@ stock_step_kernel(const Params p)
         SF(FINENV_SF_LAST_REWARD) = last_reward;
         if (TURB) SF(FINENV_SF_TURBULENCE) = turb;
         if (episode_inc) SI(FINENV_SI_EPISODE) += 1;
-        if (!kHandOff) {
-#pragma unroll 6
-            for (int i = 0; i < N; ++i) HOLD(i) = hcol[i * kWave];
-        }
     }
     if (park_heads) {
         if (!DIAG(1)) head_rows_parked(reinterpret_cast<const float *>(ldsp), rows, 0, kWave / 2);

@@ -1,6 +1,6 @@
 // finenv_stock_wide.inc -- step kernel for a COMPILE-TIME ticker count NT in (64, 128]
-// (NASDAQ-100: NT = 100, BASELINE configs[3]); included by finenv_stock_np128.hip inside namespace
-// np128, after finenv_stock_kernels.inc (shares its helpers and the aux kernel).
+// (NASDAQ-100: NT = 100, BASELINE configs[3]); included by finenv_stock_width.inc after
+// finenv_stock_kernels.inc (shares its helpers and the aux kernel) and instantiated in namespace np128 alone.
 //
 // Same arithmetic as stock_step_kernel (env_stocktrading.py:220-357), different resource plan.
 // The generic 128-wide kernel keeps the f32 action tile, 32-bit sorted keys and f32 observation rows
@@ -92,10 +92,7 @@ stock_step_wide_kernel(const Params p)
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // 0 trader, 1 streamer
 
     constexpr int N = NT;
-#ifndef FINENV_WIDE_SPLIT_HOLD
-#define FINENV_WIDE_SPLIT_HOLD (NT / 2)
-#endif
-    constexpr int kHoldSplit = FINENV_WIDE_SPLIT_HOLD;    // holdings [0, split) written back by the trader
+    constexpr int kHoldSplit = NT / 2;                    // holdings [0, split) written back by the trader
     const int E = p.cfg.n_envs, D = p.D, T = p.cfg.n_days, P = p.obs_pitch;
     const int e0 = ((int)blockIdx.x + p.block_base) * kWave;
     if (e0 >= E) return;                                  // block-uniform
@@ -185,9 +182,6 @@ stock_step_wide_kernel(const Params p)
         // =========================== streamer ==================================================
         // part 1: nothing to stage -- the streamer needs the day index only and starts writing at
         // once (the start-up reads of the trader overlap with these stores: the step is HBM-bound);
-#ifdef FINENV_WIDE_STREAMER_DELAY   // A/B switch: hold the stores back for ~N us (traders' reads first)
-        for (int d = 0; d < FINENV_WIDE_STREAMER_DELAY * 18; ++d) __builtin_amdgcn_s_sleep(8);
-#endif
         STAMP(2);
         STAMP(3);
         // part 2: market-data chunks of the observation rows

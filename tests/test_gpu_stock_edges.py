@@ -1,6 +1,7 @@
 """Degenerate panel sizes for the stock env: a one-day panel (every step is terminal, :221),
 two- and three-day panels (episodes of 1-2 trading steps), with 1, 5 and 32 tickers, auto-reset
-on.  HIP (through the C ABI) vs the oracle, exact."""
+on; and one small batch through every instantiation the step launchers choose between.  HIP
+(through the C ABI) vs the oracle, exact."""
 import numpy as np
 import pytest
 
@@ -45,6 +46,65 @@ def test_tiny_panels_match_oracle(T, N):
             np.testing.assert_array_equal(env.term_obs.cpu().numpy()[o_done],
                                           o_term[o_done].astype(np.float32))
     assert n_done >= 3
+    st, os_ = env.state_numpy(), orc.state()
+    np.testing.assert_array_equal(st["cash"], os_["cash"])
+    np.testing.assert_array_equal(st["shares"], os_["shares"])
+
+
+# (N, hmax, desync_hint, windows): one case per leaf of the step launcher's choice of instantiation
+_LEAVES = [
+    (30, 100, False, False),    # np32 plain
+    (30, 100, True, False),     # np32 desync-hint (DES)
+    (30, 100, False, True),     # np32 windows (DES + WIN)
+    (50, 100, False, False),    # np64 plain
+    (50, 100, False, True),     # np64 WIN
+    (100, 100, False, False),   # np128 wide N = 100
+    (100, 100, False, True),    # np128 wide N = 100, WIN
+    (100, 300, False, False),   # np128 generic at N = 100 (hmax > 255 does not fit the wide kernel's keys)
+    (100, 300, False, True),    # np128 generic at N = 100, WIN
+    (128, 100, False, False),   # np128 generic, full width
+]
+
+
+@pytest.mark.parametrize("track_stats", [False, True])
+@pytest.mark.parametrize("use_turbulence", [False, True])
+@pytest.mark.parametrize("N,hmax,desync_hint,windows", _LEAVES)
+def test_every_step_launch_leaf_matches_the_oracle(N, hmax, desync_hint, windows, use_turbulence, track_stats):
+    """Every instantiation the step launchers can select (width x TURB x STATS x the leaves above) steps
+    a batch of two full 64-env blocks and a partial one exactly like the oracle.  `windows` gives every
+    env the window [0, T): the WIN kernels run while one whole-panel oracle stays the exact reference."""
+    _need_gpu()
+    from finrl_amd import StockPanel
+    from finrl_amd.vec_env import VecStockTradingEnv
+    from oracle.stock import StockOracle
+    E, T, K = 130, 6, 2
+    rng = np.random.default_rng(1000 * N + hmax)
+    close = (50 + rng.uniform(0, 10, (T, N))).astype(np.float32).astype(np.float64)
+    tech = rng.normal(0, 1, (T, K, N)).astype(np.float32).astype(np.float64)
+    risk = np.abs(rng.normal(0, 30, T))
+    kw = dict(hmax=hmax, initial_amount=1_000_000, num_stock_shares=rng.integers(0, 40, N),
+              turbulence_threshold=(float(np.median(risk)) if use_turbulence else None))
+    env = VecStockTradingEnv(StockPanel(close, tech, risk), E, track_stats=track_stats, **kw)
+    env.enable_terminal_obs()
+    if desync_hint:
+        env.hint_desynchronised()
+    if windows:
+        env.set_windows(0, T)
+    orc = StockOracle(close, tech, risk, n_envs=E, **kw)
+    np.testing.assert_array_equal(env.reset().cpu().numpy(), orc.reset().astype(np.float32))
+    n_done = 0
+    for s in range(2 * T + 2):
+        a = rng.uniform(-1, 1, (E, N)).astype(np.float32)
+        g_obs, g_rew, g_done, _ = env.step(torch.from_numpy(a).cuda())
+        o_obs, o_rew, o_done, o_term = orc.vec_step(a)
+        np.testing.assert_array_equal(g_done.cpu().numpy().astype(bool), o_done, err_msg=f"step {s}")
+        np.testing.assert_array_equal(g_obs.cpu().numpy(), o_obs.astype(np.float32), err_msg=f"step {s}")
+        np.testing.assert_array_equal(g_rew.cpu().numpy(), o_rew.astype(np.float32), err_msg=f"step {s}")
+        if o_done.any():
+            n_done += 1
+            np.testing.assert_array_equal(env.term_obs.cpu().numpy()[o_done],
+                                          o_term[o_done].astype(np.float32))
+    assert n_done == 2
     st, os_ = env.state_numpy(), orc.state()
     np.testing.assert_array_equal(st["cash"], os_["cash"])
     np.testing.assert_array_equal(st["shares"], os_["shares"])

@@ -2,9 +2,36 @@
 # VGPR / scratch / LDS / code size of every kernel of one source file (compiles it for gfx950 with
 # the Makefile's flags and prints the compiler's resource remarks).
 #   tools/kernel_info.sh finenv_cashpenalty.hip [extra -D flags]
+# ISA digests, for diffing the device code of two trees (one line per kernel: hash, symbol):
+#   tools/kernel_info.sh --isa finenv_stock_np32.hip [extra -D flags]
+#   tools/kernel_info.sh --isa <other tree>/finrl_amd/csrc/finenv_stock_np32.hip
 set -e
-cd "$(dirname "$0")/../finrl_amd/csrc"
+isa=0
+if [ "$1" = "--isa" ]; then isa=1; shift; fi
 src=$1; shift
+case "$src" in
+  */*) cd "$(dirname "$src")"; src=$(basename "$src") ;;
+  *) cd "$(dirname "$0")/../finrl_amd/csrc" ;;
+esac
+if [ $isa = 1 ]; then
+  # gfx950 assembly of the device side; per kernel, hash its code (label .. .Lfunc_end) and its
+  # .amdhsa_kernel descriptor block (registers, LDS, scratch, launch bounds).  The per-build
+  # __hip_cuid_<hash> symbol and the function index inside local labels are masked.
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. "$@" \
+      --cuda-device-only -S -o - "$src" |
+    python3 -c '
+import sys, re, hashlib
+t = sys.stdin.read()
+t = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", t)
+t = re.sub(r"\.LBB\d+_", ".LBB_", t)
+t = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", t)
+for m in sorted(re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n.*?\.end_amdhsa_kernel", t, re.M | re.S), key=lambda m: m.group(1)):
+    k = m.group(1)
+    code = re.search(r"^%s:.*?^\.Lfunc_end:" % re.escape(k), t, re.M | re.S).group(0)
+    print(hashlib.sha256((code + m.group(0)).encode()).hexdigest()[:16], k)
+'
+  exit 0
+fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. "$@" \
     -c -o /dev/null "$src" -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
