@@ -25,73 +25,25 @@
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
-
-#ifdef FINENV_DIAG
-extern unsigned long long *g_finenv_dbg;         // finenv_stock.hip (diagnostic builds)
-#endif
+#include "finenv_twowave.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kMaxN = FINENV_CASHPENALTY_MAX_ASSETS;
-constexpr int kRow = kMaxN + 1;
+struct CpParams : TwoWaveParams<finenv_cashpenalty_config, finenv_cashpenalty_panel,
+                                finenv_cashpenalty_state, kMaxN> {};
+constexpr int kRow = CpParams::kRow, kClStride = CpParams::kClStride;
 constexpr int kWaves = 2;                    // trader + streamer
-constexpr int kClStride = kMaxN + 1;           // f64 close rows [env][33]: odd stride, conflict-free
 constexpr int kLdsRows = kWave * kRow;         // f32 [el][33]: action tile, then cash / holdings
 constexpr int kLdsClose = kClStride * kWave * 2;   // f64 closes [el][i]
 constexpr int kLdsPerBlock = kLdsRows + kLdsClose + kWave + 2;  // + the rows the trade decided (i32), flag
 constexpr int kFix = 4;                        // re-decided rows per block the streamer patches in registers
 static_assert(kWave * kWave <= kLdsClose, "the parked chunk 0 reuses the close rows");
 
-struct CpParams {
-    finenv_cashpenalty_config cfg;
-    finenv_cashpenalty_panel panel;
-    finenv_cashpenalty_state st;
-    const float *actions;
-    float *obs;
-    float *reward;
-    uint8_t *done;
-    float *term_obs;
-    const uint8_t *mask;
-    int32_t auto_reset;
-    int32_t D;
-    uint32_t magicN;
-    int32_t rs_hi;                  // random_start: draw in [0, rs_hi) on the device (0 = off)
-    unsigned long long rs_seed;
-    double *audit;                  // optional [E][FINENV_AUDIT_HEAD + N] per-step log row, or NULL
-    unsigned long long *dbg;        // FINENV_DIAG builds only: [wave][16] s_memrealtime stamps
-};
-
-#ifdef FINENV_DIAG
-#define KSTAMP(k)                                                                           \
-    do {                                                                                    \
-        if (p.dbg != nullptr && lane == 0) {                                                \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            p.dbg[(size_t)(e0 / kWave) * 16 + (k)] = __builtin_amdgcn_s_memrealtime();      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
-#else
-#define KSTAMP(k) do { } while (0)
-#endif
-
 #define KF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define KI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define KH(i) KF(FINENV_CASHPENALTY_F64_FIELDS + (i))
-
-__device__ __forceinline__ double cp_floordiv(double a, double d)       // exact floor(a/d), d > 0
-{
-    double x = __builtin_amdgcn_rcp(d);
-    x = fma(fma(-d, x, 1.0), x, x);
-    double q = floor(a * x);
-    double r = fma(-q, d, a);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
-        r = fma(-q, d, a);
-    }
-    return q;
-}
 
 __device__ __forceinline__ double cp_reward(const finenv_cashpenalty_config &c, int step,
                                             double total, double cash)     // :237-247
@@ -101,72 +53,6 @@ __device__ __forceinline__ double cp_reward(const finenv_cashpenalty_config &c, 
     double r = ((total - pen) / c.initial_amount) - 1;
     r /= (double)step;
     return r;
-}
-
-// rows[el*kRow + 0] = f32 cash, rows[el*kRow + 1 + i] = f32 holdings_i; columns > N: info row
-template <bool kCompact = false>
-__device__ __forceinline__ void cp_write_rows(float *__restrict__ dst, const CpParams &p, int e0,
-                                              int nenv_w, int row_day,
-                                              unsigned long long lane_mask, const float *rows,
-                                              int lane)
-{
-    const int N = p.cfg.n_assets, D = p.D, W = D - 1 - N;
-    write_obs_rows_generic<8, 32, kCompact>(
-        dst, W > 0 ? p.panel.info : nullptr, D, e0, nenv_w, row_day, lane_mask, rows, kRow, lane,
-        [=](int day, int col) { return day * W + col - 1 - N; },
-        [=](int col) { return col <= N ? col : -1; });
-}
-
-// f64 closes of every env's own date into LDS [el][i] (stride kClStride), 64 row loads in flight
-__device__ __forceinline__ void cp_gather_closes(double *trl, const CpParams &p, int di, int lane)
-{
-    const int N = p.cfg.n_assets;
-    const int li = min(lane, N - 1);
-    double cv[kWave];
-#pragma unroll
-    for (int j = 0; j < kWave; ++j) {
-        const int de = __builtin_amdgcn_readlane(di, j);
-        cv[j] = *at(p.panel.close, (unsigned)(de * N + li));
-    }
-#pragma unroll
-    for (int j = 0; j < kWave; ++j)
-        if (lane < N) trl[j * kClStride + lane] = cv[j];
-}
-
-// Chunk 0 of rows [el_lo, el_hi): market values parked in LDS ([el][64]) with cash / holdings
-// patched in from rows[].  Only stores towards HBM (LDS reads run ahead of them).
-template <int NCH>
-__device__ __forceinline__ void cp_head_store(float *__restrict__ dst, const CpParams &p, int e0,
-                                              int nenv_w, unsigned long long lane_mask,
-                                              const float *rows, const float *park, int lane,
-                                              int el_lo, int el_hi)
-{
-    const int N = p.cfg.n_assets, D = p.D;
-    float *const base = dst + (size_t)e0 * D;
-    const bool head = lane <= N, in = NCH > 1 || lane < D;
-    const unsigned long long want = ((el_hi - el_lo >= 64) ? ~0ull : ((1ull << (el_hi - el_lo)) - 1ull))
-                                    << el_lo;
-    if (nenv_w >= el_hi && (lane_mask & want) == want) {       // all rows: LDS reads 8 rows ahead
-        for (int g = el_lo; g < el_hi; g += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float hv = rows[(g + j) * kRow + (head ? lane : 0)];
-                const float pv = park[(g + j) * kWave + lane];
-                v[j] = head ? hv : pv;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (in) *at(base, (unsigned)((g + j) * D + lane)) = v[j];
-        }
-        return;
-    }
-    for (int el = el_lo; el < el_hi; ++el) {
-        if (el >= nenv_w || !((lane_mask >> el) & 1ull)) continue;
-        const float hv = rows[el * kRow + (head ? lane : 0)];
-        const float v = head ? hv : park[el * kWave + lane];
-        if (in) *at(base, (unsigned)(el * D + lane)) = v;
-    }
 }
 
 // (launch bounds: four 2-wave blocks per CU = two waves per SIMD, i.e. at most 256 VGPRs -- at
@@ -209,7 +95,7 @@ cashpenalty_kernel(const CpParams p)
         row[0] = (float)c.initial_amount;
         for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
         wave_sync();
-        cp_write_rows(p.obs, p, e0, nenv_w, start, __ballot(sel), rows, lane);
+        tw_write_rows(p.obs, p, e0, nenv_w, start, __ballot(sel), rows, lane);
         return;
     }
 
@@ -219,7 +105,7 @@ cashpenalty_kernel(const CpParams p)
     if (role != 0) {
         // ---- streamer ---------------------------------------------------------------------------
         if (NCH == 0) return;                 // rows wider than 320 columns: the trader writes them
-        KSTAMP(8);
+        STAMP64(8);
         const int W = p.D - 1 - N;
         const int di_s = KI(FINENV_KI_DATE_INDEX);
         const bool last = di_s == c.n_days - 1;                                   // :299
@@ -229,7 +115,7 @@ cashpenalty_kernel(const CpParams p)
                              : KI(FINENV_KI_NEXT_START);
         // the row the next observation shows unless a cash shortage ends the episode here
         const int row_spec = last ? (p.auto_reset ? ns : di_s) : di_s + 1;
-        cp_gather_closes(trl, p, di_s, lane);
+        tw_gather_closes(trl, p, di_s, lane);
         lds_barrier();                        // staging barrier: the trader reads its close rows
         const unsigned long long valid_mask = __ballot(valid);
         float *const base = p.obs + (size_t)e0 * p.D;
@@ -262,13 +148,13 @@ cashpenalty_kernel(const CpParams p)
                     t[j] = *quad_src(__builtin_amdgcn_readlane(row_spec, g + j));
 #pragma unroll
                 for (int j = 0; j < 32; ++j) pin(t[j]);
-                if (g == 0) KSTAMP(9);
+                if (g == 0) STAMP64(9);
 #pragma unroll
                 for (int j = 0; j < 32; ++j)
                     if (g + j < nenv_w && qa) *quad_dst(g + j) = t[j];
             }
         }
-        KSTAMP(10);
+        STAMP64(10);
         while (*flag == 0) __builtin_amdgcn_s_sleep(2);       // the trader has decided every env's row
         asm volatile("" ::: "memory");
         const int dec = decided[lane];
@@ -299,9 +185,9 @@ cashpenalty_kernel(const CpParams p)
         float *const park = reinterpret_cast<float *>(trl);      // (the trader is done with the closes)
 #pragma unroll
         for (int el = 0; el < kWave; ++el) park[el * kWave + lane] = t0[el];
-        KSTAMP(11);
+        STAMP64(11);
         lds_barrier();                        // cash / holdings are published; chunk 0 is parked
-        cp_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, park, lane, kWave / 2, kWave);
+        tw_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, park, lane, kWave / 2, kWave);
         if (NCH > 1 && nfix > 0 && W > 0) {
             unsigned long long m = fix;
 #pragma unroll
@@ -311,13 +197,13 @@ cashpenalty_kernel(const CpParams p)
                 m &= m - 1ull;
                 if (qa) *quad_dst(el) = tf[j];
             }
-            if (m != 0ull) cp_write_rows<true>(p.obs, p, e0, nenv_w, dec, m, rows, lane);
+            if (m != 0ull) tw_write_rows<true>(p.obs, p, e0, nenv_w, dec, m, rows, lane);
         }
-        KSTAMP(12);
+        STAMP64(12);
         return;
     }
 
-    KSTAMP(0);
+    STAMP64(0);
     // ---- round trip 1: per-env scalars (the action tile is issued behind them) ----------------
     int di = KI(FINENV_KI_DATE_INDEX);
     const int start = KI(FINENV_KI_START);
@@ -341,14 +227,14 @@ cashpenalty_kernel(const CpParams p)
     // anyway) while the trader's own loads are in flight: the date -> close-row dependency is off
     // the trader's path, which meets the streamer at the staging barrier.
     if (NCH == 0) {
-        cp_gather_closes(trl, p, di, lane);
+        tw_gather_closes(trl, p, di, lane);
         wave_sync();
     } else {
         lds_barrier();
     }
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) clb[i] = trl[lane * kClStride + min(i, N - 1)];
-    KSTAMP(1);
+    STAMP64(1);
     float act[kMaxN];
 #pragma unroll
     for (int i = 0; i < kMaxN; ++i) act[i] = row[min(i, N - 1)];
@@ -374,10 +260,10 @@ cashpenalty_kernel(const CpParams p)
             if (DISCRETE) {                                                      // :263-274
                 // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a software
                 // 64-bit division per asset, unrolled, was 30 KB of code)
-                const double q = cp_floordiv((double)a, cl);
+                const double q = tw_floordiv((double)a, cl);
                 const double inc = (double)c.shares_increment;
                 const double num = q >= 0.0 ? q : q + inc;
-                tr = cp_floordiv(num, inc) * inc;
+                tr = tw_floordiv(num, inc) * inc;
             } else {
                 tr = (double)a / cl;                                             // :276
             }
@@ -392,7 +278,7 @@ cashpenalty_kernel(const CpParams p)
         logged_cash = coh;                                                       // :312-314
         logged_total = coh + asset_value;
     }
-    KSTAMP(2);
+    STAMP64(2);
     reward = cp_reward(c, step, logged_total, logged_cash);                      // :317 / :301
     bool keep_buys = true;
     double coh_new = coh;
@@ -456,7 +342,7 @@ cashpenalty_kernel(const CpParams p)
         for (int i = 0; i < kMaxN; ++i)
             if (i < N) row[1 + i] = (float)hb[i];
     }
-    KSTAMP(3);
+    STAMP64(3);
     row[0] = (float)coh;
     if (valid) {
         *at(p.reward, (unsigned)e) = (float)reward;
@@ -471,7 +357,7 @@ cashpenalty_kernel(const CpParams p)
     int row_day = di;
     if (done_mask != 0ull) {
         if (p.term_obs != nullptr)
-            cp_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
+            tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
         if (p.auto_reset) {                                                      // reset()
             wave_sync();
             if (done) {
@@ -494,15 +380,15 @@ cashpenalty_kernel(const CpParams p)
             wave_sync();
         }
     }
-    KSTAMP(4);
+    STAMP64(4);
     if (NCH > 0) {
         lds_barrier();                        // chunk 0 is parked: rows 0..31 here, 32..63 by the streamer
-        cp_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows,
+        tw_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows,
                            reinterpret_cast<const float *>(trl), lane, 0, kWave / 2);
     } else {
-        cp_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, rows, lane);
+        tw_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, rows, lane);
     }
-    KSTAMP(5);
+    STAMP64(5);
     if (valid) {
         KF(FINENV_KF_COH) = coh;
         KI(FINENV_KI_DATE_INDEX) = di;
@@ -512,54 +398,23 @@ cashpenalty_kernel(const CpParams p)
 
 }  // namespace
 
-struct finenv_cashpenalty : finenv_host::Handle {
-    int32_t rs_hi;
-    unsigned long long rs_seed;
-    double *audit;
-    finenv_cashpenalty_config cfg;
-    finenv_cashpenalty_panel panel;
-    finenv_cashpenalty_state st;
-    uint32_t magicN;
-};
+struct finenv_cashpenalty : TwoWaveHandle<finenv_cashpenalty_config, finenv_cashpenalty_panel,
+                                         finenv_cashpenalty_state> {};
 
 namespace {
-CpParams kp_params(const finenv_cashpenalty *h)
-{
-    CpParams p;
-    memset(&p, 0, sizeof(p));
-    p.cfg = h->cfg;
-    p.panel = h->panel;
-    p.st = h->st;
-    p.D = h->D;
-    p.magicN = h->magicN;
-    p.rs_hi = h->rs_hi;
-    p.rs_seed = h->rs_seed;
-    p.audit = h->audit;
-    return p;
-}
-dim3 kp_grid(int E) { return dim3((unsigned)((E + kWave - 1) / kWave)); }
+// every step kernel runs one block per 64 envs: the wide form (NCH = 0) leaves its second wave idle
+struct CpKernels {
+    template <int NCH, bool DISCRETE>
+    static constexpr auto step() { return &cashpenalty_kernel<false, NCH, DISCRETE>; }
+    static dim3 wide_grid(int E) { return tw_grid(E); }
+};
 }  // namespace
 
 extern "C" {
 
 int finenv_cashpenalty_create(const finenv_cashpenalty_config *cfg, finenv_cashpenalty **out)
 {
-    if (!cfg || !out) return FINENV_ERR_INVALID;
-    *out = nullptr;
-    if (cfg->n_envs < 1 || cfg->n_assets < 1 || cfg->n_assets > FINENV_CASHPENALTY_MAX_ASSETS ||
-        cfg->n_cols < 0 || cfg->n_days < 1 || cfg->shares_increment < 1 || !(cfg->hmax >= 0) ||
-        !(cfg->initial_amount > 0))
-        return FINENV_ERR_INVALID;
-    const long long E = cfg->n_envs, N = cfg->n_assets, T = cfg->n_days;
-    const long long D = 1 + N + N * cfg->n_cols, lim = (1ll << 32) - 1;
-    if ((FINENV_CASHPENALTY_F64_FIELDS + N) * E * 8 > lim || T * N * cfg->n_cols * 4 > lim ||
-        T * N * 8 > lim || 64 * D * 4 > lim || E * N * 4 > lim)
-        return FINENV_ERR_INVALID;
-    finenv_cashpenalty *h = finenv_host::new_handle<finenv_cashpenalty>(cfg, D);
-    if (!h) return FINENV_ERR_NOMEM;
-    h->magicN = finenv_host::magic_for(N);
-    *out = h;
-    return FINENV_OK;
+    return tw_create(cfg, out, FINENV_CASHPENALTY_MAX_ASSETS, FINENV_CASHPENALTY_F64_FIELDS, 1);
 }
 
 void finenv_cashpenalty_destroy(finenv_cashpenalty *h) { delete h; }
@@ -572,37 +427,25 @@ int finenv_cashpenalty_obs_dim(const finenv_cashpenalty *h) { return finenv_host
 int finenv_cashpenalty_bind(finenv_cashpenalty *h, const finenv_cashpenalty_panel *panel,
                             const finenv_cashpenalty_state *st)
 {
-    if (!h || !panel || !st) return FINENV_ERR_INVALID;
-    if (!panel->close || (!panel->info && h->cfg.n_cols > 0) ||
-        (!panel->turb && h->cfg.use_turbulence) || !st->f64 || !st->i32)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    return finenv_host::bind(h, panel, st);
+    return tw_bind(h, panel, st);
 }
 
 int finenv_cashpenalty_set_random_start(finenv_cashpenalty *h, int32_t hi, uint64_t seed)
 {
-    if (!h || hi < 0 || hi > h->cfg.n_days) return FINENV_ERR_INVALID;
-    h->rs_hi = hi;
-    h->rs_seed = seed;
-    return FINENV_OK;
+    return tw_set_random_start(h, hi, seed);
 }
 
-int finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit)
-{
-    if (!h) return FINENV_ERR_INVALID;
-    h->audit = audit;
-    return FINENV_OK;
-}
+int finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit) { return tw_set_audit(h, audit); }
 
 int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *obs_out,
                              void *stream)
 {
     if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
-    CpParams p = kp_params(h);
+    CpParams p = tw_params<CpParams>(h);
     p.mask = mask;
     p.obs = obs_out;
-    hipLaunchKernelGGL((cashpenalty_kernel<true, 0, false>), kp_grid(h->cfg.n_envs), dim3(kWave * kWaves),
+    hipLaunchKernelGGL((cashpenalty_kernel<true, 0, false>), tw_grid(h->cfg.n_envs), dim3(kWave * kWaves),
                        0, (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "cashpenalty_reset");
 }
@@ -611,38 +454,8 @@ int finenv_cashpenalty_step(finenv_cashpenalty *h, const float *actions, float *
                             float *reward, uint8_t *done, float *term_obs, int32_t auto_reset,
                             void *stream)
 {
-    if (const int rc = finenv_host::ready(h, "step")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    if (!actions || !obs || !reward || !done)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
-    CpParams p = kp_params(h);
-    p.actions = actions;
-    p.obs = obs;
-    p.reward = reward;
-    p.done = done;
-    p.term_obs = term_obs;
-    p.auto_reset = auto_reset;
-#ifdef FINENV_DIAG
-    p.dbg = g_finenv_dbg;
-#endif
-    const dim3 grid = kp_grid(h->cfg.n_envs), block(kWave * kWaves);
-    const int nch = (h->D + kWave - 1) / kWave;      // chunks per observation row
-#define CP_LAUNCH(NCH_)                                                                          \
-    do {                                                                                         \
-        if (h->cfg.discrete_actions)                                                             \
-            hipLaunchKernelGGL((cashpenalty_kernel<false, NCH_, true>), grid, block, 0,          \
-                               (hipStream_t)stream, p);                                          \
-        else                                                                                     \
-            hipLaunchKernelGGL((cashpenalty_kernel<false, NCH_, false>), grid, block, 0,         \
-                               (hipStream_t)stream, p);                                          \
-    } while (0)
-    // NCH_: 1 = rows of one chunk, 2 = rows of up to 320 columns (streamer copies the market data as
-    // 16-byte quads), 0 = wider rows (one-wave form)
-    if (nch == 1) CP_LAUNCH(1);
-    else if (h->D <= kWave + 4 * kWave) CP_LAUNCH(2);
-    else CP_LAUNCH(0);
-#undef CP_LAUNCH
-    return finenv_host::check_launch(h, "cashpenalty_step");
+    return tw_step<CpKernels, CpParams>(h, actions, obs, reward, done, term_obs, auto_reset, stream,
+                                        "cashpenalty_step");
 }
 
 }  // extern "C"

@@ -26,10 +26,6 @@
 #include "finenv_dev.h"
 #include "finenv_host.h"
 
-#ifdef FINENV_DIAG
-extern unsigned long long *g_finenv_dbg;         // finenv_stock.hip (diagnostic builds)
-#endif
-
 namespace {
 
 typedef float wide4 __attribute__((ext_vector_type(4)));
@@ -78,19 +74,6 @@ struct CrParamsHist : CrParams {
 };
 template <bool HIST>
 using CrArgs = typename std::conditional<HIST, CrParamsHist, CrParams>::type;
-
-#ifdef FINENV_DIAG
-#define CSTAMP(k)                                                                           \
-    do {                                                                                    \
-        if (p.dbg != nullptr && lane == 0) {                                                \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            p.dbg[(size_t)(e0 / kWave) * 16 + (k)] = __builtin_amdgcn_s_memrealtime();      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
-#else
-#define CSTAMP(k) do { } while (0)
-#endif
 
 #define CF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define CI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
@@ -271,7 +254,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         return;
     }
 
-    CSTAMP(0);
+    STAMP64(0);
     // ---- round trip 1: everything that does not depend on `time`; the time counter first (loads
     // return in order: it is the one value the next round trip -- and the streamer -- wait for) ------
     const int time = CI(FINENV_CI_TIME) + 1;                                  // :60
@@ -319,7 +302,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         tpub[lane] = WIN ? cr_row(t_show, p.cfg) : time;
         lds_barrier();                    // the streamer takes the time counters from here
     }
-    CSTAMP(1);
+    STAMP64(1);
     const int max_step = WIN ? w_last - p.cfg.lookback : p.cfg.n_steps - p.cfg.lookback - 1;   // :24
     const bool done = time == max_step;                                       // :80
 
@@ -368,7 +351,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         }
     }
     wave_sync();
-    CSTAMP(2);
+    STAMP64(2);
 
     // Everything below runs on statically indexed registers (holdings sv[], actions act[], prices
     // prc[]): the first version kept holdings and actions in LDS and paid an LDS round trip inside
@@ -393,7 +376,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         sv[i] = ok ? s_new : sv[i];
         cash = ok ? cash_new : cash;      // (a skipped sell must not touch cash: -0.0 / rounding)
     }
-    CSTAMP(3);
+    STAMP64(3);
     // buys :73-77, serial through cash.  The refined reciprocal of every price is computed off the
     // chain; on it, `cash // price` = floor(cash * x) fixed up by the exact sign of FMA remainders.
     double xr[NP];
@@ -421,7 +404,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
         sv[i] = ok ? s_new : sv[i];
         cash = ok ? cash_new : cash;
     }
-    CSTAMP(4);
+    STAMP64(4);
     // ---- total asset: cash + np.sum(stocks * price) (NumPy pairwise order), :82 -----------
     CR_HOLDINGS_SUM(sum, sv, prc, N, NP)
     const double next = cash + sum;
@@ -429,7 +412,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     gamma_ret = gamma_ret * p.cfg.gamma + reward;                             // :85
     if (done) reward = gamma_ret;                                             // :87-88
 
-    CSTAMP(5);
+    STAMP64(5);
     // ---- observation heads -> LDS; state write-back ------------------------------------------
     // Block form (full wave, lock-step, nobody done, D <= 64, no streamer): the wave's 64 observation
     // rows are ONE contiguous [64][D] block of the output, written with 16-B-per-lane coalesced
@@ -504,7 +487,7 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
             wave_sync();
         }
     }
-    CSTAMP(6);
+    STAMP64(6);
     if (split) {
         // the streamer writes the indicator columns; here: the 64 x (1 + N) head values, read back
         // from LDS in flat order (lane = consecutive columns of a row)
@@ -561,13 +544,13 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
     } else {
         cr_write_rows(p.obs, p, e0, nenv_w, WIN ? cr_row(t_row, p.cfg) : t_row, valid_mask, rows, kRowW, lane);
     }
-    CSTAMP(7);
+    STAMP64(7);
     if (valid) {
         CF(FINENV_CF_CASH) = cash_out;
         CF(FINENV_CF_TOTAL_ASSET) = asset_out;
         CI(FINENV_CI_TIME) = t_row;       // (this wave alone reads and writes time[e])
     }
-    CSTAMP(8);
+    STAMP64(8);
 }
 
 // -------------------------------------------------------------------------------------

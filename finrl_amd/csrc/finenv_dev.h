@@ -5,6 +5,24 @@
 
 #include "finenv.h"
 
+// Phase stamps (100 MHz wall clock) of the kernels whose waves each own one group of 64 envs: stamp k
+// of the group that starts at env e0 goes to p.dbg[e0 / 64][k], 16 per group, for
+// tools/phase_times_{cashpenalty,stoploss,crypto,stocknp}.py.  Diagnostic build only; the host hands
+// g_finenv_dbg over as p.dbg.  (The stock kernels index by role: STAMP in finenv_stock_common.h.)
+#ifdef FINENV_DIAG
+extern unsigned long long *g_finenv_dbg;         // finenv_stock.hip
+#define STAMP64(k)                                                                          \
+    do {                                                                                    \
+        if (p.dbg != nullptr && lane == 0) {                                                \
+            __builtin_amdgcn_sched_barrier(0);                                              \
+            p.dbg[(size_t)(e0 / kWaveSize) * 16 + (k)] = __builtin_amdgcn_s_memrealtime();  \
+            __builtin_amdgcn_sched_barrier(0);                                              \
+        }                                                                                   \
+    } while (0)
+#else
+#define STAMP64(k) do { } while (0)
+#endif
+
 namespace {
 
 constexpr int kWaveSize = 64;

@@ -18,10 +18,6 @@
 #include "finenv_dev.h"
 #include "finenv_host.h"
 
-#ifdef FINENV_DIAG
-extern unsigned long long *g_finenv_dbg;         // finenv_stock.hip (diagnostic builds)
-#endif
-
 namespace {
 
 constexpr int kWave = 64;
@@ -51,17 +47,8 @@ struct NpParams {
 };
 
 #ifdef FINENV_DIAG
-#define NSTAMP(k)                                                                           \
-    do {                                                                                    \
-        if (p.dbg != nullptr && lane == 0) {                                                \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            p.dbg[(size_t)(e0 / kWave) * 16 + (k)] = __builtin_amdgcn_s_memrealtime();      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
 #define NDIAG(bit) (p.diag & (bit))
 #else
-#define NSTAMP(k) do { } while (0)
 #define NDIAG(bit) 0
 #endif
 
@@ -315,7 +302,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         return *reinterpret_cast<const np_f4u *>(reinterpret_cast<const char *>(p.panel.obs_tmpl) +
                                                  (size_t)((unsigned)(row * p.D + 4 * (lane & (lpr - 1))) * 4u));
     };
-    if (role == 0) NSTAMP(0);
+    if (role == 0) STAMP64(0);
     if (role == 1) {
         int day_s = NI(FINENV_NI_DAY) + 1;
         // the day counter is read (and has arrived) before the block-wide barrier; the traders
@@ -333,7 +320,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         const bool share = quad_ok && dm == 0ull && same_row;
         np_f4 hq = {0.0f, 0.0f, 0.0f, 0.0f};
         if (share) hq = head_quad_load(rd0);           // (a load behind the stores below would wait for them)
-        NSTAMP(9);
+        STAMP64(9);
         // market-data chunks.  Every env of the wave on the same panel row: 16 bytes per lane, ONE store per
         // row and 256 columns, the last quad shifted back to end at D (this wave is slot-bound: four dword
         // stores per row took 17 us for 67 MB, same process / same buffers 26.6 -> 24.4 us per step)
@@ -353,7 +340,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         } else {
             np_write_rows(p.obs, p, e0, nenv_w, rd, vm, heads, lane, kpatch);
         }
-        NSTAMP(10);
+        STAMP64(10);
         // hand-off: this wave is done ~3 us before the trader has its results; once they are final in LDS it
         // takes the upper half of the head rows and of the books (the trader the lower halves and the scalars)
         lds_barrier();                                                        // #2
@@ -417,7 +404,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     }
     if (uni && lane < kMaxN) prow_lds[lane] = prv;
     wave_sync();
-    NSTAMP(1);
+    STAMP64(1);
     const float *arow = heads + lane * kRowA;
     const float ms = (float)p.cfg.max_stock;
     const Num one_m = mk(1 - p.cfg.sell_cost_pct, FINENV_NT_PY);
@@ -453,7 +440,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
 #pragma unroll
             for (int i = 0; i < kMaxN; ++i) pr_[i] = *at(p.panel.price, pb + (unsigned)min(i, N - 1));
         }
-        NSTAMP(11);
+        STAMP64(11);
 #pragma unroll
         for (int i = 0; i < kMaxN; ++i) {                                         // sells :112-119
             if (i >= N) continue;             // (continue, not break: keeps the loop fully unrollable)
@@ -473,7 +460,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             cr[i] = ok ? 0.0f : cr[i];
             amt = ok ? amt_new : amt;
         }
-        NSTAMP(7);
+        STAMP64(7);
         double xr[kMaxN];
 #pragma unroll
         for (int i = 0; i < kMaxN; ++i) {
@@ -481,7 +468,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             const double x = __builtin_amdgcn_rcp(d);
             xr[i] = fma(fma(-d, x, 1.0), x, x);
         }
-        NSTAMP(12);
+        STAMP64(12);
 #pragma unroll
         for (int i = 0; i < kMaxN; ++i) {                                         // buys :120-129
             if (i >= N) continue;
@@ -502,7 +489,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             amt = ok ? amt_new : amt;
         }
         amount = mk(amt, FINENV_NT_F64);
-        NSTAMP(8);
+        STAMP64(8);
         // books back to LDS and, in the same pass, this env's observation head (amount | stocks |
         // cool-downs) over the consumed action rows -- every lane has read its own action row above
         wave_sync();
@@ -589,7 +576,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             }
         }
     }
-    NSTAMP(2);
+    STAMP64(2);
     if (!calm) {
         const Num t0 = mk((double)holdings_value(scol, p.panel.price, pb, N, prow), FINENV_NT_F32);
         amount = n_add(amount, n_mul(t0, one_m));
@@ -612,7 +599,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         *at(p.done, (unsigned)e) = done ? 1 : 0;
         NF(FINENV_NF_LAST_REWARD) = r.v;
     }
-    NSTAMP(3);
+    STAMP64(3);
     wave_sync();
     if (!head_filled) fill_head(amount);     // overwrites the (consumed) action rows
     wave_sync();
@@ -632,7 +619,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             wave_sync();
         }
     }
-    NSTAMP(4);
+    STAMP64(4);
     // ---- hand-off (pairs with the streamers' second barrier): heads and books are final in LDS.  With
     // every env on the same row and nobody done, the streamer -- long finished -- writes the upper half of
     // the head rows and of the books; otherwise this wave writes everything.
@@ -642,9 +629,9 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         if (share) head_quads(head_q, 0, kWave / 2);
         else np_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, heads, lane, 0, kpatch);
     }
-    NSTAMP(5);
+    STAMP64(5);
     if (valid) store_state(amount, ta, gr, ita, r.tag, row_day, 0, share ? N / 2 : N);
-    NSTAMP(6);
+    STAMP64(6);
 }
 
 }  // namespace

@@ -31,22 +31,20 @@
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
-
-#ifdef FINENV_DIAG
-extern unsigned long long *g_finenv_dbg;         // finenv_stock.hip (diagnostic builds)
-#endif
+#include "finenv_twowave.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kMaxN = FINENV_STOPLOSS_MAX_ASSETS;
-constexpr int kRow = kMaxN + 1;
+struct SlParams : TwoWaveParams<finenv_stoploss_config, finenv_stoploss_panel, finenv_stoploss_state,
+                                kMaxN> {};
+constexpr int kRow = SlParams::kRow, kClStride = SlParams::kClStride;
 constexpr int kWaves = 2;
 constexpr int kB = 8;                        // assets per load batch
 constexpr int kLdsPerWave = kWave * kRow + kMaxN * kWave * 2;   // rows + f64 transactions [i][lane]
 // two-wave step kernel
 constexpr int kHalf = 16;                      // assets [0, kHalf): trader's pass 3; the rest: streamer's
-constexpr int kClStride = kMaxN + 1;           // f64 close rows [env][33]: odd stride, conflict-free
 constexpr int kL2Rows = kWave * kRow;                          // f32 [el][33]
 constexpr int kL2Close = kClStride * kWave * 2;                // f64 closes [el][i]; later: parked chunk 0
 constexpr int kL2Trx = (kMaxN - kHalf) * kWave * 2;            // f64 transactions of assets >= kHalf [i][lane]
@@ -56,55 +54,9 @@ static_assert(kLds2 * 4 * 4 <= 160 * 1024, "four blocks per CU");
 constexpr int kFix = 4;                        // re-decided rows per block the streamer patches in registers
 static_assert(kWave * kWave <= kL2Close, "the parked chunk 0 reuses the close rows");
 
-struct SlParams {
-    finenv_stoploss_config cfg;
-    finenv_stoploss_panel panel;
-    finenv_stoploss_state st;
-    const float *actions;
-    float *obs;
-    float *reward;
-    uint8_t *done;
-    float *term_obs;
-    const uint8_t *mask;
-    int32_t auto_reset;
-    int32_t D;
-    uint32_t magicN;
-    int32_t rs_hi;                  // random_start: draw in [0, rs_hi) on the device (0 = off)
-    unsigned long long rs_seed;
-    double *audit;                  // optional [E][FINENV_AUDIT_HEAD + N] per-step log row, or NULL
-    unsigned long long *dbg;        // FINENV_DIAG builds only: [block][16] s_memrealtime stamps
-};
-
-#ifdef FINENV_DIAG
-#define SSTAMP(k)                                                                           \
-    do {                                                                                    \
-        if (p.dbg != nullptr && lane == 0) {                                                \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            p.dbg[(size_t)(e0 / kWave) * 16 + (k)] = __builtin_amdgcn_s_memrealtime();      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
-#else
-#define SSTAMP(k) do { } while (0)
-#endif
-
 #define LF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define LI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define LV(book, i) LF(FINENV_STOPLOSS_F64_FIELDS + (book) * N + (i))
-
-__device__ __forceinline__ double sl_floordiv(double a, double d)       // exact floor(a/d), d > 0
-{
-    double x = __builtin_amdgcn_rcp(d);
-    x = fma(fma(-d, x, 1.0), x, x);
-    double q = floor(a * x);
-    double r = fma(-q, d, a);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
-        r = fma(-q, d, a);
-    }
-    return q;
-}
 
 // get_reward(), :255-290, from its four sums
 __device__ __forceinline__ double sl_reward(const finenv_stoploss_config &c, int step,
@@ -119,20 +71,6 @@ __device__ __forceinline__ double sl_reward(const finenv_stoploss_config &c, int
     double r = ((total - total_penalty + add) / c.initial_amount) - 1;                  // :285-287
     r /= (double)step;                                                                  // :288
     return r;
-}
-
-// rows[el*kRow + 0] = f32 cash, rows[el*kRow + 1 + i] = f32 holdings_i; columns > N: info row
-template <bool kCompact = false>
-__device__ __forceinline__ void sl_write_rows(float *__restrict__ dst, const SlParams &p, int e0,
-                                              int nenv_w, int row_day,
-                                              unsigned long long lane_mask, const float *rows,
-                                              int lane)
-{
-    const int N = p.cfg.n_assets, D = p.D, W = D - 1 - N;
-    write_obs_rows_generic<8, 32, kCompact>(
-        dst, W > 0 ? p.panel.info : nullptr, D, e0, nenv_w, row_day, lane_mask, rows, kRow, lane,
-        [=](int day, int col) { return day * W + col - 1 - N; },
-        [=](int col) { return col <= N ? col : -1; });
 }
 
 // The one-wave kernel: reset, and steps whose observation rows are wider than 320 columns.
@@ -170,7 +108,7 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
         row[0] = (float)c.initial_amount;
         for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
         wave_sync();
-        sl_write_rows(p.obs, p, e0, nenv_w, start, __ballot(sel), rows, lane);
+        tw_write_rows(p.obs, p, e0, nenv_w, start, __ballot(sel), rows, lane);
         return;
     }
 
@@ -271,10 +209,10 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
                 if (c.discrete_actions) {                                        // :333-343
                     // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a
                     // software 64-bit division per asset, unrolled, doubled the kernel's code)
-                    const double q = cl > 0.0 ? sl_floordiv(a, cl) : 0.0;
+                    const double q = cl > 0.0 ? tw_floordiv(a, cl) : 0.0;
                     const double inc = (double)c.shares_increment;
                     const double num = q >= 0.0 ? q : q + inc;
-                    tr = sl_floordiv(num, inc) * inc;
+                    tr = tw_floordiv(num, inc) * inc;
                 } else {
                     tr = cl > 0.0 ? a / cl : 0.0;                                // :345
                 }
@@ -393,7 +331,7 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
     int row_day = di;
     if (done_mask != 0ull) {
         if (p.term_obs != nullptr)
-            sl_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
+            tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
         if (p.auto_reset) {                                                      // reset()
             wave_sync();
             if (done) {
@@ -416,64 +354,11 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
             wave_sync();
         }
     }
-    sl_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, rows, lane);
+    tw_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, rows, lane);
     if (valid) {
         LF(FINENV_LF_COH) = coh;
         LI(FINENV_LI_DATE_INDEX) = di;
         if (c.use_turbulence) LF(FINENV_LF_TURBULENCE) = turb;
-    }
-}
-
-
-// f64 closes of every env's own date into LDS [el][i] (stride kClStride), 64 row loads in flight
-__device__ __forceinline__ void sl_gather_closes(double *trl, const SlParams &p, int di, int lane)
-{
-    const int N = p.cfg.n_assets;
-    const int li = min(lane, N - 1);
-    double cv[kWave];
-#pragma unroll
-    for (int j = 0; j < kWave; ++j) {
-        const int de = __builtin_amdgcn_readlane(di, j);
-        cv[j] = *at(p.panel.close, (unsigned)(de * N + li));
-    }
-#pragma unroll
-    for (int j = 0; j < kWave; ++j)
-        if (lane < N) trl[j * kClStride + lane] = cv[j];
-}
-
-// Chunk 0 of rows [el_lo, el_hi): market values parked in LDS ([el][64]) with cash / holdings
-// patched in from rows[].  Only stores towards HBM (LDS reads run ahead of them).
-template <int NCH>
-__device__ __forceinline__ void sl_head_store(float *__restrict__ dst, const SlParams &p, int e0,
-                                              int nenv_w, unsigned long long lane_mask,
-                                              const float *rows, const float *park, int lane,
-                                              int el_lo, int el_hi)
-{
-    const int N = p.cfg.n_assets, D = p.D;
-    float *const base = dst + (size_t)e0 * D;
-    const bool head = lane <= N, in = NCH > 1 || lane < D;
-    const unsigned long long want = ((el_hi - el_lo >= 64) ? ~0ull : ((1ull << (el_hi - el_lo)) - 1ull))
-                                    << el_lo;
-    if (nenv_w >= el_hi && (lane_mask & want) == want) {       // all rows: LDS reads 8 rows ahead
-        for (int g = el_lo; g < el_hi; g += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float hv = rows[(g + j) * kRow + (head ? lane : 0)];
-                const float pv = park[(g + j) * kWave + lane];
-                v[j] = head ? hv : pv;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (in) *at(base, (unsigned)((g + j) * D + lane)) = v[j];
-        }
-        return;
-    }
-    for (int el = el_lo; el < el_hi; ++el) {
-        if (el >= nenv_w || !((lane_mask >> el) & 1ull)) continue;
-        const float hv = rows[el * kRow + (head ? lane : 0)];
-        const float v = head ? hv : park[el * kWave + lane];
-        if (in) *at(base, (unsigned)(el * D + lane)) = v;
     }
 }
 
@@ -531,7 +416,7 @@ stoploss_step2_kernel(const SlParams p)
 
     if (role != 0) {
         // ================================ streamer ===============================================
-        SSTAMP(8);
+        STAMP64(8);
         const int di_s = LI(FINENV_LI_DATE_INDEX);
         const bool last = di_s == c.n_days - 1;                                   // :302
         int ns = 0;
@@ -540,9 +425,9 @@ stoploss_step2_kernel(const SlParams p)
                              : LI(FINENV_LI_NEXT_START);
         // the row the next observation shows unless a cash shortage ends the episode here
         const int row_spec = last ? (p.auto_reset ? ns : di_s) : di_s + 1;
-        sl_gather_closes(trl, p, di_s, lane);
+        tw_gather_closes(trl, p, di_s, lane);
         lds_barrier();                        // staging barrier: the trader reads its close rows
-        SSTAMP(9);
+        STAMP64(9);
         const unsigned long long valid_mask = __ballot(valid);
         float *const base = p.obs + (size_t)e0 * p.D;
         // market-data columns [64, D) of every row (NCH == 2: 64 < D <= 320): ONE 16-byte-per-lane load
@@ -577,7 +462,7 @@ stoploss_step2_kernel(const SlParams p)
                     if (g + j < nenv_w && qa) *quad_dst(g + j) = t[j];
             }
         }
-        SSTAMP(10);
+        STAMP64(10);
         // books of its assets (they do not depend on the decision): in flight while it waits
         double hx[kMaxN - kHalf], ax[kMaxN - kHalf], nx[kMaxN - kHalf];
 #pragma unroll
@@ -589,7 +474,7 @@ stoploss_step2_kernel(const SlParams p)
         }
         while (*flag == 0) __builtin_amdgcn_s_sleep(2);       // the trader has decided
         asm volatile("" ::: "memory");
-        SSTAMP(11);
+        STAMP64(11);
         const int dec = decided[lane], ef = eflags[lane];
         const bool adv = (ef & 1) != 0, keepb = (ef & 2) != 0, at_end_s = (ef & 4) != 0;
         const unsigned long long fix = __ballot(valid && dec != row_spec);
@@ -638,13 +523,13 @@ stoploss_step2_kernel(const SlParams p)
         }
         ntrx[lane] = adv ? ntr : 0.0;
         aflags[lane] = adv ? fl : 0;
-        SSTAMP(12);
+        STAMP64(12);
         lds_barrier();                        // #1: pass 3 complete, rows[] hold every new holding
         float *const park = reinterpret_cast<float *>(trl);      // (nobody reads the closes any more)
 #pragma unroll
         for (int el = 0; el < kWave; ++el) park[el * kWave + lane] = t0[el];
         lds_barrier();                        // #2: terminal observation / reset done, chunk 0 parked
-        sl_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, park, lane, kWave / 2, kWave);
+        tw_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, park, lane, kWave / 2, kWave);
         if (NCH > 1 && nfix > 0 && W > 0) {
             unsigned long long m = fix;
 #pragma unroll
@@ -654,14 +539,14 @@ stoploss_step2_kernel(const SlParams p)
                 m &= m - 1ull;
                 if (qa) *quad_dst(el) = tf[j];
             }
-            if (m != 0ull) sl_write_rows<true>(p.obs, p, e0, nenv_w, dec, m, rows, lane);
+            if (m != 0ull) tw_write_rows<true>(p.obs, p, e0, nenv_w, dec, m, rows, lane);
         }
-        SSTAMP(13);
+        STAMP64(13);
         return;
     }
 
     // ==================================== trader =================================================
-    SSTAMP(0);
+    STAMP64(0);
     int di = LI(FINENV_LI_DATE_INDEX);
     const int start = LI(FINENV_LI_START);
     double coh = LF(FINENV_LF_COH);
@@ -673,7 +558,7 @@ stoploss_step2_kernel(const SlParams p)
     const int step = di - start;                                                 // current_step
     const bool at_end = di == c.n_days - 1;                                      // :302
     lds_barrier();                            // staging barrier: close rows gathered by the streamer
-    SSTAMP(1);
+    STAMP64(1);
 
     double slp_sum = 0.0, lpp_sum = 0.0, add = 0.0;
     const double lt_old = logged_total, lc_old = logged_cash;
@@ -754,10 +639,10 @@ stoploss_step2_kernel(const SlParams p)
                 a = turbulent ? -(h * cl) : a;                                   // :327-331
                 double tr;
                 if (DISCRETE) {                                                  // :333-343
-                    const double q = cl > 0.0 ? sl_floordiv(a, cl) : 0.0;
+                    const double q = cl > 0.0 ? tw_floordiv(a, cl) : 0.0;
                     const double inc = (double)c.shares_increment;
                     const double num = q >= 0.0 ? q : q + inc;
-                    tr = sl_floordiv(num, inc) * inc;
+                    tr = tw_floordiv(num, inc) * inc;
                 } else {
                     tr = cl > 0.0 ? a / cl : 0.0;                                // :345
                 }
@@ -798,7 +683,7 @@ stoploss_step2_kernel(const SlParams p)
         coh_new = coh1 - spend - costs;                                          // :414
     }
     const bool advance = !done;
-    SSTAMP(2);
+    STAMP64(2);
     // ---- the decision is published (LDS is in-order per wave: data first, then the flag) --------
     int ns_reset = 0;
     if (p.auto_reset && __any(done))
@@ -844,9 +729,9 @@ stoploss_step2_kernel(const SlParams p)
         di += 1;                                                                 // :430
         if (c.use_turbulence) turb = *at(p.panel.turb, (unsigned)di);            // :431-434
     }
-    SSTAMP(3);
+    STAMP64(3);
     lds_barrier();                            // #1: the streamer's pass 3 is complete
-    SSTAMP(4);
+    STAMP64(4);
     if (advance) {
         actual_num_trades = ntr + ntrx[lane];    // (counts: exact in any order)
         audit_flags |= aflags[lane];
@@ -880,7 +765,7 @@ stoploss_step2_kernel(const SlParams p)
     const unsigned long long done_mask = __ballot(done && valid);
     if (done_mask != 0ull) {
         if (p.term_obs != nullptr)
-            sl_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
+            tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
         if (p.auto_reset) {                                                      // reset()
             wave_sync();
             if (done) {
@@ -900,11 +785,11 @@ stoploss_step2_kernel(const SlParams p)
             wave_sync();
         }
     }
-    SSTAMP(5);
+    STAMP64(5);
     lds_barrier();                            // #2: rows final, chunk 0 parked by the streamer
-    sl_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, reinterpret_cast<const float *>(trl),
+    tw_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, reinterpret_cast<const float *>(trl),
                        lane, 0, kWave / 2);
-    SSTAMP(6);
+    STAMP64(6);
     if (valid) {
         LF(FINENV_LF_COH) = coh;
         LI(FINENV_LI_DATE_INDEX) = di;
@@ -914,58 +799,33 @@ stoploss_step2_kernel(const SlParams p)
 
 }  // namespace
 
-struct finenv_stoploss : finenv_host::Handle {
-    int32_t rs_hi;
-    unsigned long long rs_seed;
-    double *audit;
-    finenv_stoploss_config cfg;
-    finenv_stoploss_panel panel;
-    finenv_stoploss_state st;
-    uint32_t magicN;
-};
+struct finenv_stoploss : TwoWaveHandle<finenv_stoploss_config, finenv_stoploss_panel,
+                                      finenv_stoploss_state> {};
 
 namespace {
-SlParams sl_params(const finenv_stoploss *h)
-{
-    SlParams p;
-    memset(&p, 0, sizeof(p));
-    p.cfg = h->cfg;
-    p.panel = h->panel;
-    p.st = h->st;
-    p.D = h->D;
-    p.magicN = h->magicN;
-    p.rs_hi = h->rs_hi;
-    p.rs_seed = h->rs_seed;
-    p.audit = h->audit;
-    return p;
-}
 dim3 sl_grid(int E)
 {
     const int waves = (E + kWave - 1) / kWave;
     return dim3((unsigned)((waves + kWaves - 1) / kWaves));
 }
+// rows of up to 320 columns: the two-wave kernel; wider rows: the one-wave kernel, two 64-env groups per block
+struct SlKernels {
+    template <int NCH, bool DISCRETE>
+    static constexpr auto step()
+    {
+        if constexpr (NCH == 0) return &stoploss_kernel<false>;
+        else return &stoploss_step2_kernel<NCH, DISCRETE>;
+    }
+    static dim3 wide_grid(int E) { return sl_grid(E); }
+};
 }  // namespace
 
 extern "C" {
 
 int finenv_stoploss_create(const finenv_stoploss_config *cfg, finenv_stoploss **out)
 {
-    if (!cfg || !out) return FINENV_ERR_INVALID;
-    *out = nullptr;
-    if (cfg->n_envs < 1 || cfg->n_assets < 1 || cfg->n_assets > FINENV_STOPLOSS_MAX_ASSETS ||
-        cfg->n_cols < 0 || cfg->n_days < 1 || cfg->shares_increment < 1 || !(cfg->hmax >= 0) ||
-        !(cfg->initial_amount > 0))
-        return FINENV_ERR_INVALID;
-    const long long E = cfg->n_envs, N = cfg->n_assets, T = cfg->n_days;
-    const long long D = 1 + N + N * cfg->n_cols, lim = (1ll << 32) - 1;
-    if ((FINENV_STOPLOSS_F64_FIELDS + FINENV_STOPLOSS_BOOKS * N) * E * 8 > lim ||
-        T * N * cfg->n_cols * 4 > lim || T * N * 8 > lim || 64 * D * 4 > lim || E * N * 4 > lim)
-        return FINENV_ERR_INVALID;
-    finenv_stoploss *h = finenv_host::new_handle<finenv_stoploss>(cfg, D);
-    if (!h) return FINENV_ERR_NOMEM;
-    h->magicN = finenv_host::magic_for(N);
-    *out = h;
-    return FINENV_OK;
+    return tw_create(cfg, out, FINENV_STOPLOSS_MAX_ASSETS, FINENV_STOPLOSS_F64_FIELDS,
+                     FINENV_STOPLOSS_BOOKS);
 }
 
 void finenv_stoploss_destroy(finenv_stoploss *h) { delete h; }
@@ -978,33 +838,21 @@ int finenv_stoploss_obs_dim(const finenv_stoploss *h) { return finenv_host::obs_
 int finenv_stoploss_bind(finenv_stoploss *h, const finenv_stoploss_panel *panel,
                          const finenv_stoploss_state *st)
 {
-    if (!h || !panel || !st) return FINENV_ERR_INVALID;
-    if (!panel->close || (!panel->info && h->cfg.n_cols > 0) ||
-        (!panel->turb && h->cfg.use_turbulence) || !st->f64 || !st->i32)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
-    return finenv_host::bind(h, panel, st);
+    return tw_bind(h, panel, st);
 }
 
 int finenv_stoploss_set_random_start(finenv_stoploss *h, int32_t hi, uint64_t seed)
 {
-    if (!h || hi < 0 || hi > h->cfg.n_days) return FINENV_ERR_INVALID;
-    h->rs_hi = hi;
-    h->rs_seed = seed;
-    return FINENV_OK;
+    return tw_set_random_start(h, hi, seed);
 }
 
-int finenv_stoploss_set_audit(finenv_stoploss *h, double *audit)
-{
-    if (!h) return FINENV_ERR_INVALID;
-    h->audit = audit;
-    return FINENV_OK;
-}
+int finenv_stoploss_set_audit(finenv_stoploss *h, double *audit) { return tw_set_audit(h, audit); }
 
 int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream)
 {
     if (const int rc = finenv_host::ready(h, "reset")) return rc;
     const finenv_host::DeviceGuard guard(h->device);
-    SlParams p = sl_params(h);
+    SlParams p = tw_params<SlParams>(h);
     p.mask = mask;
     p.obs = obs_out;
     hipLaunchKernelGGL((stoploss_kernel<true>), sl_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
@@ -1015,38 +863,8 @@ int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_ou
 int finenv_stoploss_step(finenv_stoploss *h, const float *actions, float *obs, float *reward,
                          uint8_t *done, float *term_obs, int32_t auto_reset, void *stream)
 {
-    if (const int rc = finenv_host::ready(h, "step")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    if (!actions || !obs || !reward || !done)
-        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
-    SlParams p = sl_params(h);
-    p.actions = actions;
-    p.obs = obs;
-    p.reward = reward;
-    p.done = done;
-    p.term_obs = term_obs;
-    p.auto_reset = auto_reset;
-#ifdef FINENV_DIAG
-    p.dbg = g_finenv_dbg;
-#endif
-    const dim3 grid = sl_grid(h->cfg.n_envs), block(kWave * kWaves);
-    const dim3 grid2((unsigned)((h->cfg.n_envs + kWave - 1) / kWave));   // one block per 64 envs
-#define SL_LAUNCH2(NCH_)                                                                         \
-    do {                                                                                         \
-        if (h->cfg.discrete_actions)                                                             \
-            hipLaunchKernelGGL((stoploss_step2_kernel<NCH_, true>), grid2, block, 0,             \
-                               (hipStream_t)stream, p);                                          \
-        else                                                                                     \
-            hipLaunchKernelGGL((stoploss_step2_kernel<NCH_, false>), grid2, block, 0,            \
-                               (hipStream_t)stream, p);                                          \
-    } while (0)
-    // 1 = rows of one chunk, 2 = rows of up to 320 columns (the streamer copies the market data as
-    // 16-byte quads), wider rows: the one-wave kernel
-    if (h->D <= kWave) SL_LAUNCH2(1);
-    else if (h->D <= kWave + 4 * kWave) SL_LAUNCH2(2);
-    else hipLaunchKernelGGL((stoploss_kernel<false>), grid, block, 0, (hipStream_t)stream, p);
-#undef SL_LAUNCH2
-    return finenv_host::check_launch(h, "stoploss_step");
+    return tw_step<SlKernels, SlParams>(h, actions, obs, reward, done, term_obs, auto_reset, stream,
+                                        "stoploss_step");
 }
 
 }  // extern "C"

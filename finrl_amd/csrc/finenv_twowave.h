@@ -1,0 +1,243 @@
+// finenv_twowave.h -- what the cash-penalty and stop-loss envs share (finenv_cashpenalty.hip,
+// finenv_stoploss.hip): the kernel argument, the device helpers of their trader + streamer step
+// kernels (one 128-thread block per 64 envs) and the host side of their C ABI.  Everything is a
+// template on the env's own argument struct P or handle H; the kernels themselves, the state layout
+// macros and the extern "C" entry points stay in the two files.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "finenv.h"
+#include "finenv_dev.h"
+#include "finenv_host.h"
+
+namespace {
+
+// The kernel argument.  CpParams / SlParams derive from it and add nothing: the kernels keep their
+// symbols, and the helpers below read the LDS strides from the argument's type.
+template <class Cfg, class Panel, class State, int kMaxAssets>
+struct TwoWaveParams {
+    static constexpr int kRow = kMaxAssets + 1;        // f32 rows [el][cash | holdings]
+    static constexpr int kClStride = kMaxAssets + 1;   // f64 close rows [el][i]: odd stride, conflict-free
+    Cfg cfg;
+    Panel panel;
+    State st;
+    const float *actions;
+    float *obs;
+    float *reward;
+    uint8_t *done;
+    float *term_obs;
+    const uint8_t *mask;
+    int32_t auto_reset;
+    int32_t D;
+    uint32_t magicN;
+    int32_t rs_hi;                  // random_start: draw in [0, rs_hi) on the device (0 = off)
+    unsigned long long rs_seed;
+    double *audit;                  // optional [E][FINENV_AUDIT_HEAD + N] per-step log row, or NULL
+    unsigned long long *dbg;        // FINENV_DIAG builds only: [block][16] s_memrealtime stamps
+};
+
+__device__ __forceinline__ double tw_floordiv(double a, double d)       // exact floor(a/d), d > 0
+{
+    double x = __builtin_amdgcn_rcp(d);
+    x = fma(fma(-d, x, 1.0), x, x);
+    double q = floor(a * x);
+    double r = fma(-q, d, a);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
+        r = fma(-q, d, a);
+    }
+    return q;
+}
+
+// rows[el*kRow + 0] = f32 cash, rows[el*kRow + 1 + i] = f32 holdings_i; columns > N: info row
+template <bool kCompact = false, class P>
+__device__ __forceinline__ void tw_write_rows(float *__restrict__ dst, const P &p, int e0,
+                                              int nenv_w, int row_day,
+                                              unsigned long long lane_mask, const float *rows,
+                                              int lane)
+{
+    const int N = p.cfg.n_assets, D = p.D, W = D - 1 - N;
+    write_obs_rows_generic<8, 32, kCompact>(
+        dst, W > 0 ? p.panel.info : nullptr, D, e0, nenv_w, row_day, lane_mask, rows, P::kRow, lane,
+        [=](int day, int col) { return day * W + col - 1 - N; },
+        [=](int col) { return col <= N ? col : -1; });
+}
+
+// f64 closes of every env's own date into LDS [el][i] (stride kClStride), 64 row loads in flight
+template <class P>
+__device__ __forceinline__ void tw_gather_closes(double *trl, const P &p, int di, int lane)
+{
+    const int N = p.cfg.n_assets;
+    const int li = min(lane, N - 1);
+    double cv[kWaveSize];
+#pragma unroll
+    for (int j = 0; j < kWaveSize; ++j) {
+        const int de = __builtin_amdgcn_readlane(di, j);
+        cv[j] = *at(p.panel.close, (unsigned)(de * N + li));
+    }
+#pragma unroll
+    for (int j = 0; j < kWaveSize; ++j)
+        if (lane < N) trl[j * P::kClStride + lane] = cv[j];
+}
+
+// Chunk 0 of rows [el_lo, el_hi): market values parked in LDS ([el][64]) with cash / holdings
+// patched in from rows[].  Only stores towards HBM (LDS reads run ahead of them).
+template <int NCH, class P>
+__device__ __forceinline__ void tw_head_store(float *__restrict__ dst, const P &p, int e0,
+                                              int nenv_w, unsigned long long lane_mask,
+                                              const float *rows, const float *park, int lane,
+                                              int el_lo, int el_hi)
+{
+    const int N = p.cfg.n_assets, D = p.D;
+    float *const base = dst + (size_t)e0 * D;
+    const bool head = lane <= N, in = NCH > 1 || lane < D;
+    const unsigned long long want = ((el_hi - el_lo >= 64) ? ~0ull : ((1ull << (el_hi - el_lo)) - 1ull))
+                                    << el_lo;
+    if (nenv_w >= el_hi && (lane_mask & want) == want) {       // all rows: LDS reads 8 rows ahead
+        for (int g = el_lo; g < el_hi; g += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float hv = rows[(g + j) * P::kRow + (head ? lane : 0)];
+                const float pv = park[(g + j) * kWaveSize + lane];
+                v[j] = head ? hv : pv;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (in) *at(base, (unsigned)((g + j) * D + lane)) = v[j];
+        }
+        return;
+    }
+    for (int el = el_lo; el < el_hi; ++el) {
+        if (el >= nenv_w || !((lane_mask >> el) & 1ull)) continue;
+        const float hv = rows[el * P::kRow + (head ? lane : 0)];
+        const float v = head ? hv : park[el * kWaveSize + lane];
+        if (in) *at(base, (unsigned)(el * D + lane)) = v;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------
+
+// What struct finenv_cashpenalty and struct finenv_stoploss hold.
+template <class Cfg, class Panel, class State>
+struct TwoWaveHandle : finenv_host::Handle {
+    int32_t rs_hi;
+    unsigned long long rs_seed;
+    double *audit;
+    Cfg cfg;
+    Panel panel;
+    State st;
+    uint32_t magicN;
+};
+
+// the kernel argument as the handle fills it; the entry point adds its own pointers
+template <class P, class H>
+P tw_params(const H *h)
+{
+    P p;
+    memset(&p, 0, sizeof(p));
+    p.cfg = h->cfg;
+    p.panel = h->panel;
+    p.st = h->st;
+    p.D = h->D;
+    p.magicN = h->magicN;
+    p.rs_hi = h->rs_hi;
+    p.rs_seed = h->rs_seed;
+    p.audit = h->audit;
+    return p;
+}
+
+// finenv_<kind>_create: at most max_assets assets; the f64 state block has f64_fields + books * N rows
+// of E doubles.  Every byte offset the kernels form must fit 32 bits (at()).
+template <class H, class Cfg>
+int tw_create(const Cfg *cfg, H **out, int max_assets, int f64_fields, int books)
+{
+    if (!cfg || !out) return FINENV_ERR_INVALID;
+    *out = nullptr;
+    if (cfg->n_envs < 1 || cfg->n_assets < 1 || cfg->n_assets > max_assets ||
+        cfg->n_cols < 0 || cfg->n_days < 1 || cfg->shares_increment < 1 || !(cfg->hmax >= 0) ||
+        !(cfg->initial_amount > 0))
+        return FINENV_ERR_INVALID;
+    const long long E = cfg->n_envs, N = cfg->n_assets, T = cfg->n_days;
+    const long long D = 1 + N + N * cfg->n_cols, lim = (1ll << 32) - 1;
+    if ((f64_fields + books * N) * E * 8 > lim || T * N * cfg->n_cols * 4 > lim ||
+        T * N * 8 > lim || 64 * D * 4 > lim || E * N * 4 > lim)
+        return FINENV_ERR_INVALID;
+    H *h = finenv_host::new_handle<H>(cfg, D);
+    if (!h) return FINENV_ERR_NOMEM;
+    h->magicN = finenv_host::magic_for(N);
+    *out = h;
+    return FINENV_OK;
+}
+
+template <class H, class Panel, class State>
+int tw_bind(H *h, const Panel *panel, const State *st)
+{
+    if (!h || !panel || !st) return FINENV_ERR_INVALID;
+    if (!panel->close || (!panel->info && h->cfg.n_cols > 0) ||
+        (!panel->turb && h->cfg.use_turbulence) || !st->f64 || !st->i32)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null pointer");
+    return finenv_host::bind(h, panel, st);
+}
+
+template <class H>
+int tw_set_random_start(H *h, int32_t hi, uint64_t seed)
+{
+    if (!h || hi < 0 || hi > h->cfg.n_days) return FINENV_ERR_INVALID;
+    h->rs_hi = hi;
+    h->rs_seed = seed;
+    return FINENV_OK;
+}
+
+template <class H>
+int tw_set_audit(H *h, double *audit)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->audit = audit;
+    return FINENV_OK;
+}
+
+inline dim3 tw_grid(int E) { return dim3((unsigned)((E + kWaveSize - 1) / kWaveSize)); }   // one block per 64 envs
+
+template <class K, int NCH, class P>
+void tw_launch(const P &p, dim3 grid, hipStream_t stream)
+{
+    const dim3 block(2 * kWaveSize);
+    if (p.cfg.discrete_actions)
+        hipLaunchKernelGGL((K::template step<NCH, true>()), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((K::template step<NCH, false>()), grid, block, 0, stream, p);
+}
+
+// finenv_<kind>_step.  K names the env's kernels: K::step<NCH, DISCRETE>() with NCH 1 = rows of one
+// chunk, 2 = rows of up to 320 columns (the streamer copies the market data as 16-byte quads), 0 = wider
+// rows (one-wave form, on K::wide_grid(E) blocks); DISCRETE = cfg.discrete_actions.
+template <class K, class P, class H>
+int tw_step(H *h, const float *actions, float *obs, float *reward, uint8_t *done, float *term_obs,
+            int32_t auto_reset, void *stream, const char *what)
+{
+    if (const int rc = finenv_host::ready(h, "step")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    if (!actions || !obs || !reward || !done)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+    P p = tw_params<P>(h);
+    p.actions = actions;
+    p.obs = obs;
+    p.reward = reward;
+    p.done = done;
+    p.term_obs = term_obs;
+    p.auto_reset = auto_reset;
+#ifdef FINENV_DIAG
+    p.dbg = g_finenv_dbg;
+#endif
+    const int E = h->cfg.n_envs;
+    if (h->D <= kWaveSize) tw_launch<K, 1>(p, tw_grid(E), (hipStream_t)stream);
+    else if (h->D <= kWaveSize + 4 * kWaveSize) tw_launch<K, 2>(p, tw_grid(E), (hipStream_t)stream);
+    else tw_launch<K, 0>(p, K::wide_grid(E), (hipStream_t)stream);
+    return finenv_host::check_launch(h, what);
+}
+
+}  // namespace

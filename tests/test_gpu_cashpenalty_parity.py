@@ -75,7 +75,11 @@ def test_cashpenalty_hip_matches_reference_fixture(name):
     # 241 columns: the streamer copies the market data as 16-byte quads (rows up to 320 columns)
     dict(E=100, T=20, N=30, C=7, steps=30, hmax=60_000, thr=40.0, patient=False, disc=True),
     # 331 columns: wider than that, the trader writes the observation itself (no streamer)
-    dict(E=70, T=16, N=30, C=10, steps=24, hmax=60_000, thr=40.0, patient=False, disc=False)])
+    dict(E=70, T=16, N=30, C=10, steps=24, hmax=60_000, thr=40.0, patient=False, disc=False),
+    # 16 columns: one chunk with discrete actions, and a partial second block
+    dict(E=70, T=16, N=5, C=2, steps=40, hmax=300_000, thr=45.0, patient=False, disc=True),
+    # 331 columns again, with discrete actions and the patient cash-shortage branch
+    dict(E=70, T=16, N=30, C=10, steps=24, hmax=60_000, thr=40.0, patient=True, disc=True)])
 def test_cashpenalty_hip_matches_oracle_random_batch(cfg):
     _need_gpu()
     from finrl_amd.vec_cashpenalty import CashPenaltyPanel, VecCashPenaltyEnv
