@@ -44,6 +44,8 @@ struct NpParams {
     uint32_t magicN;
     unsigned long long *dbg;      // FINENV_DIAG builds only: [wave][16] s_memrealtime stamps
     int32_t diag;                 // FINENV_DIAG builds only: experiment switches (env FINENV_DIAG)
+    // finenv_stocknp_set_windows (the WIN instantiations; NULL otherwise)
+    int32_t *win;                 // [4][E]: pending start / end, active start / end
 };
 
 #ifdef FINENV_DIAG
@@ -55,6 +57,7 @@ struct NpParams {
 #define NF(fld) (*at(p.st.f64, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define NI(fld) (*at(p.st.i32, (unsigned)(fld) * (unsigned)E + (unsigned)e))
 #define NS(k, i) (*at(p.st.f32, ((unsigned)(k) * (unsigned)N + (unsigned)(i)) * (unsigned)E + (unsigned)e))
+#define NWIN(r) (*at(p.win, (unsigned)(r) * (unsigned)E + (unsigned)e))
 
 struct Num { double v; int tag; };
 __device__ __forceinline__ Num mk(double v, int tag) { Num r; r.v = v; r.tag = tag; return r; }
@@ -186,7 +189,14 @@ __device__ __forceinline__ float holdings_value(const float *scol, const float *
 // The trader issues EVERY global load it needs before the one block barrier that releases the
 // streamers' stores: the CU's memory pipeline serves requests in order, and loads queued behind
 // four streamers' stores came back after 6 us (profiles/r02_stocknp_phase_timeline.txt).
-template <bool RESET_ONLY>
+//
+// WIN: per-env episode windows (finenv_stocknp_set_windows).  Env e runs the ACTIVE window [s_e, t_e) =
+// win[2][e], win[3][e]: done when the incremented day equals t_e - 1; a reset (host or auto) first
+// copies the PENDING window win[0][e], win[1][e] into the active rows and restarts the env on the
+// price row of its start.  The active end travels with the day counter in the first round trip of
+// both roles; the pending pair is read only where an env of the wave is reset.  Window rows and the
+// day counter are clamped into the panel: a bad block is a wrong answer, never an access outside it.
+template <bool RESET_ONLY, bool WIN = false>
 __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_kernel(const NpParams p)
 {
     __shared__ float lds_all[kWaves * kLdsPerWave];
@@ -207,13 +217,15 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     float *prow_lds = cdl + kMaxN * kWave;                 // [ticker] shared price row (lock-step days)
 
     // reset(): day 0, start state, total_asset = amount + (stocks*price[0]).sum()  (:80-101)
-    auto do_reset = [&](Num &amount, Num &ta, Num &gr, Num &ita) {
+    // (WIN: on panel row `row`, the env's window start, through the per-env price path)
+    auto do_reset = [&](Num &amount, Num &ta, Num &gr, Num &ita, int row = 0) {
         for (int i = 0; i < N; ++i) {
             scol[i * kWave] = NS(2, i);
             ccol[i * kWave] = 0.0f;
         }
         amount = mk(NF(FINENV_NF_AMOUNT0), NI(FINENV_NI_AMOUNT0_TAG));
-        ta = n_add(amount, mk((double)holdings_value(scol, p.panel.price, 0u, N), FINENV_NT_F32));
+        const unsigned rpb = WIN ? (unsigned)(row * N) : 0u;
+        ta = n_add(amount, mk((double)holdings_value(scol, p.panel.price, rpb, N), FINENV_NT_F32));
         ita = ta;
         gr = mk(0.0, FINENV_NT_PY);
     };
@@ -249,12 +261,21 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     if (RESET_ONLY) {
         const bool sel = valid && (p.mask == nullptr || p.mask[e] != 0);
         Num amount, ta, gr, ita;
-        do_reset(amount, ta, gr, ita);
-        if (sel) store_state(amount, ta, gr, ita, (NI(FINENV_NI_TAGS) >> 8) & 3, 0);
+        int row0 = 0;
+        if (WIN) {                                          // pending -> active, restart on its start row
+            const int ps = NWIN(0), pt = NWIN(1);
+            row0 = min(max(ps, 0), p.cfg.n_days - 1);
+            if (sel) {
+                NWIN(2) = ps;
+                NWIN(3) = pt;
+            }
+        }
+        do_reset(amount, ta, gr, ita, row0);
+        if (sel) store_state(amount, ta, gr, ita, (NI(FINENV_NI_TAGS) >> 8) & 3, row0);
         if (p.obs == nullptr) return;
         fill_head(amount);
         wave_sync();
-        np_write_rows(p.obs, p, e0, nenv_w, 0, __ballot(sel), heads, lane);
+        np_write_rows(p.obs, p, e0, nenv_w, row0, __ballot(sel), heads, lane);
         return;
     }
 
@@ -305,15 +326,27 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     if (role == 0) STAMP64(0);
     if (role == 1) {
         int day_s = NI(FINENV_NI_DAY) + 1;
+        int last_s = p.cfg.n_days - 1;                      // WIN: the active window's end - 1
         // the day counter is read (and has arrived) before the block-wide barrier; the traders
-        // overwrite it only at the very end, long after they passed the same barrier
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(day_s) : : "memory");
+        // overwrite it (WIN: and the active window) only at the very end, long after they passed
+        // the same barrier
+        if constexpr (WIN) {
+            last_s = win_last_day(p.win + 2 * (size_t)E, E, e, p.cfg.n_days);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(day_s), "+v"(last_s) : : "memory");
+            day_s = min(max(day_s, 0), p.cfg.n_days - 1);
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(day_s) : : "memory");
+        }
         lds_barrier();
-        const bool done_s = day_s == p.cfg.n_days - 1;
+        const bool done_s = day_s == last_s;
         const unsigned long long vm = __ballot(valid), dm = __ballot(done_s && valid);
         if (dm != 0ull && p.term_obs != nullptr)
             np_write_rows<true>(p.term_obs, p, e0, nenv_w, day_s, dm, heads, lane, kpatch);
-        const int rd = (done_s && p.auto_reset) ? 0 : day_s;
+        int rd = (done_s && p.auto_reset) ? 0 : day_s;
+        if (WIN && p.auto_reset && dm != 0ull) {            // an auto-reset restarts on the pending start
+            const int ps = win_start(p.win, e, p.cfg.n_days);
+            if (done_s) rd = ps;
+        }
         const int rd0 = __builtin_amdgcn_readfirstlane(rd);
         const bool same_row = __all(!valid || rd == rd0);
         // what follows the streaming is decided from the day counters alone, identically in the trader
@@ -353,7 +386,13 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     // ---- trader: all global loads first -- the day counter (the second round trip hangs on it),
     // scalars, stocks / cool-downs, the action tile (flat and coalesced) -- then the barrier that
     // lets the streamers start storing, then the LDS images ---------------------------------------
-    const int day = NI(FINENV_NI_DAY) + 1;                                        // :106
+    int day_ld = NI(FINENV_NI_DAY) + 1;                                           // :106
+    int w_last = p.cfg.n_days - 1;                          // WIN: the active window's end - 1
+    if (WIN) {
+        w_last = win_last_day(p.win + 2 * (size_t)E, E, e, p.cfg.n_days);
+        day_ld = min(max(day_ld, 0), p.cfg.n_days - 1);
+    }
+    const int day = day_ld;
     const int tags = NI(FINENV_NI_TAGS);
     Num amount = mk(NF(FINENV_NF_AMOUNT), tags & 3);
     const Num ta_old = mk(NF(FINENV_NF_TOTAL_ASSET), (tags >> 2) & 3);
@@ -589,7 +628,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     Num ta = n_add(amount, mk((double)holdings_value(scol, p.panel.price, pb, N, prow), FINENV_NT_F32));
     Num r = n_mul(n_sub(ta, ta_old), mk(p.cfg.reward_scaling, FINENV_NT_PY));
     gr = n_add(n_mul(gr, mk(p.cfg.gamma, FINENV_NT_PY)), r);
-    const bool done = day == p.cfg.n_days - 1;
+    const bool done = day == w_last;
     if (done) {
         r = gr;
         if (valid) NF(FINENV_NF_EPISODE_RETURN) = n_div(ta, ita).v;
@@ -612,8 +651,17 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         if (p.auto_reset) {
             wave_sync();
             if (done) {
-                do_reset(amount, ta, gr, ita);
-                row_day = 0;
+                if (WIN) {                                  // pending -> active
+                    const int ps = NWIN(0), pt = NWIN(1);
+                    row_day = min(max(ps, 0), p.cfg.n_days - 1);
+                    if (valid) {
+                        NWIN(2) = ps;
+                        NWIN(3) = pt;
+                    }
+                } else {
+                    row_day = 0;
+                }
+                do_reset(amount, ta, gr, ita, row_day);
                 fill_head(amount);
             }
             wave_sync();
@@ -642,6 +690,7 @@ struct finenv_stocknp : finenv_host::Handle {
     finenv_stocknp_state st;
     int obs_pitch;        // row pitch of the obs buffers handed to step / reset (floats)
     uint32_t magicN;
+    int32_t *win;         // finenv_stocknp_set_windows
 };
 
 namespace {
@@ -655,6 +704,7 @@ NpParams np_params(const finenv_stocknp *h)
     p.D = h->D;
     p.obs_pitch = h->obs_pitch;
     p.magicN = h->magicN;
+    p.win = h->win;
     return p;
 }
 dim3 np_grid(int E)
@@ -683,6 +733,7 @@ int finenv_stocknp_create(const finenv_stocknp_config *cfg, finenv_stocknp **out
     if (!h) return FINENV_ERR_NOMEM;
     h->obs_pitch = (int)D;
     h->magicN = finenv_host::magic_for(N);
+    h->win = nullptr;
     *out = h;
     return FINENV_OK;
 }
@@ -698,6 +749,13 @@ int finenv_stocknp_set_obs_pitch(finenv_stocknp *h, int32_t pitch)
     if (pitch < h->D || (long long)pitch * 64 * 4 > (1ll << 32) - 1)
         return finenv_host::fail(h, FINENV_ERR_INVALID, "set_obs_pitch: pitch must be >= obs_dim");
     h->obs_pitch = pitch;
+    return FINENV_OK;
+}
+
+int finenv_stocknp_set_windows(finenv_stocknp *h, int32_t *win)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->win = win;
     return FINENV_OK;
 }
 
@@ -717,8 +775,12 @@ int finenv_stocknp_reset(finenv_stocknp *h, const uint8_t *mask, float *obs_out,
     NpParams p = np_params(h);
     p.mask = mask;
     p.obs = obs_out;
-    hipLaunchKernelGGL((stocknp_kernel<true>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
-                       (hipStream_t)stream, p);
+    if (p.win != nullptr)                     // a window block is attached
+        hipLaunchKernelGGL((stocknp_kernel<true, true>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
+                           (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((stocknp_kernel<true, false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
+                           (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "stocknp_reset");
 }
 
@@ -743,8 +805,12 @@ int finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, flo
         p.diag = d ? atoi(d) : 0;
     }
 #endif
-    hipLaunchKernelGGL((stocknp_kernel<false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
-                       (hipStream_t)stream, p);
+    if (p.win != nullptr)
+        hipLaunchKernelGGL((stocknp_kernel<false, true>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
+                           (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((stocknp_kernel<false, false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
+                           (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "stocknp_step");
 }
 

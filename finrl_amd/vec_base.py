@@ -231,14 +231,18 @@ class BatchedEnv:
 
 class WindowedEnv(BatchedEnv):
     """Per-env episode windows over one shared panel: the host side of ``finenv_<kind>_set_windows``,
-    shared by VecStockTradingEnv, VecStockPortfolioEnv and VecCryptoEnv (``num_envs`` and
-    ``max_step`` are theirs).  What differs between the kinds is named by four hooks:
+    shared by VecStockTradingEnv, VecStockPortfolioEnv, VecCryptoEnv and VecStockTradingEnvNP
+    (``num_envs`` and ``max_step`` are theirs).  What differs between the kinds is named by hooks:
     ``_window_rows`` (the panel's row count), ``_window_min`` (the shortest window that makes an
-    episode), ``_window_max_step`` (``max_step`` of the longest window) and ``_new_window_block``
-    (the device block the kernel reads; ``self.windows`` is its [2, E] start / end view)."""
+    episode), ``_window_max_step`` (``max_step`` of the longest window), ``_window_active`` (the
+    kernel keeps the running episodes' windows apart from the pending ones) and
+    ``_new_window_block`` (the device block the kernel reads; ``self.windows`` is its [2, E]
+    start / end view)."""
 
     windows = None
+    active_windows = None       # _window_active kinds: the running episodes' windows, kernel-owned
     _window_min = 1
+    _window_active = False
 
     @property
     def _window_rows(self):
@@ -249,10 +253,17 @@ class WindowedEnv(BatchedEnv):
 
     def _new_window_block(self):
         """Allocate the block the kernel reads -> its [2, E] view of starts and ends, every env on
-        the whole panel."""
-        win = _torch().zeros(2, self.num_envs, dtype=_torch().int32, device=self.device)
-        win[1].fill_(self._window_rows)
-        return win
+        the whole panel.  ``_window_active`` kinds: int32 [4, E], rows 0, 1 the pending windows
+        (``self.windows``, what the caller edits), rows 2, 3 the active ones
+        (``self.active_windows``, kernel-owned); both start on the whole panel, which is what an
+        env without windows is running."""
+        torch = _torch()
+        block = torch.zeros(4 if self._window_active else 2, self.num_envs, dtype=torch.int32,
+                            device=self.device)
+        block[1::2].fill_(self._window_rows)
+        if self._window_active:
+            self.active_windows = block[2:]
+        return block[:2]
 
     def _attach_windows(self, ptr):
         self._call("set_windows", ptr)
@@ -310,7 +321,7 @@ class WindowedEnv(BatchedEnv):
         torch = _torch()
         if start is None:
             self._attach_windows(None)
-            self.windows = None
+            self.windows = self.active_windows = None
             self.max_step = self._window_max_step(self._window_rows)
             return None
         if end is None:

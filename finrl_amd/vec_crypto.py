@@ -111,7 +111,7 @@ class VecCryptoEnv(WindowedEnv):
             self.state["time"].copy_(self.windows[0] + (lookback - 1))
 
     # ------------------------------------------------------------------ episode windows
-    active_windows = None
+    _window_active = True
     _window_rows = property(lambda self: self.price_array.shape[0])
 
     def _window_max_step(self, longest):
@@ -122,16 +122,6 @@ class VecCryptoEnv(WindowedEnv):
         if self._norm_table is None:
             self._norm_table = action_norm_table(self.price_array)
         return self._norm_table
-
-    def _new_window_block(self):
-        """int32 [4, E]: rows 0, 1 the pending windows (``self.windows``, what the caller edits),
-        rows 2, 3 the active ones (``self.active_windows``, kernel-owned).  Both start on the whole
-        panel, which is what an env without windows is running."""
-        import torch
-        block = torch.zeros(4, self.num_envs, dtype=torch.int32, device=self.device)
-        block[1::2].fill_(self._window_rows)
-        self.active_windows = block[2:]
-        return block[:2]
 
     def _attach_windows(self, ptr):
         import torch
@@ -166,10 +156,7 @@ class VecCryptoEnv(WindowedEnv):
         for "a fresh env object on a new slice" zero ``state["gamma_return"]`` of those envs.
         Attaching windows to a running batch leaves every env on the whole panel until its next
         reset.  ``max_step`` is that of the longest pending window."""
-        out = super().set_windows(start, end, mask)
-        if out is None:
-            self.active_windows = None
-        return out
+        return super().set_windows(start, end, mask)
 
     def window_time(self):
         """The reference's ``self.time`` of every env (int32 [E] device tensor): ``state["time"]``

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _native as nat
 from .spaces import Box
-from .vec_base import BatchedEnv
+from .vec_base import WindowedEnv
 
 TAG_PY, TAG_F32, TAG_F64 = 0, 1, 2
 
@@ -26,9 +26,16 @@ def derive_arrays(price_array, tech_array, turbulence_array, turbulence_thresh=9
     return price, tech, turb_ary, turb_bool
 
 
-class VecStockTradingEnvNP(BatchedEnv):
+class VecStockTradingEnvNP(WindowedEnv):
     """E parallel copies; constructor mirrors the reference (``config`` dict with
-    price_array / tech_array / turbulence_array / if_train)."""
+    price_array / tech_array / turbulence_array / if_train).
+
+    ``windows=(start, end)`` gives every env its own episode window of panel rows ``[start, end)``
+    (one pair for all envs, or [E] arrays / tensors): env e then equals the reference env built on
+    ``{'price_array': price_array[s:t], 'tech_array': tech_array[s:t], 'turbulence_array':
+    turbulence_array[s:t]}`` -- the train and test date ranges of finrl/train.py and finrl/test.py,
+    or random training windows, in ONE batch over one panel.  ``state["day"]`` stays the panel row;
+    ``window_day()`` is the reference's ``self.day``.  See ``set_windows``."""
 
     env_name = "StockEnv-MI355X"
     if_discrete = False
@@ -42,7 +49,7 @@ class VecStockTradingEnvNP(BatchedEnv):
     def __init__(self, config, num_envs, *, gamma=0.99, turbulence_thresh=99, min_stock_rate=0.1,
                  max_stock=1e2, initial_capital=1e6, buy_cost_pct=1e-3, sell_cost_pct=1e-3,
                  reward_scaling=2 ** -11, initial_stocks=None, auto_reset=True, device="cuda",
-                 seed=0, obs_amount_floor=0.0, obs_pitch=None):
+                 seed=0, obs_amount_floor=0.0, obs_pitch=None, windows=None):
         import torch
         self._set_device(device)
         price, tech, turb_ary, turb_bool = derive_arrays(
@@ -64,7 +71,8 @@ class VecStockTradingEnvNP(BatchedEnv):
         self.action_space = Box(-1, 1, (N,), np.float32)
         self.initial_stocks = np.zeros(N, np.float32) if initial_stocks is None else \
             np.asarray(initial_stocks, np.float32)
-        self._gen = torch.Generator(device=self.device)
+        self._stocks_dev = torch.from_numpy(self.initial_stocks).to(self.device)[:, None]
+        self.generator = self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(seed)
         self._open(nat.StockNpConfig(E, N, W, T, int(max_stock * min_stock_rate), 0,
                                      float(max_stock), float(buy_cost_pct), float(sell_cost_pct),
@@ -84,6 +92,41 @@ class VecStockTradingEnvNP(BatchedEnv):
         self._bind(self._price, self._tmpl, self._tbool)
         # obs: [E, D] view of a buffer whose rows start on 64-byte boundaries (vec_base.obs_pitch_for)
         self._alloc_outputs(E, D, obs_pitch)
+        if windows is not None:                       # the constructor's episode: each on its own window
+            self.set_windows(*self._check_windows(*windows))
+            self.active_windows.copy_(self.windows)
+            self.state["day"].copy_(self.windows[0])
+
+    # ------------------------------------------------------------------ episode windows
+    _window_active = True                             # pending / active rows, as the crypto env
+    _window_min = 2                                   # the n_days rule of finenv_stocknp_create
+    _window_rows = property(lambda self: self.price_ary.shape[0])
+
+    def set_windows(self, start, end=None, mask=None):
+        """Per-env episode windows [start, end) of panel rows (finenv_stocknp_set_windows), with the
+        arguments, validation and device-tensor rules of ``WindowedEnv.set_windows``; a window
+        needs two rows (host values are checked).  ``set_windows(None)`` detaches.
+
+        ``self.windows`` holds the PENDING windows: an env takes its pair at its next reset
+        (``reset()`` or the auto-reset inside ``step``) and runs the whole episode on it, whatever
+        is written here meanwhile; the running episodes' windows are in ``self.active_windows``
+        (kernel-owned, read-only for the caller).  So windows can be redrawn for the envs that just
+        finished with torch ops alone, also inside a captured graph, with no reset launch::
+
+            obs, rew, done, _ = env.step(actions)          # auto-reset: took the pending windows
+            env.set_windows(*random_windows(T, E, L, device=dev), mask=done)   # for the one after
+            env.draw_train_start(mask=done)                # if_train: start states on the new rows
+
+        Attaching windows to a running batch leaves every env on the whole panel until its next
+        reset.  ``max_step`` is that of the longest pending window."""
+        return super().set_windows(start, end, mask)
+
+    def window_day(self):
+        """The reference's ``self.day`` of every env (int32 [E] device tensor): ``state["day"]``
+        minus the start row of the window its episode runs on."""
+        if self.active_windows is None:
+            return self.state["day"].clone()
+        return self.state["day"] - self.active_windows[0]
 
     def set_start_state(self, stocks0, amount0, amount0_tag):
         """Per-env state that reset() restores: stocks0 [N] or [E,N], amount0 scalar or [E],
@@ -97,22 +140,40 @@ class VecStockTradingEnvNP(BatchedEnv):
         self.state["amount0_tag"].copy_(torch.from_numpy(
             np.array(np.broadcast_to(np.asarray(amount0_tag, np.int32), (E,)), copy=True)))
 
-    def _draw_train_start(self):
+    def draw_train_start(self, mask=None):
         """Train-mode start state (:85-92), drawn on device with this env's generator (the
-        reference uses the global numpy RNG, so its draws are not reproducible elsewhere)."""
+        reference uses the global numpy RNG, so its draws are not reproducible elsewhere) -- for
+        every env, or those with ``mask[e]`` set.  The cash left after the drawn holdings is priced
+        on the first row of the env's slice: ``price[pending start]`` per env with windows, row 0
+        without.  ``reset()`` calls this in train mode; call it yourself for the envs that were
+        just given new windows (see ``set_windows``), so that their next episode starts on a draw
+        priced on its own first row.  Torch ops only, no host synchronisation: it can be captured
+        in a graph (register ``self.generator`` with the graph first:
+        ``graph.register_generator_state(env.generator)``)."""
         import torch
         E, N = self.num_envs, self.action_dim
-        st = torch.from_numpy(self.initial_stocks).to(self.device)[:, None] + torch.randint(
+        st = self._stocks_dev + torch.randint(
             0, 64, (N, E), generator=self._gen, device=self.device).to(torch.float32)
         u = torch.rand(E, generator=self._gen, device=self.device, dtype=torch.float64) * 0.1 + 0.95
-        amount = (self.initial_capital * u).to(torch.float32) - (st * self._price[0][:, None]).sum(0)
-        self.state["stocks0"].copy_(st)
-        self.state["amount0"].copy_(amount.to(torch.float64))
-        self.state["amount0_tag"].fill_(TAG_F32)
+        if self.windows is None:
+            first = self._price[0][:, None]
+        else:                                         # [N, E]: the first row of every env's slice
+            rows = self.windows[0].clamp(0, self._window_rows - 1).to(torch.int64)
+            first = self._price.index_select(0, rows).T
+        amount = ((self.initial_capital * u).to(torch.float32) - (st * first).sum(0)).to(torch.float64)
+        if mask is None:
+            self.state["stocks0"].copy_(st)
+            self.state["amount0"].copy_(amount)
+            self.state["amount0_tag"].fill_(TAG_F32)
+            return
+        m = mask.to(device=self.device, dtype=torch.bool)
+        self.state["stocks0"].copy_(torch.where(m, st, self.state["stocks0"]))
+        self.state["amount0"].copy_(torch.where(m, amount, self.state["amount0"]))
+        self.state["amount0_tag"].masked_fill_(m, TAG_F32)
 
     def _before_reset(self):
         if self.if_train:
-            self._draw_train_start()
+            self.draw_train_start()
 
     def episode_return(self):
         """total_asset / initial_total_asset of each env's last finished episode (:145), f32."""

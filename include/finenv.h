@@ -736,6 +736,45 @@ int  finenv_stocknp_reset(finenv_stocknp *h, const uint8_t *mask, float *obs_out
 int  finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, float *reward,
                          uint8_t *done, float *term_obs, int32_t auto_reset, void *stream);
 
+/* Per-env episode windows of the array-state env: many StockTradingEnv / StockEnvNAS100 instances
+ * built on slices {'price_array': price[s:t], 'tech_array': tech[s:t], 'turbulence_array':
+ * turb[s:t]} of ONE bound panel in one batch (the train / test date ranges of finrl/train.py and
+ * finrl/test.py, random-window training).  The constructor's array preparation (:27-35) is
+ * elementwise, so the bound panel, the template rows and turb_bool stay as they are.  Env e on
+ * window [s_e, t_e) equals the reference env on that slice, bit for bit; FINENV_NI_DAY stays the
+ * PANEL row (the reference's self.day is FINENV_NI_DAY - s_e).  In panel rows:
+ *   - a reset (finenv_stocknp_reset or the auto-reset inside step) sets day = s_e, restores
+ *     stocks / cool-downs / amount from the start state, total_asset = amount +
+ *     (stocks * price[s_e]).sum() in the same float32 pairwise order, gamma_reward = 0, and shows
+ *     observation row s_e (:80-101);
+ *   - a step increments day, trades at price[day] under turb_bool[day] and is done when the
+ *     incremented day equals t_e - 1 (:67, :142); FINENV_NF_EPISODE_RETURN is latched as always;
+ *   - with a valid window no panel row outside [s_e, t_e) is read.
+ * A window needs t_e - s_e >= 2 (the n_days rule of finenv_stocknp_create).  The start state
+ * (stocks0, amount0, amount0_tag) is the caller's as before: a train-mode draw (:85-92) depends on
+ * price[s_e], the first row of the env's slice.
+ *
+ * win: caller-owned device block int32_t [4][E], or NULL to detach (the default: every env runs
+ * the whole panel).
+ *   rows 0, 1  the PENDING window (s_e, t_e): the caller writes them whenever it likes, the env
+ *              takes them at its next reset;
+ *   rows 2, 3  the ACTIVE window of the running episode: written only by the reset paths
+ *              (finenv_stocknp_reset for the envs it selects and the auto-reset inside step, which
+ *              copy rows 0, 1 of the envs they reset), read by step.  Initialise them to the
+ *              window of the episode in progress, or reset every env once after attaching.
+ * The crypto env's layout, not the [2][E] blocks of the stock and portfolio envs: the end row is
+ * read on every step, so an edit must not reach a running episode.  With the two extra rows,
+ * redrawing the windows of the envs that just reported done needs no reset launch (and works
+ * inside a captured graph): their auto-reset has already taken the windows that were pending, the
+ * redraw is taken at the one after.
+ * The kernels clamp window rows and the day counter into the panel whatever the block and the
+ * state hold: bad device-side content is a wrong answer, never an access outside the panel or
+ * the state.
+ * The pointer is a kernel argument: launches and graph replays see later edits of the block's
+ * CONTENTS, a graph keeps the pointer it was captured with.  Works before bind.  Returns
+ * FINENV_ERR_INVALID for a NULL handle. */
+int finenv_stocknp_set_windows(finenv_stocknp *h, int32_t *win);
+
 /* =====================================================================================
  * StockTradingEnvCashpenalty
  * (finrl/meta/env_stock_trading/env_stocktrading_cashpenalty.py:19-409): continuous (or
