@@ -260,10 +260,10 @@ cashpenalty_kernel(const CpParams p)
             if (DISCRETE) {                                                      // :263-274
                 // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a software
                 // 64-bit division per asset, unrolled, was 30 KB of code)
-                const double q = tw_floordiv((double)a, cl);
+                const double q = floordiv_true((double)a, cl);
                 const double inc = (double)c.shares_increment;
                 const double num = q >= 0.0 ? q : q + inc;
-                tr = tw_floordiv(num, inc) * inc;
+                tr = floordiv_true(num, inc) * inc;
             } else {
                 tr = (double)a / cl;                                             // :276
             }

@@ -137,6 +137,22 @@ __device__ __forceinline__ int draw_start(unsigned long long seed, int env, int 
     return (int)(((z >> 32) * (unsigned long long)(unsigned)hi) >> 32);
 }
 
+// exact floor(a/d) for d > 0 (== numpy floor_divide in float64 and, for float32 operands,
+// == npy_floor_dividef: both return the true floor at these magnitudes)
+__device__ __forceinline__ double floordiv_true(double a, double d)
+{
+    double x = __builtin_amdgcn_rcp(d);
+    x = fma(fma(-d, x, 1.0), x, x);
+    double q = floor(a * x);
+    double r = fma(-q, d, a);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
+        r = fma(-q, d, a);
+    }
+    return q;
+}
+
 // Keep a just-loaded value in a register HERE.  hipcc sinks a load into the (conditional) block
 // that holds its only use, which turns "issue a batch of loads, then consume them" back into
 // load / s_waitcnt vmcnt(0) / use, one exposed HBM round trip per element.

@@ -89,22 +89,7 @@ __device__ __forceinline__ Num n_div(Num a, Num b)
     const double r32 = (double)((float)a.v / (float)b.v), r64 = a.v / b.v;
     return mk(t == FINENV_NT_F32 ? r32 : r64, t);
 }
-// exact floor(a/d) for d > 0 (== numpy floor_divide in float64 and, for float32 operands,
-// == npy_floor_dividef: both return the true floor at these magnitudes)
-__device__ __forceinline__ double floordiv_true(double a, double d)
-{
-    double x = __builtin_amdgcn_rcp(d);
-    x = fma(fma(-d, x, 1.0), x, x);
-    double q = floor(a * x);
-    double r = fma(-q, d, a);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
-        r = fma(-q, d, a);
-    }
-    return q;
-}
-__device__ __forceinline__ Num n_floordiv(Num a, Num b)      // b > 0
+__device__ __forceinline__ Num n_floordiv(Num a, Num b)      // b > 0 (floordiv_true: finenv_dev.h)
 {
     const int t = promote(a.tag, b.tag);
     // float32 case: operands are first rounded to float32, the quotient is exact in fp64

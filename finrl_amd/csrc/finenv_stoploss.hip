@@ -209,10 +209,10 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
                 if (c.discrete_actions) {                                        // :333-343
                     // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a
                     // software 64-bit division per asset, unrolled, doubled the kernel's code)
-                    const double q = cl > 0.0 ? tw_floordiv(a, cl) : 0.0;
+                    const double q = cl > 0.0 ? floordiv_true(a, cl) : 0.0;
                     const double inc = (double)c.shares_increment;
                     const double num = q >= 0.0 ? q : q + inc;
-                    tr = tw_floordiv(num, inc) * inc;
+                    tr = floordiv_true(num, inc) * inc;
                 } else {
                     tr = cl > 0.0 ? a / cl : 0.0;                                // :345
                 }
@@ -639,10 +639,10 @@ stoploss_step2_kernel(const SlParams p)
                 a = turbulent ? -(h * cl) : a;                                   // :327-331
                 double tr;
                 if (DISCRETE) {                                                  // :333-343
-                    const double q = cl > 0.0 ? tw_floordiv(a, cl) : 0.0;
+                    const double q = cl > 0.0 ? floordiv_true(a, cl) : 0.0;
                     const double inc = (double)c.shares_increment;
                     const double num = q >= 0.0 ? q : q + inc;
-                    tr = tw_floordiv(num, inc) * inc;
+                    tr = floordiv_true(num, inc) * inc;
                 } else {
                     tr = cl > 0.0 ? a / cl : 0.0;                                // :345
                 }

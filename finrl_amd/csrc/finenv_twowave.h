@@ -38,20 +38,6 @@ struct TwoWaveParams {
     unsigned long long *dbg;        // FINENV_DIAG builds only: [block][16] s_memrealtime stamps
 };
 
-__device__ __forceinline__ double tw_floordiv(double a, double d)       // exact floor(a/d), d > 0
-{
-    double x = __builtin_amdgcn_rcp(d);
-    x = fma(fma(-d, x, 1.0), x, x);
-    double q = floor(a * x);
-    double r = fma(-q, d, a);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        q += (r < 0.0) ? -1.0 : ((r >= d) ? 1.0 : 0.0);
-        r = fma(-q, d, a);
-    }
-    return q;
-}
-
 // rows[el*kRow + 0] = f32 cash, rows[el*kRow + 1 + i] = f32 holdings_i; columns > N: info row
 template <bool kCompact = false, class P>
 __device__ __forceinline__ void tw_write_rows(float *__restrict__ dst, const P &p, int e0,

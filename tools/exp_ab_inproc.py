@@ -4,7 +4,11 @@
 handle is created by the base build, so both builds must share the layout of the finenv_<kind> handle
 structs (variants of one source tree always do).
 usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|portfolio-random63|stocknp> [rounds]
-  portfolio-random63: the portfolio env with random 63-day episode windows (VecStockPortfolioEnv.set_windows)"""
+  portfolio-random63: the portfolio env with random 63-day episode windows (VecStockPortfolioEnv.set_windows)
+  cashpenalty:c<C>:<disc|cont>, stoploss:c<C>:<disc|cont>: VecCashPenaltyEnv / VecStopLossEnv as bench.py builds
+    them (65,536 envs, 30 assets, hmax=2_000, random starts) but with C columns per asset and the given
+    discrete_actions setting -- C = 1: 61-column rows (one chunk), 5: 181 (the quad streamer; the bench.py
+    line), 10: 331 (the one-wave step)"""
 import os
 import sys
 
@@ -33,6 +37,8 @@ def main():
     nat._lib, nat.LIB_PATH = libs["base"], base_path
     dev = torch.device("cuda", 0)
     E = 65536
+    if kind.split(":")[0] in ("cashpenalty", "stoploss"):
+        return two_wave_ab(libs, nat, torch, dev, E, kind, rounds)
     if ":" in kind:                        # "<kind>:<envs>", e.g. n30:262144
         kind, e_txt = kind.split(":")
         E = int(e_txt)
@@ -53,9 +59,30 @@ def main():
         g = torch.Generator(device=dev).manual_seed(7)
         env.set_windows(*random_windows(env.panel.T, E, 63, generator=g, device=dev))
         kind = "portfolio-random63"
+    alternate(libs, envs, nat, torch, env, w.pool, kind, rounds)
+
+
+def two_wave_ab(libs, nat, torch, dev, E, kind, rounds):
+    import numpy as np
+    import bench
+    from finrl_amd.vec_cashpenalty import CashPenaltyPanel, VecCashPenaltyEnv, VecStopLossEnv
+    name, cols, act = kind.split(":")
+    T, N, Cc = bench.N_DAYS, bench.N_TICKERS, int(cols[1:])
+    rng = np.random.default_rng(0)
+    close = 50 * np.exp(np.cumsum(rng.normal(0, 0.01, (T, N)), axis=0))
+    panel = CashPenaltyPanel(close, rng.normal(0, 10, (T, N, Cc)), np.abs(rng.normal(0, 30, T)))
+    cls = VecCashPenaltyEnv if name == "cashpenalty" else VecStopLossEnv
+    env = cls(panel, E, hmax=2_000, random_start=True, discrete_actions={"disc": True, "cont": False}[act],
+              device=dev, seed=0)
+    gen = torch.Generator(device=dev).manual_seed(1234)
+    pool = [torch.rand(E, N, generator=gen, device=dev) * 2.0 - 1.0 for _ in range(8)]
+    alternate(libs, dict.fromkeys(libs), nat, torch, env, pool, kind, rounds)
+
+
+def alternate(libs, envs, nat, torch, env, pool, kind, rounds):
     env.reset()
     for i in range(2000):
-        env.step(w.pool[i % 8])
+        env.step(pool[i % 8])
     torch.cuda.synchronize()
     for r in range(rounds):
         for name in libs:
@@ -67,12 +94,12 @@ def main():
                 os.environ[envs[name].split("=")[0]] = envs[name].split("=")[1]
             env._step_args = None                # BatchedEnv.step caches the previous library's function
             for i in range(100):
-                env.step(w.pool[i % 8])
+                env.step(pool[i % 8])
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for i in range(500):
-                env.step(w.pool[i % 8])
+                env.step(pool[i % 8])
             e1.record()
             torch.cuda.synchronize()
             print(f"{kind} round {r} {name:8s} {e0.elapsed_time(e1) * 1e3 / 500:.2f} us", flush=True)
