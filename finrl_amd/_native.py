@@ -153,6 +153,17 @@ class StockNpStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p), ("f32", C.c_void_p)]
 
 
+class StockNpHistoryPtrs(C.Structure):
+    """finenv_stocknp_history: the episode-history tensors of finenv_stocknp_set_history."""
+    _fields_ = [("asset", C.c_void_p), ("tag", C.c_void_p), ("stocks", C.c_void_p),
+                ("start", C.c_void_p), ("len", C.c_void_p), ("flags", C.c_void_p),
+                ("capacity", C.c_int32)]
+
+
+# columns of finenv_stocknp_history_metrics: the FINENV_HM_* indices, n_returns = len - 1 as in the stock env
+STOCKNP_HISTORY_METRICS = STOCK_HISTORY_METRICS
+
+
 class CashPenaltyConfig(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("n_assets", C.c_int32), ("n_cols", C.c_int32),
                 ("n_days", C.c_int32), ("discrete_actions", C.c_int32),
@@ -271,7 +282,7 @@ def lib():
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
     for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs),
-                       ("crypto", CryptoHistoryPtrs)):
+                       ("crypto", CryptoHistoryPtrs), ("stocknp", StockNpHistoryPtrs)):
         if hasattr(L, f"finenv_{kind}_set_history"):       # episode history (same rule)
             getattr(L, f"finenv_{kind}_set_history").argtypes = [C.c_void_p, C.POINTER(ptrs)]
             getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3

@@ -47,6 +47,14 @@ struct NpParams {
     // finenv_stocknp_set_windows (the WIN instantiations; NULL otherwise)
     int32_t *win;                 // [4][E]: pending start / end, active start / end
 };
+// The argument of the HIST step kernels: the history behind the last older field.  A struct of its own,
+// as in the crypto env (CrParamsHist): every other instantiation takes the argument it always took
+// and compiles to the code it always was.
+struct NpParamsHist : NpParams {
+    finenv_stocknp_history hist;
+};
+template <bool HIST>
+using NpArgs = typename std::conditional<HIST, NpParamsHist, NpParams>::type;
 
 #ifdef FINENV_DIAG
 #define NDIAG(bit) (p.diag & (bit))
@@ -181,10 +189,19 @@ __device__ __forceinline__ float holdings_value(const float *scol, const float *
 // price row of its start.  The active end travels with the day counter in the first round trip of
 // both roles; the pending pair is read only where an env of the wave is reset.  Window rows and the
 // day counter are clamped into the panel: a bad block is a wrong answer, never an access outside it.
-template <bool RESET_ONLY, bool WIN = false>
-__global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_kernel(const NpParams p)
+//
+// HIST: the recording step (NpParamsHist::hist attached, finenv_stocknp_set_history; the rule is in
+// include/finenv.h).  What it records -- the step's total_asset before an auto-reset replaces it, its
+// dtype tag, the post-trade holdings -- exists only in the trader's registers and LDS.  The trader runs
+// at the register limit and on one chain of round trips, so the env's entry counter and flags are loaded
+// by its STREAMER, beside the day counter in that wave's first round trip, and parked in LDS ahead of
+// barrier #1; the trader picks them up where it stores reward / done, holds nothing across the trade
+// loops and loads nothing to decide what to store.
+template <bool RESET_ONLY, bool WIN = false, bool HIST = false>
+__global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_kernel(const NpArgs<HIST> p)
 {
-    __shared__ float lds_all[kWaves * kLdsPerWave];
+    static_assert(!(HIST && RESET_ONLY), "the record is taken by the step");
+    __shared__ float lds_all[kWaves * (kLdsPerWave + (HIST ? 2 * kWave : 0))];
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = (threadIdx.x >> 6) % kWaves;
     const int role = (threadIdx.x >> 6) / kWaves;          // 0 trader, 1 streamer (step only)
@@ -200,6 +217,8 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     float *scol = stk + lane, *ccol = cdl + lane;
     float *head = heads + lane * kRowH;
     float *prow_lds = cdl + kMaxN * kWave;                 // [ticker] shared price row (lock-step days)
+    // HIST: [2][lane] the envs' entry counters and flags, behind the four waves' regions
+    int *hpark = reinterpret_cast<int *>(lds_all + kWaves * kLdsPerWave) + wib * 2 * kWave;
 
     // reset(): day 0, start state, total_asset = amount + (stocks*price[0]).sum()  (:80-101)
     // (WIN: on panel row `row`, the env's window start, through the per-env price path)
@@ -315,7 +334,19 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         // the day counter is read (and has arrived) before the block-wide barrier; the traders
         // overwrite it (WIN: and the active window) only at the very end, long after they passed
         // the same barrier
-        if constexpr (WIN) {
+        if constexpr (HIST) {                               // the same round trip, the same wait
+            int hlen_s = *at(p.hist.len, (unsigned)e), hfl_s = *at(p.hist.flags, (unsigned)e);
+            if constexpr (WIN) {
+                last_s = win_last_day(p.win + 2 * (size_t)E, E, e, p.cfg.n_days);
+                asm volatile("s_waitcnt vmcnt(0)"
+                             : "+v"(day_s), "+v"(last_s), "+v"(hlen_s), "+v"(hfl_s) : : "memory");
+                day_s = min(max(day_s, 0), p.cfg.n_days - 1);
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(day_s), "+v"(hlen_s), "+v"(hfl_s) : : "memory");
+            }
+            hpark[lane] = hlen_s;                           // the trader reads them behind barrier #1
+            hpark[kWave + lane] = hfl_s;
+        } else if constexpr (WIN) {
             last_s = win_last_day(p.win + 2 * (size_t)E, E, e, p.cfg.n_days);
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(day_s), "+v"(last_s) : : "memory");
             day_s = min(max(day_s, 0), p.cfg.n_days - 1);
@@ -623,6 +654,28 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
         *at(p.done, (unsigned)e) = done ? 1 : 0;
         NF(FINENV_NF_LAST_REWARD) = r.v;
     }
+    if constexpr (HIST) {
+        // entry hlen of an armed, unfinished record (the terminal step included: this env trades and
+        // revalues on it), from the step's own values: `ta` before any auto-reset, the holdings final
+        // in this lane's LDS column (on a turbulence day: the zeros).  The time-major slabs are indexed
+        // in 64 bits; a store of a wave is one contiguous run of envs in every tensor.
+        const int hlen = hpark[lane], hfl = hpark[kWave + lane];
+        if (valid && hlen >= 1 && !(hfl & FINENV_HIST_COMPLETE)) {
+            const bool room = hlen < p.hist.capacity;
+            if (room) {
+                const size_t o = (size_t)hlen * (size_t)E + (size_t)e;
+                p.hist.asset[o] = ta.v;
+                if (p.hist.tag != nullptr) p.hist.tag[o] = (uint8_t)ta.tag;
+                if (p.hist.stocks != nullptr) {
+                    float *const hs = p.hist.stocks + (size_t)hlen * (size_t)N * (size_t)E + (size_t)e;
+                    for (int i = 0; i < N; ++i) hs[(size_t)i * (size_t)E] = scol[i * kWave];
+                }
+                *at(p.hist.len, (unsigned)e) = hlen + 1;
+            }
+            const int nfl = hfl | (room ? 0 : FINENV_HIST_OVERFLOW) | (done ? FINENV_HIST_COMPLETE : 0);
+            if (nfl != hfl) *at(p.hist.flags, (unsigned)e) = nfl;   // (an overflowed env: set once)
+        }
+    }
     STAMP64(3);
     wave_sync();
     if (!head_filled) fill_head(amount);     // overwrites the (consumed) action rows
@@ -667,6 +720,49 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
     STAMP64(6);
 }
 
+// -------------------------------------------------------------------------------------
+// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
+// instantiation of the step kernel above).
+// -------------------------------------------------------------------------------------
+struct NpHistArgs {
+    finenv_stocknp_history h;
+    finenv_stocknp_state st;
+    const uint8_t *mask;          // arm: envs to arm, or NULL = all
+    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
+    double annualization;
+    int32_t E, N;
+};
+
+// Entry 0 of the envs of the mask, from their current state: total_asset and its dtype tag, the
+// holdings, and the panel row the env stands on.  One lane per env.
+__global__ __launch_bounds__(256) void stocknp_history_arm_kernel(const NpHistArgs p)
+{
+    const int E = p.E, N = p.N;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E || (p.mask != nullptr && p.mask[e] == 0)) return;
+    p.h.asset[e] = NF(FINENV_NF_TOTAL_ASSET);
+    if (p.h.tag != nullptr) p.h.tag[e] = (uint8_t)((NI(FINENV_NI_TAGS) >> 2) & 3);
+    if (p.h.stocks != nullptr) {
+        for (int i = 0; i < N; ++i) p.h.stocks[(size_t)i * (size_t)E + (size_t)e] = NS(0, i);
+    }
+    p.h.start[e] = NI(FINENV_NI_DAY);
+    p.h.len[e] = 1;
+    p.h.flags[e] = 0;
+}
+
+// Backtest figures of each env's recorded account values (series_metrics, finenv_dev.h): the returns
+// are asset[k] / asset[k-1] - 1 in fp64, entry 0 carries none, so n_returns is len - 1.
+__global__ void stocknp_history_metrics_kernel(const NpHistArgs p)
+{
+    const int E = p.E;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const double *a = p.h.asset + e;
+    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
+                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
+                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
+}
+
 }  // namespace
 
 struct finenv_stocknp : finenv_host::Handle {
@@ -676,6 +772,8 @@ struct finenv_stocknp : finenv_host::Handle {
     int obs_pitch;        // row pitch of the obs buffers handed to step / reset (floats)
     uint32_t magicN;
     int32_t *win;         // finenv_stocknp_set_windows
+    int has_hist;         // finenv_stocknp_set_history
+    finenv_stocknp_history hist;
 };
 
 namespace {
@@ -696,6 +794,31 @@ dim3 np_grid(int E)
 {
     const int waves = (E + kWave - 1) / kWave;
     return dim3((unsigned)((waves + kWaves - 1) / kWaves));
+}
+NpHistArgs np_hist_args(const finenv_stocknp *h)
+{
+    NpHistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h->hist;
+    a.st = h->st;
+    a.E = h->cfg.n_envs;
+    a.N = h->cfg.n_tickers;
+    return a;
+}
+// reset (re)starts episodes: the records of the envs it resets start afresh
+void launch_history_arm(const finenv_stocknp *h, const uint8_t *mask, hipStream_t stream)
+{
+    NpHistArgs a = np_hist_args(h);
+    a.mask = mask;
+    hipLaunchKernelGGL(stocknp_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
+}
+// a step: the WIN instantiation while a window block is attached
+template <bool HIST>
+void np_launch_step(const NpArgs<HIST> &p, hipStream_t stream)
+{
+    const dim3 grid = np_grid(p.cfg.n_envs), block(kWave * kWaves * 2);
+    if (p.win != nullptr) hipLaunchKernelGGL((stocknp_kernel<false, true, HIST>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((stocknp_kernel<false, false, HIST>), grid, block, 0, stream, p);
 }
 }  // namespace
 
@@ -766,6 +889,7 @@ int finenv_stocknp_reset(finenv_stocknp *h, const uint8_t *mask, float *obs_out,
     else
         hipLaunchKernelGGL((stocknp_kernel<true, false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
                            (hipStream_t)stream, p);
+    if (h->has_hist) launch_history_arm(h, mask, (hipStream_t)stream);   // behind the reset: reads its state
     return finenv_host::check_launch(h, "stocknp_reset");
 }
 
@@ -790,13 +914,44 @@ int finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, flo
         p.diag = d ? atoi(d) : 0;
     }
 #endif
-    if (p.win != nullptr)
-        hipLaunchKernelGGL((stocknp_kernel<false, true>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
-                           (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL((stocknp_kernel<false, false>), np_grid(h->cfg.n_envs), dim3(kWave * kWaves * 2), 0,
-                           (hipStream_t)stream, p);
+    if (h->has_hist) {                       // the recording instantiation while a history is attached
+        NpParamsHist q;
+        static_cast<NpParams &>(q) = p;
+        q.hist = h->hist;
+        np_launch_step<true>(q, (hipStream_t)stream);
+    } else {
+        np_launch_step<false>(p, (hipStream_t)stream);
+    }
     return finenv_host::check_launch(h, "stocknp_step");
+}
+
+int finenv_stocknp_set_history(finenv_stocknp *h, const finenv_stocknp_history *hist)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    const bool missing = hist && (!hist->asset || !hist->start || !hist->len || !hist->flags);
+    return finenv_host::set_history(h, h->hist, h->has_hist, hist,
+                                    missing ? "set_history: null asset/start/len/flags" : nullptr);
+}
+
+int finenv_stocknp_history_arm(finenv_stocknp *h, const uint8_t *mask, void *stream)
+{
+    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    launch_history_arm(h, mask, (hipStream_t)stream);
+    return finenv_host::check_launch(h, "stocknp_history_arm");
+}
+
+int finenv_stocknp_history_metrics(finenv_stocknp *h, double annualization, double *out, void *stream)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    NpHistArgs a = np_hist_args(h);
+    a.out = out;
+    a.annualization = annualization;
+    hipLaunchKernelGGL(stocknp_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return finenv_host::check_launch(h, "stocknp_history_metrics");
 }
 
 }  // extern "C"

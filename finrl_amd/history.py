@@ -6,9 +6,9 @@ device-to-host copy per tensor.
 
 The frame builders at the top work on host arrays (time-major, as the device holds them) and need
 no GPU; ``EpisodeHistory`` owns the device tensors and is what
-``VecStockTradingEnv.enable_history()`` returns.  ``PortfolioEpisodeHistory`` and
-``CryptoEpisodeHistory`` are the same for the portfolio and the crypto env, whose step kernels write
-the record themselves.
+``VecStockTradingEnv.enable_history()`` returns.  ``PortfolioEpisodeHistory``,
+``CryptoEpisodeHistory`` and ``StockNpEpisodeHistory`` are the same for the portfolio, the crypto and
+the array-state stock env, whose step kernels write the record themselves.
 """
 from __future__ import annotations
 
@@ -21,6 +21,7 @@ from . import _native as nat
 METRIC_KEYS = nat.STOCK_HISTORY_METRICS
 PORTFOLIO_METRIC_KEYS = nat.PORTFOLIO_HISTORY_METRICS
 CRYPTO_METRIC_KEYS = nat.CRYPTO_HISTORY_METRICS
+STOCKNP_METRIC_KEYS = nat.STOCKNP_HISTORY_METRICS
 
 
 def _torch():
@@ -137,12 +138,52 @@ def crypto_rows(start, length):
     return int(start) + np.arange(int(length), dtype=np.int64)
 
 
+# the scalar type behind each FINENV_NT_* tag of the array-state env (include/finenv.h)
+_STOCKNP_SCALARS = (float, np.float32, np.float64)
+
+
+def stocknp_account_values(asset, length):
+    """One array-state env's recorded account curve: ``total_asset`` after every step
+    (env_stocktrading_np.py:137), entry 0 the value the record was armed on -> f64 [length]."""
+    return np.array(np.asarray(asset, dtype=np.float64)[:int(length)])
+
+
+def stocknp_episode_total_assets(asset, tag, length):
+    """The list DRLAgent.DRL_prediction returns (agents/elegantrl/models.py:107-131) from one env's
+    recorded ``asset`` and ``tag`` columns: element k is the scalar the reference's list holds there
+    under NumPy >= 2 -- ``float``, ``np.float32`` or ``np.float64`` by its FINENV_NT_* tag (a float32
+    total_asset is recorded widened, so the conversion back is exact).  ``tag`` None (not recorded):
+    Python floats."""
+    n = int(length)
+    a = np.asarray(asset, dtype=np.float64)[:n].tolist()
+    if tag is None:
+        return a
+    return [_STOCKNP_SCALARS[t](x) for x, t in zip(a, np.asarray(tag)[:n].tolist())]
+
+
+def stocknp_episode_returns(asset, tag, length):
+    """``episode_returns`` of the same loop (models.py:124): ``total_asset / initial_total_asset`` for
+    every entry k >= 1 over entry 0, each quotient in the dtype NumPy >= 2 promotes the two scalars to
+    (a Python float defers to a NumPy scalar, float64 beats float32) -- the reference's list when the
+    record was armed at the episode's start.  ``tag`` None: float64 quotients as Python floats."""
+    vals = stocknp_episode_total_assets(asset, tag, length)
+    if not vals:
+        return []
+    first, out = vals[0], []
+    for x in vals[1:]:
+        kinds = {type(x), type(first)}
+        kind = np.float64 if np.float64 in kinds else (np.float32 if np.float32 in kinds else float)
+        out.append(kind(kind(x) / kind(first)))
+    return out
+
+
 # ---------------------------------------------------------------------- the device side
 class _Record:
     """A device-resident episode record: what ``EpisodeHistory``, ``PortfolioEpisodeHistory`` and
     ``CryptoEpisodeHistory`` are made of.  A subclass declares its data:
       ``_ptrs_cls``    the ctypes struct of finenv_<kind>_set_history (one pointer per tensor, capacity)
-      ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]
+      ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]; those named in the
+                       constructor's ``without`` are not recorded (None)
       ``_per_ticker``  (name, dtype, rows short of capacity): the optional tensor [capacity - short, E, N]
       ``_env_last``    that tensor is [capacity - short, N, E] instead (the env is the fastest index)
       ``_per_env``     ((name, dtype), ...): the tensors [E] beside ``length`` and ``flags``
@@ -152,7 +193,7 @@ class _Record:
 
     _env_last, _per_env, _assets = False, (), "stock_dim"
 
-    def __init__(self, env, capacity, per_ticker=True):
+    def __init__(self, env, capacity, per_ticker=True, without=()):
         torch = _torch()
         E, N, dev = env.num_envs, getattr(env, self._assets), env.device
         capacity = int(capacity)
@@ -160,7 +201,8 @@ class _Record:
             raise ValueError("history capacity must be >= 2")
         self.env, self.capacity = env, capacity
         for name, dtype in self._series:
-            setattr(self, name, torch.zeros(capacity, E, dtype=getattr(torch, dtype), device=dev))
+            setattr(self, name, None if name in without else
+                    torch.zeros(capacity, E, dtype=getattr(torch, dtype), device=dev))
         name, dtype, short = self._per_ticker
         shape = (capacity - short, N, E) if self._env_last else (capacity - short, E, N)
         setattr(self, name, torch.zeros(*shape, dtype=getattr(torch, dtype), device=dev)
@@ -400,4 +442,68 @@ class CryptoEpisodeHistory(_Record):
     def rows(self, e):
         """The panel rows of env ``e``'s entries, ``start + arange(length)`` (a list for a sequence of
         envs): index your own timestamps with them."""
+        return self._frames(e, crypto_rows, "start", dates=False)
+
+
+class StockNpEpisodeHistory(_Record):
+    """Device-resident episode record of a ``VecStockTradingEnvNP`` (``env.enable_history()``): the
+    account curve of every env's episode, one entry per step, written by the step kernel itself
+    (finenv_stocknp_set_history, include/finenv.h) -- what DRLAgent.DRL_prediction
+    (agents/elegantrl/models.py:105-131) returns for the one env it runs.
+
+    Tensors (time-major; entries at or past ``length[e]`` are unspecified):
+      ``asset``   f64 [capacity, E]     total_asset after the step (env_stocktrading_np.py:137)
+      ``tag``     u8  [capacity, E]     its NumPy-2 scalar type (0 float, 1 float32, 2 float64), or None
+      ``stocks``  f32 [capacity, N, E]  holdings after the step (the state's [N, E] layout), or None
+      ``start``   i32 [E]               panel row of entry 0; entry k is panel row ``start + k``
+      ``length``  i32 [E]               entries recorded; 0 = not armed
+      ``flags``   i32 [E]               bit 0 complete, bit 1 overflow (``complete`` / ``overflow``)
+
+    Armed by the constructor (from the env's current state), by ``env.reset(mask)`` for the envs it
+    resets and by ``arm(mask)``; entry 0 is the current total asset (``initial_total_asset`` at the start
+    of an episode), its tag and the current holdings.  The terminal step is recorded -- this env trades
+    on it -- from the values before an auto-reset replaces them, and makes the record final.  An
+    auto-reset inside ``step`` does not arm: the finished episode stays readable until the next host
+    reset or ``arm``.  The pointers are launch arguments: enable the history before capturing a graph.
+    """
+
+    _ptrs_cls, metric_keys = nat.StockNpHistoryPtrs, STOCKNP_METRIC_KEYS
+    _series = (("asset", "float64"), ("tag", "uint8"))
+    _per_ticker, _env_last = ("stocks", "float32", 0), True
+    _per_env, _assets = (("start", "int32"),), "action_dim"
+
+    def __init__(self, env, capacity, stocks=True, tags=True):
+        super().__init__(env, capacity, stocks, without=() if tags else ("tag",))
+
+    def _typed(self, e, build):
+        """``build(asset, tag, length)`` per env, with ``tag`` None where it is not recorded."""
+        if self.tag is None:
+            return self._frames(e, lambda asset, n: build(asset, None, n), "asset", dates=False)
+        return self._frames(e, build, "asset", "tag", dates=False)
+
+    def account_values(self, e):
+        """The account curve of env ``e``'s recorded episode, ``asset[:length]`` -> f64 array (a list of
+        arrays for a sequence of envs)."""
+        return self._frames(e, stocknp_account_values, "asset", dates=False)
+
+    def episode_total_assets(self, e):
+        """The list DRL_prediction returns for env ``e`` (a list of lists for a sequence of envs); with
+        ``tags`` recorded every element is the scalar type the reference's list holds (``float`` /
+        ``np.float32`` / ``np.float64``), else a Python float."""
+        return self._typed(e, stocknp_episode_total_assets)
+
+    def episode_returns(self, e):
+        """``total_asset / initial_total_asset`` after every step of env ``e``'s record (models.py:124),
+        in the dtype NumPy promotes to; the reference's ``episode_returns`` when the record was armed at
+        the episode's start (a list of lists for a sequence of envs)."""
+        return self._typed(e, stocknp_episode_returns)
+
+    def positions(self, e):
+        """The holdings after every recorded entry of env ``e`` -> f32 [length, N] (a list for a sequence
+        of envs); needs ``stocks=True``."""
+        return self._frames(e, crypto_positions, "stocks", dates=False)
+
+    def rows(self, e):
+        """The panel rows of env ``e``'s entries, ``start + arange(length)`` (a list for a sequence of
+        envs): index your own dates with them."""
         return self._frames(e, crypto_rows, "start", dates=False)

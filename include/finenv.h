@@ -775,6 +775,64 @@ int  finenv_stocknp_step(finenv_stocknp *h, const float *actions, float *obs, fl
  * FINENV_ERR_INVALID for a NULL handle. */
 int finenv_stocknp_set_windows(finenv_stocknp *h, int32_t *win);
 
+/* Episode history of the array-state env: the account curve of every env's CURRENT episode, one
+ * entry per step, recorded on the device -- what DRLAgent.DRL_prediction
+ * (agents/elegantrl/models.py:105-131) returns as episode_total_assets: the env's total_asset after
+ * every step.  Opt-in and caller-owned device memory, time-major:
+ *   asset[k][e]      total_asset after the step (:137), the value as the state holds it (fp64; a
+ *                    float32 total_asset is that float32 widened)
+ *   tag[k][e]        FINENV_NT_* of that total_asset -- the NumPy-2 scalar type the reference's list
+ *                    holds at that position (Python float / np.float32 / np.float64) -- or not
+ *                    recorded (NULL)
+ *   stocks[k][i][e]  holdings of ticker i after the step (f32), or not recorded (NULL)
+ *   start[e]         panel row of entry 0; entry k belongs to panel row start[e] + k
+ *   len[e]           entries recorded so far; 0 = not armed, nothing is recorded
+ *   flags[e]         FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW, as in the stock env's history
+ * As in the crypto env's struct there is no per-entry row -- the day counter advances by exactly one
+ * panel row per step, windows included -- and stocks is [capacity][N][E], the layout of the state's
+ * books: a lane of the step kernel is an env, so every store of a wave is one contiguous 256 B.
+ * Under auto_reset the step overwrites FINENV_NF_TOTAL_ASSET with the restarted episode's value in
+ * the launch that computed the terminal one, so the record is taken INSIDE the step kernel: while a
+ * history is attached finenv_stocknp_step launches the recording instantiation of its kernel, no
+ * second launch and no further dependent load on the trading wave.  Per env, by its own counter:
+ *   - not armed (len == 0) or complete: nothing;
+ *   - else entry k = len[e]: asset[k][e] = the step's new total_asset, before any auto-reset touches
+ *     it, tag[k][e] = its dtype tag, stocks[k][i][e] = the post-trade holdings (on a turbulence day:
+ *     the zeros), len[e] = k + 1; with k == capacity nothing is written and OVERFLOW is set.  No
+ *     entry at or past `capacity` is ever written, in any tensor;
+ *   - the terminal step IS recorded -- this env trades and revalues on its last step (:103-147 has
+ *     no terminal branch) -- and then sets COMPLETE, whatever auto_reset is (also when that step
+ *     overflowed).
+ * Arming an env writes entry 0 from its current state: asset[0][e] = FINENV_NF_TOTAL_ASSET,
+ * tag[0][e] = bits 2-3 of the tags word, stocks[0][:][e] = the state's holdings, start[e] =
+ * FINENV_NI_DAY (the panel row, windows included); it sets len[e] = 1 and clears flags[e].
+ * finenv_stocknp_reset arms the envs it resets, behind the reset (with windows: on their new active
+ * window; in train mode: on the drawn start state).  An auto-reset inside step does NOT arm: the
+ * finished episode's record stays readable and the env is not recorded again until a host reset or
+ * finenv_stocknp_history_arm.
+ * The struct's pointers are LAUNCH ARGUMENTS: a step captured into a graph records only if the
+ * history was attached before the capture, and into the tensors attached then.
+ * Memory: E * (9 * capacity + 12) + 4 * E * N * capacity bytes (65,536 envs on 504-row windows of the
+ * DOW30: 0.3 GB without stocks, 4.3 GB with -- which is why stocks is optional). */
+typedef struct finenv_stocknp_history {
+    double  *asset;     /* [capacity][E]    total_asset after the step (:137), value as the state holds it */
+    uint8_t *tag;       /* [capacity][E]    FINENV_NT_* of that total_asset (NumPy-2 scalar dtype), or NULL */
+    float   *stocks;    /* [capacity][N][E] holdings after the step, or NULL                                */
+    int32_t *start;     /* [E] panel row of entry 0; entry k is panel row start[e] + k                      */
+    int32_t *len;       /* [E] entries recorded; 0 = not armed                                              */
+    int32_t *flags;     /* [E] FINENV_HIST_COMPLETE / FINENV_HIST_OVERFLOW                                  */
+    int32_t  capacity;  /* >= 2                                                                             */
+} finenv_stocknp_history;
+/* Attach a history (the struct is copied), or detach with NULL (the default).  Allowed before bind.
+ * Attaching arms nothing: zero len / flags, then finenv_stocknp_reset / _history_arm. */
+int finenv_stocknp_set_history(finenv_stocknp *h, const finenv_stocknp_history *hist);
+/* Arm every env, or those with mask[e] != 0 (device u8[E]), from its current state. */
+int finenv_stocknp_history_arm(finenv_stocknp *h, const uint8_t *mask, void *stream);
+/* Backtest figures of the recorded account values: out [E][FINENV_STOCK_HISTORY_METRICS] f64, the
+ * FINENV_HM_* columns with the stock env's convention: returns asset[k] / asset[k-1] - 1 in fp64 for
+ * k = 1 .. len-1, N_RETURNS = len - 1.  Rows of unarmed envs are NaN. */
+int finenv_stocknp_history_metrics(finenv_stocknp *h, double annualization, double *out, void *stream);
+
 /* =====================================================================================
  * StockTradingEnvCashpenalty
  * (finrl/meta/env_stock_trading/env_stocktrading_cashpenalty.py:19-409): continuous (or

@@ -1,17 +1,18 @@
 #!/usr/bin/env python3
-"""Cost of the episode history (enable_history) of the batched stock, portfolio or crypto env on
-bench.py's workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows (crypto:
-10 pairs x 40 indicator columns, 1,440-row windows, --envs 32768 / 65536 / 262144).  ONE process, ONE
+"""Cost of the episode history (enable_history) of the batched stock, portfolio, crypto or array-state
+stock env on bench.py's workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows
+(crypto: 10 pairs x 40 indicator columns, 1,440-row windows, --envs 32768 / 65536 / 262144; stocknp:
+64-row windows -- that env is done one step earlier, and the timed steps stay the same).  ONE process, ONE
 env; the variants alternate inside every round, each timed with HIP events over steps that all record:
   a  history detached (the step path of a build without the feature)
   b  history attached without the per-ticker tensor (actions=False / weights=False)
        stock +12 B written per env and step; portfolio +20 B written, 8 B read; crypto +16 B
-       written, 8 B read
+       written, 8 B read; stocknp +13 B written (asset, tag, len), 8 B read
   c  history attached with it: stock +12 + 4N B (the step kernel also writes `realised`);
-       portfolio +20 + 4N B written; crypto +16 + 4N B written
+       portfolio +20 + 4N B written; crypto +16 + 4N B written; stocknp +13 + 4N B written
   d  history detached, the host copy the history replaces after every step: one state_numpy()
      (portfolio: and one weights.cpu())
-usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio|crypto]
+usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio|crypto|stocknp]
                                       [--variants a,b,c,d] [--rounds R] [--envs E] [--json PATH]
   lockstep  every env on the window [0, 63): one record row per step, written contiguously
   desync    random 63-day windows (stock: with hint_desynchronised(True)) and a random half of the envs
@@ -26,7 +27,7 @@ FINENV_LIB=<libfinenv.so of another build> times that build; one without the his
 can run variant a only (that is how a commit before the feature is measured with this same script).
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/bench_history.py lockstep --variants c` the
 kernel stats give stock_history_record_kernel's own time (record_bytes() below is what it moves);
-with `--env portfolio` / `--env crypto`, the recording instantiation's of the step kernel."""
+with `--env portfolio` / `--env crypto` / `--env stocknp`, the recording instantiation's of the step kernel."""
 import argparse
 import ctypes as C
 import json
@@ -50,7 +51,7 @@ def record_bytes(N, actions):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("case", choices=("lockstep", "desync"))
-    ap.add_argument("--env", choices=("stock", "portfolio", "crypto"), default="stock")
+    ap.add_argument("--env", choices=("stock", "portfolio", "crypto", "stocknp"), default="stock")
     ap.add_argument("--variants", default="a,b,c,d")
     ap.add_argument("--rounds", type=int, default=0)
     ap.add_argument("--envs", type=int, default=65536)
@@ -68,10 +69,10 @@ def main():
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=False, no_stats=False,
                               env=o.env, tickers=30, turbulence_pct=None))()
     w = bench.build_workload(args, torch, dev, 0)
-    stock, crypto = o.env == "stock", o.env == "crypto"
-    env, N = w.env, w.env.crypto_num if crypto else w.env.stock_dim
-    window = CRYPTO_WINDOW if crypto else WINDOW
-    rows = env.price_array.shape[0] if crypto else env.panel.T
+    stock, crypto, stocknp = o.env == "stock", o.env == "crypto", o.env == "stocknp"
+    env, N = w.env, w.env.action_dim if crypto or stocknp else w.env.stock_dim
+    window = CRYPTO_WINDOW if crypto else WINDOW + stocknp
+    rows = env.price_array.shape[0] if crypto else env.price_ary.shape[0] if stocknp else env.panel.T
     has_api = hasattr(nat.lib(), f"finenv_{o.env}_set_history")
     if not has_api and variants != ["a"]:
         sys.exit(f"bench_history: this libfinenv.so has no {o.env} history; it can run --variants a only")
@@ -94,10 +95,11 @@ def main():
             if v in variants:
                 hists[v] = H.EpisodeHistory(env, WINDOW, actions=per_ticker) if stock else \
                     H.CryptoEpisodeHistory(env, CRYPTO_CAPACITY, stocks=per_ticker) if crypto else \
+                    H.StockNpEpisodeHistory(env, window, stocks=per_ticker) if stocknp else \
                     H.PortfolioEpisodeHistory(env, WINDOW, weights=per_ticker)
     # the step's optional per-ticker output: stock `realised`, enabled by variant c's history and passed
     # to its steps only; portfolio `weights`, variant d's host copy
-    # (the crypto step has no such output)
+    # (the crypto and stocknp steps have no such output)
     extra, extra_v = ("realised", "c") if stock else ("weights", "d")
     if o.env == "portfolio" and "d" in variants:
         env.enable_weights()
@@ -106,7 +108,7 @@ def main():
     def select(v):
         if has_api:
             env._call("set_history", C.byref(hists[v]._ptrs) if v in hists else None)
-        if not crypto:
+        if not (crypto or stocknp):
             setattr(env, extra, extra_out if v == extra_v else None)
         env._step_args = None                   # BatchedEnv.step caches the output pointers
 
@@ -153,6 +155,9 @@ def main():
         res["record_kernel_bytes_per_env_step"] = {"b": record_bytes(N, False), "c": record_bytes(N, True)}
     elif crypto:
         res["added_bytes_written_per_env_step"] = {"b": 16, "c": 16 + 4 * N}
+        res["added_bytes_read_per_env_step"] = {"b": 8, "c": 8}
+    elif stocknp:
+        res["added_bytes_written_per_env_step"] = {"b": 13, "c": 13 + 4 * N}
         res["added_bytes_read_per_env_step"] = {"b": 8, "c": 8}
     else:
         res["added_bytes_written_per_env_step"] = {"b": 20, "c": 20 + 4 * N}
