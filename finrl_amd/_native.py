@@ -278,7 +278,8 @@ def lib():
                     ("finenv_portfolio_set_last_episode", 2),
                     ("finenv_portfolio_last_episode_stats", 3), ("finenv_stock_set_windows", 2),
                     ("finenv_portfolio_set_windows", 2), ("finenv_crypto_set_windows", 3),
-                    ("finenv_stocknp_set_windows", 2)):
+                    ("finenv_stocknp_set_windows", 2), ("finenv_cashpenalty_set_windows", 2),
+                    ("finenv_stoploss_set_windows", 2)):
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
     for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs),

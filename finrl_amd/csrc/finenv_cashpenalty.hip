@@ -58,8 +58,9 @@ __device__ __forceinline__ double cp_reward(const finenv_cashpenalty_config &c, 
 // (launch bounds: four 2-wave blocks per CU = two waves per SIMD, i.e. at most 256 VGPRs -- at
 //  65,536 envs every block of the grid is then resident at once; DISCRETE = cfg.discrete_actions as
 //  a template flag: with both transaction formulas in one body the step kernel was 66 KB, over the
-//  64 KB instruction cache two CUs share)
-template <bool RESET_ONLY, int NCH, bool DISCRETE>
+//  64 KB instruction cache two CUs share; WIN = per-env episode windows, finenv_cashpenalty_set_windows:
+//  the helpers in finenv_twowave.h)
+template <bool RESET_ONLY, int NCH, bool DISCRETE, bool WIN>
 __global__ void __launch_bounds__(kWave *kWaves) __attribute__((amdgpu_waves_per_eu(2)))
 cashpenalty_kernel(const CpParams p)
 {
@@ -80,9 +81,9 @@ cashpenalty_kernel(const CpParams p)
     if (RESET_ONLY) {                                                          // :131-157
         if (role != 0) return;
         const bool sel = valid && (p.mask == nullptr || p.mask[e] != 0);
-        const int start = p.rs_hi > 0 ? draw_start(p.rs_seed, e, KI(FINENV_KI_EPISODE) + 1, p.rs_hi)
-                                      : KI(FINENV_KI_NEXT_START);
+        const int start = TW_NEXT_START(WIN, KI(FINENV_KI_EPISODE), KI(FINENV_KI_NEXT_START));
         if (sel) {
+            tw_win_promote<WIN>(p, e);
             KI(FINENV_KI_START) = start;
             KI(FINENV_KI_DATE_INDEX) = start;
             KI(FINENV_KI_EPISODE) += 1;
@@ -107,12 +108,11 @@ cashpenalty_kernel(const CpParams p)
         if (NCH == 0) return;                 // rows wider than 320 columns: the trader writes them
         STAMP64(8);
         const int W = p.D - 1 - N;
-        const int di_s = KI(FINENV_KI_DATE_INDEX);
-        const bool last = di_s == c.n_days - 1;                                   // :299
+        const int di_s = tw_date<WIN>(p, KI(FINENV_KI_DATE_INDEX));
+        const bool last = tw_last_date<WIN>(di_s, tw_win_end<WIN>(p, e));         // :299
         int ns = 0;
         if (p.auto_reset && __any(last))
-            ns = p.rs_hi > 0 ? draw_start(p.rs_seed, e, KI(FINENV_KI_EPISODE) + 1, p.rs_hi)
-                             : KI(FINENV_KI_NEXT_START);
+            ns = TW_NEXT_START(WIN, KI(FINENV_KI_EPISODE), KI(FINENV_KI_NEXT_START));
         // the row the next observation shows unless a cash shortage ends the episode here
         const int row_spec = last ? (p.auto_reset ? ns : di_s) : di_s + 1;
         tw_gather_closes(trl, p, di_s, lane);
@@ -205,8 +205,9 @@ cashpenalty_kernel(const CpParams p)
 
     STAMP64(0);
     // ---- round trip 1: per-env scalars (the action tile is issued behind them) ----------------
-    int di = KI(FINENV_KI_DATE_INDEX);
+    int di = tw_date<WIN>(p, KI(FINENV_KI_DATE_INDEX));
     const int start = KI(FINENV_KI_START);
+    const int end = tw_win_end<WIN>(p, e);
     double coh = KF(FINENV_KF_COH);
     double turb = c.use_turbulence ? KF(FINENV_KF_TURBULENCE) : 0.0;
     double sum_trades = KF(FINENV_KF_SUM_TRADES);
@@ -219,7 +220,7 @@ cashpenalty_kernel(const CpParams p)
     for (int i = 0; i < kMaxN; ++i) hb[i] = KH(min(i, N - 1));
     stage_action_tile(rows, kRow, p.actions + (size_t)e0 * N, nenv_w, N, p.magicN, lane);
     const int step = di - start;                                                 // current_step
-    const bool at_end = di == c.n_days - 1;                                      // :299
+    const bool at_end = tw_last_date<WIN>(di, end);                              // :299
     // closes: every env sits on its own date (random starts), so a per-lane load touches 64
     // different rows per instruction.  Row-wise instead: lane i < N loads close[date_el][i] for one
     // env el per instruction (one 8N-byte segment), all 64 rows in flight, parked in LDS [el][i];
@@ -317,8 +318,7 @@ cashpenalty_kernel(const CpParams p)
     // terminal step, or the new starting point on an auto-reset ----------------------------------
     int ns_reset = 0;
     if (p.auto_reset && __any(done))
-        ns_reset = p.rs_hi > 0 ? draw_start(p.rs_seed, e, KI(FINENV_KI_EPISODE) + 1, p.rs_hi)
-                               : KI(FINENV_KI_NEXT_START);
+        ns_reset = TW_NEXT_START(WIN, KI(FINENV_KI_EPISODE), KI(FINENV_KI_NEXT_START));
     const int row_final = done ? (p.auto_reset ? ns_reset : di) : di + 1;
     if (NCH > 0) {                            // publish (LDS is in-order per wave: rows first, then the flag)
         decided[lane] = row_final;
@@ -372,6 +372,7 @@ cashpenalty_kernel(const CpParams p)
                     row[1 + i] = 0.0f;
                 }
                 if (valid) {
+                    tw_win_promote<WIN>(p, e);
                     KI(FINENV_KI_START) = ns;
                     KI(FINENV_KI_EPISODE) += 1;
                     KF(FINENV_KF_SUM_TRADES) = 0.0;
@@ -404,8 +405,8 @@ struct finenv_cashpenalty : TwoWaveHandle<finenv_cashpenalty_config, finenv_cash
 namespace {
 // every step kernel runs one block per 64 envs: the wide form (NCH = 0) leaves its second wave idle
 struct CpKernels {
-    template <int NCH, bool DISCRETE>
-    static constexpr auto step() { return &cashpenalty_kernel<false, NCH, DISCRETE>; }
+    template <int NCH, bool DISCRETE, bool WIN>
+    static constexpr auto step() { return &cashpenalty_kernel<false, NCH, DISCRETE, WIN>; }
     static dim3 wide_grid(int E) { return tw_grid(E); }
 };
 }  // namespace
@@ -437,6 +438,8 @@ int finenv_cashpenalty_set_random_start(finenv_cashpenalty *h, int32_t hi, uint6
 
 int finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit) { return tw_set_audit(h, audit); }
 
+int finenv_cashpenalty_set_windows(finenv_cashpenalty *h, int32_t *win) { return tw_set_windows(h, win); }
+
 int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *obs_out,
                              void *stream)
 {
@@ -445,8 +448,9 @@ int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *
     CpParams p = tw_params<CpParams>(h);
     p.mask = mask;
     p.obs = obs_out;
-    hipLaunchKernelGGL((cashpenalty_kernel<true, 0, false>), tw_grid(h->cfg.n_envs), dim3(kWave * kWaves),
-                       0, (hipStream_t)stream, p);
+    const auto reset = p.win != nullptr ? &cashpenalty_kernel<true, 0, false, true>
+                                        : &cashpenalty_kernel<true, 0, false, false>;
+    hipLaunchKernelGGL(reset, tw_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0, (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "cashpenalty_reset");
 }
 

@@ -50,7 +50,7 @@ constexpr int kL2Close = kClStride * kWave * 2;                // f64 closes [el
 constexpr int kL2Trx = (kMaxN - kHalf) * kWave * 2;            // f64 transactions of assets >= kHalf [i][lane]
 constexpr int kL2Misc = 6 * kWave + 2;                         // decided, eflags, aflags, ntr (f64), flag
 constexpr int kLds2 = kL2Rows + kL2Close + kL2Trx + kL2Misc;
-static_assert(kLds2 * 4 * 4 <= 160 * 1024, "four blocks per CU");
+static_assert((kLds2 + kWave) * 4 * 4 <= 160 * 1024, "four blocks per CU");
 constexpr int kFix = 4;                        // re-decided rows per block the streamer patches in registers
 static_assert(kWave * kWave <= kL2Close, "the parked chunk 0 reuses the close rows");
 
@@ -73,8 +73,9 @@ __device__ __forceinline__ double sl_reward(const finenv_stoploss_config &c, int
     return r;
 }
 
-// The one-wave kernel: reset, and steps whose observation rows are wider than 320 columns.
-template <bool RESET_ONLY>
+// The one-wave kernel: reset, and steps whose observation rows are wider than 320 columns.  (WIN =
+// per-env episode windows, finenv_stoploss_set_windows: the helpers in finenv_twowave.h)
+template <bool RESET_ONLY, bool WIN>
 __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlParams p)
 {
     __shared__ __attribute__((aligned(16))) float lds_all[kWaves * kLdsPerWave];
@@ -92,9 +93,9 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
 
     if (RESET_ONLY) {                                                          // :134-165
         const bool sel = valid && (p.mask == nullptr || p.mask[e] != 0);
-        const int start = p.rs_hi > 0 ? draw_start(p.rs_seed, e, LI(FINENV_LI_EPISODE) + 1, p.rs_hi)
-                                      : LI(FINENV_LI_NEXT_START);
+        const int start = TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
         if (sel) {
+            tw_win_promote<WIN>(p, e);
             LI(FINENV_LI_START) = start;
             LI(FINENV_LI_DATE_INDEX) = start;
             LI(FINENV_LI_EPISODE) += 1;
@@ -114,15 +115,16 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
 
     // ---- action tile -> LDS rows --------------------------------------------------------------
     stage_action_tile(rows, kRow, p.actions + (size_t)e0 * N, nenv_w, N, p.magicN, lane);
-    int di = LI(FINENV_LI_DATE_INDEX);
+    int di = tw_date<WIN>(p, LI(FINENV_LI_DATE_INDEX));
     const int start = LI(FINENV_LI_START);
+    const int end = tw_win_end<WIN>(p, e);
     double coh = LF(FINENV_LF_COH);
     double turb = c.use_turbulence ? LF(FINENV_LF_TURBULENCE) : 0.0;
     double sum_trades = LF(FINENV_LF_SUM_TRADES);
     double logged_total = LF(FINENV_LF_LOGGED_TOTAL), logged_cash = LF(FINENV_LF_LOGGED_CASH);
     double actual_num_trades = LF(FINENV_LF_ACTUAL_NUM_TRADES);
     const int step = di - start;                                                 // current_step
-    const bool at_end = di == c.n_days - 1;                                      // :302
+    const bool at_end = tw_last_date<WIN>(di, end);                              // :302
     const unsigned cb = (unsigned)(di * N);
     wave_sync();
 
@@ -335,8 +337,7 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
         if (p.auto_reset) {                                                      // reset()
             wave_sync();
             if (done) {
-                const int ns = p.rs_hi > 0 ? draw_start(p.rs_seed, e, LI(FINENV_LI_EPISODE) + 1, p.rs_hi)
-                                           : LI(FINENV_LI_NEXT_START);
+                const int ns = TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
                 di = ns;
                 row_day = ns;
                 coh = c.initial_amount;
@@ -345,6 +346,7 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
                 for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
                 if (valid) {
                     for (int i = 0; i < FINENV_STOPLOSS_BOOKS * N; ++i) LV(0, i) = 0.0;
+                    tw_win_promote<WIN>(p, e);
                     LI(FINENV_LI_START) = ns;
                     LI(FINENV_LI_EPISODE) += 1;
                     LF(FINENV_LF_SUM_TRADES) = 0.0;
@@ -389,11 +391,14 @@ __device__ __forceinline__ SlBook sl_update(const finenv_stoploss_config &c, dou
     return b;
 }
 
-template <int NCH, bool DISCRETE>
+template <int NCH, bool DISCRETE, bool WIN>
 __global__ void __launch_bounds__(kWave *kWaves) __attribute__((amdgpu_waves_per_eu(2)))
 stoploss_step2_kernel(const SlParams p)
 {
-    __shared__ __attribute__((aligned(16))) float lds_all[kLds2];
+    // (WIN: + [lane] the active ends, which the streamer loads beside its date index and hands to the
+    //  trader over the staging barrier: the trader has no register to spare)
+    __shared__ __attribute__((aligned(16))) float lds_all[kLds2 + (WIN ? kWave : 0)];
+    int *const wend = reinterpret_cast<int *>(lds_all + kLds2);
     const int lane = threadIdx.x & (kWave - 1);
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float *rows = lds_all;
@@ -417,12 +422,13 @@ stoploss_step2_kernel(const SlParams p)
     if (role != 0) {
         // ================================ streamer ===============================================
         STAMP64(8);
-        const int di_s = LI(FINENV_LI_DATE_INDEX);
-        const bool last = di_s == c.n_days - 1;                                   // :302
+        const int di_s = tw_date<WIN>(p, LI(FINENV_LI_DATE_INDEX));
+        const int end_s = tw_win_end<WIN>(p, e);
+        const bool last = tw_last_date<WIN>(di_s, end_s);                         // :302
+        if (WIN) wend[lane] = end_s;
         int ns = 0;
         if (p.auto_reset && __any(last))
-            ns = p.rs_hi > 0 ? draw_start(p.rs_seed, e, LI(FINENV_LI_EPISODE) + 1, p.rs_hi)
-                             : LI(FINENV_LI_NEXT_START);
+            ns = TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
         // the row the next observation shows unless a cash shortage ends the episode here
         const int row_spec = last ? (p.auto_reset ? ns : di_s) : di_s + 1;
         tw_gather_closes(trl, p, di_s, lane);
@@ -547,7 +553,7 @@ stoploss_step2_kernel(const SlParams p)
 
     // ==================================== trader =================================================
     STAMP64(0);
-    int di = LI(FINENV_LI_DATE_INDEX);
+    int di = tw_date<WIN>(p, LI(FINENV_LI_DATE_INDEX));
     const int start = LI(FINENV_LI_START);
     double coh = LF(FINENV_LF_COH);
     double turb = c.use_turbulence ? LF(FINENV_LF_TURBULENCE) : 0.0;
@@ -556,8 +562,9 @@ stoploss_step2_kernel(const SlParams p)
     double actual_num_trades = LF(FINENV_LF_ACTUAL_NUM_TRADES);
     stage_action_tile(rows, kRow, p.actions + (size_t)e0 * N, nenv_w, N, p.magicN, lane);
     const int step = di - start;                                                 // current_step
-    const bool at_end = di == c.n_days - 1;                                      // :302
+    bool at_end = tw_last_date<false>(di, c.n_days);                             // :302
     lds_barrier();                            // staging barrier: close rows gathered by the streamer
+    if (WIN) at_end = tw_last_date<WIN>(di, wend[lane]);                         // (its active ends too)
     STAMP64(1);
 
     double slp_sum = 0.0, lpp_sum = 0.0, add = 0.0;
@@ -687,8 +694,7 @@ stoploss_step2_kernel(const SlParams p)
     // ---- the decision is published (LDS is in-order per wave: data first, then the flag) --------
     int ns_reset = 0;
     if (p.auto_reset && __any(done))
-        ns_reset = p.rs_hi > 0 ? draw_start(p.rs_seed, e, LI(FINENV_LI_EPISODE) + 1, p.rs_hi)
-                               : LI(FINENV_LI_NEXT_START);
+        ns_reset = TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
     const int row_final = done ? (p.auto_reset ? ns_reset : di) : di + 1;
     decided[lane] = row_final;
     eflags[lane] = (advance ? 1 : 0) | (keep_buys ? 2 : 0) | (at_end ? 4 : 0);
@@ -776,6 +782,7 @@ stoploss_step2_kernel(const SlParams p)
                 for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
                 if (valid) {
                     for (int i = 0; i < FINENV_STOPLOSS_BOOKS * N; ++i) LV(0, i) = 0.0;
+                    tw_win_promote<WIN>(p, e);
                     LI(FINENV_LI_START) = ns_reset;
                     LI(FINENV_LI_EPISODE) += 1;
                     LF(FINENV_LF_SUM_TRADES) = 0.0;
@@ -810,11 +817,11 @@ dim3 sl_grid(int E)
 }
 // rows of up to 320 columns: the two-wave kernel; wider rows: the one-wave kernel, two 64-env groups per block
 struct SlKernels {
-    template <int NCH, bool DISCRETE>
+    template <int NCH, bool DISCRETE, bool WIN>
     static constexpr auto step()
     {
-        if constexpr (NCH == 0) return &stoploss_kernel<false>;
-        else return &stoploss_step2_kernel<NCH, DISCRETE>;
+        if constexpr (NCH == 0) return &stoploss_kernel<false, WIN>;
+        else return &stoploss_step2_kernel<NCH, DISCRETE, WIN>;
     }
     static dim3 wide_grid(int E) { return sl_grid(E); }
 };
@@ -848,6 +855,8 @@ int finenv_stoploss_set_random_start(finenv_stoploss *h, int32_t hi, uint64_t se
 
 int finenv_stoploss_set_audit(finenv_stoploss *h, double *audit) { return tw_set_audit(h, audit); }
 
+int finenv_stoploss_set_windows(finenv_stoploss *h, int32_t *win) { return tw_set_windows(h, win); }
+
 int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream)
 {
     if (const int rc = finenv_host::ready(h, "reset")) return rc;
@@ -855,8 +864,8 @@ int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_ou
     SlParams p = tw_params<SlParams>(h);
     p.mask = mask;
     p.obs = obs_out;
-    hipLaunchKernelGGL((stoploss_kernel<true>), sl_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0,
-                       (hipStream_t)stream, p);
+    const auto reset = p.win != nullptr ? &stoploss_kernel<true, true> : &stoploss_kernel<true, false>;
+    hipLaunchKernelGGL(reset, sl_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0, (hipStream_t)stream, p);
     return finenv_host::check_launch(h, "stoploss_reset");
 }
 

@@ -36,7 +36,86 @@ struct TwoWaveParams {
     unsigned long long rs_seed;
     double *audit;                  // optional [E][FINENV_AUDIT_HEAD + N] per-step log row, or NULL
     unsigned long long *dbg;        // FINENV_DIAG builds only: [block][16] s_memrealtime stamps
+    // finenv_<kind>_set_windows (the WIN instantiations; NULL otherwise).  Last member: every other
+    // kernel argument keeps its offset
+    int32_t *win;                   // [4][E]: pending start / end, active start / end
 };
+
+// ---- per-env episode windows (finenv_<kind>_set_windows) -------------------------------------
+// WIN: env e runs the ACTIVE window [s_e, t_e) = win[2][e], win[3][e] of panel rows; a reset (host or
+// auto) first copies the PENDING window win[0][e], win[1][e] into the active rows and starts the env
+// inside it.  Every value read from the block is clamped into the panel, and so is the date index:
+// bad device-side content is a wrong answer, never an access outside the panel or the state.
+#define TWWIN(r) (*at(p.win, (unsigned)(r) * (unsigned)p.cfg.n_envs + (unsigned)e))
+
+// the active window's end t_e, in [1, n_days]; without windows: n_days
+template <bool WIN, class P>
+__device__ __forceinline__ int tw_win_end(const P &p, int e)
+{
+    if (!WIN) return p.cfg.n_days;
+    return min(max(TWWIN(3), 1), p.cfg.n_days);
+}
+
+// the pending window: s in [0, n_days - 1], t in [s + 1, n_days]; without windows: the panel
+template <bool WIN, class P>
+__device__ __forceinline__ void tw_win_pending(const P &p, int e, int *s, int *t)
+{
+    *s = 0;
+    *t = p.cfg.n_days;
+    if (!WIN) return;
+    *s = min(max(TWWIN(0), 0), p.cfg.n_days - 1);
+    *t = min(max(TWWIN(1), *s + 1), p.cfg.n_days);
+}
+
+// the date index as the state holds it; WIN: clamped into the panel
+template <bool WIN, class P>
+__device__ __forceinline__ int tw_date(const P &p, int di)
+{
+    return WIN ? min(max(di, 0), p.cfg.n_days - 1) : di;
+}
+
+// "last date" of the episode, `end` = tw_win_end().  (WIN: >=, so that a date index past a window
+// that bad content made shorter never advances out of the panel)
+template <bool WIN>
+__device__ __forceinline__ bool tw_last_date(int di, int end)
+{
+    return WIN ? di >= end - 1 : di == end - 1;
+}
+
+// The one starting-point rule of a reset (finenv_<kind>_reset, the auto-reset inside step and the
+// streamer's speculation of it): tw_next_start<WIN>(p, e, episode, next_start), where `episode` and
+// `next_start` are the kernel's own expressions for the env's episode counter and NEXT_START -- only
+// the one the rule uses is evaluated, i.e. loaded.  random_start (rs_hi > 0) draws from the first half
+// of the frame's dates (:134-138); WIN: of the PENDING window [s, t), which tw_win_promote() makes the
+// active one when the env is reset -- s + draw in [0, max(1, (t - s) >> 1)), only the sign of rs_hi
+// is read; else s + NEXT_START as an offset from the window's first row, clamped into the window.
+// (A macro around the WIN form: in a kernel scope with p and e, the no-window arm is then the
+//  expression these kernels always had, and compiles to the same instructions.)
+#define TW_NEXT_START(WIN, episode, next_start)                                                    \
+    (!(WIN) ? (p.rs_hi > 0 ? draw_start(p.rs_seed, e, (episode) + 1, p.rs_hi) : (next_start))     \
+            : tw_next_start_win(p, e, [&]() { return episode; }, [&]() { return next_start; }))
+template <class P, class Episode, class NextStart>
+__device__ __forceinline__ int tw_next_start_win(const P &p, int e, Episode episode, NextStart next_start)
+{
+    int s, t;
+    tw_win_pending<true>(p, e, &s, &t);
+    const int len = t - s;
+    return s + (p.rs_hi > 0 ? draw_start(p.rs_seed, e, episode() + 1, max(1, len >> 1))
+                            : min(max(next_start(), 0), len - 1));
+}
+
+// pending -> active, by the lane that owns env e, in the once-per-episode branch that resets it (the
+// pair tw_next_start() read in this launch, loaded again beside the episode counter that branch
+// increments rather than held in two registers across the step)
+template <bool WIN, class P>
+__device__ __forceinline__ void tw_win_promote(const P &p, int e)
+{
+    if (!WIN) return;
+    int s, t;
+    tw_win_pending<WIN>(p, e, &s, &t);
+    TWWIN(2) = s;
+    TWWIN(3) = t;
+}
 
 // rows[el*kRow + 0] = f32 cash, rows[el*kRow + 1 + i] = f32 holdings_i; columns > N: info row
 template <bool kCompact = false, class P>
@@ -117,6 +196,7 @@ struct TwoWaveHandle : finenv_host::Handle {
     Panel panel;
     State st;
     uint32_t magicN;
+    int32_t *win;                   // finenv_<kind>_set_windows
 };
 
 // the kernel argument as the handle fills it; the entry point adds its own pointers
@@ -133,6 +213,7 @@ P tw_params(const H *h)
     p.rs_hi = h->rs_hi;
     p.rs_seed = h->rs_seed;
     p.audit = h->audit;
+    p.win = h->win;
     return p;
 }
 
@@ -186,21 +267,36 @@ int tw_set_audit(H *h, double *audit)
     return FINENV_OK;
 }
 
+template <class H>
+int tw_set_windows(H *h, int32_t *win)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    h->win = win;
+    return FINENV_OK;
+}
+
 inline dim3 tw_grid(int E) { return dim3((unsigned)((E + kWaveSize - 1) / kWaveSize)); }   // one block per 64 envs
 
 template <class K, int NCH, class P>
 void tw_launch(const P &p, dim3 grid, hipStream_t stream)
 {
     const dim3 block(2 * kWaveSize);
-    if (p.cfg.discrete_actions)
-        hipLaunchKernelGGL((K::template step<NCH, true>()), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((K::template step<NCH, false>()), grid, block, 0, stream, p);
+    if (p.win != nullptr) {                   // a window block is attached
+        if (p.cfg.discrete_actions)
+            hipLaunchKernelGGL((K::template step<NCH, true, true>()), grid, block, 0, stream, p);
+        else
+            hipLaunchKernelGGL((K::template step<NCH, false, true>()), grid, block, 0, stream, p);
+    } else if (p.cfg.discrete_actions) {
+        hipLaunchKernelGGL((K::template step<NCH, true, false>()), grid, block, 0, stream, p);
+    } else {
+        hipLaunchKernelGGL((K::template step<NCH, false, false>()), grid, block, 0, stream, p);
+    }
 }
 
-// finenv_<kind>_step.  K names the env's kernels: K::step<NCH, DISCRETE>() with NCH 1 = rows of one
+// finenv_<kind>_step.  K names the env's kernels: K::step<NCH, DISCRETE, WIN>() with NCH 1 = rows of one
 // chunk, 2 = rows of up to 320 columns (the streamer copies the market data as 16-byte quads), 0 = wider
-// rows (one-wave form, on K::wide_grid(E) blocks); DISCRETE = cfg.discrete_actions.
+// rows (one-wave form, on K::wide_grid(E) blocks); DISCRETE = cfg.discrete_actions; WIN = a window
+// block is attached.
 template <class K, class P, class H>
 int tw_step(H *h, const float *actions, float *obs, float *reward, uint8_t *done, float *term_obs,
             int32_t auto_reset, void *stream, const char *what)

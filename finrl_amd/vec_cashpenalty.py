@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _native as nat
 from .spaces import Box
-from .vec_base import BatchedEnv
+from .vec_base import WindowedEnv
 
 
 class CashPenaltyPanel:
@@ -42,7 +42,12 @@ class CashPenaltyPanel:
         return cls(close, info, turb, dates, assets)
 
 
-class VecCashPenaltyEnv(BatchedEnv):
+class VecCashPenaltyEnv(WindowedEnv):
+    """``windows=(start, end)`` gives every env its own episode window of panel rows ``[start, end)``
+    (one value or ``[E]`` each): env ``e`` then equals the reference env built on the frame restricted
+    to ``dates[start_e:end_e]`` -- a train env and a trade env, ensemble validation windows or random
+    training windows, in ONE batch over one panel.  ``state["date_index"]`` and ``state["start"]`` stay
+    panel rows; ``window_day()`` is the reference's ``self.date_index``.  See ``set_windows``."""
     env_name = "StockTradingEnvCashpenalty-MI355X"
     if_discrete = False
     _kind = "cashpenalty"
@@ -60,7 +65,7 @@ class VecCashPenaltyEnv(BatchedEnv):
     def __init__(self, panel: CashPenaltyPanel, num_envs, *, buy_cost_pct=3e-3, sell_cost_pct=3e-3,
                  hmax=10, discrete_actions=False, shares_increment=1, turbulence_threshold=None,
                  initial_amount=1e6, cash_penalty_proportion=0.1, random_start=True, patient=False,
-                 auto_reset=True, device="cuda", seed=0, **extra):
+                 auto_reset=True, device="cuda", seed=0, windows=None, **extra):
         import torch
         self._set_device(device)
         self.panel = panel
@@ -70,6 +75,7 @@ class VecCashPenaltyEnv(BatchedEnv):
         self.state_dim = self.state_space = panel.D
         self.random_start = bool(random_start)
         self.auto_reset = bool(auto_reset)
+        self.max_step = T - 1
         self.observation_space = Box(-np.inf, np.inf, (panel.D,), np.float32)
         self.action_space = Box(-1, 1, (N,), np.float32)
         self._seed, self._rs_on_device = int(seed) & (2 ** 63 - 1), False
@@ -88,6 +94,39 @@ class VecCashPenaltyEnv(BatchedEnv):
         self._bind(self._close, self._info, self._turb)
         self._alloc_outputs(E, panel.D)
         self.audit = None
+        if windows is not None:                       # attached before the first reset(), which puts
+            self.set_windows(*self._check_windows(*windows))          # every env on its window
+
+    # ------------------------------------------------------------------ episode windows
+    _window_active = True                             # pending / active rows, as the crypto env
+    _window_min = 1                                   # the n_days rule of finenv_<kind>_create
+
+    def set_windows(self, start, end=None, mask=None):
+        """Per-env episode windows [start, end) of panel rows (finenv_<kind>_set_windows), with the
+        arguments, validation and device-tensor rules of ``WindowedEnv.set_windows``; a one-row
+        window is legal (its first step ends at the last date).  ``set_windows(None)`` detaches.
+
+        ``self.windows`` holds the PENDING windows: an env takes its pair at its next reset
+        (``reset()`` for the envs it selects, or the auto-reset inside ``step``), whatever is
+        written here meanwhile; the running episodes' windows are in ``self.active_windows``
+        (kernel-owned, read-only for the caller).  So windows can be redrawn for the envs that just
+        reported ``done`` with no reset launch, also inside a captured graph::
+
+            obs, rew, done, _ = env.step(actions)          # auto-reset: took the pending windows
+            env.set_windows(*random_windows(T, E, L, device=dev), mask=done)   # for the one after
+
+        A reset starts env ``e`` inside its new window ``[s, t)``: with ``random_start`` on
+        ``s + draw`` in ``[s, s + max(1, (t - s) // 2))``, else on ``s + next_start`` (see
+        ``set_next_start``).  Attaching windows to a running batch leaves every env on the whole
+        panel until its next reset.  ``max_step`` is that of the longest pending window."""
+        return super().set_windows(start, end, mask)
+
+    def window_day(self):
+        """The reference's ``self.date_index`` of every env (int32 [E], device): the panel row
+        minus the start row of the window its episode runs on."""
+        if self.active_windows is None:
+            return self.state["date_index"]
+        return self.state["date_index"] - self.active_windows[0]
 
     def enable_audit(self):
         """Per-step harness log rows [E, AUDIT_HEAD + N] f64 (begin cash, asset value, reward,
@@ -102,14 +141,19 @@ class VecCashPenaltyEnv(BatchedEnv):
 
     def set_next_start(self, starts):
         """Starting points the next reset of each env will use (the reference draws
-        random.choice(range(int(len(dates) * 0.5))), :134-138)."""
+        random.choice(range(int(len(dates) * 0.5))), :134-138).  Panel rows; with windows attached
+        OFFSETS from the first row of each env's pending window (the reference's starting point on
+        the env's own slice), clamped into the window by the kernel."""
         import torch
         self.state["next_start"].copy_(torch.as_tensor(
             np.broadcast_to(np.asarray(starts, np.int32), (self.num_envs,)).copy()))
 
     def _draw_starts(self):
         """random_start: resets draw their starting point on the device (set once; no host work
-        per step).  `set_next_start()` + random_start=False pins them for reproducible runs."""
+        per step).  `set_next_start()` + random_start=False pins them for reproducible runs.
+        With windows attached the `hi` passed here only switches the draw on: env e then draws in
+        [0, max(1, (t_e - s_e) // 2)) of the window it is reset onto -- int(len(dates) * 0.5) of
+        its own slice -- and starts on s_e + draw."""
         if not self._rs_on_device:
             hi = max(1, int(self.panel.T * 0.5))                                   # :134-138
             self._call("set_random_start", hi, int(self._seed))

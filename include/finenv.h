@@ -866,7 +866,10 @@ enum { FINENV_KF_COH = 0, FINENV_KF_TURBULENCE, FINENV_KF_SUM_TRADES, FINENV_KF_
        FINENV_KF_LOGGED_CASH, FINENV_CASHPENALTY_F64_FIELDS /* then holdings[N][E] */ };
 enum { FINENV_KI_DATE_INDEX = 0, FINENV_KI_START, FINENV_KI_EPISODE,
        FINENV_KI_NEXT_START,      /* starting point the next reset() uses (random_start: the
-                                     caller refills it; the reference draws it with `random`) */
+                                     caller refills it; the reference draws it with `random`).
+                                     A panel row; with a window block attached
+                                     (finenv_cashpenalty_set_windows) an OFFSET from the first
+                                     row of the env's pending window, clamped into the window */
        FINENV_CASHPENALTY_I32_FIELDS };
 typedef struct finenv_cashpenalty_state {
     double  *f64;                 /* [FINENV_CASHPENALTY_F64_FIELDS + N][E]                */
@@ -886,7 +889,10 @@ int  finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float 
 /* random_start (:134-138: `random.choice(range(int(len(dates) * 0.5)))`): with hi > 0 every reset
  * (explicit or inside step) draws its starting point on the device, uniformly in [0, hi), from a
  * counter-based generator keyed by (seed, env, episode) -- no host work per step; hi == 0 (default):
- * resets take FINENV_KI_NEXT_START.  Not bit-reproducible against Python's `random` by construction. */
+ * resets take FINENV_KI_NEXT_START.  Not bit-reproducible against Python's `random` by construction.
+ * With a window block attached (finenv_cashpenalty_set_windows) only the sign of hi is read: env e
+ * draws in [0, max(1, (t_e - s_e) >> 1)) of the window [s_e, t_e) it is reset onto -- the same
+ * int(len(self.dates) * 0.5) on the env's own slice -- and starts on panel row s_e + draw. */
 int  finenv_cashpenalty_set_random_start(finenv_cashpenalty *h, int32_t hi, uint64_t seed);
 int  finenv_cashpenalty_step(finenv_cashpenalty *h, const float *actions, float *obs,
                              float *reward, uint8_t *done, float *term_obs, int32_t auto_reset,
@@ -903,6 +909,48 @@ enum { FINENV_AUDIT_F_LAST_DATE = 1, FINENV_AUDIT_F_CASH_SHORTAGE = 2,
        FINENV_AUDIT_F_TURBULENCE = 4, FINENV_AUDIT_F_STOP_LOSS = 8,
        FINENV_AUDIT_F_LOW_PROFIT = 16, FINENV_AUDIT_F_HIGH_PROFIT = 32 };
 int  finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit /* [E][HEAD+N] or NULL */);
+
+/* Per-env episode windows of the cash-penalty env: many StockTradingEnvCashpenalty instances built
+ * on the frame restricted to dates[s:t] (self.dates, the cached date vectors and closings of that
+ * slice) of ONE bound panel in one batch -- train / trade splits, ensemble validation windows,
+ * random-window collection.  Env e on window [s_e, t_e) equals the reference env on that slice, with
+ * the tolerance the env has without windows; FINENV_KI_DATE_INDEX and FINENV_KI_START stay PANEL
+ * rows (the reference's date_index is FINENV_KI_DATE_INDEX - s_e; current_step =
+ * FINENV_KI_DATE_INDEX - FINENV_KI_START as always).  In panel rows:
+ *   - the episode ends at the window's last date, date_index == t_e - 1 (:299), or on a cash
+ *     shortage as always; FINENV_AUDIT_F_LAST_DATE means the window's last date;
+ *   - a reset (finenv_cashpenalty_reset or the auto-reset inside step) starts the env
+ *       with random_start on (hi > 0): on s_e + draw, the draw of (seed, env, episode) in
+ *         [0, max(1, (t_e - s_e) >> 1)) -- the per-window draw range; only the sign of hi is read;
+ *       otherwise: on s_e + clamp(FINENV_KI_NEXT_START, 0, t_e - s_e - 1) -- NEXT_START is an
+ *         OFFSET from the window's first row;
+ *   - with a valid window no row of close, info or turb outside [s_e, t_e) is read, the streamer's
+ *     speculative copy of the next row included.
+ * A window needs t_e - s_e >= 1 (the n_days rule of finenv_cashpenalty_create); the first step of a
+ * one-row window ends at the last date.
+ *
+ * win: caller-owned device block int32_t [4][E], or NULL to detach (the default: every env runs
+ * the whole panel, and everything behaves as without this call).
+ *   rows 0, 1  the PENDING window (s_e, t_e): the caller writes them whenever it likes, the env
+ *              takes them at its next reset;
+ *   rows 2, 3  the ACTIVE window of the running episode: written only by the reset paths
+ *              (finenv_cashpenalty_reset for the envs it selects and the auto-reset inside step,
+ *              which copy rows 0, 1 of the envs they reset), read by step (row 3).  Initialise
+ *              them to the window of the episode in progress, or reset every env once after
+ *              attaching.
+ * The layout of the crypto and array-state envs, not the [2][E] blocks of the stock and portfolio
+ * envs: the end row is read on every step by both waves of the step kernel, so an edit must not
+ * reach a running episode, and the random_start draw range depends on the window, so a reset must
+ * see both rows together.  With the two extra rows, redrawing the windows of the envs that just
+ * reported done needs no reset launch (and works inside a captured graph): their auto-reset has
+ * already taken the windows that were pending, the redraw is taken at the one after.
+ * The kernels clamp window rows (s into [0, T - 1], t into [s + 1, T]) and the date index into the
+ * panel whatever the block and the state hold: bad device-side content is a wrong answer, never an
+ * access outside the panel or the state.
+ * The pointer is a kernel argument: launches and graph replays see later edits of the block's
+ * CONTENTS, a graph keeps the pointer it was captured with.  Works before bind.  Returns
+ * FINENV_ERR_INVALID for a NULL handle. */
+int  finenv_cashpenalty_set_windows(finenv_cashpenalty *h, int32_t *win);
 
 /* =====================================================================================
  * StockTradingEnvStopLoss
@@ -942,7 +990,9 @@ enum { FINENV_LF_COH = 0, FINENV_LF_TURBULENCE, FINENV_LF_SUM_TRADES, FINENV_LF_
 enum { FINENV_LV_HOLDINGS = 0, FINENV_LV_PREV_HOLDINGS, FINENV_LV_CLOSING_DIFF_AVG_BUY,
        FINENV_LV_PROFIT_SELL_DIFF_AVG_BUY, FINENV_LV_N_BUYS, FINENV_LV_AVG_BUY_PRICE,
        FINENV_STOPLOSS_BOOKS };
-enum { FINENV_LI_DATE_INDEX = 0, FINENV_LI_START, FINENV_LI_EPISODE, FINENV_LI_NEXT_START,
+enum { FINENV_LI_DATE_INDEX = 0, FINENV_LI_START, FINENV_LI_EPISODE,
+       FINENV_LI_NEXT_START,      /* as FINENV_KI_NEXT_START: a panel row, or with a window block
+                                     attached an offset from the pending window's first row */
        FINENV_STOPLOSS_I32_FIELDS };
 
 typedef struct finenv_stoploss_state {
@@ -961,13 +1011,26 @@ int  finenv_stoploss_bind(finenv_stoploss *h, const finenv_stoploss_panel *panel
 /* reset(), :134-165 (mask NULL = all envs; starting points from FINENV_LI_NEXT_START) */
 int  finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream);
 /* step(), :292-442 (+ DummyVecEnv auto-reset when auto_reset != 0) */
-/* as finenv_cashpenalty_set_random_start (:142-147) */
+/* as finenv_cashpenalty_set_random_start (:142-147), the per-window draw range with a window block
+ * attached included */
 int  finenv_stoploss_set_random_start(finenv_stoploss *h, int32_t hi, uint64_t seed);
 int  finenv_stoploss_step(finenv_stoploss *h, const float *actions, float *obs, float *reward,
                           uint8_t *done, float *term_obs, int32_t auto_reset, void *stream);
 /* as finenv_cashpenalty_set_audit; flags additionally carry STOP_LOSS (:359-360) and
  * LOW_PROFIT / HIGH_PROFIT (:401-405), the reasons the reference logs for this env */
 int  finenv_stoploss_set_audit(finenv_stoploss *h, double *audit /* [E][HEAD+N] or NULL */);
+
+/* Per-env episode windows of the stop-loss env: the contract of finenv_cashpenalty_set_windows, word
+ * for word, with StockTradingEnvStopLoss on the frame restricted to dates[s:t], FINENV_LI_* for
+ * FINENV_KI_* and "last date" at :302.  win is the same caller-owned device block int32_t [4][E] --
+ * rows 0, 1 the PENDING window, rows 2, 3 the ACTIVE one, written only by finenv_stoploss_reset for
+ * the envs it selects and by the auto-reset inside step -- or NULL to detach (the default).  The
+ * per-window draw range of random_start, FINENV_LI_NEXT_START as an offset from the window's first
+ * row and the clamping of window rows and date index are the same (one implementation,
+ * finenv_twowave.h).  The pointer is a kernel argument: graph replays see later edits of the
+ * block's contents, a graph keeps the pointer it was captured with.  Works before bind.  Returns
+ * FINENV_ERR_INVALID for a NULL handle. */
+int  finenv_stoploss_set_windows(finenv_stoploss *h, int32_t *win);
 
 /* =====================================================================================
  * Risk precompute that feeds the panels.  Stateless; all buffers are

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Step time of the batched stock, portfolio, crypto and array-state stock envs with per-env episode
-windows (VecStockTradingEnv / VecStockPortfolioEnv / VecCryptoEnv / VecStockTradingEnvNP(windows=...)),
-on bench.py's workloads
+"""Step time of the batched stock, portfolio, crypto, array-state stock, cash-penalty and stop-loss envs
+with per-env episode windows (VecStockTradingEnv / VecStockPortfolioEnv / VecCryptoEnv /
+VecStockTradingEnvNP / VecCashPenaltyEnv / VecStopLossEnv(windows=...)), on bench.py's workloads
 (same synthetic panel, actions and env settings).
 usage: python3 tools/bench_windows.py <case> [envs] [steps]
   case: full      -- every env on the whole panel [0, T) (lock-step days, the WIN instantiation)
@@ -19,7 +19,12 @@ usage: python3 tools/bench_windows.py <case> [envs] [steps]
                   -- crypto, random windows of L rows (e.g. cr-random1440: one day of minutes)
         np-none, np-full, np-split, np-random63
                   -- the same on bench.py --env stocknp's workload (array-state env, DOW30 x 8);
-                     np-split: the train / test date ranges of finrl/train.py and finrl/test.py"""
+                     np-split: the train / test date ranges of finrl/train.py and finrl/test.py
+        cp-none, cp-full, cp-split, cp-random63
+                  -- the same on bench.py --env cashpenalty's workload (30 assets x 5 columns, random
+                     starts: with windows each env draws inside its own window)
+        sl-none, sl-full, sl-split, sl-random63
+                  -- the same on bench.py --env stoploss's workload"""
 import os
 import sys
 
@@ -37,9 +42,11 @@ def main():
     dev = torch.device("cuda", 0)
     n100 = case == "n100"
     pf, cr, npy = case.startswith("pf-"), case.startswith("cr-"), case.startswith("np-")
-    case = case[3:] if pf or cr or npy else case
+    cp, sl = case.startswith("cp-"), case.startswith("sl-")
+    prefix = case[:3] if pf or cr or npy or cp or sl else ""
+    case = case[len(prefix):]
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=case == "desync",
-                              no_stats=False, env="portfolio" if pf else "crypto" if cr else "stocknp" if npy else "stock", tickers=100 if n100 else 30,
+                              no_stats=False, env="portfolio" if pf else "crypto" if cr else "stocknp" if npy else "cashpenalty" if cp else "stoploss" if sl else "stock", tickers=100 if n100 else 30,
                               turbulence_pct=90.0 if n100 else None))()
     w = bench.build_workload(args, torch, dev, 0)
     env = w.env
@@ -52,7 +59,7 @@ def main():
     elif case in ("random63", "n100"):
         g = torch.Generator(device=dev).manual_seed(7)
         env.set_windows(*random_windows(T, E, 63, generator=g, device=dev))
-        if not pf and not npy:
+        if not prefix:
             env.hint_desynchronised(True)
     elif case == "split":
         cut = int(0.8 * T)
@@ -70,7 +77,7 @@ def main():
         env.step(w.pool[i % len(w.pool)])
     e1.record()
     torch.cuda.synchronize()
-    name = ("pf-" if pf else "cr-" if cr else "np-" if npy else "") + case
+    name = prefix + case
     print(f"{name} E={E} N={env.action_dim} T={T}: {e0.elapsed_time(e1) * 1e3 / steps:.2f} us/step", flush=True)
 
 
