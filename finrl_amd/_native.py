@@ -67,6 +67,7 @@ class StockHistoryPtrs(C.Structure):
 
 
 HIST_COMPLETE, HIST_OVERFLOW = 1, 2          # FINENV_HIST_*: bits of the history's flags
+HIST_ARMED = 4                               # (the cash-penalty / stop-loss record: len 0 is an armed record)
 # columns of finenv_stock_history_metrics (FINENV_HM_*)
 STOCK_HISTORY_METRICS = ("n_returns", "cumulative_return", "mean", "std", "sharpe", "max_drawdown")
 
@@ -205,6 +206,18 @@ class StopLossStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p)]
 
 
+class TwoWaveHistoryPtrs(C.Structure):
+    """finenv_twowave_history: the episode-history tensors of finenv_{cashpenalty,stoploss}_set_history."""
+    _fields_ = [("cash", C.c_void_p), ("asset_value", C.c_void_p), ("reward", C.c_void_p),
+                ("reason", C.c_void_p), ("transactions", C.c_void_p), ("actions", C.c_void_p),
+                ("start", C.c_void_p), ("end", C.c_void_p), ("ntx", C.c_void_p),
+                ("len", C.c_void_p), ("flags", C.c_void_p), ("capacity", C.c_int32)]
+
+
+# columns of finenv_{cashpenalty,stoploss}_history_metrics: the FINENV_HM_* indices over cash + asset_value,
+# n_returns = len - 1 as in the stock env
+TWOWAVE_HISTORY_METRICS = STOCK_HISTORY_METRICS
+
 _lib = None
 
 
@@ -283,7 +296,8 @@ def lib():
         if hasattr(L, name):
             getattr(L, name).argtypes = [C.c_void_p] * n
     for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs),
-                       ("crypto", CryptoHistoryPtrs), ("stocknp", StockNpHistoryPtrs)):
+                       ("crypto", CryptoHistoryPtrs), ("stocknp", StockNpHistoryPtrs),
+                       ("cashpenalty", TwoWaveHistoryPtrs), ("stoploss", TwoWaveHistoryPtrs)):
         if hasattr(L, f"finenv_{kind}_set_history"):       # episode history (same rule)
             getattr(L, f"finenv_{kind}_set_history").argtypes = [C.c_void_p, C.POINTER(ptrs)]
             getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3

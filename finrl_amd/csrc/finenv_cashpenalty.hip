@@ -440,6 +440,21 @@ int finenv_cashpenalty_set_audit(finenv_cashpenalty *h, double *audit) { return 
 
 int finenv_cashpenalty_set_windows(finenv_cashpenalty *h, int32_t *win) { return tw_set_windows(h, win); }
 
+int finenv_cashpenalty_set_history(finenv_cashpenalty *h, const finenv_twowave_history *hist)
+{
+    return tw_set_history(h, hist);
+}
+
+int finenv_cashpenalty_history_arm(finenv_cashpenalty *h, const uint8_t *mask, void *stream)
+{
+    return tw_history_arm(h, mask, stream, "cashpenalty_history_arm");
+}
+
+int finenv_cashpenalty_history_metrics(finenv_cashpenalty *h, double annualization, double *out, void *stream)
+{
+    return tw_history_metrics(h, annualization, out, stream, "cashpenalty_history_metrics");
+}
+
 int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *obs_out,
                              void *stream)
 {
@@ -451,6 +466,7 @@ int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *
     const auto reset = p.win != nullptr ? &cashpenalty_kernel<true, 0, false, true>
                                         : &cashpenalty_kernel<true, 0, false, false>;
     hipLaunchKernelGGL(reset, tw_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0, (hipStream_t)stream, p);
+    if (h->has_hist) tw_launch_history_arm(h, mask, (hipStream_t)stream);
     return finenv_host::check_launch(h, "cashpenalty_reset");
 }
 

@@ -74,20 +74,22 @@ __device__ __forceinline__ double sharpe_from_sums(int n, double s1, double s2)
 // ret(k), so n = len - k0 returns.  One lane per env, the time loop strided by E (a wave's accesses are
 // contiguous at every k), fp64; mean and std in two sequential passes as pandas takes them (.mean(),
 // .std() with ddof = 1); peak, drawdown and the cumulative return over the values.
-template <typename Ret>
-__device__ __forceinline__ void series_metrics(const double *v, int E, int len, int k0,
-                                               double annualization, double *out, Ret ret)
+// (series_metrics_of: the values through val(k) instead of a column -- the cash-penalty / stop-loss
+//  record holds the account value as two columns, cash + asset_value)
+template <typename Val, typename Ret>
+__device__ __forceinline__ void series_metrics_of(Val val, int len, int k0, double annualization,
+                                                  double *out, Ret ret)
 {
     const double nan = __builtin_nan("");
     if (len < 1) {
         for (int j = 0; j < FINENV_STOCK_HISTORY_METRICS; ++j) out[j] = nan;
         return;
     }
-    const double first = v[0];
+    const double first = val(0);
     const int n = len - k0;
     double last = first, peak = first, sum = 0.0, mdd = 0.0;
     for (int k = k0; k < len; ++k) {
-        const double x = v[(size_t)k * E];
+        const double x = val(k);
         sum = sum + ret(k);
         peak = x > peak ? x : peak;
         const double dd = x / peak - 1.0;
@@ -110,6 +112,13 @@ __device__ __forceinline__ void series_metrics(const double *v, int E, int len, 
     out[FINENV_HM_STD] = sd;
     out[FINENV_HM_SHARPE] = (n >= 2 && sd != 0.0) ? annualization * mean / sd : nan;
     out[FINENV_HM_MAX_DRAWDOWN] = mdd;
+}
+
+template <typename Ret>
+__device__ __forceinline__ void series_metrics(const double *v, int E, int len, int k0,
+                                               double annualization, double *out, Ret ret)
+{
+    series_metrics_of([=](int k) { return v[(size_t)k * E]; }, len, k0, annualization, out, ret);
 }
 
 // Per-env episode windows (finenv_stock_set_windows, finenv_portfolio_set_windows): int32 win[2][E],

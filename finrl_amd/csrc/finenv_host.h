@@ -104,9 +104,11 @@ int ready_last_episode(H *h, const char *what)
 
 // finenv_<kind>_set_history behind the handle check: NULL detaches and zeroes the stored struct.
 // `missing` is the kind's complaint about its own mandatory pointers (nullptr: all there); a refused
-// struct leaves the attached one as it was.
+// struct leaves the attached one as it was.  min_capacity: 2 where arming writes entry 0, 1 where an
+// armed record is empty.
 template <class Hist>
-int set_history(Handle *h, Hist &stored, int &has_hist, const Hist *hist, const char *missing)
+int set_history(Handle *h, Hist &stored, int &has_hist, const Hist *hist, const char *missing,
+                int min_capacity = 2)
 {
     if (!hist) {
         has_hist = 0;
@@ -114,8 +116,10 @@ int set_history(Handle *h, Hist &stored, int &has_hist, const Hist *hist, const 
         return FINENV_OK;
     }
     if (missing) return fail(h, FINENV_ERR_INVALID, missing);
-    if (hist->capacity < 2)
-        return fail(h, FINENV_ERR_INVALID, "set_history: capacity must be >= 2");
+    if (hist->capacity < min_capacity) {
+        if (h) snprintf(h->err, sizeof(h->err), "set_history: capacity must be >= %d", min_capacity);
+        return FINENV_ERR_INVALID;
+    }
     stored = *hist;
     has_hist = 1;
     return FINENV_OK;

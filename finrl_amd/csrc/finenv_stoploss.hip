@@ -857,6 +857,21 @@ int finenv_stoploss_set_audit(finenv_stoploss *h, double *audit) { return tw_set
 
 int finenv_stoploss_set_windows(finenv_stoploss *h, int32_t *win) { return tw_set_windows(h, win); }
 
+int finenv_stoploss_set_history(finenv_stoploss *h, const finenv_twowave_history *hist)
+{
+    return tw_set_history(h, hist);
+}
+
+int finenv_stoploss_history_arm(finenv_stoploss *h, const uint8_t *mask, void *stream)
+{
+    return tw_history_arm(h, mask, stream, "stoploss_history_arm");
+}
+
+int finenv_stoploss_history_metrics(finenv_stoploss *h, double annualization, double *out, void *stream)
+{
+    return tw_history_metrics(h, annualization, out, stream, "stoploss_history_metrics");
+}
+
 int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream)
 {
     if (const int rc = finenv_host::ready(h, "reset")) return rc;
@@ -866,6 +881,7 @@ int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_ou
     p.obs = obs_out;
     const auto reset = p.win != nullptr ? &stoploss_kernel<true, true> : &stoploss_kernel<true, false>;
     hipLaunchKernelGGL(reset, sl_grid(h->cfg.n_envs), dim3(kWave * kWaves), 0, (hipStream_t)stream, p);
+    if (h->has_hist) tw_launch_history_arm(h, mask, (hipStream_t)stream);
     return finenv_host::check_launch(h, "stoploss_reset");
 }
 

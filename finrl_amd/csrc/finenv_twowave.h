@@ -1,8 +1,9 @@
 // finenv_twowave.h -- what the cash-penalty and stop-loss envs share (finenv_cashpenalty.hip,
 // finenv_stoploss.hip): the kernel argument, the device helpers of their trader + streamer step
 // kernels (one 128-thread block per 64 envs) and the host side of their C ABI.  Everything is a
-// template on the env's own argument struct P or handle H; the kernels themselves, the state layout
-// macros and the extern "C" entry points stay in the two files.
+// template on the env's own argument struct P or handle H; the step kernels themselves, the state layout
+// macros and the extern "C" entry points stay in the two files.  The episode history reads the audit
+// row, which is the same for both: its kernels are one object of their own, finenv_twowave_history.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,35 @@
 #include "finenv.h"
 #include "finenv_dev.h"
 #include "finenv_host.h"
+
+// ---- episode history (finenv_<kind>_set_history) --------------------------------------------
+// account_information / actions_memory / transaction_memory of every env's current episode, kept on
+// the device: three small kernels with their own argument struct, shared by both envs -- the audit
+// head is the same and nothing here depends on the env kind.  They ride behind the step / reset
+// kernels as separate launches on the same stream and read what those left in memory: the audit row,
+// done and the caller's action tile.  The rule is in include/finenv.h.  The kernels are compiled once,
+// in finenv_twowave_history.hip, not into both envs' objects.
+namespace finenv_twowave {
+
+struct HistoryArgs {
+    finenv_twowave_history h;
+    const double *audit;          // record: this step's audit rows [E][FINENV_AUDIT_HEAD + N]
+    const float *actions;         // record: this step's action tile [E][N]
+    const uint8_t *done;          // record: this step's done [E]
+    const uint8_t *mask;          // arm: envs to arm, or NULL = all
+    const int32_t *date_index;    // arm: the state's FINENV_K?_DATE_INDEX row [E]
+    const int32_t *win;           // arm: the window block [4][E], or NULL
+    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
+    double annualization;
+    int32_t E, N, n_days;
+    uint32_t magicN;              // ceil(2^32 / N) for N >= 2
+};
+
+void launch_history_record(const HistoryArgs &a, hipStream_t stream);     // tw_history_record_kernel
+void launch_history_arm(const HistoryArgs &a, hipStream_t stream);        // tw_history_arm_kernel
+void launch_history_metrics(const HistoryArgs &a, hipStream_t stream);    // tw_history_metrics_kernel
+
+}  // namespace finenv_twowave
 
 namespace {
 
@@ -197,6 +227,8 @@ struct TwoWaveHandle : finenv_host::Handle {
     State st;
     uint32_t magicN;
     int32_t *win;                   // finenv_<kind>_set_windows
+    int has_hist;                   // finenv_<kind>_set_history
+    finenv_twowave_history hist;
 };
 
 // the kernel argument as the handle fills it; the entry point adds its own pointers
@@ -275,6 +307,66 @@ int tw_set_windows(H *h, int32_t *win)
     return FINENV_OK;
 }
 
+template <class H>
+finenv_twowave::HistoryArgs tw_history_args(const H *h)
+{
+    finenv_twowave::HistoryArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h = h->hist;
+    a.audit = h->audit;
+    static_assert((int)FINENV_KI_DATE_INDEX == (int)FINENV_LI_DATE_INDEX, "one arm kernel for both envs");
+    a.date_index = h->st.i32 + (size_t)FINENV_KI_DATE_INDEX * h->cfg.n_envs;
+    a.win = h->win;
+    a.E = h->cfg.n_envs;
+    a.N = h->cfg.n_assets;
+    a.n_days = h->cfg.n_days;
+    a.magicN = h->magicN;
+    return a;
+}
+
+// finenv_<kind>_reset restarts episodes: the reference's reset() empties the lists
+template <class H>
+void tw_launch_history_arm(const H *h, const uint8_t *mask, hipStream_t stream)
+{
+    finenv_twowave::HistoryArgs a = tw_history_args(h);
+    a.mask = mask;
+    finenv_twowave::launch_history_arm(a, stream);
+}
+
+template <class H>
+int tw_set_history(H *h, const finenv_twowave_history *hist)
+{
+    if (!h) return FINENV_ERR_INVALID;
+    const bool missing = hist && (!hist->cash || !hist->asset_value || !hist->reward ||
+                                  !hist->reason || !hist->start || !hist->end || !hist->ntx ||
+                                  !hist->len || !hist->flags);
+    return finenv_host::set_history(
+        h, h->hist, h->has_hist, hist,
+        missing ? "set_history: null cash/asset_value/reward/reason/start/end/ntx/len/flags" : nullptr, 1);
+}
+
+template <class H>
+int tw_history_arm(H *h, const uint8_t *mask, void *stream, const char *what)
+{
+    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    tw_launch_history_arm(h, mask, (hipStream_t)stream);
+    return finenv_host::check_launch(h, what);
+}
+
+template <class H>
+int tw_history_metrics(H *h, double annualization, double *out, void *stream, const char *what)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
+    const finenv_host::DeviceGuard guard(h->device);
+    finenv_twowave::HistoryArgs a = tw_history_args(h);
+    a.out = out;
+    a.annualization = annualization;
+    finenv_twowave::launch_history_metrics(a, (hipStream_t)stream);
+    return finenv_host::check_launch(h, what);
+}
+
 inline dim3 tw_grid(int E) { return dim3((unsigned)((E + kWaveSize - 1) / kWaveSize)); }   // one block per 64 envs
 
 template <class K, int NCH, class P>
@@ -305,6 +397,8 @@ int tw_step(H *h, const float *actions, float *obs, float *reward, uint8_t *done
     const finenv_host::DeviceGuard guard(h->device);
     if (!actions || !obs || !reward || !done)
         return finenv_host::fail(h, FINENV_ERR_INVALID, "step: null actions/obs/reward/done");
+    if (h->has_hist && !h->audit)
+        return finenv_host::fail(h, FINENV_ERR_INVALID, "step: history needs an audit block");
     P p = tw_params<P>(h);
     p.actions = actions;
     p.obs = obs;
@@ -319,6 +413,12 @@ int tw_step(H *h, const float *actions, float *obs, float *reward, uint8_t *done
     if (h->D <= kWaveSize) tw_launch<K, 1>(p, tw_grid(E), (hipStream_t)stream);
     else if (h->D <= kWaveSize + 4 * kWaveSize) tw_launch<K, 2>(p, tw_grid(E), (hipStream_t)stream);
     else tw_launch<K, 0>(p, K::wide_grid(E), (hipStream_t)stream);
+    if (h->has_hist) {                        // the record of this step, from what the kernel above leaves
+        finenv_twowave::HistoryArgs a = tw_history_args(h);
+        a.actions = actions;
+        a.done = done;
+        finenv_twowave::launch_history_record(a, (hipStream_t)stream);
+    }
     return finenv_host::check_launch(h, what);
 }
 

@@ -8,7 +8,9 @@ The frame builders at the top work on host arrays (time-major, as the device hol
 no GPU; ``EpisodeHistory`` owns the device tensors and is what
 ``VecStockTradingEnv.enable_history()`` returns.  ``PortfolioEpisodeHistory``,
 ``CryptoEpisodeHistory`` and ``StockNpEpisodeHistory`` are the same for the portfolio, the crypto and
-the array-state stock env, whose step kernels write the record themselves.
+the array-state stock env, whose step kernels write the record themselves; ``TwoWaveEpisodeHistory``
+is the record of the cash-penalty and stop-loss envs, a copy of their audit rows taken by one small
+kernel behind each step.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ METRIC_KEYS = nat.STOCK_HISTORY_METRICS
 PORTFOLIO_METRIC_KEYS = nat.PORTFOLIO_HISTORY_METRICS
 CRYPTO_METRIC_KEYS = nat.CRYPTO_HISTORY_METRICS
 STOCKNP_METRIC_KEYS = nat.STOCKNP_HISTORY_METRICS
+TWOWAVE_METRIC_KEYS = nat.TWOWAVE_HISTORY_METRICS
 
 
 def _torch():
@@ -177,36 +180,98 @@ def stocknp_episode_returns(asset, tag, length):
     return out
 
 
+def _own_dates(dates, end, length):
+    """The ``date`` column of the cash-penalty / stop-loss frames: ``self.dates[-len(cash):]``
+    (env_stocktrading_cashpenalty.py:395, :405) -- the LAST ``length`` dates of the env's own frame,
+    ``dates[end - length:end]`` of the panel's, whatever dates the entries were recorded on."""
+    return list(dates[int(end) - int(length):int(end)])
+
+
+def dollar_asset_memory_frame(dates, cash, asset_value, reward, end, length):
+    """save_asset_memory() of the cash-penalty and stop-loss envs (env_stocktrading_cashpenalty.py:390-397,
+    env_stocktrading_stoploss.py:444-451) from one env's recorded columns: ``account_information`` with
+    ``total_assets = cash + asset_value`` as the reference forms it (:314) and the ``date`` column of
+    ``_own_dates``; None for an empty record (``current_step == 0``)."""
+    import pandas as pd
+    n = int(length)
+    if n == 0:
+        return None
+    cash = np.asarray(cash, dtype=np.float64)[:n]
+    asset_value = np.asarray(asset_value, dtype=np.float64)[:n]
+    info = {"cash": cash.tolist(), "asset_value": asset_value.tolist(),
+            "total_assets": (cash + asset_value).tolist(),
+            "reward": np.asarray(reward, dtype=np.float64)[:n].tolist()}
+    info["date"] = _own_dates(dates, end, n)
+    return pd.DataFrame(info)
+
+
+def stoploss_actions_memory(raw, hmax, close_rows):
+    """What the stop-loss env appends to ``actions_memory`` (env_stocktrading_stoploss.py:321-324):
+    ``(actions * hmax) * closings`` from the raw float32 action rows [n, N] and the close rows [n, N]
+    of the entries' dates -- the product with ``hmax`` in float32, as the caller's array makes it, the
+    one with the float64 closings in float64."""
+    return (np.asarray(raw, dtype=np.float32) * hmax) * np.asarray(close_rows, dtype=np.float64)
+
+
+def dollar_action_memory_frame(dates, actions, transactions, end, length, ntx):
+    """save_action_memory() of the two envs (:399-409, :453-459): ``{date, actions, transactions}``,
+    one array per day in both list columns.  ``actions``: [>= length, N] as the env's ``actions_memory``
+    holds them (the raw rows; ``stoploss_actions_memory`` for the stop-loss env); ``transactions``:
+    [>= ntx, N].  The lists have the reference's lengths: an episode that ended on a cash shortage holds
+    one transaction row fewer (``ntx == length - 1``, :341-344 returns before the append), and pandas
+    raises its ValueError here as it does in the reference's call.  None for an empty record."""
+    import pandas as pd
+    n = int(length)
+    if n == 0:
+        return None
+    return pd.DataFrame({"date": _own_dates(dates, end, n),
+                         "actions": list(np.asarray(actions)[:n]),
+                         "transactions": list(np.asarray(transactions, dtype=np.float64)[:int(ntx)])})
+
+
 # ---------------------------------------------------------------------- the device side
 class _Record:
-    """A device-resident episode record: what ``EpisodeHistory``, ``PortfolioEpisodeHistory`` and
-    ``CryptoEpisodeHistory`` are made of.  A subclass declares its data:
+    """A device-resident episode record: what ``EpisodeHistory``, ``PortfolioEpisodeHistory``,
+    ``CryptoEpisodeHistory`` and ``TwoWaveEpisodeHistory`` are made of.  A subclass declares its data:
       ``_ptrs_cls``    the ctypes struct of finenv_<kind>_set_history (one pointer per tensor, capacity)
       ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]; those named in the
                        constructor's ``without`` are not recorded (None)
-      ``_per_ticker``  (name, dtype, rows short of capacity): the optional tensor [capacity - short, E, N]
-      ``_env_last``    that tensor is [capacity - short, N, E] instead (the env is the fastest index)
+      ``_per_ticker``  (name, dtype, rows short of capacity): the optional tensor [capacity - short, E, N],
+                       or a tuple of such triples (the constructor's ``per_ticker`` is then one switch
+                       for all of them or a tuple of switches)
+      ``_env_last``    those tensors are [capacity - short, N, E] instead (the env is the fastest index)
       ``_per_env``     ((name, dtype), ...): the tensors [E] beside ``length`` and ``flags``
+      ``_attr``        {struct field: attribute} where the tensor's attribute has another name
       ``_assets``      the env attribute that holds N
+      ``_min_capacity`` 2 where arming writes entry 0, 1 where an armed record is empty
       ``metric_keys``  the columns of ``metrics()``
     """
 
-    _env_last, _per_env, _assets = False, (), "stock_dim"
+    _env_last, _per_env, _assets, _min_capacity = False, (), "stock_dim", 2
+    _attr = {"len": "length"}
+
+    @classmethod
+    def _tickers(cls):
+        """``_per_ticker`` as a tuple of (name, dtype, short) triples."""
+        pt = cls._per_ticker
+        return (pt,) if isinstance(pt[0], str) else tuple(pt)
 
     def __init__(self, env, capacity, per_ticker=True, without=()):
         torch = _torch()
         E, N, dev = env.num_envs, getattr(env, self._assets), env.device
         capacity = int(capacity)
-        if capacity < 2:
-            raise ValueError("history capacity must be >= 2")
+        if capacity < self._min_capacity:
+            raise ValueError(f"history capacity must be >= {self._min_capacity}")
         self.env, self.capacity = env, capacity
         for name, dtype in self._series:
             setattr(self, name, None if name in without else
                     torch.zeros(capacity, E, dtype=getattr(torch, dtype), device=dev))
-        name, dtype, short = self._per_ticker
-        shape = (capacity - short, N, E) if self._env_last else (capacity - short, E, N)
-        setattr(self, name, torch.zeros(*shape, dtype=getattr(torch, dtype), device=dev)
-                if per_ticker else None)
+        specs = self._tickers()
+        wanted = per_ticker if isinstance(per_ticker, tuple) else (per_ticker,) * len(specs)
+        for (name, dtype, short), on in zip(specs, wanted):
+            shape = (capacity - short, N, E) if self._env_last else (capacity - short, E, N)
+            setattr(self, name, torch.zeros(*shape, dtype=getattr(torch, dtype), device=dev)
+                    if on else None)
         for name, dtype in self._per_env:
             setattr(self, name, torch.zeros(E, dtype=getattr(torch, dtype), device=dev))
         self.length = torch.zeros(E, dtype=torch.int32, device=dev)
@@ -218,8 +283,8 @@ class _Record:
         self.arm()
 
     def _tensors(self):
-        """The tensors in the pointer struct's field order (None: the per-ticker one, disabled)."""
-        return [getattr(self, "length" if f == "len" else f) for f, _ in self._ptrs_cls._fields_[:-1]]
+        """The tensors in the pointer struct's field order (None: a per-ticker one, disabled)."""
+        return [getattr(self, self._attr.get(f, f)) for f, _ in self._ptrs_cls._fields_[:-1]]
 
     @property
     def nbytes(self):
@@ -278,13 +343,14 @@ class _Record:
         idx = torch.as_tensor(envs, dtype=torch.int64, device=self.env.device)
         out = {"length": self.length.index_select(0, idx).cpu().numpy()}
         per_env = [name for name, _ in self._per_env]
+        switch = {a: f for f, a in self._attr.items()}
         for k in names:
             t = getattr(self, k)
             if t is None:
-                raise nat.FinenvError(f"this history was enabled with {k}=False")
+                raise nat.FinenvError(f"this history was enabled with {switch.get(k, k)}=False")
             if k in per_env:
                 out[k] = t.index_select(0, idx).cpu().numpy()
-            elif self._env_last and k == self._per_ticker[0]:
+            elif self._env_last and k in [name for name, _, _ in self._tickers()]:
                 out[k] = t.index_select(2, idx).cpu().numpy().transpose(0, 2, 1)
             else:
                 out[k] = t.index_select(1, idx).cpu().numpy()
@@ -506,4 +572,95 @@ class StockNpEpisodeHistory(_Record):
     def rows(self, e):
         """The panel rows of env ``e``'s entries, ``start + arange(length)`` (a list for a sequence of
         envs): index your own dates with them."""
+        return self._frames(e, crypto_rows, "start", dates=False)
+
+
+class TwoWaveEpisodeHistory(_Record):
+    """Device-resident episode record of a ``VecCashPenaltyEnv`` / ``VecStopLossEnv``
+    (``env.enable_history()``): the reference's ``account_information``, ``actions_memory`` and
+    ``transaction_memory`` (env_stocktrading_cashpenalty.py:308-355, env_stocktrading_stoploss.py:315-385)
+    of every env's current episode -- the audit row of every step, copied by one small kernel behind the
+    step kernel (finenv_<kind>_set_history, include/finenv.h), with no host work per step.
+
+    Tensors (time-major; entries at or past ``length[e]`` are unspecified):
+      ``cash``         f64 [capacity, E]     begin cash of the step (:312)
+      ``asset_value``  f64 [capacity, E]     asset value (:310); total assets are ``cash + asset_value``
+      ``reward``       f64 [capacity, E]     the f64 reward (:317)
+      ``reason``       i32 [capacity, E]     the step's reason flags (``nat.AUDIT_F_*``)
+      ``tx``           f64 [capacity, E, N]  transaction_memory, or None (``transactions=False``)
+      ``actions``      f32 [capacity, E, N]  the raw action rows ``step`` was given, or None
+      ``start``        i32 [E]               panel row of entry 0; entry k is panel row ``start + k``
+      ``end``          i32 [E]               end of the window the record was armed on
+      ``ntx``          i32 [E]               rows of transaction_memory: ``length``, or one fewer when the
+                                             episode ended on a cash shortage
+      ``length``       i32 [E]               entries recorded (0: armed and empty, or not armed)
+      ``flags``        i32 [E]               bit 2 armed, bit 0 complete, bit 1 overflow
+
+    Armed by the constructor (at the env's current date), by ``env.reset(mask)`` for the envs it resets
+    and by ``arm(mask)``; an armed record is EMPTY, as the reference's lists are after ``reset()``.  The
+    step that ends at the last date appends nothing (:299-301); either ending makes the record final.
+    An auto-reset inside ``step`` does not arm: the finished episode stays readable until the next host
+    reset or ``arm``.  The pointers are launch arguments: enable the history before capturing a graph.
+    """
+
+    _ptrs_cls, metric_keys = nat.TwoWaveHistoryPtrs, TWOWAVE_METRIC_KEYS
+    _series = (("cash", "float64"), ("asset_value", "float64"), ("reward", "float64"), ("reason", "int32"))
+    _per_ticker = (("tx", "float64", 0), ("actions", "float32", 0))
+    _per_env = (("start", "int32"), ("end", "int32"), ("ntx", "int32"))
+    _attr = {"len": "length", "transactions": "tx"}
+    _assets, _min_capacity = "action_dim", 1
+
+    def __init__(self, env, capacity, transactions=True, actions=True):
+        super().__init__(env, capacity, (transactions, actions))
+
+    @property
+    def armed(self):
+        """bool [E]: the env has a record (possibly empty)."""
+        return (self.flags & nat.HIST_ARMED) != 0
+
+    def _actions_memory(self, raw, start, n):
+        """The env's ``actions_memory`` rows from the raw ones: themselves (:264), or for the stop-loss
+        env ``(actions * hmax) * closings`` with the panel's close rows of the entries."""
+        if self.env._kind != "stoploss":
+            return raw
+        lo = int(start)
+        return stoploss_actions_memory(raw[:int(n)], float(self.env._cfg.hmax),
+                                       self.env.panel.close[lo:lo + int(n)])
+
+    def save_asset_memory(self, e):
+        """The reference's save_asset_memory() frame of env ``e`` -- ``cash, asset_value, total_assets,
+        reward, date`` -- or None for an empty record (a list for a sequence of envs)."""
+        return self._frames(e, dollar_asset_memory_frame, "cash", "asset_value", "reward", "end")
+
+    def save_action_memory(self, e):
+        """The reference's save_action_memory() frame ``{date, actions, transactions}`` of env ``e``, or
+        None for an empty record (a list for a sequence of envs); needs both optional tensors.  For an
+        episode that ended on a cash shortage it raises the ValueError the reference's call raises."""
+        return self._frames(
+            e, lambda dates, actions, tx, start, end, ntx, n: dollar_action_memory_frame(
+                dates, self._actions_memory(actions, start, n), tx, end, n, ntx),
+            "actions", "tx", "start", "end", "ntx")
+
+    def account_values(self, e):
+        """Total assets ``cash + asset_value`` of env ``e``'s entries -> f64 [length] (a list for a
+        sequence of envs)."""
+        return self._frames(e, lambda cash, av, n: np.asarray(cash[:int(n)] + av[:int(n)], np.float64),
+                            "cash", "asset_value", dates=False)
+
+    def transactions(self, e):
+        """transaction_memory of env ``e`` -> f64 [ntx, N]; needs ``transactions=True``."""
+        return self._frames(e, lambda tx, ntx, n: np.array(tx[:int(ntx)]), "tx", "ntx", dates=False)
+
+    def raw_actions(self, e):
+        """The action rows ``step`` was given on env ``e``'s entries -> f32 [length, N]; needs
+        ``actions=True``."""
+        return self._frames(e, lambda a, n: np.array(a[:int(n)]), "actions", dates=False)
+
+    def reasons(self, e):
+        """The reason flag words (``nat.AUDIT_F_*``) of env ``e``'s entries -> i32 [length]."""
+        return self._frames(e, lambda r, n: np.array(r[:int(n)]), "reason", dates=False)
+
+    def rows(self, e):
+        """The panel rows of env ``e``'s entries, ``start + arange(length)``: the dates the steps were
+        taken on (the frames' ``date`` column is the reference's, see ``dollar_asset_memory_frame``)."""
         return self._frames(e, crypto_rows, "start", dates=False)

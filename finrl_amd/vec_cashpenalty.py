@@ -139,6 +139,33 @@ class VecCashPenaltyEnv(WindowedEnv):
             self._call("set_audit", C.c_void_p(self.audit.data_ptr()))
         return self.audit
 
+    history = None              # enable_history()
+
+    def enable_history(self, capacity=None, transactions=True, actions=True):
+        """Record every env's episode on the device: the reference's ``account_information``,
+        ``actions_memory`` (with ``actions``) and ``transaction_memory`` (with ``transactions``), copied
+        from the audit row by one small kernel behind every step (finenv_<kind>_set_history) -- no
+        device-to-host copy per step, no host loop, it sits in a captured graph, and under
+        ``auto_reset`` the finished episode stays readable.  Calls ``enable_audit()`` first: the record
+        is a copy of the audit row.  Returns the ``finrl_amd.history.TwoWaveEpisodeHistory`` (also
+        ``self.history``) with ``save_asset_memory(e)`` / ``save_action_memory(e)``, the frames of the
+        reference's methods for a whole batch of back-test windows; idempotent: a second call returns the
+        same object whatever its arguments.
+
+        ``capacity``: entries per env, by default the longest episode (``max_step + 1``: the rows of
+        the longest pending window, ``T`` without windows) AS IT IS AT THIS CALL: windows made longer
+        by a later ``set_windows`` do not grow the record, an episode that outruns it sets ``overflow``
+        and keeps its first ``capacity`` entries.  Memory: ``E * (28 * capacity + 20)`` bytes plus
+        ``8 * E * N * capacity`` for the transactions and ``4 * E * N * capacity`` for the actions.
+        Every env is armed at its current date with an empty record; ``reset(mask)`` arms the envs it
+        resets, the auto-reset inside ``step`` does not.  Enable it before capturing a graph."""
+        if self.history is None:
+            from .history import TwoWaveEpisodeHistory
+            self.enable_audit()
+            self.history = TwoWaveEpisodeHistory(
+                self, self.max_step + 1 if capacity is None else capacity, transactions, actions)
+        return self.history
+
     def set_next_start(self, starts):
         """Starting points the next reset of each env will use (the reference draws
         random.choice(range(int(len(dates) * 0.5))), :134-138).  Panel rows; with windows attached

@@ -1032,6 +1032,74 @@ int  finenv_stoploss_set_audit(finenv_stoploss *h, double *audit /* [E][HEAD+N] 
  * FINENV_ERR_INVALID for a NULL handle. */
 int  finenv_stoploss_set_windows(finenv_stoploss *h, int32_t *win);
 
+/* Episode history of the cash-penalty and stop-loss envs: what the reference keeps in
+ * account_information, actions_memory and transaction_memory (env_stocktrading_cashpenalty.py:308-355,
+ * env_stocktrading_stoploss.py:315-385) and hands out through save_asset_memory() /
+ * save_action_memory(), for every env's CURRENT episode, recorded on the device.  Opt-in and
+ * caller-owned device memory, time-major:
+ *   cash[k][e], asset_value[k][e], reward[k][e], reason[k][e]
+ *                          the audit head of the k-th recorded step: begin cash, asset value, the f64
+ *                          reward, the FINENV_AUDIT_F_* reason flags (total_assets is cash + asset_value,
+ *                          formed by the reader as the reference forms it)
+ *   transactions[k][e][:]  the N transactions of that step (f64), or not recorded (NULL)
+ *   actions[k][e][:]       the raw f32 action row finenv_<kind>_step was given, or not recorded (NULL)
+ *   start[e]               panel row of entry 0; entry k belongs to panel row start[e] + k
+ *   end[e]                 end of the window the record was armed on (n_days without windows): the
+ *                          reference's `date` column is the last len dates of the env's own frame
+ *   ntx[e]                 transaction rows the reference's list holds: len[e], or one fewer when the
+ *                          episode ended on a cash shortage (it returns before the append, :341-344)
+ *   len[e]                 entries recorded so far; 0 is a legal armed record (the lists are empty
+ *                          after reset())
+ *   flags[e]               FINENV_HIST_ARMED | FINENV_HIST_COMPLETE | FINENV_HIST_OVERFLOW
+ * The record is a copy of the audit row, so a history needs the audit block
+ * (finenv_<kind>_set_audit): while a history is attached finenv_<kind>_step launches one more small
+ * kernel behind the step kernel on the same stream (the step kernels do not know about it) and
+ * returns FINENV_ERR_INVALID, "history needs an audit block", without one.  Per env that is armed
+ * and not complete, from the audit row the step left and its done[e]:
+ *   - flags contain FINENV_AUDIT_F_LAST_DATE: nothing is appended (:299-301), COMPLETE is set;
+ *   - else len[e] == capacity: OVERFLOW is set, nothing is written; COMPLETE too if done[e];
+ *   - else entry k = len[e]: the four scalars, the action row, and the transactions unless the step
+ *     ended the episode on a cash shortage (CASH_SHORTAGE and done[e]); len[e] = k + 1, ntx[e]
+ *     counts the transaction rows; COMPLETE if done[e].
+ *   No entry at or past `capacity` is ever written, in any tensor.
+ * Arming an env sets len = ntx = 0, flags = ARMED, start[e] = its current FINENV_KI_DATE_INDEX and
+ * end[e] = its active window's end.  finenv_<kind>_reset arms the envs it resets, behind the reset.
+ * An auto-reset inside step does NOT arm: the finished episode's record stays readable and the env
+ * is not recorded again until a host reset or finenv_<kind>_history_arm.
+ * The struct's pointers are LAUNCH ARGUMENTS: a step captured into a graph records only if the
+ * history was attached before the capture, and into the tensors attached then.
+ * Memory: E * (28 * capacity + 20) + 12 * E * N * capacity bytes with both optional tensors. */
+enum { FINENV_HIST_ARMED = 4 };    /* beside FINENV_HIST_COMPLETE / _OVERFLOW; these two envs only */
+typedef struct finenv_twowave_history {
+    double  *cash;          /* [capacity][E]    begin cash of the step (:312)                       */
+    double  *asset_value;   /* [capacity][E]    asset value (:310)                                  */
+    double  *reward;        /* [capacity][E]    the f64 reward (:317)                               */
+    int32_t *reason;        /* [capacity][E]    FINENV_AUDIT_F_* flags of the step                  */
+    double  *transactions;  /* [capacity][E][N] transaction_memory, or NULL                         */
+    float   *actions;       /* [capacity][E][N] the raw action rows, or NULL                        */
+    int32_t *start;         /* [E] panel row of entry 0; entry k is panel row start[e] + k          */
+    int32_t *end;           /* [E] end of the window the record was armed on                        */
+    int32_t *ntx;           /* [E] transaction rows recorded                                        */
+    int32_t *len;           /* [E] entries recorded                                                 */
+    int32_t *flags;         /* [E] FINENV_HIST_ARMED / _COMPLETE / _OVERFLOW                        */
+    int32_t  capacity;      /* >= 1                                                                 */
+} finenv_twowave_history;
+/* Attach a history (the struct is copied), or detach with NULL (the default).  Allowed before bind.
+ * Attaching arms nothing: zero len / flags, then finenv_<kind>_reset / _history_arm. */
+int finenv_cashpenalty_set_history(finenv_cashpenalty *h, const finenv_twowave_history *hist);
+int finenv_stoploss_set_history(finenv_stoploss *h, const finenv_twowave_history *hist);
+/* Arm every env, or those with mask[e] != 0 (device u8[E]), at its current date. */
+int finenv_cashpenalty_history_arm(finenv_cashpenalty *h, const uint8_t *mask, void *stream);
+int finenv_stoploss_history_arm(finenv_stoploss *h, const uint8_t *mask, void *stream);
+/* Backtest figures of the recorded total assets cash + asset_value: out
+ * [E][FINENV_STOCK_HISTORY_METRICS] f64, the FINENV_HM_* columns with the stock env's convention:
+ * returns total[k] / total[k-1] - 1 in fp64 for k = 1 .. len-1, N_RETURNS = len - 1.  Rows of
+ * unarmed envs and of empty records are NaN. */
+int finenv_cashpenalty_history_metrics(finenv_cashpenalty *h, double annualization, double *out,
+                                       void *stream);
+int finenv_stoploss_history_metrics(finenv_stoploss *h, double annualization, double *out,
+                                    void *stream);
+
 /* =====================================================================================
  * Risk precompute that feeds the panels.  Stateless; all buffers are
  * caller-owned device memory; launches go to `stream`; nothing synchronises.

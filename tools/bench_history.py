@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Cost of the episode history (enable_history) of the batched stock, portfolio, crypto or array-state
-stock env on bench.py's workload for that env: 65,536 envs x DOW30 x 8 indicators, 63-day episode windows
+"""Cost of the episode history (enable_history) of the batched stock, portfolio, crypto, array-state
+stock, cash-penalty or stop-loss env on bench.py's workload for that env: 65,536 envs x DOW30 x 8
+indicators, 63-day episode windows
 (crypto: 10 pairs x 40 indicator columns, 1,440-row windows, --envs 32768 / 65536 / 262144; stocknp:
 64-row windows -- that env is done one step earlier, and the timed steps stay the same).  ONE process, ONE
 env; the variants alternate inside every round, each timed with HIP events over steps that all record:
@@ -12,7 +13,15 @@ env; the variants alternate inside every round, each timed with HIP events over 
        portfolio +20 + 4N B written; crypto +16 + 4N B written; stocknp +13 + 4N B written
   d  history detached, the host copy the history replaces after every step: one state_numpy()
      (portfolio: and one weights.cpu())
-usage: python3 tools/bench_history.py <lockstep|desync> [--env stock|portfolio|crypto|stocknp]
+--env cashpenalty / stoploss (30 assets x 5 columns, starts pinned to each window's first row): the
+record is a copy of the audit row taken by tw_history_record_kernel behind the step, so there is one
+more variant, and b / c / d keep the audit block:
+  u  history detached, audit block attached (the step kernel writes its 8 (4 + N) B row per env)
+  b  history without transactions and actions: record_bytes_twowave(N, False) read / written
+  c  history with both: record_bytes_twowave(N, True)
+  d  history detached, one state_numpy() and one audit.cpu() after every step
+usage: python3 tools/bench_history.py <lockstep|desync>
+                                      [--env stock|portfolio|crypto|stocknp|cashpenalty|stoploss]
                                       [--variants a,b,c,d] [--rounds R] [--envs E] [--json PATH]
   lockstep  every env on the window [0, 63): one record row per step, written contiguously
   desync    random 63-day windows (stock: with hint_desynchronised(True)) and a random half of the envs
@@ -26,7 +35,8 @@ env, not of the whole window: 262,144 envs x 100 x (16 + 4N) B is 1.5 GB).
 FINENV_LIB=<libfinenv.so of another build> times that build; one without the history entry points
 can run variant a only (that is how a commit before the feature is measured with this same script).
 Under `rocprofv3 --kernel-trace --stats -- python3 tools/bench_history.py lockstep --variants c` the
-kernel stats give stock_history_record_kernel's own time (record_bytes() below is what it moves);
+kernel stats give stock_history_record_kernel's own time (record_bytes() below is what it moves) or,
+with `--env cashpenalty` / `--env stoploss`, tw_history_record_kernel's (record_bytes_twowave());
 with `--env portfolio` / `--env crypto` / `--env stocknp`, the recording instantiation's of the step kernel."""
 import argparse
 import ctypes as C
@@ -48,16 +58,25 @@ def record_bytes(N, actions):
     return 25 + 4 * N + 16 + (8 * N if actions else 0)
 
 
+def record_bytes_twowave(N, both):
+    """(read, written) bytes per env and step of tw_history_record_kernel: it reads flags, len, ntx
+    (12), done (1) and the audit head (32) [+ the N transactions of the audit row (8N) and the action row
+    (4N)] and writes the four scalar columns (28), len and ntx (8) [+ transactions and actions (12N)]."""
+    return 45 + (12 * N if both else 0), 36 + (12 * N if both else 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("case", choices=("lockstep", "desync"))
-    ap.add_argument("--env", choices=("stock", "portfolio", "crypto", "stocknp"), default="stock")
-    ap.add_argument("--variants", default="a,b,c,d")
+    ap.add_argument("--env", choices=("stock", "portfolio", "crypto", "stocknp", "cashpenalty",
+                                     "stoploss"), default="stock")
+    ap.add_argument("--variants", default=None)
     ap.add_argument("--rounds", type=int, default=0)
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--json", default=None)
     o = ap.parse_args()
-    variants = o.variants.split(",")
+    twowave = o.env in ("cashpenalty", "stoploss")
+    variants = (o.variants or ("a,u,b,c,d" if twowave else "a,b,c,d")).split(",")
     import torch
     import bench
     from finrl_amd import _native as nat
@@ -70,7 +89,12 @@ def main():
                               env=o.env, tickers=30, turbulence_pct=None))()
     w = bench.build_workload(args, torch, dev, 0)
     stock, crypto, stocknp = o.env == "stock", o.env == "crypto", o.env == "stocknp"
-    env, N = w.env, w.env.action_dim if crypto or stocknp else w.env.stock_dim
+    env, N = w.env, w.env.action_dim if crypto or stocknp or twowave else w.env.stock_dim
+    if twowave:                                 # every env starts on its window's first row
+        env.random_start = False
+        env._call("set_random_start", 0, 0)
+        env.set_next_start(0)
+        audit = C.c_void_p(env.enable_audit().data_ptr())
     window = CRYPTO_WINDOW if crypto else WINDOW + stocknp
     rows = env.price_array.shape[0] if crypto else env.price_ary.shape[0] if stocknp else env.panel.T
     has_api = hasattr(nat.lib(), f"finenv_{o.env}_set_history")
@@ -94,6 +118,7 @@ def main():
         for v, per_ticker in (("b", False), ("c", True)):
             if v in variants:
                 hists[v] = H.EpisodeHistory(env, WINDOW, actions=per_ticker) if stock else \
+                    H.TwoWaveEpisodeHistory(env, WINDOW, per_ticker, per_ticker) if twowave else \
                     H.CryptoEpisodeHistory(env, CRYPTO_CAPACITY, stocks=per_ticker) if crypto else \
                     H.StockNpEpisodeHistory(env, window, stocks=per_ticker) if stocknp else \
                     H.PortfolioEpisodeHistory(env, WINDOW, weights=per_ticker)
@@ -108,7 +133,9 @@ def main():
     def select(v):
         if has_api:
             env._call("set_history", C.byref(hists[v]._ptrs) if v in hists else None)
-        if not (crypto or stocknp):
+        if twowave:
+            env._call("set_audit", None if v == "a" else audit)
+        elif not (crypto or stocknp):
             setattr(env, extra, extra_out if v == extra_v else None)
         env._step_args = None                   # BatchedEnv.step caches the output pointers
 
@@ -129,13 +156,15 @@ def main():
                 env.state_numpy()
                 if o.env == "portfolio":
                     env.weights.cpu()
+                if twowave:
+                    env.audit.cpu()
         e1.record()
         torch.cuda.synchronize()
         if record:
             times[v].append(e0.elapsed_time(e1) * 1e3 / timed)
         if v in hists:                          # every env recorded on every timed step
             h = hists[v]
-            assert int(h.length.min()) >= timed + 1 and not bool(h.complete.any()) \
+            assert int(h.length.min()) >= timed + (not twowave) and not bool(h.complete.any()) \
                 and not bool(h.overflow.any()), "a timed step did not record"
 
     times = {v: [] for v in variants}
@@ -159,6 +188,10 @@ def main():
     elif stocknp:
         res["added_bytes_written_per_env_step"] = {"b": 13, "c": 13 + 4 * N}
         res["added_bytes_read_per_env_step"] = {"b": 8, "c": 8}
+    elif twowave:
+        res["audit_row_bytes_per_env_step"] = 8 * (4 + N)
+        res["record_kernel_bytes_read_written_per_env_step"] = {
+            "b": record_bytes_twowave(N, False), "c": record_bytes_twowave(N, True)}
     else:
         res["added_bytes_written_per_env_step"] = {"b": 20, "c": 20 + 4 * N}
     line = json.dumps(res)
