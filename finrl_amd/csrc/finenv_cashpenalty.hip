@@ -447,12 +447,14 @@ int finenv_cashpenalty_set_history(finenv_cashpenalty *h, const finenv_twowave_h
 
 int finenv_cashpenalty_history_arm(finenv_cashpenalty *h, const uint8_t *mask, void *stream)
 {
-    return tw_history_arm(h, mask, stream, "cashpenalty_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "cashpenalty_history_arm",
+                                    tw_launch_history_arm<finenv_cashpenalty>);
 }
 
 int finenv_cashpenalty_history_metrics(finenv_cashpenalty *h, double annualization, double *out, void *stream)
 {
-    return tw_history_metrics(h, annualization, out, stream, "cashpenalty_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "cashpenalty_history_metrics",
+                                        tw_history_series<finenv_cashpenalty>);
 }
 
 int finenv_cashpenalty_reset(finenv_cashpenalty *h, const uint8_t *mask, float *obs_out,

@@ -554,16 +554,14 @@ __global__ void __launch_bounds__(kWave *(TWO ? 2 * kWaves : kWaves), 1) crypto_
 }
 
 // -------------------------------------------------------------------------------------
-// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
-// instantiation of the step kernel above).
+// Episode history, off the step path: arming (the recording itself is the HIST instantiation of the
+// step kernel above, the metrics kernel is every kind's, finenv_history.hip).
 // -------------------------------------------------------------------------------------
 struct CrHistArgs {
     finenv_crypto_history h;
     finenv_crypto_state st;
     const double *price;          // [T][N]
     const uint8_t *mask;          // arm: envs to arm, or NULL = all
-    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
-    double annualization;
     int32_t E, N, T;
 };
 
@@ -597,19 +595,6 @@ __global__ __launch_bounds__(256) void crypto_history_arm_kernel(const CrHistArg
     p.h.start[e] = time;
     p.h.len[e] = 1;
     p.h.flags[e] = 0;
-}
-
-// Backtest figures of each env's recorded account values (series_metrics, finenv_dev.h): the returns
-// are asset[k] / asset[k-1] - 1, entry 0 carries none, so n_returns is len - 1 (the stock env's rule).
-__global__ void crypto_history_metrics_kernel(const CrHistArgs p)
-{
-    const int E = p.E;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double *a = p.h.asset + e;
-    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
-                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
-                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
 }
 
 }  // namespace
@@ -661,6 +646,12 @@ void launch_history_arm(const finenv_crypto *h, const uint8_t *mask, hipStream_t
     CrHistArgs a = cr_hist_args(h);
     a.mask = mask;
     hipLaunchKernelGGL(crypto_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
+}
+
+// the metrics' series: the account values and their pct_change() (the stock env's rule)
+finenv_host::HistorySeries history_series(const finenv_crypto *h)
+{
+    return {h->hist.asset, nullptr, nullptr, h->hist.len, h->hist.flags, 0, h->hist.capacity, h->cfg.n_envs};
 }
 
 constexpr int kSmallWaves = 2048;      // up to here: one env wave per block (spread over every CU)
@@ -852,23 +843,12 @@ int finenv_crypto_set_history(finenv_crypto *h, const finenv_crypto_history *his
 
 int finenv_crypto_history_arm(finenv_crypto *h, const uint8_t *mask, void *stream)
 {
-    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    launch_history_arm(h, mask, (hipStream_t)stream);
-    return finenv_host::check_launch(h, "crypto_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "crypto_history_arm", launch_history_arm);
 }
 
 int finenv_crypto_history_metrics(finenv_crypto *h, double annualization, double *out, void *stream)
 {
-    if (!h || !out) return FINENV_ERR_INVALID;
-    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    CrHistArgs a = cr_hist_args(h);
-    a.out = out;
-    a.annualization = annualization;
-    hipLaunchKernelGGL(crypto_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    return finenv_host::check_launch(h, "crypto_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "crypto_history_metrics", history_series);
 }
 
 }  // extern "C"

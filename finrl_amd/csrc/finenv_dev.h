@@ -68,14 +68,12 @@ __device__ __forceinline__ double sharpe_from_sums(int n, double s1, double s2)
     return sharpe;
 }
 
-// Backtest figures of one env's recorded series (finenv_{stock,portfolio}_history_metrics) -> the
-// FINENV_HM_* columns of `out`.  v: the env's values, entry k at v[k * E], `len` of them (clamped to the
-// capacity by the caller; < 1 = not armed: a NaN row).  Entries k0 .. len - 1 carry a daily return,
-// ret(k), so n = len - k0 returns.  One lane per env, the time loop strided by E (a wave's accesses are
-// contiguous at every k), fp64; mean and std in two sequential passes as pandas takes them (.mean(),
-// .std() with ddof = 1); peak, drawdown and the cumulative return over the values.
-// (series_metrics_of: the values through val(k) instead of a column -- the cash-penalty / stop-loss
-//  record holds the account value as two columns, cash + asset_value)
+// Backtest figures of one env's recorded series (finenv_<kind>_history_metrics, the kernel is in
+// finenv_history.hip) -> the FINENV_HM_* columns of `out`.  val(k): the env's value at entry k, `len` of
+// them (clamped to the capacity by the caller; < 1 = not armed: a NaN row).  Entries k0 .. len - 1 carry
+// a daily return, ret(k), so n = len - k0 returns.  One lane per env, fp64; mean and std in two
+// sequential passes as pandas takes them (.mean(), .std() with ddof = 1); peak, drawdown and the
+// cumulative return over the values.
 template <typename Val, typename Ret>
 __device__ __forceinline__ void series_metrics_of(Val val, int len, int k0, double annualization,
                                                   double *out, Ret ret)
@@ -112,13 +110,6 @@ __device__ __forceinline__ void series_metrics_of(Val val, int len, int k0, doub
     out[FINENV_HM_STD] = sd;
     out[FINENV_HM_SHARPE] = (n >= 2 && sd != 0.0) ? annualization * mean / sd : nan;
     out[FINENV_HM_MAX_DRAWDOWN] = mdd;
-}
-
-template <typename Ret>
-__device__ __forceinline__ void series_metrics(const double *v, int E, int len, int k0,
-                                               double annualization, double *out, Ret ret)
-{
-    series_metrics_of([=](int k) { return v[(size_t)k * E]; }, len, k0, annualization, out, ret);
 }
 
 // Per-env episode windows (finenv_stock_set_windows, finenv_portfolio_set_windows): int32 win[2][E],

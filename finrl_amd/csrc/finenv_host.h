@@ -88,8 +88,8 @@ inline int ready_block(Handle *h, bool attached, const char *what, const char *m
     return FINENV_ERR_INVALID;
 }
 
-// The two optional blocks of the stock and portfolio handles (members `has_hist`, `last`): null handle,
-// then ready_block().
+// The two optional blocks of an env handle (members `has_hist`, and `last` where the kind has one): null
+// handle, then ready_block().
 template <class H>
 int ready_history(H *h, const char *what)
 {
@@ -123,6 +123,47 @@ int set_history(Handle *h, Hist &stored, int &has_hist, const Hist *hist, const 
     stored = *hist;
     has_hist = 1;
     return FINENV_OK;
+}
+
+// finenv_<kind>_history_arm: `launch(h, mask, stream)` is the kind's own arm kernel, `what` the label of
+// a failed launch.
+template <class H, class Launch>
+int history_arm(H *h, const uint8_t *mask, void *stream, const char *what, Launch launch)
+{
+    if (const int rc = ready_history(h, "history_arm")) return rc;
+    const DeviceGuard guard(h->device);
+    launch(h, mask, (hipStream_t)stream);
+    return check_launch(h, what);
+}
+
+// The series finenv_<kind>_history_metrics reads, and the argument of the one kernel that does
+// (finenv_history.hip).  Every column is time-major, entry k of env e at [k * E + e].
+struct HistorySeries {
+    const double *value;          // the account value [capacity][E]
+    const double *plus;           // added to `value` entry by entry, or NULL (two-wave: cash + asset_value)
+    const double *ret;            // the recorded returns, read from entry 0, or NULL: total(k) / total(k-1) - 1
+                                  // from entry 1.  `plus` is ignored when `ret` is set (no kind has both).
+    const int32_t *len, *flags;   // [E]
+    int32_t need;                 // FINENV_HIST_* bits a row must carry to count (0: `flags` is not read)
+    int32_t capacity, E;
+    double annualization;
+    double *out;                  // [E][FINENV_STOCK_HISTORY_METRICS]
+};
+
+void launch_history_metrics(const HistorySeries &s, hipStream_t stream);
+
+// finenv_<kind>_history_metrics: `series(h)` names the kind's columns (need, capacity and E with them).
+template <class H, class Series>
+int history_metrics(H *h, double annualization, double *out, void *stream, const char *what, Series series)
+{
+    if (!h || !out) return FINENV_ERR_INVALID;
+    if (const int rc = ready_history(h, "history_metrics")) return rc;
+    const DeviceGuard guard(h->device);
+    HistorySeries s = series(h);
+    s.annualization = annualization;
+    s.out = out;
+    launch_history_metrics(s, (hipStream_t)stream);
+    return check_launch(h, what);
 }
 
 inline const char *last_error(const Handle *h) { return h ? h->err : "null handle"; }

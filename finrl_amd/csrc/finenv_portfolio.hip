@@ -357,15 +357,13 @@ __global__ void portfolio_last_stats_kernel(const PfParams p)
 }
 
 // -------------------------------------------------------------------------------------
-// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
-// instantiation of the step kernel above).
+// Episode history, off the step path: arming (the recording itself is the HIST instantiation of the
+// step kernel above, the metrics kernel is every kind's, finenv_history.hip).
 // -------------------------------------------------------------------------------------
 struct PfHistArgs {
     finenv_portfolio_history h;
     finenv_portfolio_state st;
     const uint8_t *mask;          // arm: envs to arm, or NULL = all
-    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
-    double annualization;
     int32_t E, N;
     uint32_t magicN;              // ceil(2^32 / N) for N >= 2
 };
@@ -395,20 +393,6 @@ __global__ __launch_bounds__(kArmThreads) void portfolio_history_arm_kernel(cons
         const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
         if (p.mask == nullptr || p.mask[e0 + el] != 0) p.h.weights[(size_t)e0 * N + f] = w0;
     }
-}
-
-// Backtest figures of each env's recorded series (series_metrics, finenv_dev.h).  The daily returns are
-// the RECORDED ones, leading 0 included, as the terminal branch's pandas calls take them (:145-152): every
-// entry carries one, so n_returns is len.
-__global__ void portfolio_history_metrics_kernel(const PfHistArgs p)
-{
-    const int E = p.E;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double *r = p.h.ret + e;
-    series_metrics(p.h.value + e, E, min(p.h.len[e], p.h.capacity), 0, p.annualization,
-                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
-                   [=](int k) { return r[(size_t)k * E]; });
 }
 
 }  // namespace
@@ -459,6 +443,14 @@ void launch_history_arm(const finenv_portfolio *h, const uint8_t *mask, hipStrea
     a.mask = mask;
     hipLaunchKernelGGL(portfolio_history_arm_kernel, dim3((a.E + kArmThreads - 1) / kArmThreads),
                        dim3(kArmThreads), 0, stream, a);
+}
+
+// the metrics' series: the values, and the RECORDED returns, leading 0 included, as the terminal branch's
+// pandas calls take them (:145-152)
+finenv_host::HistorySeries history_series(const finenv_portfolio *h)
+{
+    return {h->hist.value, nullptr, h->hist.ret, h->hist.len, h->hist.flags, 0, h->hist.capacity,
+            h->cfg.n_envs};
 }
 
 template <bool WIN, bool HIST>
@@ -579,23 +571,13 @@ int finenv_portfolio_set_history(finenv_portfolio *h, const finenv_portfolio_his
 
 int finenv_portfolio_history_arm(finenv_portfolio *h, const uint8_t *mask, void *stream)
 {
-    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    launch_history_arm(h, mask, (hipStream_t)stream);
-    return finenv_host::check_launch(h, "portfolio_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "portfolio_history_arm", launch_history_arm);
 }
 
 int finenv_portfolio_history_metrics(finenv_portfolio *h, double annualization, double *out, void *stream)
 {
-    if (!h || !out) return FINENV_ERR_INVALID;
-    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    PfHistArgs a = pf_hist_args(h);
-    a.out = out;
-    a.annualization = annualization;
-    hipLaunchKernelGGL(portfolio_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    return finenv_host::check_launch(h, "portfolio_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "portfolio_history_metrics",
+                                        history_series);
 }
 
 }  // extern "C"

@@ -99,10 +99,10 @@ __global__ void stock_last_stats_kernel(const Params p)
 
 // -------------------------------------------------------------------------------------
 // Episode history (finenv_stock_set_history): asset_memory / date_memory / actions_memory of every
-// env's current episode, kept on the device.  Three small kernels with their own argument struct; they
-// ride behind the step / init / reset kernels as separate launches on the same stream and read the
-// state those left in memory.  Time-major layout ([k][E], actions [k][E][N]): a lock-step batch writes
-// whole contiguous rows.
+// env's current episode, kept on the device.  Two small kernels with their own argument struct (the
+// metrics kernel is every kind's, finenv_history.hip); they ride behind the step / init / reset kernels
+// as separate launches on the same stream and read the state those left in memory.  Time-major layout
+// ([k][E], actions [k][E][N]): a lock-step batch writes whole contiguous rows.
 // -------------------------------------------------------------------------------------
 struct HistoryArgs {
     finenv_stock_history h;
@@ -111,8 +111,8 @@ struct HistoryArgs {
     const uint8_t *done;          // record: this step's done [E]
     const int32_t *realised;      // record: this step's realised trades [E][N] (NULL without actions)
     const uint8_t *mask;          // arm: envs to arm, or NULL = all
-    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
-    double annualization;
+    double *out;                  // (unused since the metrics kernel is finenv_history.hip's: the two stay so
+    double annualization;         //  that the record kernel behind every step keeps the bytes it was timed with)
     int32_t E, N;
     uint32_t magicN;              // ceil(2^32 / N) for N >= 2
 };
@@ -190,19 +190,6 @@ __global__ void stock_history_arm_kernel(const HistoryArgs p)
     p.h.flags[e] = 0;
 }
 
-// Backtest figures of each env's recorded series (series_metrics, finenv_dev.h).  The daily returns are
-// asset_memory.pct_change(): entry 0 carries none, so n_returns is len - 1.
-__global__ void stock_history_metrics_kernel(const HistoryArgs p)
-{
-    const int E = p.E;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double *a = p.h.asset + e;
-    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
-                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
-                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
-}
-
 }  // namespace
 
 // =====================================================================================
@@ -275,6 +262,12 @@ void launch_history_arm(const finenv_stock *h, const uint8_t *mask, hipStream_t 
     HistoryArgs a = make_history_args(h);
     a.mask = mask;
     hipLaunchKernelGGL(stock_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
+}
+
+// the metrics' series: asset_memory and its pct_change()
+finenv_host::HistorySeries history_series(const finenv_stock *h)
+{
+    return {h->hist.asset, nullptr, nullptr, h->hist.len, h->hist.flags, 0, h->hist.capacity, h->cfg.n_envs};
 }
 
 }  // namespace
@@ -535,23 +528,12 @@ int finenv_stock_set_history(finenv_stock *h, const finenv_stock_history *hist)
 
 int finenv_stock_history_arm(finenv_stock *h, const uint8_t *mask, void *stream)
 {
-    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    launch_history_arm(h, mask, (hipStream_t)stream);
-    return finenv_host::check_launch(h, "stock_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "stock_history_arm", launch_history_arm);
 }
 
 int finenv_stock_history_metrics(finenv_stock *h, double annualization, double *out, void *stream)
 {
-    if (!h || !out) return FINENV_ERR_INVALID;
-    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    HistoryArgs a = make_history_args(h);
-    a.out = out;
-    a.annualization = annualization;
-    hipLaunchKernelGGL(stock_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    return finenv_host::check_launch(h, "stock_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "stock_history_metrics", history_series);
 }
 
 }  // extern "C"

@@ -721,15 +721,13 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
 }
 
 // -------------------------------------------------------------------------------------
-// Episode history, off the step path: arming and the metrics (the recording itself is the HIST
-// instantiation of the step kernel above).
+// Episode history, off the step path: arming (the recording itself is the HIST instantiation of the
+// step kernel above, the metrics kernel is every kind's, finenv_history.hip).
 // -------------------------------------------------------------------------------------
 struct NpHistArgs {
     finenv_stocknp_history h;
     finenv_stocknp_state st;
     const uint8_t *mask;          // arm: envs to arm, or NULL = all
-    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
-    double annualization;
     int32_t E, N;
 };
 
@@ -748,19 +746,6 @@ __global__ __launch_bounds__(256) void stocknp_history_arm_kernel(const NpHistAr
     p.h.start[e] = NI(FINENV_NI_DAY);
     p.h.len[e] = 1;
     p.h.flags[e] = 0;
-}
-
-// Backtest figures of each env's recorded account values (series_metrics, finenv_dev.h): the returns
-// are asset[k] / asset[k-1] - 1 in fp64, entry 0 carries none, so n_returns is len - 1.
-__global__ void stocknp_history_metrics_kernel(const NpHistArgs p)
-{
-    const int E = p.E;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double *a = p.h.asset + e;
-    series_metrics(a, E, min(p.h.len[e], p.h.capacity), 1, p.annualization,
-                   p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
-                   [=](int k) { return a[(size_t)k * E] / a[(size_t)(k - 1) * E] - 1.0; });
 }
 
 }  // namespace
@@ -811,6 +796,11 @@ void launch_history_arm(const finenv_stocknp *h, const uint8_t *mask, hipStream_
     NpHistArgs a = np_hist_args(h);
     a.mask = mask;
     hipLaunchKernelGGL(stocknp_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
+}
+// the metrics' series: the account values and their pct_change() in fp64
+finenv_host::HistorySeries history_series(const finenv_stocknp *h)
+{
+    return {h->hist.asset, nullptr, nullptr, h->hist.len, h->hist.flags, 0, h->hist.capacity, h->cfg.n_envs};
 }
 // a step: the WIN instantiation while a window block is attached
 template <bool HIST>
@@ -935,23 +925,12 @@ int finenv_stocknp_set_history(finenv_stocknp *h, const finenv_stocknp_history *
 
 int finenv_stocknp_history_arm(finenv_stocknp *h, const uint8_t *mask, void *stream)
 {
-    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    launch_history_arm(h, mask, (hipStream_t)stream);
-    return finenv_host::check_launch(h, "stocknp_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "stocknp_history_arm", launch_history_arm);
 }
 
 int finenv_stocknp_history_metrics(finenv_stocknp *h, double annualization, double *out, void *stream)
 {
-    if (!h || !out) return FINENV_ERR_INVALID;
-    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    NpHistArgs a = np_hist_args(h);
-    a.out = out;
-    a.annualization = annualization;
-    hipLaunchKernelGGL(stocknp_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    return finenv_host::check_launch(h, "stocknp_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "stocknp_history_metrics", history_series);
 }
 
 }  // extern "C"

@@ -864,12 +864,14 @@ int finenv_stoploss_set_history(finenv_stoploss *h, const finenv_twowave_history
 
 int finenv_stoploss_history_arm(finenv_stoploss *h, const uint8_t *mask, void *stream)
 {
-    return tw_history_arm(h, mask, stream, "stoploss_history_arm");
+    return finenv_host::history_arm(h, mask, stream, "stoploss_history_arm",
+                                    tw_launch_history_arm<finenv_stoploss>);
 }
 
 int finenv_stoploss_history_metrics(finenv_stoploss *h, double annualization, double *out, void *stream)
 {
-    return tw_history_metrics(h, annualization, out, stream, "stoploss_history_metrics");
+    return finenv_host::history_metrics(h, annualization, out, stream, "stoploss_history_metrics",
+                                        tw_history_series<finenv_stoploss>);
 }
 
 int finenv_stoploss_reset(finenv_stoploss *h, const uint8_t *mask, float *obs_out, void *stream)

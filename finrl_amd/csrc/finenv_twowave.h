@@ -15,7 +15,7 @@
 
 // ---- episode history (finenv_<kind>_set_history) --------------------------------------------
 // account_information / actions_memory / transaction_memory of every env's current episode, kept on
-// the device: three small kernels with their own argument struct, shared by both envs -- the audit
+// the device: two small kernels with their own argument struct, shared by both envs -- the audit
 // head is the same and nothing here depends on the env kind.  They ride behind the step / reset
 // kernels as separate launches on the same stream and read what those left in memory: the audit row,
 // done and the caller's action tile.  The rule is in include/finenv.h.  The kernels are compiled once,
@@ -30,15 +30,14 @@ struct HistoryArgs {
     const uint8_t *mask;          // arm: envs to arm, or NULL = all
     const int32_t *date_index;    // arm: the state's FINENV_K?_DATE_INDEX row [E]
     const int32_t *win;           // arm: the window block [4][E], or NULL
-    double *out;                  // metrics: [E][FINENV_STOCK_HISTORY_METRICS]
-    double annualization;
+    double *out;                  // (unused since the metrics kernel is finenv_history.hip's: the two stay so
+    double annualization;         //  that the record kernel behind every step keeps the bytes it was timed with)
     int32_t E, N, n_days;
     uint32_t magicN;              // ceil(2^32 / N) for N >= 2
 };
 
 void launch_history_record(const HistoryArgs &a, hipStream_t stream);     // tw_history_record_kernel
 void launch_history_arm(const HistoryArgs &a, hipStream_t stream);        // tw_history_arm_kernel
-void launch_history_metrics(const HistoryArgs &a, hipStream_t stream);    // tw_history_metrics_kernel
 
 }  // namespace finenv_twowave
 
@@ -345,26 +344,12 @@ int tw_set_history(H *h, const finenv_twowave_history *hist)
         missing ? "set_history: null cash/asset_value/reward/reason/start/end/ntx/len/flags" : nullptr, 1);
 }
 
+// the metrics' series: the total assets cash + asset_value of the armed records and their pct_change()
 template <class H>
-int tw_history_arm(H *h, const uint8_t *mask, void *stream, const char *what)
+finenv_host::HistorySeries tw_history_series(const H *h)
 {
-    if (const int rc = finenv_host::ready_history(h, "history_arm")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    tw_launch_history_arm(h, mask, (hipStream_t)stream);
-    return finenv_host::check_launch(h, what);
-}
-
-template <class H>
-int tw_history_metrics(H *h, double annualization, double *out, void *stream, const char *what)
-{
-    if (!h || !out) return FINENV_ERR_INVALID;
-    if (const int rc = finenv_host::ready_history(h, "history_metrics")) return rc;
-    const finenv_host::DeviceGuard guard(h->device);
-    finenv_twowave::HistoryArgs a = tw_history_args(h);
-    a.out = out;
-    a.annualization = annualization;
-    finenv_twowave::launch_history_metrics(a, (hipStream_t)stream);
-    return finenv_host::check_launch(h, what);
+    return {h->hist.cash, h->hist.asset_value, nullptr, h->hist.len, h->hist.flags, FINENV_HIST_ARMED,
+            h->hist.capacity, h->cfg.n_envs};
 }
 
 inline dim3 tw_grid(int E) { return dim3((unsigned)((E + kWaveSize - 1) / kWaveSize)); }   // one block per 64 envs

@@ -1,9 +1,10 @@
 // finenv_twowave_history.hip -- MI355X (gfx950) kernels of the episode history of the cash-penalty and
 // stop-loss envs (finenv_{cashpenalty,stoploss}_set_history, include/finenv.h): the reference's
 // account_information / actions_memory / transaction_memory of every env's current episode, kept on the
-// device.  The record is a copy of the audit row both step kernels write, so one set of kernels serves
-// both envs; finenv_twowave.h declares their argument and launchers and holds the host side.  Time-major
-// layout ([k][E], transactions / actions [k][E][N]): a lock-step batch writes whole contiguous rows.
+// device: the record and the arm kernel (the metrics kernel is every kind's, finenv_history.hip).  The
+// record is a copy of the audit row both step kernels write, so one set of kernels serves both envs;
+// finenv_twowave.h declares their argument and launchers and holds the host side.  Time-major layout
+// ([k][E], transactions / actions [k][E][N]): a lock-step batch writes whole contiguous rows.
 // An object of its own: the two step files keep exactly the kernels they had.
 
 #include <hip/hip_runtime.h>
@@ -125,20 +126,6 @@ __global__ void tw_history_arm_kernel(const HistoryArgs p)
     p.h.end[e] = p.win != nullptr ? min(max(p.win[(size_t)3 * E + e], 1), p.n_days) : p.n_days;
 }
 
-// Backtest figures of each env's recorded total assets cash + asset_value (series_metrics_of,
-// finenv_dev.h).  The daily returns are pct_change(): entry 0 carries none, so n_returns is len - 1.
-__global__ void tw_history_metrics_kernel(const HistoryArgs p)
-{
-    const int E = p.E;
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const double *c = p.h.cash + e, *a = p.h.asset_value + e;
-    const auto total = [=](int k) { return c[(size_t)k * E] + a[(size_t)k * E]; };
-    const int len = (p.h.flags[e] & FINENV_HIST_ARMED) ? min(p.h.len[e], p.h.capacity) : 0;
-    series_metrics_of(total, len, 1, p.annualization, p.out + (size_t)e * FINENV_STOCK_HISTORY_METRICS,
-                      [=](int k) { return total(k) / total(k - 1) - 1.0; });
-}
-
 }  // namespace
 
 namespace finenv_twowave {
@@ -152,11 +139,6 @@ void launch_history_record(const HistoryArgs &a, hipStream_t stream)
 void launch_history_arm(const HistoryArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(tw_history_arm_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
-}
-
-void launch_history_metrics(const HistoryArgs &a, hipStream_t stream)
-{
-    hipLaunchKernelGGL(tw_history_metrics_kernel, dim3((a.E + 255) / 256), dim3(256), 0, stream, a);
 }
 
 }  // namespace finenv_twowave

@@ -232,7 +232,8 @@ def dollar_action_memory_frame(dates, actions, transactions, end, length, ntx):
 # ---------------------------------------------------------------------- the device side
 class _Record:
     """A device-resident episode record: what ``EpisodeHistory``, ``PortfolioEpisodeHistory``,
-    ``CryptoEpisodeHistory`` and ``TwoWaveEpisodeHistory`` are made of.  A subclass declares its data:
+    ``CryptoEpisodeHistory``, ``StockNpEpisodeHistory`` and ``TwoWaveEpisodeHistory`` are made of.  A
+    subclass declares its data:
       ``_ptrs_cls``    the ctypes struct of finenv_<kind>_set_history (one pointer per tensor, capacity)
       ``_series``      ((name, dtype), ...): the time-major tensors [capacity, E]; those named in the
                        constructor's ``without`` are not recorded (None)

@@ -231,8 +231,9 @@ class BatchedEnv:
 
 class WindowedEnv(BatchedEnv):
     """Per-env episode windows over one shared panel: the host side of ``finenv_<kind>_set_windows``,
-    shared by VecStockTradingEnv, VecStockPortfolioEnv, VecCryptoEnv and VecStockTradingEnvNP
-    (``num_envs`` and ``max_step`` are theirs).  What differs between the kinds is named by hooks:
+    shared by VecStockTradingEnv, VecStockPortfolioEnv, VecCryptoEnv, VecStockTradingEnvNP,
+    VecCashPenaltyEnv and VecStopLossEnv (``num_envs`` and ``max_step`` are theirs).  What differs
+    between the kinds is named by hooks:
     ``_window_rows`` (the panel's row count), ``_window_min`` (the shortest window that makes an
     episode), ``_window_max_step`` (``max_step`` of the longest window), ``_window_active`` (the
     kernel keeps the running episodes' windows apart from the pending ones) and

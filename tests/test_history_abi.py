@@ -1,0 +1,175 @@
+"""CPU-side checks of the episode-history C ABI (finenv_<kind>_set_history / _history_arm /
+_history_metrics), one table for the six env kinds: the header declares the struct and the three entry
+points and the library exports them, ABI version and struct sizes are unchanged, and the entry points
+validate their arguments without a GPU.  What is a kind's own (builders, readers, the step's checks) is in
+tests/test_<kind>_history_abi.py."""
+import ctypes as C
+import itertools
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HDR = os.path.join(ROOT, "include", "finenv.h")
+E, N = 64, 5
+DTYPES = {"double": np.float64, "int32_t": np.int32, "float": np.float32, "uint8_t": np.uint8}
+# the v3 structs, by their sizes as that version laid them out (the history structs are in no size table)
+V3_STRUCT_SIZES = [72, 24, 16, 24, 16, 16, 56, 24, 24, 72, 24, 24, 80, 24, 16, 96, 24, 16]
+METRICS = ("n_returns", "cumulative_return", "mean", "std", "sharpe", "max_drawdown")
+
+_TAIL = [("int32_t", "len", "E"), ("int32_t", "flags", "E")]
+_TWOWAVE = dict(
+    struct="finenv_twowave_history", ptrs="TwoWaveHistoryPtrs", metrics="TWOWAVE_HISTORY_METRICS",
+    # (C type, member, host buffer shape: k = capacity, E envs, N assets); capacity follows
+    fields=[("double", "cash", "kE"), ("double", "asset_value", "kE"), ("double", "reward", "kE"),
+            ("int32_t", "reason", "kE"), ("double", "transactions", "kEN"), ("float", "actions", "kEN"),
+            ("int32_t", "start", "E"), ("int32_t", "end", "E"), ("int32_t", "ntx", "E")] + _TAIL,
+    optional=("transactions", "actions"), min_capacity=1)          # an armed record is empty
+_TWOWAVE_CFG = (E, N, 2, 50, 0, 1, 0, 0, 100.0, 1e-3, 1e-3, 1e6, 0.1, 0.0)
+KINDS = {
+    "stock": dict(
+        struct="finenv_stock_history", ptrs="StockHistoryPtrs", metrics="STOCK_HISTORY_METRICS",
+        config=lambda nat: nat.StockConfig(E, N, 8, 100, 100, 0, 1, 1, 1, 0, 1e-3, 1e-3, 1e-4, 0.0),
+        fields=[("double", "asset", "kE"), ("int32_t", "row", "kE"), ("int32_t", "actions", "jEN")] + _TAIL,
+        optional=("actions",), min_capacity=2),                    # arming writes entry 0
+    "portfolio": dict(
+        struct="finenv_portfolio_history", ptrs="PortfolioHistoryPtrs", metrics="PORTFOLIO_HISTORY_METRICS",
+        config=lambda nat: nat.PortfolioConfig(E, N, 4, 50, 1e6),
+        fields=[("double", "value", "kE"), ("double", "ret", "kE"), ("int32_t", "row", "kE"),
+                ("float", "weights", "kEN")] + _TAIL,
+        optional=("weights",), min_capacity=2),
+    "crypto": dict(
+        struct="finenv_crypto_history", ptrs="CryptoHistoryPtrs", metrics="CRYPTO_HISTORY_METRICS",
+        config=lambda nat: nat.CryptoConfig(E, N, 4, 50, 1, 0, 1e6, 1e-3, 1e-3, 0.99),
+        fields=[("double", "asset", "kE"), ("double", "holdings", "kE"), ("float", "stocks", "kNE"),
+                ("int32_t", "start", "E")] + _TAIL,
+        optional=("stocks",), min_capacity=2),
+    "stocknp": dict(
+        struct="finenv_stocknp_history", ptrs="StockNpHistoryPtrs", metrics="STOCKNP_HISTORY_METRICS",
+        config=lambda nat: nat.StockNpConfig(E, N, 10, 50, 10, 0, 100.0, 1e-3, 1e-3, 2 ** -11, 0.99, 0.0),
+        fields=[("double", "asset", "kE"), ("uint8_t", "tag", "kE"), ("float", "stocks", "kNE"),
+                ("int32_t", "start", "E")] + _TAIL,
+        optional=("tag", "stocks"), min_capacity=2),
+    "cashpenalty": dict(_TWOWAVE, config=lambda nat: nat.CashPenaltyConfig(*_TWOWAVE_CFG)),
+    "stoploss": dict(_TWOWAVE, config=lambda nat: nat.StopLossConfig(*_TWOWAVE_CFG, 0.9, 1.2)),
+}
+
+
+@pytest.fixture(scope="module")
+def L():
+    from finrl_amd import _native
+    _native.build()
+    return _native.lib()
+
+
+def _host_history(nat, kind, cap=5, off=()):
+    """A history struct over host arrays (the members named in `off` NULL): enough for the argument
+    checks, which never launch."""
+    k = KINDS[kind]
+    dims = {"k": cap, "j": cap - 1, "E": E, "N": N}
+    bufs = {f: np.zeros([dims[d] for d in shape], DTYPES[t]) for t, f, shape in k["fields"]}
+    ptrs = [None if f in off else bufs[f].ctypes.data_as(C.c_void_p) for _, f, _ in k["fields"]]
+    return getattr(nat, k["ptrs"])(*ptrs, cap), bufs
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_header_declares_and_library_exports_the_history_api(L, kind):
+    from finrl_amd import _native as nat
+    k = KINDS[kind]
+    hdr = open(HDR).read()
+    for name in ("set_history", "history_arm", "history_metrics"):
+        fn = f"finenv_{kind}_{name}"
+        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
+        assert hasattr(L, fn), fn
+    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (k["struct"], k["struct"]), hdr, flags=re.S)
+    assert m, "struct " + k["struct"]
+    want = [(t, f) for t, f, _ in k["fields"]] + [("int32_t", "capacity")]
+    assert re.findall(r"^\s*(double|int32_t|float|uint8_t)\s+\*?(\w+);", m.group(1), flags=re.M) == want
+    pointers = re.findall(r"^\s*\w+\s+\*(\w+);", m.group(1), flags=re.M)
+    assert pointers == [f for _, f in want[:-1]]             # every member but capacity is a pointer
+    ptrs = getattr(nat, k["ptrs"])
+    assert [f[0] for f in ptrs._fields_] == [f for _, f in want]
+    assert [f[1] for f in ptrs._fields_] == [C.c_void_p] * (len(want) - 1) + [C.c_int32]
+    cols = re.findall(r"^\s+FINENV_HM_([A-Z0-9_]+)", hdr, flags=re.M)
+    assert tuple(c.lower() for c in cols) == getattr(nat, k["metrics"]) == nat.STOCK_HISTORY_METRICS == METRICS
+
+
+def test_flag_values_abi_version_and_struct_sizes(L):
+    """What no kind changes: the flag bits, and that the history API is additive -- same ABI version, same
+    v3 structs."""
+    from finrl_amd import _native as nat
+    hdr = open(HDR).read()
+    assert re.search(r"FINENV_HIST_COMPLETE\s*=\s*1\b", hdr) and nat.HIST_COMPLETE == 1
+    assert re.search(r"FINENV_HIST_OVERFLOW\s*=\s*2\b", hdr) and nat.HIST_OVERFLOW == 2
+    assert re.search(r"FINENV_HIST_ARMED\s*=\s*4\b", hdr) and nat.HIST_ARMED == 4
+    assert "#define FINENV_ABI_VERSION 3" in hdr
+    assert L.finenv_abi_version() == nat.ABI_VERSION == 3
+    assert [L.finenv_struct_size(i) for i in range(18)] == V3_STRUCT_SIZES
+    assert L.finenv_struct_size(18) == -1
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_entry_points_validate_arguments(L, kind):
+    from finrl_amd import _native as nat
+    k = KINDS[kind]
+    fn = {n: getattr(L, f"finenv_{kind}_{n}") for n in
+          ("set_history", "history_arm", "history_metrics", "create", "destroy", "last_error")}
+    written = []                                             # every host buffer a struct pointed to
+
+    def host_history(**kw):
+        hist, bufs = _host_history(nat, kind, **kw)
+        written.extend(bufs.values())
+        return hist
+
+    hist = host_history()
+    out = np.zeros((E, len(METRICS)))
+    outp = out.ctypes.data_as(C.c_void_p)
+    # NULL handle
+    assert fn["set_history"](None, C.byref(hist)) == -1
+    assert fn["history_arm"](None, None, None) == -1
+    assert fn["history_metrics"](None, 2.0, outp, None) == -1
+    h = C.c_void_p()
+    cfg = k["config"](nat)
+    assert fn["create"](C.byref(cfg), C.byref(h)) == 0
+    try:
+        # nothing attached (the default): arm / metrics refuse, with a message
+        assert fn["history_arm"](h, None, None) == -1
+        assert b"no history attached" in fn["last_error"](h)
+        assert fn["history_metrics"](h, 2.0, outp, None) == -1
+        assert b"no history attached" in fn["last_error"](h)
+        # a NULL mandatory pointer, a capacity below the kind's minimum
+        for _, name, _ in k["fields"]:
+            if name in k["optional"]:
+                continue
+            bad = host_history(off=(name,))
+            assert fn["set_history"](h, C.byref(bad)) == -1, name
+            assert b"null" in fn["last_error"](h)
+        for cap in (*range(k["min_capacity"] - 1, -1, -1), -3):
+            bad = host_history()
+            bad.capacity = cap
+            assert fn["set_history"](h, C.byref(bad)) == -1, cap
+            assert b"capacity" in fn["last_error"](h)
+        # a refused struct attaches nothing
+        assert fn["history_arm"](h, None, None) == -1
+        assert b"no history attached" in fn["last_error"](h)
+        # attaching works before bind, whichever optional tensors are NULL and at the minimum capacity
+        # (one entry for the two-wave kinds); arm / metrics then need the bound state
+        for n_off in range(len(k["optional"]), -1, -1):
+            for off in itertools.combinations(k["optional"], n_off):
+                now = host_history(off=off)
+                assert fn["set_history"](h, C.byref(now)) == 0, off
+        least = host_history(cap=k["min_capacity"])
+        assert fn["set_history"](h, C.byref(least)) == 0
+        assert fn["set_history"](h, C.byref(hist)) == 0
+        assert fn["history_arm"](h, None, None) == -2
+        assert fn["history_metrics"](h, 2.0, outp, None) == -2
+        assert fn["history_metrics"](h, 2.0, None, None) == -1
+        # NULL detaches again
+        assert fn["set_history"](h, None) == 0
+        assert fn["history_arm"](h, None, None) == -1
+        assert fn["history_metrics"](h, 2.0, outp, None) == -1
+    finally:
+        fn["destroy"](h)
+    assert not any(b.any() for b in written) and not out.any()

@@ -1,110 +1,15 @@
-"""CPU-side checks of the portfolio env's episode history (finenv_portfolio_set_history): the header
-declares the struct and the three entry points and the library exports them, ABI version and struct
-sizes are unchanged, the entry points validate their arguments without a GPU, and the frame builders of
-finrl_amd.history reproduce the frames the unmodified reference returned
+"""CPU-side checks of the portfolio env's episode history (finenv_portfolio_set_history; the C ABI of its
+entry points is in tests/test_history_abi.py): the frame builders of finrl_amd.history reproduce the
+frames the unmodified reference returned
 (tests/golden/harness_portfolio_*.npz, written by tests/golden/make_golden_portfolio_history.py) from
 the reference's own memories laid out as the device holds them."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-
-@pytest.fixture(scope="module")
-def L():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
-
-
-def _host_history(nat, E=64, N=5, cap=5, weights=True):
-    """A history struct over host arrays: enough for the argument checks, which never launch."""
-    bufs = dict(value=np.zeros((cap, E)), ret=np.zeros((cap, E)), row=np.zeros((cap, E), np.int32),
-                weights=np.zeros((cap, E, N), np.float32), len=np.zeros(E, np.int32),
-                flags=np.zeros(E, np.int32))
-    ptr = {k: v.ctypes.data_as(C.c_void_p) for k, v in bufs.items()}
-    hist = nat.PortfolioHistoryPtrs(ptr["value"], ptr["ret"], ptr["row"],
-                                    ptr["weights"] if weights else None, ptr["len"], ptr["flags"], cap)
-    return hist, bufs
-
-
-def test_header_declares_and_library_exports_the_history_api(L):
-    hdr = open(HDR).read()
-    for fn in ("finenv_portfolio_set_history", "finenv_portfolio_history_arm",
-               "finenv_portfolio_history_metrics"):
-        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
-        assert hasattr(L, fn), fn
-    m = re.search(r"typedef struct finenv_portfolio_history \{(.*?)\} finenv_portfolio_history;", hdr,
-                  flags=re.S)
-    assert m, "struct finenv_portfolio_history"
-    fields = re.findall(r"^\s*(double|int32_t|float)\s+\*?(\w+);", m.group(1), flags=re.M)
-    assert fields == [("double", "value"), ("double", "ret"), ("int32_t", "row"), ("float", "weights"),
-                      ("int32_t", "len"), ("int32_t", "flags"), ("int32_t", "capacity")]
-    from finrl_amd import _native as nat
-    assert [f[0] for f in nat.PortfolioHistoryPtrs._fields_] == [f[1] for f in fields]
-    assert nat.PORTFOLIO_HISTORY_METRICS == ("n_returns", "cumulative_return", "mean", "std", "sharpe",
-                                             "max_drawdown")
-    # additive: same ABI version, same v3 structs
-    assert "#define FINENV_ABI_VERSION 3" in hdr
-    assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    sizes = [72, 24, 16, 24, 16, 16, 56, 24, 24, 72, 24, 24, 80, 24, 16, 96, 24, 16]
-    assert [L.finenv_struct_size(i) for i in range(18)] == sizes
-    assert L.finenv_struct_size(18) == -1
-
-
-def test_entry_points_validate_arguments(L):
-    from finrl_amd import _native as nat
-    hist, bufs = _host_history(nat)
-    out = np.zeros((64, 6))
-    outp = out.ctypes.data_as(C.c_void_p)
-    # NULL handle
-    assert L.finenv_portfolio_set_history(None, C.byref(hist)) == -1
-    assert L.finenv_portfolio_history_arm(None, None, None) == -1
-    assert L.finenv_portfolio_history_metrics(None, 2.0, outp, None) == -1
-    h = C.c_void_p()
-    cfg = nat.PortfolioConfig(64, 5, 4, 50, 1e6)
-    assert L.finenv_portfolio_create(C.byref(cfg), C.byref(h)) == 0
-    try:
-        # nothing attached (the default): arm / metrics refuse, with a message
-        assert L.finenv_portfolio_history_arm(h, None, None) == -1
-        assert b"no history attached" in L.finenv_portfolio_last_error(h)
-        assert L.finenv_portfolio_history_metrics(h, 2.0, outp, None) == -1
-        assert b"no history attached" in L.finenv_portfolio_last_error(h)
-        # a NULL mandatory pointer, capacity < 2
-        for name in ("value", "ret", "row", "len", "flags"):
-            bad, _ = _host_history(nat)
-            setattr(bad, name, None)
-            assert L.finenv_portfolio_set_history(h, C.byref(bad)) == -1, name
-            assert b"null" in L.finenv_portfolio_last_error(h)
-        for cap in (1, 0, -3):
-            bad, _ = _host_history(nat)
-            bad.capacity = cap
-            assert L.finenv_portfolio_set_history(h, C.byref(bad)) == -1, cap
-            assert b"capacity" in L.finenv_portfolio_last_error(h)
-        # a refused struct attaches nothing
-        assert L.finenv_portfolio_history_arm(h, None, None) == -1
-        # attaching works before bind (weights may be NULL); arm / metrics then need the bound state
-        now, _ = _host_history(nat, weights=False)
-        assert L.finenv_portfolio_set_history(h, C.byref(now)) == 0
-        assert L.finenv_portfolio_set_history(h, C.byref(hist)) == 0
-        assert L.finenv_portfolio_history_arm(h, None, None) == -2
-        assert L.finenv_portfolio_history_metrics(h, 2.0, outp, None) == -2
-        assert L.finenv_portfolio_history_metrics(h, 2.0, None, None) == -1
-        # NULL detaches again
-        assert L.finenv_portfolio_set_history(h, None) == 0
-        assert L.finenv_portfolio_history_arm(h, None, None) == -1
-        assert L.finenv_portfolio_history_metrics(h, 2.0, outp, None) == -1
-    finally:
-        L.finenv_portfolio_destroy(h)
-    assert not any(b.any() for b in bufs.values())
-
-
 FIXTURES = ("dow30", "n5", "n2k1", "const")
 
 

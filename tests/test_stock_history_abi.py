@@ -1,17 +1,14 @@
-"""CPU-side checks of the stock env's episode history (finenv_stock_set_history): the header declares
-the struct and the three entry points and the library exports them, ABI version and struct sizes are
-unchanged, the entry points validate their arguments without a GPU, and the frame builders of
-finrl_amd.history reproduce the reference's frames (tests/golden/harness_sb3_stock.npz) from hand-made
-host arrays."""
+"""CPU-side checks of the stock env's episode history (finenv_stock_set_history; the C ABI of its entry
+points is in tests/test_history_abi.py): a step that records actions needs `realised`, and the frame
+builders of finrl_amd.history reproduce the reference's frames (tests/golden/harness_sb3_stock.npz) from
+hand-made host arrays."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
@@ -35,78 +32,6 @@ def _host_history(nat, E=64, N=30, cap=5, actions=True):
     hist = nat.StockHistoryPtrs(ptr["asset"], ptr["row"], ptr["actions"] if actions else None,
                                 ptr["len"], ptr["flags"], cap)
     return hist, bufs
-
-
-def test_header_declares_and_library_exports_the_history_api(L):
-    hdr = open(HDR).read()
-    for fn in ("finenv_stock_set_history", "finenv_stock_history_arm", "finenv_stock_history_metrics"):
-        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
-        assert hasattr(L, fn), fn
-    m = re.search(r"typedef struct finenv_stock_history \{(.*?)\} finenv_stock_history;", hdr, flags=re.S)
-    assert m, "struct finenv_stock_history"
-    fields = re.findall(r"^\s*(double|int32_t)\s+\*?(\w+);", m.group(1), flags=re.M)
-    assert fields == [("double", "asset"), ("int32_t", "row"), ("int32_t", "actions"),
-                      ("int32_t", "len"), ("int32_t", "flags"), ("int32_t", "capacity")]
-    from finrl_amd import _native as nat
-    assert [f[0] for f in nat.StockHistoryPtrs._fields_] == [f[1] for f in fields]
-    cols = re.findall(r"^\s+FINENV_HM_([A-Z0-9_]+)", hdr, flags=re.M)
-    assert tuple(c.lower() for c in cols) == nat.STOCK_HISTORY_METRICS
-    assert re.search(r"FINENV_HIST_COMPLETE\s*=\s*1\b", hdr) and nat.HIST_COMPLETE == 1
-    assert re.search(r"FINENV_HIST_OVERFLOW\s*=\s*2\b", hdr) and nat.HIST_OVERFLOW == 2
-    # additive: same ABI version, same v3 structs
-    assert "#define FINENV_ABI_VERSION 3" in hdr
-    assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    # the v3 structs, by their sizes as that version laid them out
-    sizes = [72, 24, 16, 24, 16, 16, 56, 24, 24, 72, 24, 24, 80, 24, 16, 96, 24, 16]
-    assert [L.finenv_struct_size(i) for i in range(18)] == sizes
-    assert L.finenv_struct_size(18) == -1
-
-
-def test_entry_points_validate_arguments(L):
-    from finrl_amd import _native as nat
-    hist, bufs = _host_history(nat)
-    out = np.zeros((64, 6))
-    outp = out.ctypes.data_as(C.c_void_p)
-    # NULL handle
-    assert L.finenv_stock_set_history(None, C.byref(hist)) == -1
-    assert L.finenv_stock_history_arm(None, None, None) == -1
-    assert L.finenv_stock_history_metrics(None, 2.0, outp, None) == -1
-    h = C.c_void_p()
-    cfg = _cfg(nat)
-    assert L.finenv_stock_create(C.byref(cfg), C.byref(h)) == 0
-    try:
-        # nothing attached (the default): arm / metrics refuse, with a message
-        assert L.finenv_stock_history_arm(h, None, None) == -1
-        assert b"no history attached" in L.finenv_stock_last_error(h)
-        assert L.finenv_stock_history_metrics(h, 2.0, outp, None) == -1
-        assert b"no history attached" in L.finenv_stock_last_error(h)
-        # a NULL mandatory pointer, capacity < 2
-        for name in ("asset", "row", "len", "flags"):
-            bad, _ = _host_history(nat)
-            setattr(bad, name, None)
-            assert L.finenv_stock_set_history(h, C.byref(bad)) == -1, name
-            assert b"null" in L.finenv_stock_last_error(h)
-        for cap in (1, 0, -3):
-            bad, _ = _host_history(nat)
-            bad.capacity = cap
-            assert L.finenv_stock_set_history(h, C.byref(bad)) == -1, cap
-            assert b"capacity" in L.finenv_stock_last_error(h)
-        # a refused struct attaches nothing
-        assert L.finenv_stock_history_arm(h, None, None) == -1
-        # attaching works before bind (actions may be NULL); arm / metrics then need the bound state
-        noact, _ = _host_history(nat, actions=False)
-        assert L.finenv_stock_set_history(h, C.byref(noact)) == 0
-        assert L.finenv_stock_set_history(h, C.byref(hist)) == 0
-        assert L.finenv_stock_history_arm(h, None, None) == -2
-        assert L.finenv_stock_history_metrics(h, 2.0, outp, None) == -2
-        assert L.finenv_stock_history_metrics(h, 2.0, None, None) == -1
-        # NULL detaches again
-        assert L.finenv_stock_set_history(h, None) == 0
-        assert L.finenv_stock_history_arm(h, None, None) == -1
-        assert L.finenv_stock_history_metrics(h, 2.0, outp, None) == -1
-    finally:
-        L.finenv_stock_destroy(h)
-    assert not any(b.any() for b in bufs.values())
 
 
 def test_step_with_recorded_actions_needs_realised(L):

@@ -1,118 +1,19 @@
-"""CPU-side checks of the array-state stock env's episode history (finenv_stocknp_set_history): the
-header declares the struct and the three entry points and the library exports them, ABI version and
-struct sizes are unchanged, the entry points validate their arguments without a GPU, and the builders
-and readers of finrl_amd.history reproduce, from the reference-recorded total_asset / ta_tag of
+"""CPU-side checks of the array-state stock env's episode history (finenv_stocknp_set_history; the C ABI
+of its entry points is in tests/test_history_abi.py): the builders and readers of finrl_amd.history
+reproduce, from the reference-recorded total_asset / ta_tag of
 tests/golden/stocknp_*.npz laid out as the device holds them, the list DRLAgent.DRL_prediction returns
 (agents/elegantrl/models.py:105-131), element types included."""
-import ctypes as C
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-MANDATORY = ("asset", "start", "len", "flags")
-FUNCS = ("finenv_stocknp_set_history", "finenv_stocknp_history_arm", "finenv_stocknp_history_metrics")
 NAMES = sorted(os.path.basename(p)[len("stocknp_"):-4]
                for p in glob.glob(os.path.join(GOLDEN, "stocknp_*.npz")))
 SCALARS = (float, np.float32, np.float64)          # FINENV_NT_PY / _F32 / _F64
-
-
-@pytest.fixture(scope="module")
-def L():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
-
-
-def _host_history(nat, E=64, N=5, cap=5, tag=True, stocks=True):
-    """A history struct over host arrays: enough for the argument checks, which never launch."""
-    bufs = dict(asset=np.zeros((cap, E)), tag=np.zeros((cap, E), np.uint8),
-                stocks=np.zeros((cap, N, E), np.float32), start=np.zeros(E, np.int32),
-                len=np.zeros(E, np.int32), flags=np.zeros(E, np.int32))
-    ptr = {k: v.ctypes.data_as(C.c_void_p) for k, v in bufs.items()}
-    hist = nat.StockNpHistoryPtrs(ptr["asset"], ptr["tag"] if tag else None,
-                                  ptr["stocks"] if stocks else None, ptr["start"], ptr["len"],
-                                  ptr["flags"], cap)
-    return hist, bufs
-
-
-def test_header_declares_and_library_exports_the_history_api(L):
-    hdr = open(HDR).read()
-    for fn in FUNCS:
-        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
-        assert hasattr(L, fn), fn
-    m = re.search(r"typedef struct finenv_stocknp_history \{(.*?)\} finenv_stocknp_history;", hdr,
-                  flags=re.S)
-    assert m, "struct finenv_stocknp_history"
-    fields = re.findall(r"^\s*(double|int32_t|float|uint8_t)\s+\*?(\w+);", m.group(1), flags=re.M)
-    assert fields == [("double", "asset"), ("uint8_t", "tag"), ("float", "stocks"),
-                      ("int32_t", "start"), ("int32_t", "len"), ("int32_t", "flags"),
-                      ("int32_t", "capacity")]
-    pointers = re.findall(r"^\s*\w+\s+\*(\w+);", m.group(1), flags=re.M)
-    assert pointers == [f[1] for f in fields[:-1]]          # every member but capacity is a pointer
-    from finrl_amd import _native as nat
-    assert [f[0] for f in nat.StockNpHistoryPtrs._fields_] == [f[1] for f in fields]
-    assert [f[1] for f in nat.StockNpHistoryPtrs._fields_] == [C.c_void_p] * 6 + [C.c_int32]
-    assert nat.STOCKNP_HISTORY_METRICS == nat.STOCK_HISTORY_METRICS
-    # additive: same ABI version, same v3 structs (the history structs are in no size table)
-    assert "#define FINENV_ABI_VERSION 3" in hdr
-    assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    sizes = [72, 24, 16, 24, 16, 16, 56, 24, 24, 72, 24, 24, 80, 24, 16, 96, 24, 16]
-    assert [L.finenv_struct_size(i) for i in range(18)] == sizes
-    assert L.finenv_struct_size(18) == -1
-
-
-def test_entry_points_validate_arguments(L):
-    from finrl_amd import _native as nat
-    hist, bufs = _host_history(nat)
-    out = np.zeros((64, 6))
-    outp = out.ctypes.data_as(C.c_void_p)
-    # NULL handle
-    assert L.finenv_stocknp_set_history(None, C.byref(hist)) == -1
-    assert L.finenv_stocknp_history_arm(None, None, None) == -1
-    assert L.finenv_stocknp_history_metrics(None, 2.0, outp, None) == -1
-    h = C.c_void_p()
-    cfg = nat.StockNpConfig(64, 5, 10, 50, 10, 0, 100.0, 1e-3, 1e-3, 2 ** -11, 0.99, 0.0)
-    assert L.finenv_stocknp_create(C.byref(cfg), C.byref(h)) == 0
-    try:
-        # nothing attached (the default): arm / metrics refuse, with the crypto env's error and message
-        assert L.finenv_stocknp_history_arm(h, None, None) == -1
-        assert b"no history attached" in L.finenv_stocknp_last_error(h)
-        assert L.finenv_stocknp_history_metrics(h, 2.0, outp, None) == -1
-        assert b"no history attached" in L.finenv_stocknp_last_error(h)
-        # a NULL mandatory pointer, capacity < 2
-        for name in MANDATORY:
-            bad, _ = _host_history(nat)
-            setattr(bad, name, None)
-            assert L.finenv_stocknp_set_history(h, C.byref(bad)) == -1, name
-            assert b"null" in L.finenv_stocknp_last_error(h)
-        for cap in (1, 0, -3):
-            bad, _ = _host_history(nat)
-            bad.capacity = cap
-            assert L.finenv_stocknp_set_history(h, C.byref(bad)) == -1, cap
-            assert b"capacity" in L.finenv_stocknp_last_error(h)
-        # a refused struct attaches nothing
-        assert L.finenv_stocknp_history_arm(h, None, None) == -1
-        # attaching works before bind (tag and stocks may be NULL); arm / metrics then need the state
-        for tag, stocks in ((False, False), (True, False), (False, True)):
-            now, _ = _host_history(nat, tag=tag, stocks=stocks)
-            assert L.finenv_stocknp_set_history(h, C.byref(now)) == 0
-        assert L.finenv_stocknp_set_history(h, C.byref(hist)) == 0
-        assert L.finenv_stocknp_history_arm(h, None, None) == -2
-        assert L.finenv_stocknp_history_metrics(h, 2.0, outp, None) == -2
-        assert L.finenv_stocknp_history_metrics(h, 2.0, None, None) == -1
-        # NULL detaches again
-        assert L.finenv_stocknp_set_history(h, None) == 0
-        assert L.finenv_stocknp_history_arm(h, None, None) == -1
-        assert L.finenv_stocknp_history_metrics(h, 2.0, outp, None) == -1
-    finally:
-        L.finenv_stocknp_destroy(h)
-    assert not any(b.any() for b in bufs.values()) and not out.any()
 
 
 def _fixture(name):

@@ -1,129 +1,17 @@
 """CPU-side checks of the episode history of the cash-penalty and stop-loss envs
-(finenv_{cashpenalty,stoploss}_set_history): the header declares the struct and the six entry points and
-the library exports them, ABI version and struct sizes are unchanged, the entry points validate their
-arguments without a GPU, and the frame builders of finrl_amd.history reproduce, from the reference's
+(finenv_{cashpenalty,stoploss}_set_history; the C ABI of their entry points is in
+tests/test_history_abi.py): the frame builders of finrl_amd.history reproduce, from the reference's
 recorded account_* / action_* columns of tests/golden/harness_sb3_*.npz laid out as the device holds
 them, the frames save_asset_memory() / save_action_memory() return."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 KINDS = ("cashpenalty", "stoploss")
-FIELDS = [("double", "cash"), ("double", "asset_value"), ("double", "reward"), ("int32_t", "reason"),
-          ("double", "transactions"), ("float", "actions"), ("int32_t", "start"), ("int32_t", "end"),
-          ("int32_t", "ntx"), ("int32_t", "len"), ("int32_t", "flags"), ("int32_t", "capacity")]
-OPTIONAL = ("transactions", "actions")
-MANDATORY = tuple(f for _, f in FIELDS[:-1] if f not in OPTIONAL)
 FIXTURES = ("sb3_cashpenalty", "sb3_cashpenalty_patient", "sb3_stoploss", "sb3_stoploss_patient")
-
-
-@pytest.fixture(scope="module")
-def L():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
-
-
-def _host_history(nat, E=64, N=5, cap=5, **off):
-    """A history struct over host arrays: enough for the argument checks, which never launch."""
-    bufs = dict(cash=np.zeros((cap, E)), asset_value=np.zeros((cap, E)), reward=np.zeros((cap, E)),
-                reason=np.zeros((cap, E), np.int32), transactions=np.zeros((cap, E, N)),
-                actions=np.zeros((cap, E, N), np.float32), start=np.zeros(E, np.int32),
-                end=np.zeros(E, np.int32), ntx=np.zeros(E, np.int32), len=np.zeros(E, np.int32),
-                flags=np.zeros(E, np.int32))
-    ptrs = [None if off.get(f) is False else bufs[f].ctypes.data_as(C.c_void_p) for _, f in FIELDS[:-1]]
-    return nat.TwoWaveHistoryPtrs(*ptrs, cap), bufs
-
-
-def _config(nat, kind):
-    base = (64, 5, 2, 50, 0, 1, 0, 0, 100.0, 1e-3, 1e-3, 1e6, 0.1, 0.0)
-    return nat.CashPenaltyConfig(*base) if kind == "cashpenalty" else nat.StopLossConfig(*base, 0.9, 1.2)
-
-
-def test_header_declares_and_library_exports_the_history_api(L):
-    from finrl_amd import _native as nat
-    hdr = open(HDR).read()
-    for kind in KINDS:
-        for name in ("set_history", "history_arm", "history_metrics"):
-            fn = f"finenv_{kind}_{name}"
-            assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
-            assert hasattr(L, fn), fn
-    m = re.search(r"typedef struct finenv_twowave_history \{(.*?)\} finenv_twowave_history;", hdr,
-                  flags=re.S)
-    assert m, "struct finenv_twowave_history"
-    fields = re.findall(r"^\s*(double|int32_t|float|uint8_t)\s+\*?(\w+);", m.group(1), flags=re.M)
-    assert fields == FIELDS
-    pointers = re.findall(r"^\s*\w+\s+\*(\w+);", m.group(1), flags=re.M)
-    assert pointers == [f for _, f in FIELDS[:-1]]           # every member but capacity is a pointer
-    assert [f[0] for f in nat.TwoWaveHistoryPtrs._fields_] == [f for _, f in FIELDS]
-    assert [f[1] for f in nat.TwoWaveHistoryPtrs._fields_] == [C.c_void_p] * 11 + [C.c_int32]
-    assert nat.TWOWAVE_HISTORY_METRICS == nat.STOCK_HISTORY_METRICS
-    assert re.search(r"FINENV_HIST_ARMED\s*=\s*4\b", hdr) and nat.HIST_ARMED == 4
-    # additive: same ABI version, same v3 structs (the history structs are in no size table)
-    assert "#define FINENV_ABI_VERSION 3" in hdr
-    assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    sizes = [72, 24, 16, 24, 16, 16, 56, 24, 24, 72, 24, 24, 80, 24, 16, 96, 24, 16]
-    assert [L.finenv_struct_size(i) for i in range(18)] == sizes
-    assert L.finenv_struct_size(18) == -1
-
-
-@pytest.mark.parametrize("kind", KINDS)
-def test_entry_points_validate_arguments(L, kind):
-    from finrl_amd import _native as nat
-    fn = {n: getattr(L, f"finenv_{kind}_{n}") for n in
-          ("set_history", "history_arm", "history_metrics", "create", "destroy", "last_error", "step")}
-    hist, bufs = _host_history(nat)
-    out = np.zeros((64, 6))
-    outp = out.ctypes.data_as(C.c_void_p)
-    # NULL handle
-    assert fn["set_history"](None, C.byref(hist)) == -1
-    assert fn["history_arm"](None, None, None) == -1
-    assert fn["history_metrics"](None, 2.0, outp, None) == -1
-    h = C.c_void_p()
-    cfg = _config(nat, kind)
-    assert fn["create"](C.byref(cfg), C.byref(h)) == 0
-    try:
-        # nothing attached (the default): arm / metrics refuse, with the other envs' error and message
-        assert fn["history_arm"](h, None, None) == -1
-        assert b"no history attached" in fn["last_error"](h)
-        assert fn["history_metrics"](h, 2.0, outp, None) == -1
-        assert b"no history attached" in fn["last_error"](h)
-        # a NULL mandatory pointer, capacity < 1
-        for name in MANDATORY:
-            bad, _ = _host_history(nat, **{name: False})
-            assert fn["set_history"](h, C.byref(bad)) == -1, name
-            assert b"null" in fn["last_error"](h)
-        for cap in (0, -3):
-            bad, _ = _host_history(nat)
-            bad.capacity = cap
-            assert fn["set_history"](h, C.byref(bad)) == -1, cap
-            assert b"capacity" in fn["last_error"](h)
-        # a refused struct attaches nothing
-        assert fn["history_arm"](h, None, None) == -1
-        # attaching works before bind (transactions and actions may be NULL, one entry is a capacity);
-        # arm / metrics then need the state
-        for tx, act in ((False, False), (True, False), (False, True)):
-            now, _ = _host_history(nat, transactions=tx, actions=act)
-            assert fn["set_history"](h, C.byref(now)) == 0
-        one, _ = _host_history(nat, cap=1)
-        assert fn["set_history"](h, C.byref(one)) == 0
-        assert fn["set_history"](h, C.byref(hist)) == 0
-        assert fn["history_arm"](h, None, None) == -2
-        assert fn["history_metrics"](h, 2.0, outp, None) == -2
-        assert fn["history_metrics"](h, 2.0, None, None) == -1
-        # NULL detaches again
-        assert fn["set_history"](h, None) == 0
-        assert fn["history_arm"](h, None, None) == -1
-        assert fn["history_metrics"](h, 2.0, outp, None) == -1
-    finally:
-        fn["destroy"](h)
-    assert not any(b.any() for b in bufs.values()) and not out.any()
 
 
 # ------------------------------------------------------------------------------------------

@@ -16,13 +16,15 @@ esac
 if [ $isa = 1 ]; then
   # gfx950 assembly of the device side; per kernel, hash its code (label .. .Lfunc_end) and its
   # .amdhsa_kernel descriptor block (registers, LDS, scratch, launch bounds).  The per-build
-  # __hip_cuid_<hash> symbol and the function index inside local labels are masked.
+  # __hip_cuid_<hash> symbol and the function index inside local labels are masked and the comments
+  # dropped, so a kernel keeps its digest when another one joins or leaves the file.
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I../../include -I. "$@" \
       --cuda-device-only -S -o - "$src" |
     python3 -c '
 import sys, re, hashlib
 t = sys.stdin.read()
 t = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", t)
+t = re.sub(r"[ \t]*;.*$", "", t, flags=re.M)      # comments name blocks by function index, at a column that moves with it
 t = re.sub(r"\.LBB\d+_", ".LBB_", t)
 t = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", t)
 for m in sorted(re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n.*?\.end_amdhsa_kernel", t, re.M | re.S), key=lambda m: m.group(1)):
