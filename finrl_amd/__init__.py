@@ -15,7 +15,7 @@ __version__ = "0.1.0"
 _LAZY = {      # name -> module; lazy because these need the native library
     "VecStockTradingEnv": "vec_env", "SB3VecEnvAdapter": "vec_env", "SingleEnvVecAdapter": "vec_env",
     "VecStockPortfolioEnv": "vec_portfolio", "VecCryptoEnv": "vec_crypto",
-    "VecStockTradingEnvNP": "vec_stocknp", "VecCashPenaltyEnv": "vec_cashpenalty",
+    "VecBitcoinEnv": "vec_btc", "VecStockTradingEnvNP": "vec_stocknp", "VecCashPenaltyEnv": "vec_cashpenalty",
     "VecStopLossEnv": "vec_cashpenalty", "CashPenaltyPanel": "vec_cashpenalty",
     "RolloutBuffer": "rollout", "GraphedSegment": "graph",
 }

@@ -218,6 +218,31 @@ class TwoWaveHistoryPtrs(C.Structure):
 # n_returns = len - 1 as in the stock env
 TWOWAVE_HISTORY_METRICS = STOCK_HISTORY_METRICS
 
+
+class BtcConfig(C.Structure):
+    _fields_ = [("n_envs", C.c_int32), ("n_price_cols", C.c_int32), ("n_tech_cols", C.c_int32),
+                ("n_rows", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+                ("initial_account", C.c_double), ("transaction_fee_percent", C.c_double),
+                ("gamma", C.c_double)]
+
+
+class BtcPanelPtrs(C.Structure):
+    _fields_ = [("price0", C.c_void_p), ("obs_tmpl", C.c_void_p)]
+
+
+BTC_F64_FIELDS = ("account", "stocks", "total_asset", "gamma_return", "episode_return", "last_reward")
+BTC_I32_FIELDS = ("day", "stocks_tag")
+BTC_MAX_PRICE_COLS = 245   # FINENV_BTC_MAX_PRICE_COLS
+
+
+class BtcStatePtrs(C.Structure):
+    _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p)]
+
+
+# finenv_struct_size indices of the struct trios added after the first v3 list (0 .. 17 are the six
+# kinds of lib()'s table in order; 18 stays invalid)
+_LATER_STRUCTS = {19: BtcConfig, 20: BtcPanelPtrs, 21: BtcStatePtrs}
+
 _lib = None
 
 
@@ -242,7 +267,10 @@ def lib():
             ("crypto", CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs),
             ("stocknp", StockNpConfig, StockNpPanelPtrs, StockNpStatePtrs),
             ("cashpenalty", CashPenaltyConfig, CashPenaltyPanelPtrs, CashPenaltyStatePtrs),
-            ("stoploss", StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs)):
+            ("stoploss", StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs),
+            ("btc", BtcConfig, BtcPanelPtrs, BtcStatePtrs)):
+        if kind == "btc" and not hasattr(L, "finenv_btc_create"):
+            continue            # (a build of an earlier commit: see the note on the windows below)
         create, destroy, last_error, obs_dim, bind, reset = (
             getattr(L, f"finenv_{kind}_{name}")
             for name in ("create", "destroy", "last_error", "obs_dim", "bind", "reset"))
@@ -275,6 +303,10 @@ def lib():
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.finenv_stoploss_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    if hasattr(L, "finenv_btc_create"):
+        L.finenv_btc_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int32, C.c_void_p]
+        L.finenv_btc_set_windows.argtypes = [C.c_void_p] * 2
     L.finenv_riskpre_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.finenv_riskpre_turbulence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_void_p]
@@ -306,12 +338,12 @@ def lib():
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
-    for which, cls in enumerate((StockConfig, StockPanelPtrs, StockStatePtrs, PortfolioConfig,
-                                 PortfolioPanelPtrs, PortfolioStatePtrs, CryptoConfig,
-                                 CryptoPanelPtrs, CryptoStatePtrs, StockNpConfig,
-                                 StockNpPanelPtrs, StockNpStatePtrs, CashPenaltyConfig,
-                                 CashPenaltyPanelPtrs, CashPenaltyStatePtrs, StopLossConfig,
-                                 StopLossPanelPtrs, StopLossStatePtrs)):
+    first = (StockConfig, StockPanelPtrs, StockStatePtrs, PortfolioConfig, PortfolioPanelPtrs,
+             PortfolioStatePtrs, CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs, StockNpConfig,
+             StockNpPanelPtrs, StockNpStatePtrs, CashPenaltyConfig, CashPenaltyPanelPtrs,
+             CashPenaltyStatePtrs, StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs)
+    later = sorted(_LATER_STRUCTS.items()) if hasattr(L, "finenv_btc_create") else []
+    for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(
                 f"ABI struct size mismatch for {cls.__name__}: python {C.sizeof(cls)} vs "

@@ -303,6 +303,10 @@ int finenv_struct_size(int which)
     case 15: return (int)sizeof(finenv_stoploss_config);
     case 16: return (int)sizeof(finenv_stoploss_panel);
     case 17: return (int)sizeof(finenv_stoploss_state);
+    // (18 stays invalid: the end of the first v3 list, include/finenv.h)
+    case 19: return (int)sizeof(finenv_btc_config);
+    case 20: return (int)sizeof(finenv_btc_panel);
+    case 21: return (int)sizeof(finenv_btc_state);
     default: return FINENV_ERR_INVALID;
     }
 }

@@ -59,6 +59,8 @@ def env_class(kind):
         from .vec_portfolio import VecStockPortfolioEnv as cls
     elif kind == "crypto":
         from .vec_crypto import VecCryptoEnv as cls
+    elif kind == "btc":
+        from .vec_btc import VecBitcoinEnv as cls
     elif kind == "cashpenalty":
         from .vec_cashpenalty import VecCashPenaltyEnv as cls
     elif kind == "stoploss":
@@ -72,7 +74,8 @@ def make_sharded_env(panel, global_envs: int, *, kind="stock", rank=None, world=
                      device=None, **kw):
     """This rank's shard of a global batch of `kind` envs (market panel / config replicated on the
     local GPU).  `panel` is whatever the env class takes first: a StockPanel / PortfolioPanel /
-    CashPenaltyPanel, or the reference-style config dict of the array-state and crypto envs."""
+    CashPenaltyPanel, the reference-style config dict of the array-state and crypto envs, or the
+    ``(price_ary, tech_ary)`` pair of kind "btc"."""
     import torch
     import torch.distributed as dist
     if rank is None:
@@ -82,7 +85,8 @@ def make_sharded_env(panel, global_envs: int, *, kind="stock", rank=None, world=
     n_local, kw = shard_env_kwargs(global_envs, rank, world, **kw)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    return env_class(kind)(panel, n_local, device=device, **kw)
+    first = tuple(panel) if kind == "btc" else (panel,)
+    return env_class(kind)(*first, n_local, device=device, **kw)
 
 
 class _PendingGather:

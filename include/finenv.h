@@ -142,8 +142,10 @@ typedef struct finenv_stock finenv_stock;   /* opaque host-side handle */
 int         finenv_abi_version(void);
 /* sizeof() of the ABI structs as the library was compiled (0 = finenv_stock_config,
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
- * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio): lets a foreign-language binding verify its
- * struct declarations at load time instead of corrupting memory. */
+ * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio):
+ * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
+ * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
+ * bindings probe it as such. */
 int         finenv_struct_size(int which);
 const char *finenv_strerror(int code);
 /* Number of HIP devices visible, or a negative FINENV_ERR_HIP. */
@@ -1099,6 +1101,100 @@ int finenv_cashpenalty_history_metrics(finenv_cashpenalty *h, double annualizati
                                        void *stream);
 int finenv_stoploss_history_metrics(finenv_stoploss *h, double annualization, double *out,
                                     void *stream);
+
+/* =====================================================================================
+ * BitcoinEnv (finrl/meta/env_cryptocurrency_trading/env_btc_ccxt.py:6-215), the single-asset
+ * ElegantRL demo env.  NOT CryptoEnv with one asset: it may go short, buys fractional amounts, and
+ * ADDS the discounted return to the terminal reward.
+ *   actions [E][1] f32 (what ElegantRL's act(...).cpu().numpy()[0] hands over)
+ *   obs     [E][D] f32, D = P + 9 = [account*2^-18 | price[day][0..P)*2^-15 |
+ *           tech[day][0..7)*(2^-1, 2^-15, 2^-15, 2^-6, 2^-6, 2^-15, 2^-15) | stocks*2^-4] (:62-79)
+ *   reward  (delta total asset) * 2^-16; on the last step PLUS the discounted return (:121-128)
+ * Contract: price_ary [T][P] and tech_ary [T][W], W >= 7, are float64 and actions float32; every
+ * other combination changes the reference's arithmetic under NumPy 2 (NEP 50) and is refused by
+ * the Python layers.  Trades use price column 0.  With adj = price[day][0], a = action:
+ *   a < 0   q = min(-a, (0.5 * total_asset) / adj + stocks) (ties keep -a), sold if q > 0 -- stocks may
+ *           go NEGATIVE -- account += (adj * q) * (1 - fee); else account += (adj * 0) * (1 - fee) (:86-90)
+ *   a > 0   q = min(a, account / adj), not clamped at 0; account -= (adj * q) * (1 + fee) (:92-95)
+ *   then    day += 1; next = account + price[day][0] * stocks; reward = (next - total_asset) * 2^-16;
+ *           gamma_return = gamma_return * gamma + reward; done = (day + 1 == rows); on done
+ *           reward += gamma_return, gamma_return = 0, episode_return = next / initial_account
+ * Every *, /, + is a float64 operation rounded on its own, in that order -- except `stocks`, whose
+ * NumPy scalar type the reference's arithmetic depends on: a Python float after reset(), float32
+ * after a trade of the action's own size, float64 once a cap has bound.  FINENV_BI_STOCKS_TAG keeps
+ * it (FINENV_NT_PY / _F32 / _F64; a trade sets it to the larger of its own and the quantity's: F32
+ * for the action, F64 for a cap), and while it is F32 `stocks +/- q` is a float32 operation.
+ * reset() (:53-60) restores day, account, stocks (0.0, FINENV_NT_PY) and total_asset and, as in the
+ * reference, leaves gamma_return and episode_return alone.
+ * Defined here (the reference raises IndexError): an env stepped again on its terminal row --
+ * after done, auto_reset off, no reset -- makes no trade and keeps its state; the step writes the
+ * current observation, reward 0 (FINENV_BF_LAST_REWARD too) and done 1, and reads no row outside
+ * the panel.
+ * ===================================================================================== */
+#define FINENV_BTC_MAX_PRICE_COLS 245   /* D <= 254: a wave's observation rows fit one block's LDS */
+
+typedef struct finenv_btc_config {
+    int32_t n_envs;
+    int32_t n_price_cols;         /* P = price_ary.shape[1] >= 1                         */
+    int32_t n_tech_cols;          /* W = tech_ary.shape[1] >= 7 (the first 7 are shown)  */
+    int32_t n_rows;               /* T = rows of the panel >= 2                          */
+    int32_t reserved0;
+    int32_t reserved1;
+    double  initial_account;      /* :17                                                 */
+    double  transaction_fee_percent;   /* :19                                            */
+    double  gamma;                /* :21                                                 */
+} finenv_btc_config;
+
+typedef struct finenv_btc_panel {
+    const double *price0;         /* [T] f64 = price_ary[:, 0], the traded column        */
+    const float  *obs_tmpl;       /* [T][P + 7] f32: columns 1 .. D-2 of the observation row of each
+                                     panel row, the reference's scaling expressions evaluated in
+                                     float64 by the host and cast; the kernel copies them */
+} finenv_btc_panel;
+
+enum { FINENV_BF_ACCOUNT = 0, FINENV_BF_STOCKS, FINENV_BF_TOTAL_ASSET, FINENV_BF_GAMMA_RETURN,
+       FINENV_BF_EPISODE_RETURN, FINENV_BF_LAST_REWARD, FINENV_BTC_F64_FIELDS };
+enum { FINENV_BI_DAY = 0, FINENV_BI_STOCKS_TAG, FINENV_BTC_I32_FIELDS };
+typedef struct finenv_btc_state {
+    double  *f64;                 /* [FINENV_BTC_F64_FIELDS][E]; LAST_REWARD: the float64 reward of
+                                     the last step (the reward output is its float32 cast) */
+    int32_t *i32;                 /* [FINENV_BTC_I32_FIELDS][E]; DAY is the PANEL row     */
+} finenv_btc_state;
+
+typedef struct finenv_btc finenv_btc;
+
+int  finenv_btc_create(const finenv_btc_config *cfg, finenv_btc **out);
+void finenv_btc_destroy(finenv_btc *h);
+const char *finenv_btc_last_error(const finenv_btc *h);
+int  finenv_btc_obs_dim(const finenv_btc *h);
+int  finenv_btc_bind(finenv_btc *h, const finenv_btc_panel *panel, const finenv_btc_state *state);
+/* reset() (:53-79) of every env, or of those with mask[e] != 0; obs_out (may be NULL) receives the
+ * rows of the envs it resets. */
+int  finenv_btc_reset(finenv_btc *h, const uint8_t *mask, float *obs_out, void *stream);
+/* step() (:81-129).  obs [E][D] f32 packed, reward [E] f32, done [E] u8; term_obs [E][D] or NULL:
+ * rows of the envs that report done receive the observation the reference's last step() returns.
+ * auto_reset: DummyVecEnv semantics inside the launch (a done env is reset and obs holds its first
+ * observation).  The output pointers may address slice t of rollout tensors [n_steps][E][...]:
+ * collecting a rollout needs no extra copy (any 4-byte aligned obs is taken; a 16-byte aligned one
+ * is written faster). */
+int  finenv_btc_step(finenv_btc *h, const float *actions, float *obs, float *reward, uint8_t *done,
+                     float *term_obs, int32_t auto_reset, void *stream);
+
+/* Per-env episode windows: many BitcoinEnv instances on row ranges of ONE bound panel in one batch
+ * -- the train / test / trade modes of load_data (:176-215) side by side, or random training
+ * windows.  The contract of finenv_stock_set_windows: caller-owned device block int32_t win[2][E],
+ * win[0][e] = s_e (first panel row), win[1][e] = t_e (end, exclusive); env e then equals the
+ * reference env whose arrays are rows [s_e, t_e): done when the incremented day equals t_e - 1, a
+ * reset (host or auto) goes back to row s_e.  FINENV_BI_DAY stays the panel row (the reference's
+ * self.day is FINENV_BI_DAY - s_e).  step() reads t_e on every step and s_e only when it resets an
+ * env, so an edited end applies from the next step and an edited start at the env's next reset.
+ * The kernels clamp both rows into the panel whatever the block holds: a bad window is a wrong
+ * answer, never an access outside the panel; valid windows (0 <= s_e, s_e + 2 <= t_e <= n_rows) read
+ * no row outside [s_e, t_e).  The pointer is a kernel argument: launches and graph replays see later
+ * edits of the block's CONTENTS, a graph keeps the pointer it was captured with.  NULL detaches
+ * (the default: every env runs rows 0 .. n_rows-1).  Works before bind.  Returns FINENV_ERR_INVALID
+ * for a NULL handle. */
+int  finenv_btc_set_windows(finenv_btc *h, int32_t *win);
 
 /* =====================================================================================
  * Risk precompute that feeds the panels.  Stateless; all buffers are
