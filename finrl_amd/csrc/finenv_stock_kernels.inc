@@ -14,7 +14,10 @@ constexpr bool kWide = kNPad > 32;
 constexpr int kRow = kNPad + 1;                         // LDS row stride in dwords (odd)
 constexpr int kAuxWaves = kWide ? 1 : 4;                // waves per block of the aux kernel
 constexpr int kLdsPerWave = kWave * kRow;               // >= kNPad * kWave
-constexpr int kAMax = 1 << (30 - kLog2NPad);            // |scaled action| clamp (key packing)
+// |scaled action| saturates here (key packing: kAMax * kNPad + i fits int32); the two values
+// include/finenv.h states ("Action domain"), so the 64-wide build does not use its spare bit
+constexpr int kAMax = kWide ? 1 << 23 : 1 << 25;
+static_assert((long long)kAMax * kNPad + kNPad <= (1ll << 31), "keys must fit int32");
 static_assert((1 << kLog2NPad) == kNPad, "NP must be a power of two");
 
 // Batcher network on kNPad statically indexed VGPRs.

@@ -7,8 +7,8 @@
 // in 67 KB of LDS -> two blocks per CU -> half the chip's SIMDs idle and two rounds of blocks at
 // 65,536 envs (profiles/r02_head_n100_phase_timeline.txt).  This one fits 40.7 KB -> four blocks
 // per CU, all 1024 blocks of a 65,536-env batch resident at once, one trader wave per SIMD:
-//   * sorted keys are parked as 16-bit values (a * 128 + i fits int16 for hmax <= 255; larger hmax
-//     goes to the generic kernel);
+//   * sorted keys are parked as 16-bit values (a * 128 + i fits int16 for |a| <= 255: larger hmax
+//     goes to the generic kernel, and a scaled action beyond +-255 saturates there);
 //   * the action tile never sits in LDS as a whole: the trader copies it through the (not yet
 //     used) key region half a tile at a time -- coalesced 16-B loads, flat ds_write_b128, then
 //     every lane reads ITS OWN 400-B row back with ds_read_b128 (rows 100 dwords apart: the 16
@@ -272,7 +272,9 @@ stock_step_wide_kernel(const Params p)
             const int i = 4 * j + u;
             const float x = c[u] * hmaxf;                                     // f32 mul, :304
             int a = (int)x;                                                   // trunc, :305
-            a = max(-kAMax, min(kAMax, a));
+            // saturates at what the int16 park below holds (include/finenv.h, "Action domain"): an
+            // action beyond it stays a trade of its own sign instead of wrapping into the other one
+            a = max(-G::kMaxHmax, min(G::kMaxHmax, a));
             a = turbulent ? -hmax : a;
             a = term ? 0 : a;                                                 // no trading
             keys[i] = a * kNPad + i;      // unique; order == stable argsort(actions), :317

@@ -49,6 +49,22 @@ enum {
 #define FINENV_STOCK_MAX_TICKERS 128  /* two kernel variants: N <= 32 (DOW30), N <= 128
                                          (NASDAQ-100)                               */
 
+/* Action domain of finenv_stock_step (stated here once; `hmax` below and the step's `actions` refer
+ * to it).  An action is any finite f32: the reference does not clip, it trades
+ * a = int(action * hmax) shares -- a float32 multiply, then truncation toward zero (:304-305) -- so
+ * an action of 3.0 asks for 3 * hmax shares.  [-1, 1] is only the env's nominal action_space.  The
+ * kernels do the same up to a SATURATION value of |a| that depends on the kernel stepping the batch
+ * (a and the ticker index share one sort key):
+ *     n_tickers <= 32                                 2^25
+ *     n_tickers <= 128                                2^23
+ *     n_tickers == 100 and hmax <= 255 (the NASDAQ-100 fast kernel: 16-bit sort keys)   255
+ * Beyond it an action trades exactly as the saturated one does: same sign, same place in the trade
+ * order among equally saturated actions (ticker order), never a wrapped value.  Inside it the step
+ * equals the reference for every action, whatever binds the trade (the action, the holdings or
+ * `cash // unit`, which is the exact floor division at every quotient).  Holdings are int32: keeping
+ * them below 2^31 is the caller's business.  NaN and +-inf actions are unspecified (the reference's own
+ * cast is undefined there); they trade some saturated or zero amount and never fault. */
+
 /* Constructor arguments of StockTradingEnv that shape the arithmetic
  * (env_stocktrading.py:24-47). */
 typedef struct finenv_stock_config {
@@ -56,8 +72,8 @@ typedef struct finenv_stock_config {
     int32_t n_tickers;            /* stock_dim, :50                                      */
     int32_t n_tech;               /* len(tech_indicator_list), :59                       */
     int32_t n_days;               /* len(df.index.unique()), :221                        */
-    int32_t hmax;                 /* :51; |action*hmax| must stay below 2^25 (N <= 32) or
-                                     2^23 (N <= 128)                                      */
+    int32_t hmax;                 /* :51; at most 2^24 (N <= 32) or 2^22; int(action * hmax)
+                                     saturates per kernel: see "Action domain" above       */
     int32_t use_turbulence;       /* turbulence_threshold is not None, :68               */
     int32_t reset_quirk;          /* 1: reset() builds obs from the row held before the
                                      rewind (reference behaviour, :361 vs :380-381)      */
@@ -198,7 +214,7 @@ int finenv_stock_observe(finenv_stock *h, float *obs_out, void *stream);
 int finenv_stock_refresh(finenv_stock *h, void *stream);
 
 /* step() (:220-357) for all envs in ONE launch.
- *   actions   [E][N] f32 in [-1, 1]
+ *   actions   [E][N] f32, any finite value (nominally [-1, 1]): "Action domain" above
  *   obs       [E][D] f32 (next observation; after auto-reset: the reset observation)
  *   reward    [E]    f32 (float32 cast of the fp64 reward, as DummyVecEnv stores it)
  *   done      [E]    u8

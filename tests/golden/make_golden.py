@@ -98,6 +98,15 @@ def run_stock(name, *, seed, T, N, K, S, variant, actions="uniform", hmax=100,
             act[rng.random((S, N)) < zero_frac] = 0.0
     elif actions == "tiefree":
         act = tiefree_actions(rng, S, N, hmax)
+    elif actions == "big":
+        # outside [-1, 1]: the reference does not clip (:304-305), so |a| = 300 asks for 300 * hmax
+        # shares.  A third of the entries are whole multiples of 100 and a third lie in [-1, 1] on
+        # multiples of 0.5: equal scaled actions (ties) occur in most steps, across both ranges
+        act = rng.uniform(-300, 300, (S, N))
+        kind = rng.integers(0, 3, (S, N))
+        act = np.where(kind == 1, rng.integers(-3, 4, (S, N)) * 100.0, act)
+        act = np.where(kind == 2, rng.integers(-2, 3, (S, N)) * 0.5, act)
+        act = act.astype(np.float32)
     else:
         raise ValueError(actions)
 
@@ -237,6 +246,10 @@ STOCK_SCENARIOS = {
     "n1_turb": dict(seed=33, T=18, N=1, K=2, S=45, variant="O-stable", actions="uniform",
                     initial_amount=4_000, hmax=25, shares0=[5], turbulence_threshold=30.0,
                     flag_frac=0.1),
+    # actions far outside [-1, 1] (up to 300: 30,000 shares at hmax = 100) with ties; holdings, cash and
+    # the action itself each bind in some steps
+    "bigactions": dict(seed=35, T=8, N=5, K=2, S=20, variant="O-stable", actions="big",
+                       initial_amount=3_000_000, shares0=[0, 40_000, 150, 20_000, 7]),
     "n1_prevstate": dict(seed=34, T=18, N=1, K=3, S=45, variant="O-stable", actions="uniform",
                          initial_amount=6_000, hmax=30, shares0=[9], previous_state=True),
 }

@@ -138,7 +138,7 @@ def test_unaffordable_buy_zero_fill():
     assert (st["shares"] == 0).all() and st["cash"][0] == 50.0 and st["trades"][0] == fx.N
 
 
-@pytest.mark.parametrize("name", ["ties", "turbulence", "cashbound", "tiefree"])
+@pytest.mark.parametrize("name", ["ties", "turbulence", "cashbound", "tiefree", "bigactions"])
 def test_pandas_shaped_env_matches_reference(name):
     """oracle/pandas_env.py (the reference-SHAPED Python env timed as `cpu_baseline_python`) replays
     the reference-recorded episodes exactly: float64 observations, rewards, cash, shares, cost,
