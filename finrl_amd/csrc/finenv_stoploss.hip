@@ -8,6 +8,13 @@
 // (1) previous-state reward terms, (2) transactions + stop-loss override + cash test inputs,
 // (3) book update.  Sums run in asset order, like the oracle.
 //
+// The reference's step() is written once, in the helpers ahead of the kernels: sl_reward, sl_pass1 (the
+// reward terms of one asset), sl_closing_diff / sl_transaction (one asset's transaction),
+// sl_cash_decision (what the step decides), sl_update / sl_store_book (pass 3 of one asset),
+// sl_audit_row, sl_episode_end (terminal observation, auto-reset).  The two step kernels below differ in
+// who loads what and when, and in where a transaction waits for pass 3 (registers, or LDS for the
+// streamer's assets) -- not in the rule.
+//
 // Observation rows of up to 320 columns (stoploss_step2_kernel): one 128-thread block per 64 envs,
 // two specialised waves --
 //   wave 0 "trader"  : passes 1 and 2 over every asset, the cash decision, pass 3 for assets
@@ -73,6 +80,183 @@ __device__ __forceinline__ double sl_reward(const finenv_stoploss_config &c, int
     return r;
 }
 
+// One asset's share of get_reward()'s sums (and of the trade counter), from the books as the
+// previous step left them.  The last-date loop (pass 1) and the pass-2 loop of both kernels call it.
+__device__ __forceinline__ void sl_pass1(float act, double h, double ph, double ps, double cd,
+                                         double &sum_trades, double &slp_sum, double &lpp_sum,
+                                         double &add)
+{
+    sum_trades += fabs((double)act);                                 // :294
+    slp_sum += ph * fmin(cd, 0.0);                                   // :262,:273-275
+    lpp_sum += h * fmin(ps, 0.0);                                    // :263-265,:278-280
+    add += h * fmax(ps, 0.0);                                        // :266-268,:283
+}
+
+// closing_diff_avg_buy of one asset: pass 2 takes it for the stop-loss, pass 3 stores it
+__device__ __forceinline__ double sl_closing_diff(const finenv_stoploss_config &c, double cl, double abp)
+{
+    return cl - (c.stoploss_penalty * abp);                          // :350-352
+}
+
+// The transaction of one asset (:321-360) from its action, holdings, close and closing_diff_avg_buy;
+// flags collects the audit bit of a stop-loss sale.  (The caller computes cd: with cd and the stop-loss
+// bit handed back in a struct the one-wave kernel ran 0.4-0.8 % longer, profiles/twowave_passes.md)
+__device__ __forceinline__ double sl_transaction(const finenv_stoploss_config &c, float act, double h,
+                                                 double cl, double cd, float hmaxf, bool turbulent,
+                                                 bool stop_armed, bool discrete, int &flags)
+{
+    const float a32 = act * hmaxf;                                   // :321 (float32)
+    double a = cl > 0.0 ? (double)a32 : 0.0;                         // :326
+    a = turbulent ? -(h * cl) : a;                                   // :327-331
+    double tr;
+    if (discrete) {                                                  // :333-343
+        // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a
+        // software 64-bit division per asset, unrolled, doubled the kernel's code)
+        const double q = cl > 0.0 ? floordiv_true(a, cl) : 0.0;
+        const double inc = (double)c.shares_increment;
+        const double num = q >= 0.0 ? q : q + inc;
+        tr = floordiv_true(num, inc) * inc;
+    } else {
+        tr = cl > 0.0 ? a / cl : 0.0;                                // :345
+    }
+    tr = fmax(tr, -h);                                               // :348
+    flags |= (stop_armed && cd < 0.0) ? FINENV_AUDIT_F_STOP_LOSS : 0;   // :359-360
+    return (stop_armed && cd < 0.0) ? -h : tr;                       // :353-357
+}
+
+// What a step decides once every transaction is known (:313-317, :363-383, :414).  A kernel starts
+// one with the last date's values (:302-304: done, nothing traded) and replaces it on any other date.
+struct SlDecision {
+    double coh_new, reward, logged_total, logged_cash;
+    bool keep_buys, done;
+    int flags;                                 // audit bits
+};
+__device__ __forceinline__ SlDecision sl_cash_decision(const finenv_stoploss_config &c, int step,
+                                                       double coh, double asset_value,
+                                                       double proceeds, double spend, bool turbulent,
+                                                       double lt_old, double lc_old, double slp_sum,
+                                                       double slp_new, double lpp_sum, double add)
+{
+    SlDecision d;
+    d.keep_buys = true;
+    d.done = false;
+    d.reward = sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add);        // :313 (stale log)
+    d.logged_cash = coh;                                                         // :315-317
+    d.logged_total = coh + asset_value;
+    double costs = proceeds * c.sell_cost_pct;                                   // :365
+    const double coh1 = coh + proceeds;                                          // :366
+    costs += spend * c.buy_cost_pct;                                             // :370
+    d.flags = turbulent ? FINENV_AUDIT_F_TURBULENCE : 0;
+    if (spend + costs > coh1) {                                                  // :372
+        d.flags |= FINENV_AUDIT_F_CASH_SHORTAGE;
+        if (c.patient) {                                                         // :373-378
+            d.keep_buys = false;
+            spend = 0.0;
+            costs = 0.0;
+        } else {                                                                 // :379-383
+            d.done = true;
+            d.reward = sl_reward(c, step, d.logged_total, d.logged_cash, slp_new, lpp_sum, add);
+        }
+    }
+    d.coh_new = coh1 - spend - costs;                                            // :414
+    return d;
+}
+
+// pass 3 (:388-428) for one asset: new books from (transaction, close, holdings, average buy price,
+// buy count).  Returns the new holdings; *ntr counts applied transactions, *flags the audit bits.
+struct SlBook { double ps, hu, nb, abp; };
+__device__ __forceinline__ SlBook sl_update(const finenv_stoploss_config &c, double tr0, double cl,
+                                            double h, double abp, double nb, bool keep_buys,
+                                            double &ntr, int &flags)
+{
+    const bool sold = tr0 < 0.0;                                     // sells > 0
+    const bool bought = tr0 > 0.0;                                   // buys > 0 (:418)
+    const double tr = (bought && !keep_buys) ? 0.0 : tr0;            // :376
+    const double scp = sold ? cl : 0.0;                              // :388-390
+    const bool profit = scp - abp > 0.0;                             // :391-393
+    SlBook b;
+    b.ps = profit ? cl - (c.min_profit_penalty * abp) : 0.0;         // :395-399
+    flags |= b.ps < 0.0 ? FINENV_AUDIT_F_LOW_PROFIT                  // :401-405
+                        : (b.ps > 0.0 ? FINENV_AUDIT_F_HIGH_PROFIT : 0);
+    ntr += tr != 0.0 ? 1.0 : 0.0;                                    // :411
+    b.hu = h + tr;                                                   // :415
+    nb += bought ? 1.0 : 0.0;                                        // :419
+    const double abp_new = abp + ((cl - abp) / nb);                  // :420-424
+    abp = bought ? abp_new : abp;
+    const bool held = b.hu > 0.0;                                    // :427-428
+    b.nb = held ? nb : 0.0;
+    b.abp = held ? abp : 0.0;
+    return b;
+}
+
+// pass 3's stores of asset i: `h` becomes the previous holdings, `b` the rest
+__device__ __forceinline__ void sl_store_book(const SlParams &p, int e, int i, double h, const SlBook &b)
+{
+    const int E = p.cfg.n_envs, N = p.cfg.n_assets;
+    LV(FINENV_LV_PROFIT_SELL_DIFF_AVG_BUY, i) = b.ps;
+    LV(FINENV_LV_PREV_HOLDINGS, i) = h;
+    LV(FINENV_LV_HOLDINGS, i) = b.hu;
+    LV(FINENV_LV_N_BUYS, i) = b.nb;
+    LV(FINENV_LV_AVG_BUY_PRICE, i) = b.abp;
+}
+
+// harness log row (account_information / transaction_memory); tr_of(i) gives transaction i as pass 2
+// left it
+template <class Tr>
+__device__ __forceinline__ void sl_audit_row(const SlParams &p, int e, double coh_begin,
+                                             double asset_value, double reward, int flags,
+                                             bool at_end, bool keep_buys, Tr tr_of)
+{
+    const int N = p.cfg.n_assets;
+    double *au = p.audit + (size_t)e * (size_t)(FINENV_AUDIT_HEAD + N);
+    au[FINENV_AUDIT_BEGIN_CASH] = coh_begin;                                     // :307
+    au[FINENV_AUDIT_ASSET_VALUE] = asset_value;                                  // :311
+    au[FINENV_AUDIT_REWARD] = reward;
+    au[FINENV_AUDIT_FLAGS] = (double)flags;
+#pragma unroll
+    for (int i = 0; i < kMaxN; ++i) {
+        if (i >= N) continue;
+        const double tr = at_end ? 0.0 : tr_of(i);
+        au[FINENV_AUDIT_HEAD + i] = (tr > 0.0 && !keep_buys) ? 0.0 : tr;         // :376 / :385
+    }
+}
+
+// The end of a step in both kernels, once rows[] hold this step's rows: the terminal observation of
+// the envs whose episode ended here and, under auto_reset, reset() (:134-165) for them -- next_start()
+// gives the restart row; di, coh and turb are the lane's registers, which the kernel stores last.
+template <bool WIN, class NextStart>
+__device__ __forceinline__ void sl_episode_end(const SlParams &p, int e, int e0, int nenv_w,
+                                               float *rows, int lane, bool valid, bool done,
+                                               NextStart next_start, int &di, double &coh,
+                                               double &turb)
+{
+    const int E = p.cfg.n_envs, N = p.cfg.n_assets;
+    float *row = rows + lane * kRow;
+    const unsigned long long done_mask = __ballot(done && valid);
+    if (done_mask == 0ull) return;
+    if (p.term_obs != nullptr)
+        tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
+    if (!p.auto_reset) return;
+    wave_sync();                                                                 // reset()
+    if (done) {
+        const int ns = next_start();
+        di = ns;
+        coh = p.cfg.initial_amount;
+        turb = 0.0;
+        row[0] = (float)coh;
+        for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
+        if (valid) {
+            for (int i = 0; i < FINENV_STOPLOSS_BOOKS * N; ++i) LV(0, i) = 0.0;
+            tw_win_promote<WIN>(p, e);
+            LI(FINENV_LI_START) = ns;
+            LI(FINENV_LI_EPISODE) += 1;
+            LF(FINENV_LF_SUM_TRADES) = 0.0;
+            LF(FINENV_LF_ACTUAL_NUM_TRADES) = 0.0;
+        }
+    }
+    wave_sync();
+}
+
 // The one-wave kernel: reset, and steps whose observation rows are wider than 320 columns.  (WIN =
 // per-env episode windows, finenv_stoploss_set_windows: the helpers in finenv_twowave.h)
 template <bool RESET_ONLY, bool WIN>
@@ -121,7 +305,7 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
     double coh = LF(FINENV_LF_COH);
     double turb = c.use_turbulence ? LF(FINENV_LF_TURBULENCE) : 0.0;
     double sum_trades = LF(FINENV_LF_SUM_TRADES);
-    double logged_total = LF(FINENV_LF_LOGGED_TOTAL), logged_cash = LF(FINENV_LF_LOGGED_CASH);
+    const double lt_old = LF(FINENV_LF_LOGGED_TOTAL), lc_old = LF(FINENV_LF_LOGGED_CASH);
     double actual_num_trades = LF(FINENV_LF_ACTUAL_NUM_TRADES);
     const int step = di - start;                                                 // current_step
     const bool at_end = tw_last_date<WIN>(di, end);                              // :302
@@ -133,7 +317,6 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
     // re-reading the holdings and previous-holdings books: the three-pass form moved 1.34x the
     // algorithmic bytes (PMC, profiles/side_traffic.json).
     double slp_sum = 0.0, lpp_sum = 0.0, add = 0.0;
-    const double lt_old = logged_total, lc_old = logged_cash;
     // (every per-asset loop below runs in batches of kB assets with the batch's global loads issued
     //  first: a rolled loop exposes one HBM round trip per asset at one wave per SIMD)
     if (at_end) {
@@ -152,25 +335,20 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
 #pragma unroll
             for (int j = 0; j < kB; ++j) {
                 if (i0 + j >= N) continue;
-                sum_trades += fabs((double)row[i0 + j]);                         // :294
-                slp_sum += ph[j] * fmin(cd[j], 0.0);                             // :262,:273-275
-                lpp_sum += hh[j] * fmin(ps[j], 0.0);                             // :263-265,:278-280
-                add += hh[j] * fmax(ps[j], 0.0);                                 // :266-268,:283
+                sl_pass1(row[i0 + j], hh[j], ph[j], ps[j], cd[j], sum_trades, slp_sum, lpp_sum, add);
             }
         }
     }
-    double reward = at_end ? sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add) : 0.0;  // :304
-    bool done = at_end;
+    SlDecision d = {coh, at_end ? sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add) : 0.0,   // :304
+                    lt_old, lc_old, true, at_end, at_end ? FINENV_AUDIT_F_LAST_DATE : 0};
 
     // ---- pass 2: transactions (:320-357), proceeds / spend (:363-370) --------------------------
     const float hmaxf = (float)c.hmax;
     const bool turbulent = c.use_turbulence && turb >= c.turbulence_threshold;
     const bool stop_armed = coh >= c.stoploss_penalty * c.initial_amount;        // :353
     double asset_value = 0.0, proceeds = 0.0, spend = 0.0, slp_new = 0.0;
-    bool keep_buys = true;
-    double coh_new = coh;
     const double coh_begin = coh;
-    int audit_flags = at_end ? FINENV_AUDIT_F_LAST_DATE : 0;
+    int audit_flags = d.flags;
     // holdings, closes, average buy prices and transactions stay in statically indexed registers
     // from pass 2 to pass 3 (the batch loops are unrolled over the kMaxN slots): pass 3 used to
     // re-read the first three (1.22x the algorithmic traffic, profiles/side_traffic.json)
@@ -199,31 +377,13 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
                 const int i = i0 + j;
                 if (i >= N) continue;          // (continue, not break: keeps the loop fully unrollable)
                 const double h = hb[j], cl = clb[j], abp = ab[j];
-                sum_trades += fabs((double)row[i]);                              // :294
-                slp_sum += pb[j] * fmin(cdo[j], 0.0);                            // :262,:273-275
-                lpp_sum += h * fmin(pso[j], 0.0);                                // :263-265,:278-280
-                add += h * fmax(pso[j], 0.0);                                    // :266-268,:283
+                sl_pass1(row[i], h, pb[j], pso[j], cdo[j], sum_trades, slp_sum, lpp_sum, add);
                 asset_value += h * cl;                                           // :311
-                const float a32 = row[i] * hmaxf;                                // :321 (float32)
-                double a = cl > 0.0 ? (double)a32 : 0.0;                         // :326
-                a = turbulent ? -(h * cl) : a;                                   // :327-331
-                double tr;
-                if (c.discrete_actions) {                                        // :333-343
-                    // integer-valued doubles instead of int64 arithmetic (exact below 2^53; a
-                    // software 64-bit division per asset, unrolled, doubled the kernel's code)
-                    const double q = cl > 0.0 ? floordiv_true(a, cl) : 0.0;
-                    const double inc = (double)c.shares_increment;
-                    const double num = q >= 0.0 ? q : q + inc;
-                    tr = floordiv_true(num, inc) * inc;
-                } else {
-                    tr = cl > 0.0 ? a / cl : 0.0;                                // :345
-                }
-                tr = fmax(tr, -h);                                               // :348
-                const double cd = cl - (c.stoploss_penalty * abp);               // :350-352
+                const double cd = sl_closing_diff(c, cl, abp);
                 if (valid) LV(FINENV_LV_CLOSING_DIFF_AVG_BUY, i) = cd;
                 slp_new += pb[j] * fmin(cd, 0.0);
-                tr = (stop_armed && cd < 0.0) ? -h : tr;                         // :353-357
-                audit_flags |= (stop_armed && cd < 0.0) ? FINENV_AUDIT_F_STOP_LOSS : 0;   // :359-360
+                const double tr = sl_transaction(c, row[i], h, cl, cd, hmaxf, turbulent, stop_armed,
+                                                 c.discrete_actions, audit_flags);
                 hS[i] = h;
                 clS[i] = cl;
                 abS[i] = abp;
@@ -232,31 +392,16 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
                 spend += (tr > 0.0 ? tr : 0.0) * cl;                             // :368-369
             }
         }
-        reward = sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add);      // :313 (stale log)
-        logged_cash = coh;                                                       // :315-317
-        logged_total = coh + asset_value;
-        double costs = proceeds * c.sell_cost_pct;                               // :365
-        const double coh1 = coh + proceeds;                                      // :366
-        costs += spend * c.buy_cost_pct;                                         // :370
-        audit_flags |= turbulent ? FINENV_AUDIT_F_TURBULENCE : 0;
-        if (spend + costs > coh1) {                                              // :372
-            audit_flags |= FINENV_AUDIT_F_CASH_SHORTAGE;
-            if (c.patient) {                                                     // :373-378
-                keep_buys = false;
-                spend = 0.0;
-                costs = 0.0;
-            } else {                                                             // :379-383
-                done = true;
-                reward = sl_reward(c, step, logged_total, logged_cash, slp_new, lpp_sum, add);
-            }
-        }
-        coh_new = coh1 - spend - costs;                                          // :414
+        d = sl_cash_decision(c, step, coh, asset_value, proceeds, spend, turbulent, lt_old, lc_old,
+                             slp_sum, slp_new, lpp_sum, add);
+        audit_flags |= d.flags;
     }
+    const bool done = d.done;
 
     // ---- pass 3: book update (:388-428) --------------------------------------------------------
     const bool advance = !done;
     if (advance) {
-        coh = coh_new;
+        coh = d.coh_new;
         double ntr = 0.0;
         // buy counts: the one book pass 2 did not read -- all of them in one batch, before this
         // pass's first store
@@ -270,33 +415,10 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
             for (int j = 0; j < kB; ++j) {
                 const int i = i0 + j;
                 if (i >= N) continue;          // (continue, not break: keeps the loop fully unrollable)
-                const double tr0 = trS[i];
-                const double cl = clS[i], h = hS[i];
-                double abp = abS[i], nb = nbS[i];
-                const bool sold = tr0 < 0.0;                                     // sells > 0
-                const bool bought = tr0 > 0.0;                                   // buys > 0 (:418)
-                const double tr = (bought && !keep_buys) ? 0.0 : tr0;            // :376
-                const double scp = sold ? cl : 0.0;                              // :388-390
-                const bool profit = scp - abp > 0.0;                             // :391-393
-                const double ps = profit ? cl - (c.min_profit_penalty * abp) : 0.0;  // :395-399
-                audit_flags |= ps < 0.0 ? FINENV_AUDIT_F_LOW_PROFIT                   // :401-405
-                                        : (ps > 0.0 ? FINENV_AUDIT_F_HIGH_PROFIT : 0);
-                ntr += tr != 0.0 ? 1.0 : 0.0;                                    // :411
-                const double hu = h + tr;                                        // :415
-                nb += bought ? 1.0 : 0.0;                                        // :419
-                const double abp_new = abp + ((cl - abp) / nb);                  // :420-424
-                abp = bought ? abp_new : abp;
-                const bool held = hu > 0.0;                                      // :427-428
-                nb = held ? nb : 0.0;
-                abp = held ? abp : 0.0;
-                if (valid) {
-                    LV(FINENV_LV_PROFIT_SELL_DIFF_AVG_BUY, i) = ps;
-                    LV(FINENV_LV_PREV_HOLDINGS, i) = h;
-                    LV(FINENV_LV_HOLDINGS, i) = hu;
-                    LV(FINENV_LV_N_BUYS, i) = nb;
-                    LV(FINENV_LV_AVG_BUY_PRICE, i) = abp;
-                }
-                row[1 + i] = (float)hu;
+                const SlBook b = sl_update(c, trS[i], clS[i], hS[i], abS[i], nbS[i], d.keep_buys, ntr,
+                                           audit_flags);
+                if (valid) sl_store_book(p, e, i, hS[i], b);
+                row[1 + i] = (float)b.hu;
             }
         }
         actual_num_trades = ntr;
@@ -305,90 +427,29 @@ __global__ void __launch_bounds__(kWave *kWaves, 1) stoploss_kernel(const SlPara
     } else {
         for (int i = 0; i < N; ++i) row[1 + i] = (float)LV(FINENV_LV_HOLDINGS, i);
     }
-    if (p.audit != nullptr && valid) {      // harness log row (account_information / transaction_memory)
-        double *au = p.audit + (size_t)e * (size_t)(FINENV_AUDIT_HEAD + N);
-        au[FINENV_AUDIT_BEGIN_CASH] = coh_begin;                                 // :307
-        au[FINENV_AUDIT_ASSET_VALUE] = asset_value;                              // :311
-        au[FINENV_AUDIT_REWARD] = reward;
-        au[FINENV_AUDIT_FLAGS] = (double)audit_flags;
-#pragma unroll
-        for (int i = 0; i < kMaxN; ++i) {
-            if (i >= N) continue;
-            const double tr = at_end ? 0.0 : trS[i];
-            au[FINENV_AUDIT_HEAD + i] = (tr > 0.0 && !keep_buys) ? 0.0 : tr;     // :376 / :385
-        }
-    }
+    if (p.audit != nullptr && valid)
+        sl_audit_row(p, e, coh_begin, asset_value, d.reward, audit_flags, at_end, d.keep_buys,
+                     [&](int i) { return trS[i]; });
     row[0] = (float)coh;
     if (valid) {
-        *at(p.reward, (unsigned)e) = (float)reward;
+        *at(p.reward, (unsigned)e) = (float)d.reward;
         *at(p.done, (unsigned)e) = done ? 1 : 0;
         LF(FINENV_LF_SUM_TRADES) = sum_trades;
-        LF(FINENV_LF_LOGGED_TOTAL) = logged_total;
-        LF(FINENV_LF_LOGGED_CASH) = logged_cash;
+        LF(FINENV_LF_LOGGED_TOTAL) = d.logged_total;
+        LF(FINENV_LF_LOGGED_CASH) = d.logged_cash;
         LF(FINENV_LF_ACTUAL_NUM_TRADES) = actual_num_trades;
     }
     wave_sync();
     const unsigned long long valid_mask = __ballot(valid);
-    const unsigned long long done_mask = __ballot(done && valid);
-    int row_day = di;
-    if (done_mask != 0ull) {
-        if (p.term_obs != nullptr)
-            tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
-        if (p.auto_reset) {                                                      // reset()
-            wave_sync();
-            if (done) {
-                const int ns = TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
-                di = ns;
-                row_day = ns;
-                coh = c.initial_amount;
-                turb = 0.0;
-                row[0] = (float)coh;
-                for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
-                if (valid) {
-                    for (int i = 0; i < FINENV_STOPLOSS_BOOKS * N; ++i) LV(0, i) = 0.0;
-                    tw_win_promote<WIN>(p, e);
-                    LI(FINENV_LI_START) = ns;
-                    LI(FINENV_LI_EPISODE) += 1;
-                    LF(FINENV_LF_SUM_TRADES) = 0.0;
-                    LF(FINENV_LF_ACTUAL_NUM_TRADES) = 0.0;
-                }
-            }
-            wave_sync();
-        }
-    }
-    tw_write_rows(p.obs, p, e0, nenv_w, row_day, valid_mask, rows, lane);
+    sl_episode_end<WIN>(p, e, e0, nenv_w, rows, lane, valid, done, [&]() {
+        return TW_NEXT_START(WIN, LI(FINENV_LI_EPISODE), LI(FINENV_LI_NEXT_START));
+    }, di, coh, turb);
+    tw_write_rows(p.obs, p, e0, nenv_w, di, valid_mask, rows, lane);
     if (valid) {
         LF(FINENV_LF_COH) = coh;
         LI(FINENV_LI_DATE_INDEX) = di;
         if (c.use_turbulence) LF(FINENV_LF_TURBULENCE) = turb;
     }
-}
-
-// pass 3 (:388-428) for one asset: new books from (transaction, close, holdings, average buy price,
-// buy count).  Returns the new holdings; *ntr counts applied transactions, *flags the audit bits.
-struct SlBook { double ps, hu, nb, abp; };
-__device__ __forceinline__ SlBook sl_update(const finenv_stoploss_config &c, double tr0, double cl,
-                                            double h, double abp, double nb, bool keep_buys,
-                                            double &ntr, int &flags)
-{
-    const bool sold = tr0 < 0.0;                                     // sells > 0
-    const bool bought = tr0 > 0.0;                                   // buys > 0 (:418)
-    const double tr = (bought && !keep_buys) ? 0.0 : tr0;            // :376
-    const double scp = sold ? cl : 0.0;                              // :388-390
-    const bool profit = scp - abp > 0.0;                             // :391-393
-    SlBook b;
-    b.ps = profit ? cl - (c.min_profit_penalty * abp) : 0.0;         // :395-399
-    flags |= b.ps < 0.0 ? FINENV_AUDIT_F_LOW_PROFIT                  // :401-405
-                        : (b.ps > 0.0 ? FINENV_AUDIT_F_HIGH_PROFIT : 0);
-    ntr += tr != 0.0 ? 1.0 : 0.0;                                    // :411
-    b.hu = h + tr;                                                   // :415
-    nb += bought ? 1.0 : 0.0;                                        // :419
-    const double abp_new = abp + ((cl - abp) / nb);                  // :420-424
-    abp = bought ? abp_new : abp;
-    const bool held = b.hu > 0.0;                                    // :427-428
-    b.nb = held ? nb : 0.0;
-    b.abp = held ? abp : 0.0;
-    return b;
 }
 
 template <int NCH, bool DISCRETE, bool WIN>
@@ -516,15 +577,9 @@ stoploss_step2_kernel(const SlParams p)
             const int i = kHalf + u;
             if (i >= N) continue;              // (continue, not break: keeps the loop fully unrollable)
             const double cl = trl[lane * kClStride + i], h = hx[u], abp = ax[u];
-            if (keep_cd) LV(FINENV_LV_CLOSING_DIFF_AVG_BUY, i) = cl - (c.stoploss_penalty * abp);   // :350-352
+            if (keep_cd) LV(FINENV_LV_CLOSING_DIFF_AVG_BUY, i) = sl_closing_diff(c, cl, abp);
             const SlBook b = sl_update(c, trx[u * kWave + lane], cl, h, abp, nx[u], keepb, ntr, fl);
-            if (valid && adv) {
-                LV(FINENV_LV_PROFIT_SELL_DIFF_AVG_BUY, i) = b.ps;
-                LV(FINENV_LV_PREV_HOLDINGS, i) = h;
-                LV(FINENV_LV_HOLDINGS, i) = b.hu;
-                LV(FINENV_LV_N_BUYS, i) = b.nb;
-                LV(FINENV_LV_AVG_BUY_PRICE, i) = b.abp;
-            }
+            if (valid && adv) sl_store_book(p, e, i, h, b);
             row[1 + i] = (float)(adv ? b.hu : h);
         }
         ntrx[lane] = adv ? ntr : 0.0;
@@ -558,7 +613,7 @@ stoploss_step2_kernel(const SlParams p)
     double coh = LF(FINENV_LF_COH);
     double turb = c.use_turbulence ? LF(FINENV_LF_TURBULENCE) : 0.0;
     double sum_trades = LF(FINENV_LF_SUM_TRADES);
-    double logged_total = LF(FINENV_LF_LOGGED_TOTAL), logged_cash = LF(FINENV_LF_LOGGED_CASH);
+    const double lt_old = LF(FINENV_LF_LOGGED_TOTAL), lc_old = LF(FINENV_LF_LOGGED_CASH);
     double actual_num_trades = LF(FINENV_LF_ACTUAL_NUM_TRADES);
     stage_action_tile(rows, kRow, p.actions + (size_t)e0 * N, nenv_w, N, p.magicN, lane);
     const int step = di - start;                                                 // current_step
@@ -568,7 +623,6 @@ stoploss_step2_kernel(const SlParams p)
     STAMP64(1);
 
     double slp_sum = 0.0, lpp_sum = 0.0, add = 0.0;
-    const double lt_old = logged_total, lc_old = logged_cash;
     double hS[kHalf], abS[kHalf], trS[kHalf];  // own assets, pass 2 -> pass 3 (statically indexed)
 #pragma unroll
     for (int i = 0; i < kHalf; ++i) { hS[i] = 0.0; abS[i] = 0.0; trS[i] = 0.0; }
@@ -592,27 +646,22 @@ stoploss_step2_kernel(const SlParams p)
             for (int j = 0; j < kB; ++j) {
                 const int i = i0 + j;
                 if (i >= N) continue;
-                sum_trades += fabs((double)row[i]);                              // :294
-                slp_sum += ph[j] * fmin(cd[j], 0.0);                             // :262,:273-275
-                lpp_sum += hh[j] * fmin(ps[j], 0.0);                             // :263-265,:278-280
-                add += hh[j] * fmax(ps[j], 0.0);                                 // :266-268,:283
+                sl_pass1(row[i], hh[j], ph[j], ps[j], cd[j], sum_trades, slp_sum, lpp_sum, add);
                 if (i < kHalf) hS[i < kHalf ? i : 0] = hh[j];
                 else trx[(i >= kHalf ? i - kHalf : 0) * kWave + lane] = 0.0;
             }
         }
     }
-    double reward = at_end ? sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add) : 0.0;  // :304
-    bool done = at_end;
+    SlDecision d = {coh, at_end ? sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add) : 0.0,   // :304
+                    lt_old, lc_old, true, at_end, at_end ? FINENV_AUDIT_F_LAST_DATE : 0};
 
     // ---- pass 2: transactions (:320-357), proceeds / spend (:363-370) --------------------------
     const float hmaxf = (float)c.hmax;
     const bool turbulent = c.use_turbulence && turb >= c.turbulence_threshold;
     const bool stop_armed = coh >= c.stoploss_penalty * c.initial_amount;        // :353
     double asset_value = 0.0, proceeds = 0.0, spend = 0.0, slp_new = 0.0;
-    bool keep_buys = true;
-    double coh_new = coh;
     const double coh_begin = coh;
-    int audit_flags = at_end ? FINENV_AUDIT_F_LAST_DATE : 0;
+    int audit_flags = d.flags;
     if (!at_end) {
 #pragma unroll
         for (int i0 = 0; i0 < kMaxN; i0 += kB) {
@@ -636,28 +685,12 @@ stoploss_step2_kernel(const SlParams p)
                 const int i = i0 + j;
                 if (i >= N) continue;          // (continue, not break: keeps the loop fully unrollable)
                 const double h = hb[j], cl = trl[lane * kClStride + i], abp = ab[j];
-                sum_trades += fabs((double)row[i]);                              // :294
-                slp_sum += pb[j] * fmin(cdo[j], 0.0);                            // :262,:273-275
-                lpp_sum += h * fmin(pso[j], 0.0);                                // :263-265,:278-280
-                add += h * fmax(pso[j], 0.0);                                    // :266-268,:283
+                sl_pass1(row[i], h, pb[j], pso[j], cdo[j], sum_trades, slp_sum, lpp_sum, add);
                 asset_value += h * cl;                                           // :311
-                const float a32 = row[i] * hmaxf;                                // :321 (float32)
-                double a = cl > 0.0 ? (double)a32 : 0.0;                         // :326
-                a = turbulent ? -(h * cl) : a;                                   // :327-331
-                double tr;
-                if (DISCRETE) {                                                  // :333-343
-                    const double q = cl > 0.0 ? floordiv_true(a, cl) : 0.0;
-                    const double inc = (double)c.shares_increment;
-                    const double num = q >= 0.0 ? q : q + inc;
-                    tr = floordiv_true(num, inc) * inc;
-                } else {
-                    tr = cl > 0.0 ? a / cl : 0.0;                                // :345
-                }
-                tr = fmax(tr, -h);                                               // :348
-                const double cd = cl - (c.stoploss_penalty * abp);               // :350-352
+                const double cd = sl_closing_diff(c, cl, abp);
                 slp_new += pb[j] * fmin(cd, 0.0);
-                tr = (stop_armed && cd < 0.0) ? -h : tr;                         // :353-357
-                audit_flags |= (stop_armed && cd < 0.0) ? FINENV_AUDIT_F_STOP_LOSS : 0;   // :359-360
+                const double tr = sl_transaction(c, row[i], h, cl, cd, hmaxf, turbulent, stop_armed, DISCRETE,
+                                                 audit_flags);
                 if (i < kHalf) {
                     hS[i < kHalf ? i : 0] = h;
                     abS[i < kHalf ? i : 0] = abp;
@@ -669,27 +702,11 @@ stoploss_step2_kernel(const SlParams p)
                 spend += (tr > 0.0 ? tr : 0.0) * cl;                             // :368-369
             }
         }
-        reward = sl_reward(c, step, lt_old, lc_old, slp_sum, lpp_sum, add);      // :313 (stale log)
-        logged_cash = coh;                                                       // :315-317
-        logged_total = coh + asset_value;
-        double costs = proceeds * c.sell_cost_pct;                               // :365
-        const double coh1 = coh + proceeds;                                      // :366
-        costs += spend * c.buy_cost_pct;                                         // :370
-        audit_flags |= turbulent ? FINENV_AUDIT_F_TURBULENCE : 0;
-        if (spend + costs > coh1) {                                              // :372
-            audit_flags |= FINENV_AUDIT_F_CASH_SHORTAGE;
-            if (c.patient) {                                                     // :373-378
-                keep_buys = false;
-                spend = 0.0;
-                costs = 0.0;
-            } else {                                                             // :379-383
-                done = true;
-                reward = sl_reward(c, step, logged_total, logged_cash, slp_new, lpp_sum, add);
-            }
-        }
-        coh_new = coh1 - spend - costs;                                          // :414
+        d = sl_cash_decision(c, step, coh, asset_value, proceeds, spend, turbulent, lt_old, lc_old,
+                             slp_sum, slp_new, lpp_sum, add);
+        audit_flags |= d.flags;
     }
-    const bool advance = !done;
+    const bool done = d.done, keep_buys = d.keep_buys, advance = !done;
     STAMP64(2);
     // ---- the decision is published (LDS is in-order per wave: data first, then the flag) --------
     int ns_reset = 0;
@@ -712,26 +729,20 @@ stoploss_step2_kernel(const SlParams p)
         for (int i = 0; i < kHalf; ++i) {
             if (i >= N) continue;
             const double cl = trl[lane * kClStride + i], h = hS[i], abp = abS[i];
-            if (keep_cd) LV(FINENV_LV_CLOSING_DIFF_AVG_BUY, i) = cl - (c.stoploss_penalty * abp);   // :350-352
+            if (keep_cd) LV(FINENV_LV_CLOSING_DIFF_AVG_BUY, i) = sl_closing_diff(c, cl, abp);
             int fl = 0;
             double nt = 0.0;
             const SlBook b = sl_update(c, trS[i], cl, h, abp, nbS[i], keep_buys, nt, fl);
             if (advance) {
                 ntr += nt;
                 audit_flags |= fl;
-                if (valid) {
-                    LV(FINENV_LV_PROFIT_SELL_DIFF_AVG_BUY, i) = b.ps;
-                    LV(FINENV_LV_PREV_HOLDINGS, i) = h;
-                    LV(FINENV_LV_HOLDINGS, i) = b.hu;
-                    LV(FINENV_LV_N_BUYS, i) = b.nb;
-                    LV(FINENV_LV_AVG_BUY_PRICE, i) = b.abp;
-                }
+                if (valid) sl_store_book(p, e, i, h, b);
             }
             row[1 + i] = (float)(advance ? b.hu : h);
         }
     }
     if (advance) {
-        coh = coh_new;
+        coh = d.coh_new;
         di += 1;                                                                 // :430
         if (c.use_turbulence) turb = *at(p.panel.turb, (unsigned)di);            // :431-434
     }
@@ -742,56 +753,23 @@ stoploss_step2_kernel(const SlParams p)
         actual_num_trades = ntr + ntrx[lane];    // (counts: exact in any order)
         audit_flags |= aflags[lane];
     }
-    if (p.audit != nullptr && valid) {      // harness log row (account_information / transaction_memory)
-        double *au = p.audit + (size_t)e * (size_t)(FINENV_AUDIT_HEAD + N);
-        au[FINENV_AUDIT_BEGIN_CASH] = coh_begin;                                 // :307
-        au[FINENV_AUDIT_ASSET_VALUE] = asset_value;                              // :311
-        au[FINENV_AUDIT_REWARD] = reward;
-        au[FINENV_AUDIT_FLAGS] = (double)audit_flags;
-#pragma unroll
-        for (int i = 0; i < kMaxN; ++i) {
-            if (i >= N) continue;
-            const double trv = i < kHalf ? trS[i < kHalf ? i : 0]
-                                         : trx[(i >= kHalf ? i - kHalf : 0) * kWave + lane];
-            const double tr = at_end ? 0.0 : trv;
-            au[FINENV_AUDIT_HEAD + i] = (tr > 0.0 && !keep_buys) ? 0.0 : tr;     // :376 / :385
-        }
-    }
+    if (p.audit != nullptr && valid)
+        sl_audit_row(p, e, coh_begin, asset_value, d.reward, audit_flags, at_end, keep_buys, [&](int i) {
+            return i < kHalf ? trS[i < kHalf ? i : 0] : trx[(i >= kHalf ? i - kHalf : 0) * kWave + lane];
+        });
     row[0] = (float)coh;
     if (valid) {
-        *at(p.reward, (unsigned)e) = (float)reward;
+        *at(p.reward, (unsigned)e) = (float)d.reward;
         *at(p.done, (unsigned)e) = done ? 1 : 0;
         LF(FINENV_LF_SUM_TRADES) = sum_trades;
-        LF(FINENV_LF_LOGGED_TOTAL) = logged_total;
-        LF(FINENV_LF_LOGGED_CASH) = logged_cash;
+        LF(FINENV_LF_LOGGED_TOTAL) = d.logged_total;
+        LF(FINENV_LF_LOGGED_CASH) = d.logged_cash;
         LF(FINENV_LF_ACTUAL_NUM_TRADES) = actual_num_trades;
     }
     wave_sync();
     const unsigned long long valid_mask = __ballot(valid);
-    const unsigned long long done_mask = __ballot(done && valid);
-    if (done_mask != 0ull) {
-        if (p.term_obs != nullptr)
-            tw_write_rows<true>(p.term_obs, p, e0, nenv_w, di, done_mask, rows, lane);   // once per episode
-        if (p.auto_reset) {                                                      // reset()
-            wave_sync();
-            if (done) {
-                di = ns_reset;
-                coh = c.initial_amount;
-                turb = 0.0;
-                row[0] = (float)coh;
-                for (int i = 0; i < N; ++i) row[1 + i] = 0.0f;
-                if (valid) {
-                    for (int i = 0; i < FINENV_STOPLOSS_BOOKS * N; ++i) LV(0, i) = 0.0;
-                    tw_win_promote<WIN>(p, e);
-                    LI(FINENV_LI_START) = ns_reset;
-                    LI(FINENV_LI_EPISODE) += 1;
-                    LF(FINENV_LF_SUM_TRADES) = 0.0;
-                    LF(FINENV_LF_ACTUAL_NUM_TRADES) = 0.0;
-                }
-            }
-            wave_sync();
-        }
-    }
+    sl_episode_end<WIN>(p, e, e0, nenv_w, rows, lane, valid, done, [&]() { return ns_reset; }, di, coh,
+                        turb);
     STAMP64(5);
     lds_barrier();                            // #2: rows final, chunk 0 parked by the streamer
     tw_head_store<NCH>(p.obs, p, e0, nenv_w, valid_mask, rows, reinterpret_cast<const float *>(trl),

@@ -86,7 +86,14 @@ def test_stoploss_hip_matches_reference_fixture(name):
     # 16 columns: one chunk with discrete actions, and a partial second block
     dict(E=70, T=16, N=5, C=2, steps=40, hmax=300_000, thr=45.0, patient=False, disc=True),
     # 331 columns again, with discrete actions and the patient cash-shortage branch
-    dict(E=70, T=16, N=30, C=10, steps=24, hmax=60_000, thr=40.0, patient=True, disc=True)])
+    dict(E=70, T=16, N=30, C=10, steps=24, hmax=60_000, thr=40.0, patient=True, disc=True),
+    # the trader / streamer split of the assets at 16.  69 columns: the streamer's pass 3 holds exactly
+    # one asset, two quads per row; cash shortages end nearly every episode
+    dict(E=70, T=16, N=17, C=3, steps=40, hmax=60_000, thr=40.0, patient=False, disc=True),
+    # the same with the patient branch: every episode ends on the last date
+    dict(E=70, T=16, N=17, C=3, steps=40, hmax=60_000, thr=40.0, patient=True, disc=False),
+    # 65 columns: the streamer's pass 3 holds no asset
+    dict(E=130, T=16, N=16, C=3, steps=40, hmax=60_000, thr=None, patient=False, disc=False)])
 def test_stoploss_hip_matches_oracle_random_batch(cfg):
     _need_gpu()
     from finrl_amd.vec_cashpenalty import CashPenaltyPanel, VecStopLossEnv

@@ -8,7 +8,8 @@ usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|portfoli
   cashpenalty:c<C>:<disc|cont>, stoploss:c<C>:<disc|cont>: VecCashPenaltyEnv / VecStopLossEnv as bench.py builds
     them (65,536 envs, 30 assets, hmax=2_000, random starts) but with C columns per asset and the given
     discrete_actions setting -- C = 1: 61-column rows (one chunk), 5: 181 (the quad streamer; the bench.py
-    line), 10: 331 (the one-wave step)"""
+    line), 10: 331 (the one-wave step); a fourth field ":win63" attaches random 63-row windows (the WIN
+    instantiations of the same kernels), drawn as for portfolio-random63"""
 import os
 import sys
 
@@ -66,7 +67,9 @@ def two_wave_ab(libs, nat, torch, dev, E, kind, rounds):
     import numpy as np
     import bench
     from finrl_amd.vec_cashpenalty import CashPenaltyPanel, VecCashPenaltyEnv, VecStopLossEnv
-    name, cols, act = kind.split(":")
+    name, cols, act, *win = kind.split(":")
+    if win not in ([], ["win63"]):
+        raise SystemExit(f"{kind}: the only fourth field is win63")
     T, N, Cc = bench.N_DAYS, bench.N_TICKERS, int(cols[1:])
     rng = np.random.default_rng(0)
     close = 50 * np.exp(np.cumsum(rng.normal(0, 0.01, (T, N)), axis=0))
@@ -76,6 +79,10 @@ def two_wave_ab(libs, nat, torch, dev, E, kind, rounds):
               device=dev, seed=0)
     gen = torch.Generator(device=dev).manual_seed(1234)
     pool = [torch.rand(E, N, generator=gen, device=dev) * 2.0 - 1.0 for _ in range(8)]
+    if win:
+        from finrl_amd.data import random_windows
+        g = torch.Generator(device=dev).manual_seed(7)
+        env.set_windows(*random_windows(T, E, 63, generator=g, device=dev))
     alternate(libs, dict.fromkeys(libs), nat, torch, env, pool, kind, rounds)
 
 
