@@ -65,6 +65,24 @@ enum {
  * them below 2^31 is the caller's business.  NaN and +-inf actions are unspecified (the reference's own
  * cast is undefined there); they trade some saturated or zero amount and never fault. */
 
+/* Panel domain of finenv_stock_step (stated here once; finenv_stock_panel below refers to it).
+ * Closes are finite and >= 0, at any magnitude: min(a, cash // unit) is the reference's at every
+ * quotient (exact floor division below 2^40; beyond that the saturated action is always the smaller).
+ * A close of 0 -- what FinRL's preprocessing writes for a missing price -- is a valid value:
+ *   - a buy at close == 0 fills 0 shares and counts no trade (the reference divides by zero there:
+ *     the one deliberate deviation);
+ *   - a sell outside turbulence looks at the flag and the holdings only: at close == 0 it removes
+ *     min(-a, held) shares, adds +0.0 to cash and cost and counts one trade (:105-129);
+ *   - the turbulent liquidation sells a ticker only where close > 0 (:139-163): shares of a
+ *     zero-priced ticker stay held, whatever its flag; a flagged ticker with close > 0 is sold.
+ * The untradable flag is the fp64 compare tech_0 == 1.0 (:105, :174): neither fp64 neighbour of 1.0
+ * is a flag, nor a value that only rounds to 1.0f in the observation.  It travels in the sign bit of
+ * `close`, so a flagged zero close is -0.0 and an unflagged one +0.0; every valuation uses |close|.
+ * An env is turbulent when turbulence >= turbulence_threshold (:308): equality liquidates, the next
+ * double below does not, and with a threshold of 0.0 so do risk rows of +-0.0 and the 0 that reset()
+ * leaves in `turbulence`.  NaN and +-inf closes, indicators and risk values are unspecified.
+ * tests/test_gpu_stock_panel_domain.py holds every kernel to this. */
+
 /* Constructor arguments of StockTradingEnv that shape the arithmetic
  * (env_stocktrading.py:24-47). */
 typedef struct finenv_stock_config {
@@ -103,7 +121,8 @@ typedef struct finenv_stock_panel {
                                      "untradable" flag of ticker i: set <=> its first
                                      indicator == 1.0 on day t (the fork's `!= True` test,
                                      :105, :174, evaluated on the fp64 values); prices
-                                     themselves are >= 0 by contract                     */
+                                     themselves are >= 0 by contract, 0 included (-0.0
+                                     when flagged): see "Panel domain" above             */
     const float    *obs_tmpl;     /* [T][D]  f32 observation rows with the cash and
                                      holdings slots zero: f32(close) and f32(tech) in obs
                                      order (what DummyVecEnv's float32 buffer would hold) */
@@ -523,6 +542,10 @@ typedef struct finenv_crypto_config {
     double  gamma;                /* :19                                                 */
 } finenv_crypto_config;
 
+/* Prices are finite and >= 0 (any magnitude: `cash // price` is the exact floor division).  A trade
+ * needs price > 0, as in the reference (:67-77): at a price of 0 neither a sell nor a buy touches
+ * holdings or cash, and the asset is valued at 0.  Row 0 must be > 0 throughout (action_norm_vector
+ * takes its logarithm).  tests/test_gpu_crypto_panel_domain.py. */
 typedef struct finenv_crypto_panel {
     const double *price;          /* [T][N] f64                                          */
     const float  *tech_scaled;    /* [T][W] f32 = float32(tech * 2^-15), :95-97          */
@@ -718,6 +741,10 @@ typedef struct finenv_stocknp_config {
                                      (env_nas100_wrds.py:154, floor = 1e4)                 */
 } finenv_stocknp_config;
 
+/* Prices are finite f32 >= 0.  A trade needs price > 0, as in the reference (:112-129): at a price of
+ * 0 neither a sell nor a buy touches holdings, amount or the cool-down, which goes on counting; the
+ * turbulent liquidation (:131-134) sells everything and values a zero-priced holding at 0.  A day is
+ * turbulent when turbulence > thresh (:32): equality is calm.  tests/test_gpu_stocknp_panel_domain.py. */
 typedef struct finenv_stocknp_panel {
     const float *price;           /* [T][N] price_ary (f32), :27                          */
     const float *obs_tmpl;        /* [T][D] f32 rows: turbulence / price*2^-6 / tech filled,

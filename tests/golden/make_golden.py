@@ -51,6 +51,39 @@ def synth_panel(seed, T, N, K, *, flag_frac=0.0, fp32_prices=True, price0=100.0)
     return close, tech, risk
 
 
+def pricedomain_prices(rng, T, N, lo, hi, sigma, keep_row0):
+    """Price levels 10^U(lo, hi) per ticker (both ends present) times a random walk, ~15 % of the
+    cells zero, ticker 1 zero throughout and row 3 zero -- what FinRL's preprocessing leaves where a
+    close is missing.  keep_row0: no zero in the first row."""
+    level = 10.0 ** rng.uniform(lo, hi, N)
+    level[0], level[-1] = 10.0 ** lo * 1.7, 10.0 ** hi * 0.8
+    price = level * np.exp(np.cumsum(rng.normal(0, sigma, (T, N)), axis=0))
+    zero = rng.random((T, N)) < 0.15
+    if N > 1:
+        zero[:, 1] = True
+    zero[3, :] = True
+    zero[0, :] = zero[0, :] & (not keep_row0)
+    zero[0, 0] = False
+    price[zero] = 0.0
+    return price
+
+
+def pricedomain_panel(seed, T, N, K, threshold):
+    """The stock env's panel domain in one small panel (fp64 throughout): prices 1e-4 .. 3e5 with
+    zero closes, the untradable flag on ~15 % of the cells (zeros included) and the fp64 neighbours
+    of 1.0 on as many, risk rows at the threshold, its two neighbours and 0.0."""
+    rng = np.random.default_rng(seed)
+    close = pricedomain_prices(rng, T, N, -4.0, 5.5, 0.02, keep_row0=False)
+    tech = rng.normal(0, 1, (T, K, N))
+    pick = rng.random((T, N))
+    tech[:, 0, :][pick < 0.15] = 1.0
+    near = [np.nextafter(1.0, 0.0), np.nextafter(1.0, 2.0), 1.0 + 2.0 ** -30]
+    tech[:, 0, :][pick > 0.85] = rng.choice(near, int((pick > 0.85).sum()))
+    lo, hi = np.nextafter(threshold, 0.0), np.nextafter(threshold, np.inf)
+    risk = np.resize(np.array([1.0, lo, threshold, lo, hi, 0.0, threshold, lo]), T)
+    return close, tech, risk
+
+
 def tiefree_actions(rng, S, N, hmax):
     """float32 actions whose (a*hmax).astype(int) are distinct and non-zero per step."""
     pool = np.concatenate([np.arange(-hmax, 0), np.arange(1, hmax + 1)])
@@ -68,7 +101,7 @@ def run_stock(name, *, seed, T, N, K, S, variant, actions="uniform", hmax=100,
               initial_amount=1_000_000, shares0=None, buy_cost_pct=1e-3, sell_cost_pct=1e-3,
               reward_scaling=1e-4, turbulence_threshold=None, flag_frac=0.0,
               previous_state=False, store_obs=True, zero_frac=0.0, fp32_prices=True,
-              day0=0, reset_first=True):
+              day0=0, reset_first=True, panel=None):
     mod = rh.load_stocktrading()
     if variant == "O-stable":
         rh.stable_argsort_patch(mod)
@@ -76,6 +109,10 @@ def run_stock(name, *, seed, T, N, K, S, variant, actions="uniform", hmax=100,
         raise ValueError(variant)
     rng = np.random.default_rng(seed + 1000)
     close, tech, risk = synth_panel(seed, T, N, K, flag_frac=flag_frac, fp32_prices=fp32_prices)
+    if panel == "pricedomain":
+        close, tech, risk = pricedomain_panel(seed, T, N, K, turbulence_threshold)
+    elif panel is not None:
+        raise ValueError(panel)
     names = [f"ind{k}" for k in range(K)]
     df = rh.make_stock_frame(close, tech, risk, names, risk_col="turbulence")
     if shares0 is None:
@@ -127,6 +164,13 @@ def run_stock(name, *, seed, T, N, K, S, variant, actions="uniform", hmax=100,
                 rec["reset_obs"].append(np.asarray(env.reset(), dtype=np.float64))
             for s in range(S):
                 a_in = act[s].copy()
+                if panel == "pricedomain":
+                    # a buy at an unflagged zero close divides by zero in the reference (:178-180): the
+                    # fixture asks for a sale of the same size there instead
+                    held = np.asarray(env.state[1:1 + N])
+                    flag = np.asarray(env.state[1 + 2 * N:1 + 3 * N])
+                    a_in = np.where((held == 0.0) & (flag != 1.0) & (a_in > 0), -a_in, a_in)
+                    act[s] = a_in
                 n_act_before = len(env.actions_memory)
                 obs, rew, done, info = env.step(a_in)
                 rec["obs"].append(np.asarray(obs, dtype=np.float64))
@@ -250,6 +294,11 @@ STOCK_SCENARIOS = {
     # the action itself each bind in some steps
     "bigactions": dict(seed=35, T=8, N=5, K=2, S=20, variant="O-stable", actions="big",
                        initial_amount=3_000_000, shares0=[0, 40_000, 150, 20_000, 7]),
+    # the panel value domain: zero closes (flagged and not), price levels 1e-4 .. 3e5, tech_0 at the
+    # neighbours of 1.0, risk rows at the threshold, next to it and at 0.0; 2.5 episodes
+    "pricedomain": dict(seed=36, T=9, N=6, K=2, S=20, variant="O-stable", actions="uniform",
+                        panel="pricedomain", turbulence_threshold=37.3, initial_amount=20_000,
+                        shares0=[3, 25, 0, 12, 7, 30], fp32_prices=False),
     "n1_prevstate": dict(seed=34, T=18, N=1, K=3, S=45, variant="O-stable", actions="uniform",
                          initial_amount=6_000, hmax=30, shares0=[9], previous_state=True),
 }
@@ -338,13 +387,15 @@ PORTFOLIO_SCENARIOS = {
 
 # ----------------------------------------------------------------- multi-crypto env
 def run_crypto(name, *, seed, T, N, W, S, lookback=1, initial_capital=1e6, price0=None,
-               gamma=0.99, buy_cost_pct=1e-3, sell_cost_pct=1e-3, act_scale=1.0):
+               gamma=0.99, buy_cost_pct=1e-3, sell_cost_pct=1e-3, act_scale=1.0, panel=None):
     """Unmodified reference CryptoEnv (env_multiple_crypto.py), float64 price/tech arrays."""
     mod = rh.load_multiple_crypto()
     rng = np.random.default_rng(seed + 3000)
     if price0 is None:
         price0 = 10.0 ** rng.uniform(-1, 4.5, N)
     price = np.asarray(price0) * np.exp(np.cumsum(rng.normal(0, 0.004, (T, N)), axis=0))
+    if panel == "pricedomain":      # levels 1e-8 .. 1e5, zero prices everywhere but in the row the normaliser reads
+        price = pricedomain_prices(rng, T, N, -8.0, 5.0, 0.004, keep_row0=True)
     tech = rng.normal(0, 3000, (T, W))
     act = (rng.uniform(-1, 1, (S, N)) * act_scale).astype(np.float32)
     act[rng.random((S, N)) < 0.1] = 0.0
@@ -395,6 +446,7 @@ CRYPTO_SCENARIOS = {
     "n1": dict(seed=43, T=20, N=1, W=3, S=45, initial_capital=5e4, price0=[123.4],
                buy_cost_pct=0.002, sell_cost_pct=0.0005, gamma=0.97),
     "n9_poor": dict(seed=44, T=25, N=9, W=5, S=60, initial_capital=2e3, act_scale=3.0),
+    "pricedomain": dict(seed=45, T=10, N=6, W=4, S=22, initial_capital=3e4, panel="pricedomain"),
 }
 
 
@@ -408,7 +460,7 @@ def _tag(x):
 
 def run_stocknp(name, *, seed, T, N, K, S, if_train=False, initial_capital=1e6, max_stock=1e2,
                 turb_scale=60.0, buy_cost_pct=1e-3, sell_cost_pct=1e-3, gamma=0.99, nas100=False,
-                data_gap=1, turbulence_thresh=99):
+                data_gap=1, turbulence_thresh=99, panel=None):
     """Unmodified reference env_stocktrading_np.StockTradingEnv (NumPy-version dependent mixed
     float32/float64 arithmetic: the dtype of every scalar is recorded next to its value).
     nas100=True: env_nas100_wrds.StockEnvNAS100 instead -- the same step on float32 arrays handed
@@ -437,6 +489,9 @@ def run_stocknp(name, *, seed, T, N, K, S, if_train=False, initial_capital=1e6, 
         price = 100 * np.exp(np.cumsum(rng.normal(0, 0.01, (T, N)), axis=0))
         tech = rng.normal(0, 50, (T, N * K))
         turb = np.abs(rng.normal(0, turb_scale, T))
+        if panel == "pricedomain":  # levels 1e-3 .. 1e5 with zero prices; a day on the threshold, one above
+            price = pricedomain_prices(rng, T, N, -3.0, 5.0, 0.01, keep_row0=True)
+            turb[[4, 6]] = turbulence_thresh, 150.0
         cfg = {"price_array": price, "tech_array": tech, "turbulence_array": turb,
                "if_train": if_train}
         env = mod.StockTradingEnv(cfg, initial_capital=initial_capital, max_stock=max_stock,
@@ -509,6 +564,7 @@ STOCKNP_SCENARIOS = {
     "eval_dow30": dict(seed=51, T=40, N=30, K=8, S=95),
     "eval_poor": dict(seed=52, T=30, N=30, K=8, S=70, initial_capital=3e4),
     "train_dow30": dict(seed=53, T=30, N=30, K=8, S=70, if_train=True),
+    "pricedomain": dict(seed=57, T=10, N=6, K=2, S=22, initial_capital=3e4, panel="pricedomain"),
     "eval_n3": dict(seed=54, T=25, N=3, K=2, S=60, initial_capital=5e3, max_stock=50.0,
                     buy_cost_pct=0.002, sell_cost_pct=0.0005, gamma=0.97, turb_scale=90.0),
     # StockEnvNAS100 (env_nas100_wrds.py): random start at every reset, obs shows max(amount, 1e4);
