@@ -885,8 +885,19 @@ int finenv_stocknp_history_metrics(finenv_stocknp *h, double annualization, doub
  * (assets - cash-shortfall penalty) / initial - 1, per elapsed step (:237-247); episode ends at
  * the last date or on a cash shortage (unless patient) (:333-344).
  *   actions [E][N] f32;  obs [E][D] f32, D = 1 + N + N*C = [cash | holdings | info[N][C]]
- * Contract: close > 0, scalar hmax.  The three dot products per step are summed left to right
+ * Contract: scalar hmax.  The three dot products per step are summed left to right
  * (the reference uses BLAS ddot, order unspecified: agreement ~1e-15 relative).
+ *
+ * Panel domain.  Closes are finite and > 0, at any magnitude.  The reference divides by the close
+ * unguarded (:276, :286): at close == 0 its continuous form yields NaN holdings and its discrete form
+ * the platform's integer cast of a NaN, so a zero close is outside the domain here (the kernel then
+ * sells the holdings of that asset: unspecified, no fault).  Discrete actions: integer share
+ * counts from `act * hmax // close` (:263-274), which is NumPy's floor_divide and not floor(a / close)
+ * (3.0 // 0.1 == 29); the kernel's division is that one for |act * hmax / close| < 2^50.  Equality at
+ * a compare is decided as the reference decides it: turbulence == turbulence_threshold liquidates
+ * (`>=`, :282), spend + costs == cash is no shortage (`>`, :333: the step is applied and cash lands on
+ * 0.0), total * cash_penalty_proportion == cash is no penalty (:241).  NaN and +-inf closes and risk
+ * values are unspecified.  tests/test_gpu_cashpenalty_panel_domain.py holds every launch form to this.
  * ===================================================================================== */
 #define FINENV_CASHPENALTY_MAX_ASSETS 32
 
@@ -1007,6 +1018,20 @@ int  finenv_cashpenalty_set_windows(finenv_cashpenalty *h, int32_t *win);
  * logged totals (:313 precedes :315-318); the turbulence sell-off goes through
  * (h*close)/close (:330,:345); patient mode still books the cancelled buys (:376 vs :418).
  *   actions [E][N] f32;  obs [E][D] f32, D = 1 + N + N*C  (same layout as the cash-penalty env)
+ *
+ * Panel domain.  Closes are finite and >= 0, at any magnitude, and 0 means "missing data" as in the
+ * reference, which guards every division with close > 0 (:326, :335, :345): a request at close == 0
+ * trades nothing, whatever its sign, the turbulent sell-off -(h * 0) is a transaction of 0 that keeps
+ * the asset held, and neither counts in actual_num_trades (:411).  The stop-loss itself looks at no
+ * price guard (:350-357): closing_diff_avg_buy = 0 - stoploss_penalty * avg_buy_price < 0 for a held
+ * asset, so an armed env gives such a position away at 0.0, as the reference does.  Discrete actions:
+ * `a // close` (:335) is NumPy's floor_divide, not floor(a / close), and the kernel's division is that
+ * one for |act * hmax / close| < 2^50.  Equality at a compare is decided as the reference decides
+ * it: turbulence == threshold liquidates (`>=`, :329); cash == stoploss_penalty * initial_amount arms the
+ * stop-loss (`>=`, :353); closing_diff_avg_buy == 0 forces no sale (`<`, :356); spend + costs == cash is
+ * no shortage (`>`, :372); a sale at close == avg_buy_price is no profit (`>`, :392); holdings of
+ * exactly 0 clear the buy book (`>`, :427).  NaN and +-inf closes and risk values are unspecified.
+ * tests/test_gpu_stoploss_panel_domain.py holds every launch form to this.
  * ===================================================================================== */
 #define FINENV_STOPLOSS_MAX_ASSETS 32
 

@@ -9,7 +9,9 @@
  * (tests/golden/stoploss_*.npz).  As in cashpenalty_oracle.c the reference's np.dot calls
  * (BLAS, order unspecified) are summed left to right here: money agrees to ~1e-15 relative
  * (tests: rtol 1e-12); flags, steps, average buy prices and the market part of the
- * observation are exact.  Contract: close > 0, scalar hmax, float32 actions.
+ * observation are exact.  Contract: close >= 0 (0 is the reference's "missing data": every division
+ * is guarded, :326 / :335 / :345, and nothing trades there but the stop-loss of an armed env, which
+ * sells a held asset at 0.0 -- pinned by stoploss_zerocloses.npz), scalar hmax, float32 actions.
  *
  * Quirks kept on purpose (each checked against the goldens):
  *  - get_reward() is called BEFORE this step's account_information entry is appended (:313 vs

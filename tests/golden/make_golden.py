@@ -581,16 +581,20 @@ def run_cashpenalty(name, *, seed, T, N, S, cols=("open", "close", "high", "low"
                     hmax=10, initial_amount=1e6, discrete_actions=False, shares_increment=1,
                     turbulence_threshold=None, patient=False, random_start=False,
                     cash_penalty_proportion=0.1, buy_cost_pct=3e-3, sell_cost_pct=3e-3,
-                    act_scale=1.0):
-    """Unmodified reference StockTradingEnvCashpenalty on a synthetic OHLCV frame."""
+                    act_scale=1.0, close=None, turb=None, actions=None):
+    """Unmodified reference StockTradingEnvCashpenalty on a synthetic OHLCV frame.  close [T, N] /
+    turb [T]: an explicit panel instead of the seeded walk; actions(s, first) -> [N] f32: a script
+    instead of uniform draws (first: the env is on the first step of an episode)."""
     import pandas as pd
     mod = _fresh_cashpenalty()
     rng = np.random.default_rng(seed + 5000)
-    close = 50 * np.exp(np.cumsum(rng.normal(0, 0.01, (T, N)), axis=0))
+    walk = 50 * np.exp(np.cumsum(rng.normal(0, 0.01, (T, N)), axis=0))
+    close = walk if close is None else np.asarray(close, np.float64).reshape(T, N)
     data = {"open": close * rng.uniform(0.99, 1.01, (T, N)), "close": close,
             "high": close * 1.01, "low": close * 0.99,
             "volume": rng.integers(1e5, 1e6, (T, N)).astype(np.float64)}
-    turb = np.abs(rng.normal(0, 30, T))
+    drawn = np.abs(rng.normal(0, 30, T))
+    turb = drawn if turb is None else np.asarray(turb, np.float64).reshape(T)
     tics = [f"TIC{i:03d}" for i in range(N)]
     frame = {"date": np.repeat([f"2020-{1 + t // 28:02d}-{1 + t % 28:02d}" for t in range(T)], N),
              "tic": np.tile(tics, T)}
@@ -613,6 +617,8 @@ def run_cashpenalty(name, *, seed, T, N, S, cols=("open", "close", "high", "low"
         resets = dict(step=[-1], obs=[np.asarray(env.reset(), np.float64)],
                       start=[env.starting_point])
         for s in range(S):
+            if actions is not None:
+                act[s] = actions(s, env.date_index == env.starting_point)
             obs, rew, done, info = env.step(act[s].copy())
             rec["obs"].append(np.asarray(obs, np.float64))
             rec["reward"].append(float(rew)); rec["done"].append(bool(done))
@@ -662,6 +668,11 @@ CASHPENALTY_SCENARIOS = {
     "discrete": dict(seed=64, T=20, N=8, S=45, hmax=30_000, discrete_actions=True,
                      shares_increment=5, cols=("close", "volume")),
     "randstart": dict(seed=65, T=30, N=3, S=60, hmax=50_000, random_start=True),
+    # tests/twowave_domain_cases.py: closes on a cent .. quarter grid, whole-dollar requests
+    "ticks": dict(domain="tick_prices", seed=66, N=5, S=60, args=dict(inc=3, turbulence=True)),
+    # levels 1e-8 .. 3e5, quotients up to 2^49
+    "pricescales": dict(domain="price_scales", seed=67, N=5, S=60,
+                        args=dict(initial_amount=1e6, discrete=True)),
 }
 
 
@@ -670,19 +681,23 @@ def run_stoploss(name, *, seed, T, N, S, cols=("open", "close", "high", "low", "
                  hmax=10, initial_amount=1e6, discrete_actions=False, shares_increment=1,
                  stoploss_penalty=0.9, profit_loss_ratio=2, turbulence_threshold=None,
                  patient=False, random_start=False, cash_penalty_proportion=0.1,
-                 buy_cost_pct=3e-3, sell_cost_pct=3e-3, act_scale=1.0, sigma=0.05):
-    """Unmodified reference StockTradingEnvStopLoss on a synthetic (volatile) OHLCV frame."""
+                 buy_cost_pct=3e-3, sell_cost_pct=3e-3, act_scale=1.0, sigma=0.05, close=None,
+                 turb=None, actions=None):
+    """Unmodified reference StockTradingEnvStopLoss on a synthetic (volatile) OHLCV frame.  close, turb,
+    actions: as in run_cashpenalty."""
     import pandas as pd
     rh.install()
     import importlib
     sys.modules.pop("finrl.meta.env_stock_trading.env_stocktrading_stoploss", None)
     mod = importlib.import_module("finrl.meta.env_stock_trading.env_stocktrading_stoploss")
     rng = np.random.default_rng(seed + 6000)
-    close = 50 * np.exp(np.cumsum(rng.normal(0, sigma, (T, N)), axis=0))
+    walk = 50 * np.exp(np.cumsum(rng.normal(0, sigma, (T, N)), axis=0))
+    close = walk if close is None else np.asarray(close, np.float64).reshape(T, N)
     data = {"open": close * rng.uniform(0.99, 1.01, (T, N)), "close": close,
             "high": close * 1.01, "low": close * 0.99,
             "volume": rng.integers(1e5, 1e6, (T, N)).astype(np.float64)}
-    turb = np.abs(rng.normal(0, 30, T))
+    drawn = np.abs(rng.normal(0, 30, T))
+    turb = drawn if turb is None else np.asarray(turb, np.float64).reshape(T)
     tics = [f"TIC{i:03d}" for i in range(N)]
     frame = {"date": np.repeat([f"2020-{1 + t // 28:02d}-{1 + t % 28:02d}" for t in range(T)], N),
              "tic": np.tile(tics, T)}
@@ -708,6 +723,8 @@ def run_stoploss(name, *, seed, T, N, S, cols=("open", "close", "high", "low", "
         resets = dict(step=[-1], obs=[np.asarray(env.reset(), np.float64)],
                       start=[env.starting_point])
         for s in range(S):
+            if actions is not None:
+                act[s] = actions(s, env.date_index == env.starting_point)
             obs, rew, done, info = env.step(act[s].copy())
             rec["obs"].append(np.asarray(obs, np.float64))
             rec["reward"].append(float(rew)); rec["done"].append(bool(done))
@@ -759,7 +776,30 @@ STOPLOSS_SCENARIOS = {
                      shares_increment=5, cols=("close", "volume"), turbulence_threshold=40.0),
     "randstart": dict(seed=75, T=30, N=3, S=60, hmax=30_000, random_start=True,
                       stoploss_penalty=0.95, profit_loss_ratio=3),
+    # tests/twowave_domain_cases.py: zero closes ("missing data", row 0 included) on a random walk
+    "zerocloses": dict(domain="zero_closes", seed=76, N=5, S=60, args=dict(discrete=True, turbulence=True)),
+    # dyadic prices, every compare of the rule at equality; the scripted armed / shortage ties
+    "ties": dict(domain="dyadic_ties", seed=84, N=5, S=100, args=dict(scripted=True, turbulence=True)),
+    "ticks": dict(domain="tick_prices", seed=78, N=5, S=60, args=dict(inc=1, patient=True)),
 }
+
+
+def domain_scenario(kind, *, domain, seed, N, S, args, cols=("close", "volume")):
+    """A case of tests/twowave_domain_cases.py as runner arguments: its panel and env arguments, and the
+    action rows of its script -- episode k plays the row of env (1, 2, 3, 5)[k % 4], so that the scripted envs
+    of `dyadic_ties` (e % 16 == 1, 2, 3) and a free one take turns."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import twowave_domain_cases as tc
+    case = tc.BUILDERS[domain](N, len(cols), seed, **args)
+    rows, state = (1, 2, 3, 5), dict(episode=-1)
+
+    def actions(s, first):
+        state["episode"] += int(first)
+        return case.script(s, np.full(tc.E, bool(first)))[rows[state["episode"] % len(rows)]]
+
+    kw = dict(tc.env_kwargs(kind, case))
+    return dict(seed=seed, T=tc.T, N=N, S=S, cols=cols, close=case.close, turb=case.turb,
+                actions=actions, **kw)
 
 
 # ----------------------------------------------------------------- turbulence / covariance
@@ -1124,9 +1164,11 @@ def main(argv):
         elif n.startswith("portfolio:") and n[10:] in PORTFOLIO_SCENARIOS:
             run_portfolio(n[10:], **PORTFOLIO_SCENARIOS[n[10:]])
         elif n.startswith("cashpenalty:") and n[12:] in CASHPENALTY_SCENARIOS:
-            run_cashpenalty(n[12:], **CASHPENALTY_SCENARIOS[n[12:]])
+            sc = CASHPENALTY_SCENARIOS[n[12:]]
+            run_cashpenalty(n[12:], **(domain_scenario("cashpenalty", **sc) if "domain" in sc else sc))
         elif n.startswith("stoploss:") and n[9:] in STOPLOSS_SCENARIOS:
-            run_stoploss(n[9:], **STOPLOSS_SCENARIOS[n[9:]])
+            sc = STOPLOSS_SCENARIOS[n[9:]]
+            run_stoploss(n[9:], **(domain_scenario("stoploss", **sc) if "domain" in sc else sc))
         elif n.startswith("harness:") and n[8:] in HARNESS_SCENARIOS:
             run_harness(n[8:], **HARNESS_SCENARIOS[n[8:]])
         elif n.startswith("riskpre:") and n[8:] in RISKPRE_SCENARIOS:

@@ -96,8 +96,9 @@ class Twins:
     logged_cash surviving a reset until the new episode's first trading step (the reference's reset
     leaves them alone)."""
 
-    def __init__(self, kind, sc, close, info, turb, start, end):
+    def __init__(self, kind, sc, close, info, turb, start, end, kw=None):
         self.kind, self.sc = kind, sc
+        self.kw = env_kwargs(sc) if kw is None else kw          # the env arguments of every oracle
         self.Oracle = classes(kind)[2]
         self.close, self.info, self.turb = close, info, turb
         E = sc["E"]
@@ -126,8 +127,8 @@ class Twins:
         if self.orc[e] is None or (s, t) != tuple(self.active[:, e]):
             if self.orc[e] is not None:
                 self.n_reset_on_new_window += 1
-            kw = env_kwargs(self.sc)
-            self.orc[e] = self.Oracle(self.close[s:t], self.info[s:t], self.turb[s:t], n_envs=1, **kw)
+            self.orc[e] = self.Oracle(self.close[s:t], self.info[s:t], self.turb[s:t], n_envs=1,
+                                      **self.kw)
             self.fresh[e] = True
         self.active[:, e] = s, t
         self.one_row_episodes += int(t - s == 1)
