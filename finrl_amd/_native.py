@@ -243,6 +243,25 @@ class BtcStatePtrs(C.Structure):
 # kinds of lib()'s table in order; 18 stays invalid)
 _LATER_STRUCTS = {19: BtcConfig, 20: BtcPanelPtrs, 21: BtcStatePtrs}
 
+
+class ReplayViewPtrs(C.Structure):
+    """finenv_replay_view: the four ring tensors of a replay buffer and S, E, D, P, A."""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p),
+                ("dones", C.c_void_p), ("n_slots", C.c_int32), ("n_envs", C.c_int32),
+                ("obs_dim", C.c_int32), ("obs_pitch", C.c_int32), ("action_dim", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class ReplayBatchPtrs(C.Structure):
+    """finenv_replay_batch: the five outputs of a sampled batch, B and the observation row pitch."""
+    _fields_ = [("observations", C.c_void_p), ("next_observations", C.c_void_p),
+                ("actions", C.c_void_p), ("rewards", C.c_void_p), ("dones", C.c_void_p),
+                ("batch_size", C.c_int32), ("obs_pitch", C.c_int32)]
+
+
+# the replay buffer's pointer structs (22 stays invalid, like 18)
+_REPLAY_STRUCTS = {23: ReplayViewPtrs, 24: ReplayBatchPtrs}
+
 _lib = None
 
 
@@ -335,6 +354,14 @@ def lib():
             getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3
             getattr(L, f"finenv_{kind}_history_metrics").argtypes = [C.c_void_p, C.c_double,
                                                                      C.c_void_p, C.c_void_p]
+    if hasattr(L, "finenv_replay_put"):                    # replay buffer (same rule)
+        L.finenv_replay_put.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p]
+        L.finenv_replay_sample.argtypes = [C.POINTER(ReplayViewPtrs), C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.POINTER(ReplayBatchPtrs), C.c_void_p,
+                                           C.c_void_p]
+        L.finenv_replay_gather.argtypes = [C.POINTER(ReplayViewPtrs), C.c_void_p,
+                                           C.POINTER(ReplayBatchPtrs), C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
@@ -343,6 +370,8 @@ def lib():
              StockNpPanelPtrs, StockNpStatePtrs, CashPenaltyConfig, CashPenaltyPanelPtrs,
              CashPenaltyStatePtrs, StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs)
     later = sorted(_LATER_STRUCTS.items()) if hasattr(L, "finenv_btc_create") else []
+    if hasattr(L, "finenv_replay_put"):
+        later += sorted(_REPLAY_STRUCTS.items())
     for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(

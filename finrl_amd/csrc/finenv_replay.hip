@@ -1,0 +1,246 @@
+// finenv_replay.hip -- replay buffer for the off-policy agents (gfx950): the one-launch store of a
+// step's actions plus the ring head, and the sampler -- draw (slot, env) pairs with Philox4x32-10 or
+// take the caller's, then gather obs / next_obs / action / reward / done rows into a batch.  Contract:
+// include/finenv.h.  Pure data movement, HBM/L2-bound: 2 * (4D read + 4D write) + 8A + 21 bytes per
+// sample (indices_out: + 8).  No LDS, no barrier; every offset is 64-bit (the ring may pass 4 GiB).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "finenv.h"
+#include "finenv_host.h"
+
+namespace {
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+// actions -> their ring slot, and the head words after this step (set, never incremented: a replayed
+// capture publishes the head of the slots it writes)
+template <typename V>
+__global__ void __launch_bounds__(256) replay_put_kernel(const V *src, V *dst, int n, int32_t *head,
+                                                         int32_t pos_next, int32_t n_valid_next)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+    if (i == 0) {
+        head[0] = pos_next;
+        head[1] = n_valid_next;
+    }
+}
+
+struct GatherArgs {
+    finenv_replay_view v;
+    finenv_replay_batch o;
+    const int32_t *head;          // DRAW: {pos, n_valid}
+    const int64_t *draw;          // DRAW: the draw number
+    const int32_t *indices;       // !DRAW: [2][B]
+    int32_t *indices_out;         // DRAW: [2][B] or NULL
+    uint32_t seed_lo, seed_hi;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11; Random123): counter c[4], key k[2] -> first two output words
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t &x0, uint32_t &x1)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    x0 = c0;
+    x1 = c1;
+}
+
+// One sample per group of G lanes (G = 64: per wave, and (slot, env) is made scalar so the row bases
+// are).  A row is `nu` units of V (f4 where pitches and bases allow, else float) plus, for f4, a tail
+// of D % 4 floats moved as dwords: columns D .. pitch-1 of the outputs are never written.  The first
+// two units per lane of both rows, the action row's first unit, the tail and the reward / done words
+// are all loaded before the first store -- a load behind the wave's own stores waits for them
+// (DESIGN.md 4.1); rows longer than 2G units (none of the shipped env shapes at their G) loop on.
+template <int G, typename V, bool DRAW>
+__global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
+{
+    constexpr int PER_BLOCK = 256 / G;
+    constexpr int VW = (int)(sizeof(V) / sizeof(float));
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+    const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
+
+    int s, e;
+    if (DRAW) {
+        const int32_t pos = a.head[0];
+        int32_t nv = a.head[1];
+        nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
+        const uint64_t draw = (uint64_t)*a.draw;
+        uint32_t x0, x1;
+        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
+                      x0, x1);
+        const long long j = (long long)__umulhi(x0, (uint32_t)nv);
+        long long m = ((long long)pos - 1 - j) % S;
+        s = (int)(m < 0 ? m + S : m);
+        e = (int)__umulhi(x1, (uint32_t)E);
+        if (a.indices_out != nullptr && lane == 0) {
+            a.indices_out[b] = s;
+            a.indices_out[(long long)B + b] = e;
+        }
+    } else {
+        s = a.indices[b];
+        e = a.indices[(long long)B + b];
+        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
+        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+    }
+    if (G == 64) {
+        s = __builtin_amdgcn_readfirstlane(s);
+        e = __builtin_amdgcn_readfirstlane(e);
+    }
+    const int s1 = s + 1 == S ? 0 : s + 1;
+    const long long se = (long long)s * E + e, se1 = (long long)s1 * E + e;
+    const float *row0 = a.v.obs + se * a.v.obs_pitch;
+    const float *row1 = a.v.obs + se1 * a.v.obs_pitch;
+    const float *arow = a.v.actions + se * A;
+    float *out0 = a.o.observations + b * a.o.obs_pitch;
+    float *out1 = a.o.next_observations + b * a.o.obs_pitch;
+    float *aout = a.o.actions + b * A;
+    const V *src0 = (const V *)row0, *src1 = (const V *)row1;
+    V *dst0 = (V *)out0, *dst1 = (V *)out1;
+
+    const int nu = D / VW;                    // whole units per row
+    const int tail = D - nu * VW;             // f4: the last D % 4 floats
+    const int k0 = lane, k1 = lane + G;
+    const bool p0 = k0 < nu, p1 = k1 < nu, pa = lane < A, pt = VW > 1 && lane < tail;
+    V x0 = {}, x1 = {}, y0 = {}, y1 = {};
+    float av = 0.0f, t0 = 0.0f, t1 = 0.0f, rew = 0.0f;
+    uint8_t dn = 0;
+    if (p0) {
+        x0 = src0[k0];
+        y0 = src1[k0];
+    }
+    if (p1) {
+        x1 = src0[k1];
+        y1 = src1[k1];
+    }
+    if (pa) av = arow[lane];
+    if (pt) {
+        t0 = row0[nu * VW + lane];
+        t1 = row1[nu * VW + lane];
+    }
+    if (lane == 0) {
+        rew = a.v.rewards[se];
+        dn = a.v.dones[se];
+    }
+    if (p0) {
+        dst0[k0] = x0;
+        dst1[k0] = y0;
+    }
+    if (p1) {
+        dst0[k1] = x1;
+        dst1[k1] = y1;
+    }
+    if (pa) aout[lane] = av;
+    if (pt) {
+        out0[nu * VW + lane] = t0;
+        out1[nu * VW + lane] = t1;
+    }
+    if (lane == 0) {
+        a.o.rewards[b] = rew;
+        a.o.dones[b] = (float)dn;
+    }
+    for (int k = lane + 2 * G; k < nu; k += G) {
+        const V x = src0[k], y = src1[k];
+        dst0[k] = x;
+        dst1[k] = y;
+    }
+    for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
+}
+
+template <typename V, bool DRAW>
+void launch_gather_groups(int G, const GatherArgs &a, hipStream_t stream)
+{
+    const long long B = a.o.batch_size;
+#define FINENV_REPLAY_LAUNCH(GG)                                                                     \
+    hipLaunchKernelGGL((replay_gather_kernel<GG, V, DRAW>), dim3((unsigned)((B * GG + 255) / 256)), \
+                       dim3(256), 0, stream, a)
+    switch (G) {
+    case 4: FINENV_REPLAY_LAUNCH(4); break;
+    case 8: FINENV_REPLAY_LAUNCH(8); break;
+    case 16: FINENV_REPLAY_LAUNCH(16); break;
+    case 32: FINENV_REPLAY_LAUNCH(32); break;
+    default: FINENV_REPLAY_LAUNCH(64); break;
+    }
+#undef FINENV_REPLAY_LAUNCH
+}
+
+// Shape checks of the two structs (no HIP call before they pass), then the row path and the lane
+// group: 16-byte units when the pitches and the three bases allow, and the smallest power of two in
+// [4, 64] that covers a row with the two units a lane loads up front -- a 3-unit row takes 4 lanes, a
+// 51-dword crypto row half a wave, the 76 units of a DOW30 row a whole one.
+template <bool DRAW>
+int launch_gather(GatherArgs &a, void *stream)
+{
+    const finenv_replay_view &v = a.v;
+    const finenv_replay_batch &o = a.o;
+    if (!v.obs || !v.actions || !v.rewards || !v.dones || !o.observations || !o.next_observations ||
+        !o.actions || !o.rewards || !o.dones)
+        return FINENV_ERR_INVALID;
+    if (v.n_slots < 2 || v.n_envs < 1 || v.obs_dim < 1 || v.action_dim < 1 || v.obs_pitch < v.obs_dim ||
+        o.batch_size < 1 || o.obs_pitch < v.obs_dim)
+        return FINENV_ERR_INVALID;
+    const uintptr_t bits = (uintptr_t)v.obs | (uintptr_t)o.observations | (uintptr_t)o.next_observations;
+    const bool vec = (bits & 15) == 0 && (v.obs_pitch & 3) == 0 && (o.obs_pitch & 3) == 0 && v.obs_dim >= 4;
+    const int units = vec ? (v.obs_dim + 3) / 4 : v.obs_dim;
+    int G = 4;
+    while (G < 64 && 2 * G < units) G *= 2;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(o.observations));
+    if (vec)
+        launch_gather_groups<f4, DRAW>(G, a, (hipStream_t)stream);
+    else
+        launch_gather_groups<float, DRAW>(G, a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" int finenv_replay_put(const float *actions, float *actions_slot, int32_t n_floats,
+                                 int32_t *head, int32_t pos_next, int32_t n_valid_next, void *stream)
+{
+    if (!actions || !actions_slot || !head || n_floats < 1 || n_floats > (1 << 30) || pos_next < 0 ||
+        n_valid_next < 0)
+        return FINENV_ERR_INVALID;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(actions_slot));
+    if ((((uintptr_t)actions | (uintptr_t)actions_slot) & 15) == 0 && (n_floats & 3) == 0) {
+        const int n4 = n_floats / 4;
+        hipLaunchKernelGGL(replay_put_kernel<f4>, dim3((n4 + 255) / 256), dim3(256), 0,
+                           (hipStream_t)stream, (const f4 *)actions, (f4 *)actions_slot, n4, head,
+                           pos_next, n_valid_next);
+    } else {
+        hipLaunchKernelGGL(replay_put_kernel<float>, dim3((n_floats + 255) / 256), dim3(256), 0,
+                           (hipStream_t)stream, actions, actions_slot, n_floats, head, pos_next,
+                           n_valid_next);
+    }
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+}
+
+extern "C" int finenv_replay_sample(const finenv_replay_view *view, const int32_t *head,
+                                    const int64_t *draw, uint64_t seed,
+                                    const finenv_replay_batch *batch, int32_t *indices_out, void *stream)
+{
+    if (!view || !batch || !head || !draw) return FINENV_ERR_INVALID;
+    GatherArgs a = {*view, *batch, head, draw, nullptr, indices_out, (uint32_t)seed,
+                    (uint32_t)(seed >> 32)};
+    return launch_gather<true>(a, stream);
+}
+
+extern "C" int finenv_replay_gather(const finenv_replay_view *view, const int32_t *indices,
+                                    const finenv_replay_batch *batch, void *stream)
+{
+    if (!view || !batch || !indices) return FINENV_ERR_INVALID;
+    GatherArgs a = {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
+    return launch_gather<false>(a, stream);
+}

@@ -307,6 +307,9 @@ int finenv_struct_size(int which)
     case 19: return (int)sizeof(finenv_btc_config);
     case 20: return (int)sizeof(finenv_btc_panel);
     case 21: return (int)sizeof(finenv_btc_state);
+    // (22 stays invalid: bindings of the list that ended at 21 probe it as its end)
+    case 23: return (int)sizeof(finenv_replay_view);
+    case 24: return (int)sizeof(finenv_replay_batch);
     default: return FINENV_ERR_INVALID;
     }
 }

@@ -1,0 +1,182 @@
+"""Device-resident replay buffer for the off-policy agents (DDPG / TD3 / SAC): a ring the env
+kernels fill through ``step(out=...)`` without a copy, and a one-launch sampler that draws
+(slot, env) pairs and gathers the batch (finenv_replay_* in include/finenv.h)."""
+from __future__ import annotations
+
+import ctypes as C
+from collections import namedtuple
+
+from . import _native as nat
+from .vec_base import obs_pitch_for
+
+# stable-baselines3's ReplayBufferSamples: the same field order and shapes
+ReplayBufferSamples = namedtuple(
+    "ReplayBufferSamples", ("observations", "actions", "next_observations", "dones", "rewards"))
+
+
+class ReplayBuffer:
+    """Ring of ``n_slots`` time steps of ``num_envs`` envs on the env's device, in the layout of SB3's
+    ``ReplayBuffer(optimize_memory_usage=True, handle_timeout_termination=False)``: ``obs[s]`` is what
+    the policy saw before the step stored in slot ``s`` and its next observation is
+    ``obs[(s + 1) % n_slots]``, so every observation is stored once.
+
+    ``obs_pitch`` is the env's: ``None`` / "aligned" / an int for the pitched envs
+    (VecStockTradingEnv, VecStockTradingEnvNP: rows ``obs_pitch_for(obs_dim, obs_pitch)`` floats
+    apart), "packed" for every other env, whose kernels write packed rows.
+
+    Under the envs' in-kernel auto-reset the next observation of a ``done`` transition is the first
+    observation of the next episode (what SB3 stores in that mode); the TD target masks it with
+    ``1 - dones``.
+
+    After ``n`` steps ``len(buf) = min(n, n_slots - 1)`` slots hold a complete transition: the slots
+    ``(pos - 1 - j) % n_slots``, ``j < len(buf)``.  Slot ``pos`` of a full ring is not among them --
+    its observation has been overwritten by the newest next observation.
+
+    ``head`` (int32 [2] = pos, n_valid) and ``draw`` (int64 [1]) are the device words the sampler
+    reads; ``pos``, ``len(buf)`` and ``draws`` mirror them on the host.  ``step`` SETS the head to the
+    values of the host mirror, so a replayed capture of ``step`` publishes the head that belongs to
+    the slots it writes, and a captured ``sample`` sees ring and draw number as they are at each
+    replay (the host mirror does not follow replays)."""
+
+    def __init__(self, n_slots, num_envs, obs_dim, action_dim, obs_pitch=None, device="cuda", seed=0):
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise nat.FinenvError("finrl_amd has no CPU path: device must be a HIP GPU")
+        S, E, D, A = int(n_slots), int(num_envs), int(obs_dim), int(action_dim)
+        if S < 2 or E < 1 or D < 1 or A < 1:
+            raise ValueError("ReplayBuffer needs n_slots >= 2 and num_envs, obs_dim, action_dim >= 1")
+        P = obs_pitch_for(D, obs_pitch)
+        self.n_slots, self.num_envs, self.obs_dim, self.action_dim, self.obs_pitch = S, E, D, A, P
+        self.device, self.seed = dev, int(seed) & (2 ** 64 - 1)
+        self._obs_buf = torch.zeros(S, E, P, dtype=torch.float32, device=dev)
+        self.obs = self._obs_buf[:, :, :D]
+        self.actions = torch.zeros(S, E, A, dtype=torch.float32, device=dev)
+        self.rewards = torch.zeros(S, E, dtype=torch.float32, device=dev)
+        self.dones = torch.zeros(S, E, dtype=torch.uint8, device=dev)
+        self.head = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.pos = self._n_valid = self.draws = 0
+        self.last_indices = None
+        self._view = nat.ReplayViewPtrs(self._obs_buf.data_ptr(), self.actions.data_ptr(),
+                                        self.rewards.data_ptr(), self.dones.data_ptr(), S, E, D, P, A, 0)
+        self._batches = {}          # batch size -> (samples, ctypes struct, indices)
+        self._slots = {}            # pos -> (actions[pos], the env's out tuple of that slot)
+        self._lib = nat.lib()
+
+    def __len__(self):
+        return self._n_valid
+
+    def _stream(self):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ------------------------------------------------------------------ filling
+    def start(self, env, first_obs):
+        """Begin collecting: the reset observation goes to ``obs[pos]`` (slot 0 of a fresh buffer)."""
+        self.obs[self.pos].copy_(first_obs)
+        return self.obs[self.pos]
+
+    def step(self, env, actions):
+        """Store ``actions`` [E, A] in slot ``pos`` and publish the head after this step (one launch,
+        finenv_replay_put), then step the env from that slot straight into the ring:
+        obs -> ``obs[(pos + 1) % S]``, reward and done -> slot ``pos``.  Returns the env's tuple."""
+        import torch
+        if not env.auto_reset:
+            raise ValueError("ReplayBuffer.step needs env.auto_reset: a masked reset() writes into "
+                             "the env's own output, not into the ring")
+        S, E, A = self.n_slots, self.num_envs, self.action_dim
+        if not getattr(env, "_pitched", False) and self.obs_pitch != self.obs_dim:
+            raise ValueError(f"{type(env).__name__} writes packed observation rows: build the "
+                             "ReplayBuffer with obs_pitch=\"packed\"")
+        a = actions.to(self.device, torch.float32).contiguous()
+        if a.numel() != E * A:
+            raise ValueError(f"step: expected actions [{E}, {A}]")
+        pos, nxt = self.pos, (self.pos + 1) % S
+        n_valid = min(self._n_valid + 1, S - 1)
+        if pos not in self._slots:      # the slot's views, made once: slicing is host time per step
+            self._slots[pos] = (self.actions[pos], (self.obs[nxt], self.rewards[pos], self.dones[pos]))
+        slot, out = self._slots[pos]
+        rc = self._lib.finenv_replay_put(
+            C.c_void_p(a.data_ptr()), C.c_void_p(slot.data_ptr()), E * A,
+            C.c_void_p(self.head.data_ptr()), nxt, n_valid, self._stream())
+        if rc:
+            nat.check(rc, None, "finenv_replay_put")
+        ret = env.step(slot, out=out)
+        self.pos, self._n_valid = nxt, n_valid
+        return ret
+
+    # ------------------------------------------------------------------ sampling
+    def _batch(self, B, out):
+        """(samples, finenv_replay_batch) of the persistent outputs of batch size B, or of ``out``."""
+        import torch
+        D, A = self.obs_dim, self.action_dim
+        if out is None:
+            if B not in self._batches:
+                kw = dict(dtype=torch.float32, device=self.device)
+                o, n = (torch.zeros(B, self.obs_pitch, **kw) for _ in range(2))
+                smp = ReplayBufferSamples(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
+                                          torch.zeros(B, 1, **kw), torch.zeros(B, 1, **kw))
+                self._batches[B] = (smp, self._batch_struct(smp, B, self.obs_pitch),
+                                    torch.zeros(2, B, dtype=torch.int32, device=self.device))
+            return self._batches[B][:2]
+        smp = ReplayBufferSamples(*out)
+        for t, shape, what in ((smp.observations, (B, D), "observations"), (smp.actions, (B, A), "actions"),
+                               (smp.next_observations, (B, D), "next_observations"),
+                               (smp.dones, (B, 1), "dones"), (smp.rewards, (B, 1), "rewards")):
+            if t.dtype != torch.float32 or t.device != self.head.device or tuple(t.shape) != shape:
+                raise ValueError(f"out.{what} must be {shape} float32 on {self.head.device}")
+        o, n = smp.observations, smp.next_observations
+        if not (smp.actions.is_contiguous() and smp.dones.is_contiguous() and smp.rewards.is_contiguous()):
+            raise ValueError("out.actions / dones / rewards must be contiguous")
+        pitch = D if B == 1 else o.stride(0)
+        if o.stride(1) != 1 or n.stride(1) != 1 or pitch < D or (B > 1 and n.stride(0) != pitch):
+            raise ValueError("out.observations / next_observations need unit column stride and one "
+                             "common row stride >= obs_dim")
+        return smp, self._batch_struct(smp, B, pitch)
+
+    @staticmethod
+    def _batch_struct(smp, B, pitch):
+        return nat.ReplayBatchPtrs(smp.observations.data_ptr(), smp.next_observations.data_ptr(),
+                                   smp.actions.data_ptr(), smp.rewards.data_ptr(), smp.dones.data_ptr(),
+                                   B, pitch)
+
+    def sample(self, batch_size, out=None):
+        """Draw ``batch_size`` transitions uniformly from the valid slots x envs and gather them: one
+        launch (finenv_replay_sample), plus the in-stream bump of the draw word.  Returns a
+        ``ReplayBufferSamples`` of persistent tensors per batch size (overwritten by the next call
+        of that size) or of ``out``, the caller's five tensors in the same order;
+        ``buf.last_indices`` is the int32 [2, B] block of (slots, envs) the kernel drew.  The draw is
+        a pure function of (seed, draw number, ring head): Philox4x32-10, include/finenv.h."""
+        if self._n_valid == 0:
+            raise ValueError("sample: the buffer holds no complete transition yet")
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("sample: batch_size must be >= 1")
+        smp, bs = self._batch(B, out)
+        if out is None:
+            idx = self._batches[B][2]
+        else:
+            import torch
+            idx = torch.empty(2, B, dtype=torch.int32, device=self.device)
+        nat.check(self._lib.finenv_replay_sample(
+            C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
+            self.seed, C.byref(bs), C.c_void_p(idx.data_ptr()), self._stream()), None,
+            "finenv_replay_sample")
+        self.draw.add_(1)
+        self.draws += 1
+        self.last_indices = idx
+        return smp
+
+    def gather(self, indices, out=None):
+        """The batch of caller-chosen transitions: ``indices`` int [2, B] on the device (row 0 slots,
+        row 1 envs), clamped into the ring by the kernel.  One launch (finenv_replay_gather)."""
+        import torch
+        idx = indices.to(device=self.device, dtype=torch.int32).contiguous()
+        if idx.dim() != 2 or idx.shape[0] != 2 or idx.shape[1] < 1:
+            raise ValueError("gather: indices must be [2, B]")
+        smp, bs = self._batch(int(idx.shape[1]), out)
+        nat.check(self._lib.finenv_replay_gather(
+            C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), self._stream()), None,
+            "finenv_replay_gather")
+        return smp

@@ -177,7 +177,8 @@ typedef struct finenv_stock finenv_stock;   /* opaque host-side handle */
 int         finenv_abi_version(void);
 /* sizeof() of the ABI structs as the library was compiled (0 = finenv_stock_config,
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
- * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio):
+ * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio,
+ * 23 = finenv_replay_view, 24 = finenv_replay_batch; 22, like 18, stays invalid as the end of an earlier list):
  * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
  * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
  * bindings probe it as such. */
@@ -711,6 +712,91 @@ int finenv_gae_scan(const float *rewards, const float *values, const uint8_t *do
 int finenv_rollout_put(const float *actions, const float *values, const float *log_probs,
                        float *actions_out, float *values_out, float *log_probs_out,
                        int32_t n_envs, int32_t action_dim, void *stream);
+
+/* =====================================================================================
+ * Replay buffer for the off-policy agents (DDPG / TD3 / SAC; the reference configures them with
+ * buffer_size 50,000 .. 1,000,000 and batch_size 64 .. 128, finrl/config.py:41-50): a device-resident
+ * ring the env kernels fill through their own output pointers, and a one-launch sampler.
+ *
+ * Ring (S slots, E envs, time-major, caller-owned):
+ *   obs     [S][E][P] f32   P = row pitch in floats >= D; columns D .. P-1 are never read
+ *   actions [S][E][A] f32
+ *   rewards [S][E]    f32
+ *   dones   [S][E]    u8
+ * obs[s] is what the policy saw BEFORE the step stored in slot s; the next observation of slot s is
+ * obs[(s+1) % S].  Every observation is stored once: the layout of stable-baselines3's
+ * ReplayBuffer(optimize_memory_usage=True, handle_timeout_termination=False).
+ *
+ * Auto-reset.  The envs reset inside the step launch, so the next observation of a transition with
+ * done == 1 is the FIRST observation of the next episode (what SB3 stores in that mode too).  The TD
+ * target masks that row with 1 - done.  `done` is the reference's end of data (terminal =
+ * day >= len(df.index.unique()) - 1, env_stocktrading.py:221): a time limit, which the reference's
+ * agents nevertheless treat as termination -- so does this buffer.
+ *
+ * Head.  int32 head[2] = {pos, n_valid} in device memory: pos is the next slot to write, n_valid the
+ * number of slots holding a complete transition, min(steps stored, S - 1); they are the slots
+ * (pos - 1 - j) mod S for j in [0, n_valid).  Slot pos of a full ring is excluded: its observation
+ * has been overwritten by the newest next observation (SB3: (randint(1, S) + pos) % S).  S >= 2.
+ * finenv_replay_put SETS the head from by-value arguments (it never increments), so a replayed
+ * capture publishes the head that belongs to the slots the capture writes; the sampler READS it from
+ * device memory, so a captured sample sees the ring as it is at each replay.
+ *
+ * Draw.  Stateless and reproducible: Philox4x32-10 with key = (seed lo, seed hi) and counter =
+ * (i, 0, draw lo, draw hi) for sample i; with the output words x0, x1:
+ *   j = umulhi(x0, n_valid);  slot = (pos - 1 - j) mod S;  env = umulhi(x1, E).
+ * The multiply-high map of a uniform 32-bit word onto [0, n) has a bias of at most n / 2^32 per
+ * value (1.5e-5 at n = 65,536).  `draw` is read from a device int64 the caller bumps in-stream after
+ * each sample, so a captured sample-plus-update graph draws fresh pairs at every replay.  Head words
+ * are device data and are not trusted: n_valid < 1 is taken as 1, n_valid > S - 1 as S - 1, and the
+ * slot is reduced mod S whatever pos holds -- bad words give wrong samples, never a fault.
+ *
+ * Gather.  For sample b = (s, e):  observations[b] = obs[s][e][:D];
+ *   next_observations[b] = obs[(s+1) % S][e][:D];  actions[b] = actions[s][e];
+ *   rewards[b] = rewards[s][e];  dones[b] = (float)dones[s][e].
+ * Output columns D .. pitch-1 are not written.  All offsets are 64-bit: the 4 GiB limit of the env
+ * arrays does not apply to the ring.  Rows move in 16-byte pieces when P and the output pitch are
+ * multiples of 4 floats and the three bases are 16-byte aligned, in dwords otherwise.
+ * ===================================================================================== */
+typedef struct finenv_replay_view {      /* finenv_struct_size 23 */
+    const float   *obs;                  /* [S][E][P]                                           */
+    const float   *actions;              /* [S][E][A]                                           */
+    const float   *rewards;              /* [S][E]                                              */
+    const uint8_t *dones;                /* [S][E]                                              */
+    int32_t n_slots;                     /* S >= 2                                              */
+    int32_t n_envs;                      /* E >= 1                                              */
+    int32_t obs_dim;                     /* D >= 1                                              */
+    int32_t obs_pitch;                   /* P >= D, floats                                      */
+    int32_t action_dim;                  /* A >= 1                                              */
+    int32_t reserved0;                   /* 0                                                   */
+} finenv_replay_view;
+
+typedef struct finenv_replay_batch {     /* finenv_struct_size 24 */
+    float *observations;                 /* [B][pitch], columns 0 .. D-1 written                */
+    float *next_observations;            /* [B][pitch]                                          */
+    float *actions;                      /* [B][A] packed                                       */
+    float *rewards;                      /* [B]                                                 */
+    float *dones;                        /* [B] 0.0f / 1.0f                                     */
+    int32_t batch_size;                  /* B >= 1                                              */
+    int32_t obs_pitch;                   /* row pitch of the two observation outputs, >= D      */
+} finenv_replay_batch;
+
+/* One launch: copy this step's actions (n_floats = E * A contiguous f32) into their ring slot and
+ * store head[0] = pos_next, head[1] = n_valid_next (both >= 0).  `actions` may be the slot itself. */
+int finenv_replay_put(const float *actions, float *actions_slot, int32_t n_floats, int32_t *head,
+                      int32_t pos_next, int32_t n_valid_next, void *stream);
+
+/* One launch: draw `batch->batch_size` (slot, env) pairs as stated above from the ring state in
+ * `head` and the draw number in `*draw` (device int64), gather the five outputs, and, when
+ * indices_out != NULL, store the pairs there as int32 [2][B] (row 0 slots, row 1 envs). */
+int finenv_replay_sample(const finenv_replay_view *view, const int32_t *head, const int64_t *draw,
+                         uint64_t seed, const finenv_replay_batch *batch, int32_t *indices_out,
+                         void *stream);
+
+/* One launch: the same gather for caller-supplied pairs, indices int32 [2][B] on the device (row 0
+ * slots, row 1 envs; prioritised replay, n-step users).  Slots are clamped into [0, S) and envs into
+ * [0, E); whether a slot holds a complete transition is the caller's business. */
+int finenv_replay_gather(const finenv_replay_view *view, const int32_t *indices,
+                         const finenv_replay_batch *batch, void *stream);
 
 /* =====================================================================================
  * Array-state StockTradingEnv (finrl/meta/env_stock_trading/env_stocktrading_np.py:8-169),

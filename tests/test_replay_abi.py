@@ -1,0 +1,137 @@
+"""CPU-side checks of the replay buffer: the NumPy model of the draw (tests/replay_model.py) against
+the published Philox4x32-10 known answers and the ring's slot rule, and the argument validation of
+finenv_replay_put / _sample / _gather, which refuses bad shapes before any launch."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import replay_model as rm
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from finrl_amd import _native
+    _native.build()
+    return _native.lib()
+
+
+# Random123's kat_vectors, philox4x32 10 rounds: counter, key -> output
+KAT = (
+    ((0, 0, 0, 0), (0, 0), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+    ((0xffffffff,) * 4, (0xffffffff,) * 2, (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+    ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0),
+     (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1)),
+)
+
+
+@pytest.mark.parametrize("counter,key,want", KAT)
+def test_model_philox_known_answers(counter, key, want):
+    got = rm.philox4x32_10(counter, key)
+    assert tuple(int(x) for x in got) == want
+
+
+def test_model_philox_is_elementwise():
+    """The vectorised form over an array of counters equals the scalar form per element."""
+    i = np.array([0, 1, 0xffffffff, 12345], dtype=np.uint64)
+    got = rm.philox4x32_10((i, 0, 7, 9), (3, 4))
+    for n, c0 in enumerate(i):
+        one = rm.philox4x32_10((int(c0), 0, 7, 9), (3, 4))
+        assert [int(w[n]) for w in got] == [int(w) for w in one]
+
+
+@pytest.mark.parametrize("S", [2, 3, 5])
+def test_model_slot_rule(S):
+    """Before the ring fills the valid slots are exactly [0, n); on a full ring they are every slot
+    but pos -- for every pos -- and the draw stays inside them."""
+    for n in range(1, S):
+        pos, n_valid = rm.head_after(n, S)
+        assert (pos, n_valid) == (n, n)
+        assert sorted(rm.valid_slots(pos, n_valid, S)) == list(range(n))
+        drawn = rm.draw_pairs(5, n, 512, pos, n_valid, S, 3)[0]
+        assert set(drawn.tolist()) <= set(range(n))
+    for n in range(S, 3 * S):
+        pos, n_valid = rm.head_after(n, S)
+        assert n_valid == S - 1 and pos == n % S
+        slots = rm.valid_slots(pos, n_valid, S)
+        assert sorted(slots) == [s for s in range(S) if s != pos]
+        drawn = rm.draw_pairs(5, n, 512, pos, n_valid, S, 3)
+        assert pos not in set(drawn[0].tolist())
+        assert set(drawn[0].tolist()) == set(slots)          # 512 draws over at most 4 slots
+        assert drawn[1].min() >= 0 and drawn[1].max() <= 2
+
+
+def test_struct_sizes(lib):
+    from finrl_amd import _native as nat
+    assert lib.finenv_struct_size(23) == C.sizeof(nat.ReplayViewPtrs) == 56
+    assert lib.finenv_struct_size(24) == C.sizeof(nat.ReplayBatchPtrs) == 48
+    assert lib.finenv_struct_size(22) == -1 and lib.finenv_struct_size(25) == -1
+    assert lib.finenv_abi_version() == 3
+
+
+FAKE = 0x1000       # a non-null address that is never dereferenced: every call below is refused first
+
+
+def _view(nat, **kw):
+    f = dict(obs=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE, n_slots=4, n_envs=3, obs_dim=5,
+             obs_pitch=8, action_dim=2, reserved0=0)
+    f.update(kw)
+    return nat.ReplayViewPtrs(**f)
+
+
+def _batch(nat, **kw):
+    f = dict(observations=FAKE, next_observations=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE,
+             batch_size=7, obs_pitch=5)
+    f.update(kw)
+    return nat.ReplayBatchPtrs(**f)
+
+
+BAD_VIEWS = [dict(obs=None), dict(actions=None), dict(rewards=None), dict(dones=None),
+             dict(n_slots=1), dict(n_slots=0), dict(n_envs=0), dict(obs_dim=0), dict(action_dim=0),
+             dict(obs_pitch=4)]
+BAD_BATCHES = [dict(observations=None), dict(next_observations=None), dict(actions=None),
+               dict(rewards=None), dict(dones=None), dict(batch_size=0), dict(batch_size=-3),
+               dict(obs_pitch=4)]
+
+
+def test_sample_and_gather_reject_bad_arguments(lib):
+    from finrl_amd import _native as nat
+    INV = -1                                                     # FINENV_ERR_INVALID
+    good_v, good_b = _view(nat), _batch(nat)
+
+    def sample(v, b, head=FAKE, draw=FAKE):
+        return lib.finenv_replay_sample(v, head, draw, 1, b, None, None)
+
+    def gather(v, b, idx=FAKE):
+        return lib.finenv_replay_gather(v, idx, b, None)
+
+    for kw in BAD_VIEWS:
+        assert sample(C.byref(_view(nat, **kw)), C.byref(good_b)) == INV, kw
+        assert gather(C.byref(_view(nat, **kw)), C.byref(good_b)) == INV, kw
+    for kw in BAD_BATCHES:
+        assert sample(C.byref(good_v), C.byref(_batch(nat, **kw))) == INV, kw
+        assert gather(C.byref(good_v), C.byref(_batch(nat, **kw))) == INV, kw
+    assert sample(None, C.byref(good_b)) == INV and sample(C.byref(good_v), None) == INV
+    assert gather(None, C.byref(good_b)) == INV and gather(C.byref(good_v), None) == INV
+    assert sample(C.byref(good_v), C.byref(good_b), head=None) == INV
+    assert sample(C.byref(good_v), C.byref(good_b), draw=None) == INV
+    assert gather(C.byref(good_v), C.byref(good_b), idx=None) == INV
+
+
+def test_put_rejects_bad_arguments(lib):
+    INV = -1
+    put = lib.finenv_replay_put
+    assert put(None, FAKE, 8, FAKE, 1, 1, None) == INV
+    assert put(FAKE, None, 8, FAKE, 1, 1, None) == INV
+    assert put(FAKE, FAKE, 8, None, 1, 1, None) == INV
+    assert put(FAKE, FAKE, 0, FAKE, 1, 1, None) == INV
+    assert put(FAKE, FAKE, 8, FAKE, -1, 1, None) == INV
+    assert put(FAKE, FAKE, 8, FAKE, 1, -1, None) == INV
+
+
+def test_replay_buffer_needs_a_gpu_and_two_slots(lib):
+    pytest.importorskip("torch")
+    from finrl_amd import ReplayBuffer
+    from finrl_amd._native import FinenvError
+    with pytest.raises(FinenvError):
+        ReplayBuffer(4, 3, 5, 2, device="cpu")
