@@ -18,6 +18,7 @@ _LAZY = {      # name -> module; lazy because these need the native library
     "VecBitcoinEnv": "vec_btc", "VecStockTradingEnvNP": "vec_stocknp", "VecCashPenaltyEnv": "vec_cashpenalty",
     "VecStopLossEnv": "vec_cashpenalty", "CashPenaltyPanel": "vec_cashpenalty",
     "RolloutBuffer": "rollout", "ReplayBuffer": "replay", "GraphedSegment": "graph",
+    "ReplayBufferSamples": "replay", "NStepReplayBufferSamples": "replay",
 }
 
 

@@ -259,8 +259,16 @@ class ReplayBatchPtrs(C.Structure):
                 ("batch_size", C.c_int32), ("obs_pitch", C.c_int32)]
 
 
+class ReplayNStepPtrs(C.Structure):
+    """finenv_replay_nstep: the head words, the discount / steps outputs, n_steps and gamma."""
+    _fields_ = [("head", C.c_void_p), ("discounts", C.c_void_p), ("steps", C.c_void_p),
+                ("n_steps", C.c_int32), ("gamma", C.c_float)]
+
+
 # the replay buffer's pointer structs (22 stays invalid, like 18)
 _REPLAY_STRUCTS = {23: ReplayViewPtrs, 24: ReplayBatchPtrs}
+# the n-step sampler's (25 stays invalid: the end of the list above)
+_REPLAY_NSTEP_STRUCTS = {26: ReplayNStepPtrs}
 
 _lib = None
 
@@ -362,6 +370,13 @@ def lib():
                                            C.c_void_p]
         L.finenv_replay_gather.argtypes = [C.POINTER(ReplayViewPtrs), C.c_void_p,
                                            C.POINTER(ReplayBatchPtrs), C.c_void_p]
+    if hasattr(L, "finenv_replay_sample_nstep"):           # n-step sampler (same rule)
+        L.finenv_replay_sample_nstep.argtypes = [
+            C.POINTER(ReplayViewPtrs), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
+            C.POINTER(ReplayNStepPtrs), C.c_void_p, C.c_void_p]
+        L.finenv_replay_gather_nstep.argtypes = [
+            C.POINTER(ReplayViewPtrs), C.c_void_p, C.POINTER(ReplayBatchPtrs),
+            C.POINTER(ReplayNStepPtrs), C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
@@ -372,6 +387,8 @@ def lib():
     later = sorted(_LATER_STRUCTS.items()) if hasattr(L, "finenv_btc_create") else []
     if hasattr(L, "finenv_replay_put"):
         later += sorted(_REPLAY_STRUCTS.items())
+    if hasattr(L, "finenv_replay_sample_nstep"):
+        later += sorted(_REPLAY_NSTEP_STRUCTS.items())
     for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(

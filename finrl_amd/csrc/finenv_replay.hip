@@ -3,6 +3,8 @@
 // take the caller's, then gather obs / next_obs / action / reward / done rows into a batch.  Contract:
 // include/finenv.h.  Pure data movement, HBM/L2-bound: 2 * (4D read + 4D write) + 8A + 21 bytes per
 // sample (indices_out: + 8).  No LDS, no barrier; every offset is 64-bit (the ring may pass 4 GiB).
+// The n-step form (replay_nstep_kernel) adds the h reward / done words of a pair's window and the
+// discount: + 5h + 4 bytes per sample, and a second round trip for the late next-observation row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -160,6 +162,183 @@ __global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
     for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
 }
 
+struct NStepArgs {
+    GatherArgs g;                 // head is read in both forms: the horizon ends at the newest step
+    float *discounts;             // [B]
+    int32_t *steps;               // [B] or NULL
+    int32_t n_steps;
+    float gamma;
+};
+
+// The n-step form of the gather (contract: include/finenv.h, "n-step returns").  Same lane groups,
+// units and row bases as replay_gather_kernel; what is new is that the next-observation row is known
+// only after the return's length m.  Round trip 1: lane i of the group loads the reward and done
+// words of step i of the window (slot (s+i) mod S, i < h), beside the observation row of s and the
+// action row.  Then m by a ballot over the group's done words, the sum in the stated order (every
+// lane of the group forms it, from shuffled rewards), round trip 2 for the row of slot (s+m) mod S,
+// and only then the stores: a load behind the wave's own stores waits for them.
+// n > G (only the narrow groups of short rows) takes one more round trip per further chunk of G
+// steps.  All control flow but the loads' and stores' predicates is uniform over the launch, so the
+// ballot and the shuffles see every lane of a live group.  h <= n <= S - 1 (host-checked) keeps
+// every slot below 2S before its one conditional subtract.
+template <int G, typename V, bool DRAW>
+__global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
+{
+    const GatherArgs &a = na.g;
+    constexpr int PER_BLOCK = 256 / G;
+    constexpr int VW = (int)(sizeof(V) / sizeof(float));
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+    const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
+    const int n = na.n_steps;
+    const float gamma = na.gamma;
+
+    const int32_t pos = a.head[0];
+    int s, e, h;                                  // h - 1 = stored steps between s and the newest
+    if (DRAW) {
+        int32_t nv = a.head[1];
+        nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
+        const uint64_t draw = (uint64_t)*a.draw;
+        uint32_t x0, x1;
+        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
+                      x0, x1);
+        const long long j = (long long)__umulhi(x0, (uint32_t)nv);
+        long long q = ((long long)pos - 1 - j) % S;
+        s = (int)(q < 0 ? q + S : q);
+        e = (int)__umulhi(x1, (uint32_t)E);
+        h = (int)j;
+    } else {
+        s = a.indices[b];
+        e = a.indices[(long long)B + b];
+        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
+        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+        const long long q = ((long long)pos - 1 - s) % S;
+        h = (int)(q < 0 ? q + S : q);
+    }
+    h = h + 1 < n ? h + 1 : n;
+    if (G == 64) {
+        s = __builtin_amdgcn_readfirstlane(s);
+        e = __builtin_amdgcn_readfirstlane(e);
+        h = __builtin_amdgcn_readfirstlane(h);
+    }
+    const long long se = (long long)s * E + e;
+    const float *row0 = a.v.obs + se * a.v.obs_pitch;
+    const float *arow = a.v.actions + se * A;
+    float *out0 = a.o.observations + b * a.o.obs_pitch;
+    float *out1 = a.o.next_observations + b * a.o.obs_pitch;
+    float *aout = a.o.actions + b * A;
+    const V *src0 = (const V *)row0;
+    V *dst0 = (V *)out0, *dst1 = (V *)out1;
+
+    const int nu = D / VW;
+    const int tail = D - nu * VW;
+    const int k0 = lane, k1 = lane + G;
+    const bool p0 = k0 < nu, p1 = k1 < nu, pa = lane < A, pt = VW > 1 && lane < tail;
+    V x0 = {}, x1 = {}, y0 = {}, y1 = {};
+    float av = 0.0f, t0 = 0.0f, t1 = 0.0f, rew = 0.0f;
+    uint8_t dn = 0;
+    // round trip 1
+    if (p0) x0 = src0[k0];
+    if (p1) x1 = src0[k1];
+    if (pa) av = arow[lane];
+    if (pt) t0 = row0[nu * VW + lane];
+    if (lane < h) {
+        int sw = s + lane;
+        sw = sw >= S ? sw - S : sw;
+        const long long w = (long long)sw * E + e;
+        rew = a.v.rewards[w];
+        dn = a.v.dones[w];
+    }
+
+    const int gshift = ((int)threadIdx.x & 63) & ~(G - 1);
+    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
+    double acc = 0.0;
+    float g = 1.0f, dlast = 0.0f;
+    int m = 0;
+    bool open = true;                             // neither a done nor the horizon reached yet
+    for (int base = 0; base < n; base += G) {
+        if (base > 0) {                           // n > G: the next chunk of the window
+            rew = 0.0f;
+            dn = 0;
+            if (open && base + lane < h) {
+                int sw = s + base + lane;
+                sw = sw >= S ? sw - S : sw;
+                const long long w = (long long)sw * E + e;
+                rew = a.v.rewards[w];
+                dn = a.v.dones[w];
+            }
+        }
+        const int cnt = h - base < G ? h - base : G;       // steps of the window in this chunk
+        const unsigned long long hit = (__ballot(dn != 0) >> gshift) & gmask;
+        const int k = hit ? __builtin_ctzll(hit) : cnt - 1; // the chunk's last step of the return
+        const int lim = n - base < G ? n - base : G;
+        for (int i = 0; i < lim; ++i) {
+            const float ri = __shfl(rew, i, G);
+            const bool on = open && i <= k;
+            const double t = (double)g * (double)ri;
+            acc = on ? (base + i == 0 ? t : acc + t) : acc;
+            g = on ? g * gamma : g;
+        }
+        const float dk = (float)__shfl((int)dn, k & (G - 1), G);
+        if (open && cnt > 0) {
+            m = base + k + 1;
+            dlast = dk;
+            open = hit == 0 && m < h;
+        }
+    }
+    if (G == 64) m = __builtin_amdgcn_readfirstlane(m);
+
+    // round trip 2: the row of slot (s + m) mod S
+    int s1 = s + m;
+    s1 = s1 >= S ? s1 - S : s1;
+    const float *row1 = a.v.obs + ((long long)s1 * E + e) * a.v.obs_pitch;
+    const V *src1 = (const V *)row1;
+    if (p0) y0 = src1[k0];
+    if (p1) y1 = src1[k1];
+    if (pt) t1 = row1[nu * VW + lane];
+
+    if (p0) {
+        dst0[k0] = x0;
+        dst1[k0] = y0;
+    }
+    if (p1) {
+        dst0[k1] = x1;
+        dst1[k1] = y1;
+    }
+    if (pa) aout[lane] = av;
+    if (pt) {
+        out0[nu * VW + lane] = t0;
+        out1[nu * VW + lane] = t1;
+    }
+    if (lane == 0) {
+        a.o.rewards[b] = (float)acc;
+        a.o.dones[b] = dlast;
+        na.discounts[b] = g;
+        if (na.steps != nullptr) na.steps[b] = m;
+        if (DRAW && a.indices_out != nullptr) {   // with the other stores, not ahead of the loads
+            a.indices_out[b] = s;
+            a.indices_out[(long long)B + b] = e;
+        }
+    }
+    for (int k = lane + 2 * G; k < nu; k += G) {
+        const V x = src0[k], y = src1[k];
+        dst0[k] = x;
+        dst1[k] = y;
+    }
+    for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
+}
+
+#define FINENV_REPLAY_GROUPS(LAUNCH)                                                                  \
+    switch (G) {                                                                                      \
+    case 4: LAUNCH(4); break;                                                                         \
+    case 8: LAUNCH(8); break;                                                                         \
+    case 16: LAUNCH(16); break;                                                                       \
+    case 32: LAUNCH(32); break;                                                                       \
+    default: LAUNCH(64); break;                                                                       \
+    }
+
 template <typename V, bool DRAW>
 void launch_gather_groups(int G, const GatherArgs &a, hipStream_t stream)
 {
@@ -167,41 +346,74 @@ void launch_gather_groups(int G, const GatherArgs &a, hipStream_t stream)
 #define FINENV_REPLAY_LAUNCH(GG)                                                                     \
     hipLaunchKernelGGL((replay_gather_kernel<GG, V, DRAW>), dim3((unsigned)((B * GG + 255) / 256)), \
                        dim3(256), 0, stream, a)
-    switch (G) {
-    case 4: FINENV_REPLAY_LAUNCH(4); break;
-    case 8: FINENV_REPLAY_LAUNCH(8); break;
-    case 16: FINENV_REPLAY_LAUNCH(16); break;
-    case 32: FINENV_REPLAY_LAUNCH(32); break;
-    default: FINENV_REPLAY_LAUNCH(64); break;
-    }
+    FINENV_REPLAY_GROUPS(FINENV_REPLAY_LAUNCH)
 #undef FINENV_REPLAY_LAUNCH
 }
+
+template <typename V, bool DRAW>
+void launch_nstep_groups(int G, const NStepArgs &na, hipStream_t stream)
+{
+    const long long B = na.g.o.batch_size;
+#define FINENV_REPLAY_LAUNCH(GG)                                                                     \
+    hipLaunchKernelGGL((replay_nstep_kernel<GG, V, DRAW>), dim3((unsigned)((B * GG + 255) / 256)),  \
+                       dim3(256), 0, stream, na)
+    FINENV_REPLAY_GROUPS(FINENV_REPLAY_LAUNCH)
+#undef FINENV_REPLAY_LAUNCH
+}
+#undef FINENV_REPLAY_GROUPS
 
 // Shape checks of the two structs (no HIP call before they pass), then the row path and the lane
 // group: 16-byte units when the pitches and the three bases allow, and the smallest power of two in
 // [4, 64] that covers a row with the two units a lane loads up front -- a 3-unit row takes 4 lanes, a
-// 51-dword crypto row half a wave, the 76 units of a DOW30 row a whole one.
-template <bool DRAW>
-int launch_gather(GatherArgs &a, void *stream)
+// 51-dword crypto row half a wave, the 76 units of a DOW30 row a whole one.  Returns the group width
+// (and whether the units are 16 bytes), or 0 for a shape that is refused.
+int gather_group(const finenv_replay_view &v, const finenv_replay_batch &o, bool &vec)
 {
-    const finenv_replay_view &v = a.v;
-    const finenv_replay_batch &o = a.o;
     if (!v.obs || !v.actions || !v.rewards || !v.dones || !o.observations || !o.next_observations ||
         !o.actions || !o.rewards || !o.dones)
-        return FINENV_ERR_INVALID;
+        return 0;
     if (v.n_slots < 2 || v.n_envs < 1 || v.obs_dim < 1 || v.action_dim < 1 || v.obs_pitch < v.obs_dim ||
         o.batch_size < 1 || o.obs_pitch < v.obs_dim)
-        return FINENV_ERR_INVALID;
+        return 0;
     const uintptr_t bits = (uintptr_t)v.obs | (uintptr_t)o.observations | (uintptr_t)o.next_observations;
-    const bool vec = (bits & 15) == 0 && (v.obs_pitch & 3) == 0 && (o.obs_pitch & 3) == 0 && v.obs_dim >= 4;
+    vec = (bits & 15) == 0 && (v.obs_pitch & 3) == 0 && (o.obs_pitch & 3) == 0 && v.obs_dim >= 4;
     const int units = vec ? (v.obs_dim + 3) / 4 : v.obs_dim;
     int G = 4;
     while (G < 64 && 2 * G < units) G *= 2;
-    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(o.observations));
+    return G;
+}
+
+template <bool DRAW>
+int launch_gather(GatherArgs &a, void *stream)
+{
+    bool vec = false;
+    const int G = gather_group(a.v, a.o, vec);
+    if (G == 0) return FINENV_ERR_INVALID;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(a.o.observations));
     if (vec)
         launch_gather_groups<f4, DRAW>(G, a, (hipStream_t)stream);
     else
         launch_gather_groups<float, DRAW>(G, a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+}
+
+// The n-step launch: the gather's checks, then 1 <= n_steps <= S - 1 (a window never reaches round
+// to its own start), gamma finite in [0, 1], head and discounts present.
+template <bool DRAW>
+int launch_nstep(GatherArgs &a, const finenv_replay_nstep *ns, void *stream)
+{
+    bool vec = false;
+    const int G = gather_group(a.v, a.o, vec);
+    if (G == 0 || !ns->head || !ns->discounts || ns->n_steps < 1 || ns->n_steps > a.v.n_slots - 1 ||
+        !(ns->gamma >= 0.0f && ns->gamma <= 1.0f))
+        return FINENV_ERR_INVALID;
+    if (!DRAW) a.head = ns->head;
+    const NStepArgs na = {a, ns->discounts, ns->steps, ns->n_steps, ns->gamma};
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(a.o.observations));
+    if (vec)
+        launch_nstep_groups<f4, DRAW>(G, na, (hipStream_t)stream);
+    else
+        launch_nstep_groups<float, DRAW>(G, na, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
 }
 
@@ -243,4 +455,25 @@ extern "C" int finenv_replay_gather(const finenv_replay_view *view, const int32_
     if (!view || !batch || !indices) return FINENV_ERR_INVALID;
     GatherArgs a = {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
     return launch_gather<false>(a, stream);
+}
+
+extern "C" int finenv_replay_sample_nstep(const finenv_replay_view *view, const int32_t *head,
+                                          const int64_t *draw, uint64_t seed,
+                                          const finenv_replay_batch *batch,
+                                          const finenv_replay_nstep *nstep, int32_t *indices_out,
+                                          void *stream)
+{
+    if (!view || !batch || !head || !draw || !nstep) return FINENV_ERR_INVALID;
+    GatherArgs a = {*view, *batch, head, draw, nullptr, indices_out, (uint32_t)seed,
+                    (uint32_t)(seed >> 32)};
+    return launch_nstep<true>(a, nstep, stream);
+}
+
+extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const int32_t *indices,
+                                          const finenv_replay_batch *batch,
+                                          const finenv_replay_nstep *nstep, void *stream)
+{
+    if (!view || !batch || !indices || !nstep) return FINENV_ERR_INVALID;
+    GatherArgs a = {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
+    return launch_nstep<false>(a, nstep, stream);
 }

@@ -310,6 +310,8 @@ int finenv_struct_size(int which)
     // (22 stays invalid: bindings of the list that ended at 21 probe it as its end)
     case 23: return (int)sizeof(finenv_replay_view);
     case 24: return (int)sizeof(finenv_replay_batch);
+    // (25 stays invalid: bindings of the list that ended at 24 probe it as its end)
+    case 26: return (int)sizeof(finenv_replay_nstep);
     default: return FINENV_ERR_INVALID;
     }
 }

@@ -12,6 +12,9 @@ from .vec_base import obs_pitch_for
 # stable-baselines3's ReplayBufferSamples: the same field order and shapes
 ReplayBufferSamples = namedtuple(
     "ReplayBufferSamples", ("observations", "actions", "next_observations", "dones", "rewards"))
+# the n-step batch: the same five, then the bootstrap discount gamma^m [B, 1]
+NStepReplayBufferSamples = namedtuple(
+    "NStepReplayBufferSamples", ReplayBufferSamples._fields + ("discounts",))
 
 
 class ReplayBuffer:
@@ -36,7 +39,10 @@ class ReplayBuffer:
     reads; ``pos``, ``len(buf)`` and ``draws`` mirror them on the host.  ``step`` SETS the head to the
     values of the host mirror, so a replayed capture of ``step`` publishes the head that belongs to
     the slots it writes, and a captured ``sample`` sees ring and draw number as they are at each
-    replay (the host mirror does not follow replays)."""
+    replay (the host mirror does not follow replays).
+
+    ``sample_nstep`` / ``gather_nstep`` return n-step batches (discounted reward sum, the observation
+    m steps later, ``gamma^m``) from the same ring, head and draw, also in one launch."""
 
     def __init__(self, n_slots, num_envs, obs_dim, action_dim, obs_pitch=None, device="cuda", seed=0):
         import torch
@@ -58,9 +64,11 @@ class ReplayBuffer:
         self.draw = torch.zeros(1, dtype=torch.int64, device=dev)
         self.pos = self._n_valid = self.draws = 0
         self.last_indices = None
+        self.last_steps = None      # int32 [B]: the lengths m of the last n-step batch
         self._view = nat.ReplayViewPtrs(self._obs_buf.data_ptr(), self.actions.data_ptr(),
                                         self.rewards.data_ptr(), self.dones.data_ptr(), S, E, D, P, A, 0)
         self._batches = {}          # batch size -> (samples, ctypes struct, indices)
+        self._nstep_batches = {}    # batch size -> (samples, ctypes struct, indices, steps)
         self._slots = {}            # pos -> (actions[pos], the env's out tuple of that slot)
         self._lib = nat.lib()
 
@@ -121,19 +129,30 @@ class ReplayBuffer:
                                     torch.zeros(2, B, dtype=torch.int32, device=self.device))
             return self._batches[B][:2]
         smp = ReplayBufferSamples(*out)
-        for t, shape, what in ((smp.observations, (B, D), "observations"), (smp.actions, (B, A), "actions"),
-                               (smp.next_observations, (B, D), "next_observations"),
-                               (smp.dones, (B, 1), "dones"), (smp.rewards, (B, 1), "rewards")):
+        pitch = self._check_out(smp, B)
+        return smp, self._batch_struct(smp, B, pitch)
+
+    def _check_out(self, smp, B):
+        """Validate a caller's output tuple (either namedtuple) -> the common observation row pitch."""
+        import torch
+        D, A = self.obs_dim, self.action_dim
+        fields = [(smp.observations, (B, D), "observations"), (smp.actions, (B, A), "actions"),
+                  (smp.next_observations, (B, D), "next_observations"),
+                  (smp.dones, (B, 1), "dones"), (smp.rewards, (B, 1), "rewards")]
+        if hasattr(smp, "discounts"):
+            fields.append((smp.discounts, (B, 1), "discounts"))
+        for t, shape, what in fields:
             if t.dtype != torch.float32 or t.device != self.head.device or tuple(t.shape) != shape:
                 raise ValueError(f"out.{what} must be {shape} float32 on {self.head.device}")
         o, n = smp.observations, smp.next_observations
-        if not (smp.actions.is_contiguous() and smp.dones.is_contiguous() and smp.rewards.is_contiguous()):
-            raise ValueError("out.actions / dones / rewards must be contiguous")
+        if not all(t.is_contiguous() for t, _, what in fields[1:] if what != "next_observations"):
+            raise ValueError("out.actions / dones / rewards" +
+                             (" / discounts" if len(fields) == 6 else "") + " must be contiguous")
         pitch = D if B == 1 else o.stride(0)
         if o.stride(1) != 1 or n.stride(1) != 1 or pitch < D or (B > 1 and n.stride(0) != pitch):
             raise ValueError("out.observations / next_observations need unit column stride and one "
                              "common row stride >= obs_dim")
-        return smp, self._batch_struct(smp, B, pitch)
+        return pitch
 
     @staticmethod
     def _batch_struct(smp, B, pitch):
@@ -179,4 +198,86 @@ class ReplayBuffer:
         nat.check(self._lib.finenv_replay_gather(
             C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), self._stream()), None,
             "finenv_replay_gather")
+        return smp
+
+    # ------------------------------------------------------------------ n-step returns
+    def _nstep_batch(self, B, out):
+        """(samples, finenv_replay_batch, indices, steps) of the persistent n-step outputs of batch
+        size B, or of ``out`` (six tensors) with fresh index / steps blocks."""
+        import torch
+        D, A = self.obs_dim, self.action_dim
+        if out is None:
+            if B not in self._nstep_batches:
+                kw = dict(dtype=torch.float32, device=self.device)
+                o, n = (torch.zeros(B, self.obs_pitch, **kw) for _ in range(2))
+                smp = NStepReplayBufferSamples(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
+                                               *(torch.zeros(B, 1, **kw) for _ in range(3)))
+                self._nstep_batches[B] = (
+                    smp, self._batch_struct(smp, B, self.obs_pitch),
+                    torch.zeros(2, B, dtype=torch.int32, device=self.device),
+                    torch.zeros(B, dtype=torch.int32, device=self.device))
+            return self._nstep_batches[B]
+        if len(out) != 6:
+            raise ValueError("out must be the six tensors of NStepReplayBufferSamples")
+        smp = NStepReplayBufferSamples(*out)
+        pitch = self._check_out(smp, B)
+        return (smp, self._batch_struct(smp, B, pitch),
+                torch.empty(2, B, dtype=torch.int32, device=self.device),
+                torch.empty(B, dtype=torch.int32, device=self.device))
+
+    def _nstep_struct(self, smp, steps, n_steps, gamma):
+        n, g = int(n_steps), float(gamma)
+        if not 1 <= n <= self.n_slots - 1:
+            raise ValueError(f"n_steps must be in [1, n_slots - 1 = {self.n_slots - 1}]")
+        if not 0.0 <= g <= 1.0:                  # refuses NaN too
+            raise ValueError("gamma must be in [0, 1]")
+        return nat.ReplayNStepPtrs(self.head.data_ptr(), smp.discounts.data_ptr(), steps.data_ptr(),
+                                   n, g)
+
+    def sample_nstep(self, batch_size, n_steps, gamma, out=None):
+        """``sample`` with n-step returns, in one launch (finenv_replay_sample_nstep) plus the
+        in-stream bump of the draw word.  The pairs are the ones ``sample`` draws for the same seed,
+        draw number and head.  From each start (s, e) the kernel walks up to ``n_steps`` stored steps
+        forward, stopping after the first ``done`` or at the ring's newest step (a start close to the
+        head yields a shorter return; it is not excluded): with m the steps taken,
+        ``rewards = sum_{i<m} gamma^i r_i`` (float32 powers, float64 sum), ``dones`` is that of the
+        last step, ``next_observations`` the observation m steps later and ``discounts = gamma^m``,
+        so the TD target is ``rewards + (1 - dones) * discounts * Q'(next_observations)``.  Returns an
+        ``NStepReplayBufferSamples`` of persistent tensors per batch size (separate from those of
+        ``sample``) or of ``out``, the caller's six tensors; ``buf.last_indices`` is as for
+        ``sample`` and ``buf.last_steps`` (int32 [B]) holds m.  ``n_steps`` and ``gamma`` are
+        by-value launch arguments: a captured call keeps the values it was captured with, while
+        ring, head and draw number are read at each replay."""
+        if self._n_valid == 0:
+            raise ValueError("sample_nstep: the buffer holds no complete transition yet")
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("sample_nstep: batch_size must be >= 1")
+        smp, bs, idx, steps = self._nstep_batch(B, out)
+        ns = self._nstep_struct(smp, steps, n_steps, gamma)
+        nat.check(self._lib.finenv_replay_sample_nstep(
+            C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
+            self.seed, C.byref(bs), C.byref(ns), C.c_void_p(idx.data_ptr()), self._stream()), None,
+            "finenv_replay_sample_nstep")
+        self.draw.add_(1)
+        self.draws += 1
+        self.last_indices, self.last_steps = idx, steps
+        return smp
+
+    def gather_nstep(self, indices, n_steps, gamma, out=None):
+        """The n-step batch of caller-chosen starts: ``indices`` as for ``gather`` (clamped into the
+        ring by the kernel; whether a slot is a valid start is the caller's business), the rule of
+        ``sample_nstep`` with the horizon measured from the device head.  One launch
+        (finenv_replay_gather_nstep); ``buf.last_steps`` holds m.  ``n_steps`` and ``gamma`` are
+        by-value launch arguments, as in ``sample_nstep``."""
+        import torch
+        idx = indices.to(device=self.device, dtype=torch.int32).contiguous()
+        if idx.dim() != 2 or idx.shape[0] != 2 or idx.shape[1] < 1:
+            raise ValueError("gather_nstep: indices must be [2, B]")
+        smp, bs, _, steps = self._nstep_batch(int(idx.shape[1]), out)
+        ns = self._nstep_struct(smp, steps, n_steps, gamma)
+        nat.check(self._lib.finenv_replay_gather_nstep(
+            C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), C.byref(ns),
+            self._stream()), None, "finenv_replay_gather_nstep")
+        self.last_steps = steps
         return smp

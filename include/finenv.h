@@ -178,7 +178,7 @@ int         finenv_abi_version(void);
 /* sizeof() of the ABI structs as the library was compiled (0 = finenv_stock_config,
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
  * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio,
- * 23 = finenv_replay_view, 24 = finenv_replay_batch; 22, like 18, stays invalid as the end of an earlier list):
+ * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep; 22 and 25, like 18, stay invalid as the ends of earlier lists):
  * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
  * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
  * bindings probe it as such. */
@@ -793,10 +793,63 @@ int finenv_replay_sample(const finenv_replay_view *view, const int32_t *head, co
                          void *stream);
 
 /* One launch: the same gather for caller-supplied pairs, indices int32 [2][B] on the device (row 0
- * slots, row 1 envs; prioritised replay, n-step users).  Slots are clamped into [0, S) and envs into
+ * slots, row 1 envs; prioritised replay).  Slots are clamped into [0, S) and envs into
  * [0, E); whether a slot holds a complete transition is the caller's business. */
 int finenv_replay_gather(const finenv_replay_view *view, const int32_t *indices,
                          const finenv_replay_batch *batch, void *stream);
+
+/* n-step returns.  The same ring, head and draw; one launch that also walks each pair's reward /
+ * done words forward.  For a start (s, e), n = n_steps and g = gamma:
+ *
+ * Horizon.  h = min(n, ((pos - 1 - s) mod S) + 1), mod non-negative: a start j slots behind the
+ * newest stored step has j + 1 stored steps ahead of it (for the drawn pairs j is the draw's own j).
+ * Every slot that is valid for the one-step sampler stays a valid start: a start too close to the
+ * head yields a shorter return, it is not excluded.
+ *
+ * Length.  m is the smallest i in [1, h] with dones[(s+i-1) % S][e] != 0, or h if there is none.
+ *
+ * Return.  acc is a double; g_0 = 1.0f and g_{i+1} = g_i * g in one float32 multiply;
+ *   acc = sum_{i=0}^{m-1} (double)g_i * (double)rewards[(s+i) % S][e], summed in increasing i
+ * (the first term starts the sum);  rewards_out[b] = (float)acc.  The product of two floats is exact
+ * in double, so the result does not depend on whether the compiler contracts the multiply-add, and
+ * tests/replay_nstep_model.py states it bit for bit.  With n = 1 it is the stored reward, unchanged.
+ *
+ * Outputs.  dones_out[b] = (float)dones[(s+m-1) % S][e];  next_observations[b] =
+ * obs[(s+m) % S][e][:D];  observations[b] and actions[b] are those of (s, e), as in the one-step
+ * gather;  discounts[b] = g_m (float32): the caller's target is
+ *   rewards + (1 - dones) * discounts * Q'(next_observations);
+ * steps[b] = m (int32) when the pointer is not NULL.
+ *
+ * The draw is unchanged -- same Philox counter and key, same slot / env maps: for one (seed, draw
+ * number, head), finenv_replay_sample_nstep returns the pairs finenv_replay_sample returns.
+ *
+ * Head words are untrusted, as above: every slot index is reduced mod S and n_valid is clamped as in
+ * the one-step draw; bad words give wrong samples and never an address outside the ring.  In the
+ * gather form slots and envs are clamped as finenv_replay_gather clamps them, and whether a slot is
+ * a valid start is the caller's business.
+ *
+ * Arguments, checked on the host before any HIP call: 1 <= n_steps <= S - 1 (a window never comes
+ * round to its own start), gamma finite and in [0, 1], head and discounts not NULL; anything else
+ * returns FINENV_ERR_INVALID.  n_steps and gamma are by-value launch arguments: a captured call
+ * keeps the values it was captured with. */
+typedef struct finenv_replay_nstep {     /* finenv_struct_size 26 (25 stays invalid)            */
+    const int32_t *head;                 /* {pos, n_valid}: read by both entry points           */
+    float   *discounts;                  /* [B] g_m                                             */
+    int32_t *steps;                      /* [B] m, or NULL                                      */
+    int32_t n_steps;                     /* 1 .. S - 1                                          */
+    float   gamma;                       /* [0, 1]                                              */
+} finenv_replay_nstep;
+
+/* One launch each, on the caller's stream, nothing allocated, no synchronisation: the n-step forms
+ * of finenv_replay_sample and finenv_replay_gather.  The sample form reads its `head` argument for
+ * the draw and the horizon alike; the gather form reads nstep->head.  The struct is checked by one
+ * rule in both forms (head not NULL): a caller passes the same pointer twice. */
+int finenv_replay_sample_nstep(const finenv_replay_view *view, const int32_t *head,
+                               const int64_t *draw, uint64_t seed, const finenv_replay_batch *batch,
+                               const finenv_replay_nstep *nstep, int32_t *indices_out, void *stream);
+int finenv_replay_gather_nstep(const finenv_replay_view *view, const int32_t *indices,
+                               const finenv_replay_batch *batch, const finenv_replay_nstep *nstep,
+                               void *stream);
 
 /* =====================================================================================
  * Array-state StockTradingEnv (finrl/meta/env_stock_trading/env_stocktrading_np.py:8-169),
