@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "finenv.h"
 #include "finenv_host.h"
 
@@ -58,12 +60,63 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     x1 = c1;
 }
 
-// One sample per group of G lanes (G = 64: per wave, and (slot, env) is made scalar so the row bases
-// are).  A row is `nu` units of V (f4 where pitches and bases allow, else float) plus, for f4, a tail
-// of D % 4 floats moved as dwords: columns D .. pitch-1 of the outputs are never written.  The first
-// two units per lane of both rows, the action row's first unit, the tail and the reward / done words
-// are all loaded before the first store -- a load behind the wave's own stores waits for them
-// (DESIGN.md 4.1); rows longer than 2G units (none of the shipped env shapes at their G) loop on.
+// The clamped (slot, env) of sample b -> s, e; returns its age, the stored steps between it and the
+// newest.  DRAW: the Philox words give an age below n_valid (not trusted: clamped into [1, S - 1]) and
+// an env below E; the slot is (pos - 1 - age) mod S, never slot pos of a full ring.  !DRAW: the
+// caller's indices, clamped, and the age from (pos - 1 - s) mod S.  G = 64: (slot, env) is made scalar,
+// so the row bases are.  A kernel that ignores the age loses it and, !DRAW, the head load when compiled.
+template <int G, bool DRAW>
+__device__ __forceinline__ int sample_pair(const GatherArgs &a, long long b, int &s, int &e)
+{
+    const int S = a.v.n_slots, E = a.v.n_envs;
+    const int32_t pos = a.head[0];
+    long long age;
+    if (DRAW) {
+        int32_t nv = a.head[1];
+        nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
+        const uint64_t draw = (uint64_t)*a.draw;
+        uint32_t x0, x1;
+        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
+                      x0, x1);
+        age = (long long)__umulhi(x0, (uint32_t)nv);
+        const long long q = ((long long)pos - 1 - age) % S;
+        s = (int)(q < 0 ? q + S : q);
+        e = (int)__umulhi(x1, (uint32_t)E);
+    } else {
+        s = a.indices[b];
+        e = a.indices[(long long)a.o.batch_size + b];
+        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
+        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+        const long long q = ((long long)pos - 1 - s) % S;
+        age = q < 0 ? q + S : q;
+    }
+    if (G == 64) {
+        s = __builtin_amdgcn_readfirstlane(s);
+        e = __builtin_amdgcn_readfirstlane(e);
+    }
+    return (int)age;
+}
+
+// What the kernels' up-front loads leave: the units past 2G of both rows and the action floats past G,
+// behind the wave's stores (none of the shipped env shapes at their G has either).
+template <int G, typename V>
+__device__ __forceinline__ void copy_rest(const V *src0, const V *src1, V *dst0, V *dst1, int nu,
+                                          const float *arow, float *aout, int A, int lane)
+{
+    for (int k = lane + 2 * G; k < nu; k += G) {
+        const V x = src0[k], y = src1[k];
+        dst0[k] = x;
+        dst1[k] = y;
+    }
+    for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
+}
+
+// The one-step sampler: one sample per group of G lanes (G = 64: per wave).  A row is `nu` units of V
+// (f4 where pitches and bases allow, else float) plus, for f4, a tail of D % 4 floats moved as dwords:
+// columns D .. pitch-1 of the outputs are never written.  The first two units per lane of both rows,
+// the action row's first unit, the tail and the reward / done words are all loaded before the first
+// store -- a load behind the wave's own stores waits for them.  The two rows alternate
+// unit by unit: one row after the other measured 4 % slower (profiles/replay_share.md).
 template <int G, typename V, bool DRAW>
 __global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
 {
@@ -76,31 +129,10 @@ __global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
     const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
 
     int s, e;
-    if (DRAW) {
-        const int32_t pos = a.head[0];
-        int32_t nv = a.head[1];
-        nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
-        const uint64_t draw = (uint64_t)*a.draw;
-        uint32_t x0, x1;
-        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
-                      x0, x1);
-        const long long j = (long long)__umulhi(x0, (uint32_t)nv);
-        long long m = ((long long)pos - 1 - j) % S;
-        s = (int)(m < 0 ? m + S : m);
-        e = (int)__umulhi(x1, (uint32_t)E);
-        if (a.indices_out != nullptr && lane == 0) {
-            a.indices_out[b] = s;
-            a.indices_out[(long long)B + b] = e;
-        }
-    } else {
-        s = a.indices[b];
-        e = a.indices[(long long)B + b];
-        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
-        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
-    }
-    if (G == 64) {
-        s = __builtin_amdgcn_readfirstlane(s);
-        e = __builtin_amdgcn_readfirstlane(e);
+    sample_pair<G, DRAW>(a, b, s, e);             // the age is not needed: one step ends at the newest
+    if (DRAW && a.indices_out != nullptr && lane == 0) {
+        a.indices_out[b] = s;
+        a.indices_out[(long long)B + b] = e;
     }
     const int s1 = s + 1 == S ? 0 : s + 1;
     const long long se = (long long)s * E + e, se1 = (long long)s1 * E + e;
@@ -154,12 +186,7 @@ __global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
         a.o.rewards[b] = rew;
         a.o.dones[b] = (float)dn;
     }
-    for (int k = lane + 2 * G; k < nu; k += G) {
-        const V x = src0[k], y = src1[k];
-        dst0[k] = x;
-        dst1[k] = y;
-    }
-    for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
+    copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
 }
 
 struct NStepArgs {
@@ -170,17 +197,17 @@ struct NStepArgs {
     float gamma;
 };
 
-// The n-step form of the gather (contract: include/finenv.h, "n-step returns").  Same lane groups,
-// units and row bases as replay_gather_kernel; what is new is that the next-observation row is known
-// only after the return's length m.  Round trip 1: lane i of the group loads the reward and done
-// words of step i of the window (slot (s+i) mod S, i < h), beside the observation row of s and the
-// action row.  Then m by a ballot over the group's done words, the sum in the stated order (every
-// lane of the group forms it, from shuffled rewards), round trip 2 for the row of slot (s+m) mod S,
-// and only then the stores: a load behind the wave's own stores waits for them.
-// n > G (only the narrow groups of short rows) takes one more round trip per further chunk of G
-// steps.  All control flow but the loads' and stores' predicates is uniform over the launch, so the
-// ballot and the shuffles see every lane of a live group.  h <= n <= S - 1 (host-checked) keeps
-// every slot below 2S before its one conditional subtract.
+// The n-step sampler (contract: include/finenv.h, "n-step returns"): sample_pair, copy_rest and the
+// units per lane are those of replay_gather_kernel; what differs is that the next-observation row is
+// known only after the return's length m.  Round trip 1: lane i of the group loads the reward and done
+// words of step i of the window (slot (s+i) mod S, i < h = min(age + 1, n)), beside the observation
+// row of s and the action row.  Then m by a ballot over the group's done words, the sum in the stated
+// order (every lane of the group forms it, from shuffled rewards), round trip 2 for the row of slot
+// (s+m) mod S, and only then the stores, the drawn pair among them: a load behind the wave's own
+// stores waits for them.  n > G (only the narrow groups of short rows) takes one more
+// round trip per further chunk of G steps.  All control flow but the loads' and stores' predicates is
+// uniform over the launch, so the ballot and the shuffles see every lane of a live group.  h <= n <=
+// S - 1 (host-checked) keeps every slot below 2S before its one conditional subtract.
 template <int G, typename V, bool DRAW>
 __global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
 {
@@ -195,34 +222,10 @@ __global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
     const int n = na.n_steps;
     const float gamma = na.gamma;
 
-    const int32_t pos = a.head[0];
-    int s, e, h;                                  // h - 1 = stored steps between s and the newest
-    if (DRAW) {
-        int32_t nv = a.head[1];
-        nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
-        const uint64_t draw = (uint64_t)*a.draw;
-        uint32_t x0, x1;
-        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
-                      x0, x1);
-        const long long j = (long long)__umulhi(x0, (uint32_t)nv);
-        long long q = ((long long)pos - 1 - j) % S;
-        s = (int)(q < 0 ? q + S : q);
-        e = (int)__umulhi(x1, (uint32_t)E);
-        h = (int)j;
-    } else {
-        s = a.indices[b];
-        e = a.indices[(long long)B + b];
-        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
-        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
-        const long long q = ((long long)pos - 1 - s) % S;
-        h = (int)(q < 0 ? q + S : q);
-    }
-    h = h + 1 < n ? h + 1 : n;
-    if (G == 64) {
-        s = __builtin_amdgcn_readfirstlane(s);
-        e = __builtin_amdgcn_readfirstlane(e);
-        h = __builtin_amdgcn_readfirstlane(h);
-    }
+    int s, e;
+    const int age = sample_pair<G, DRAW>(a, b, s, e);
+    int h = age + 1 < n ? age + 1 : n;            // the horizon ends at the newest step
+    if (G == 64) h = __builtin_amdgcn_readfirstlane(h);
     const long long se = (long long)s * E + e;
     const float *row0 = a.v.obs + se * a.v.obs_pitch;
     const float *arow = a.v.actions + se * A;
@@ -322,45 +325,40 @@ __global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
             a.indices_out[(long long)B + b] = e;
         }
     }
-    for (int k = lane + 2 * G; k < nu; k += G) {
-        const V x = src0[k], y = src1[k];
-        dst0[k] = x;
-        dst1[k] = y;
-    }
-    for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
+    copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
 }
 
-#define FINENV_REPLAY_GROUPS(LAUNCH)                                                                  \
-    switch (G) {                                                                                      \
-    case 4: LAUNCH(4); break;                                                                         \
-    case 8: LAUNCH(8); break;                                                                         \
-    case 16: LAUNCH(16); break;                                                                       \
-    case 32: LAUNCH(32); break;                                                                       \
-    default: LAUNCH(64); break;                                                                       \
-    }
+// The kernels are function templates: a functor each names the instantiation for the launcher.
+struct GatherKernel {
+    template <int G, typename V, bool DRAW>
+    static constexpr auto get() { return &replay_gather_kernel<G, V, DRAW>; }
+};
+struct NStepKernel {
+    template <int G, typename V, bool DRAW>
+    static constexpr auto get() { return &replay_nstep_kernel<G, V, DRAW>; }
+};
 
-template <typename V, bool DRAW>
-void launch_gather_groups(int G, const GatherArgs &a, hipStream_t stream)
+// One launch of K's kernel for lane groups of G and 16-byte (vec) or dword units: 256 / G samples per
+// block, on the device of the batch.
+template <typename K, bool DRAW, typename Args>
+int launch_sampler(int G, bool vec, const Args &args, const finenv_replay_batch &o, void *stream)
 {
-    const long long B = a.o.batch_size;
-#define FINENV_REPLAY_LAUNCH(GG)                                                                     \
-    hipLaunchKernelGGL((replay_gather_kernel<GG, V, DRAW>), dim3((unsigned)((B * GG + 255) / 256)), \
-                       dim3(256), 0, stream, a)
-    FINENV_REPLAY_GROUPS(FINENV_REPLAY_LAUNCH)
-#undef FINENV_REPLAY_LAUNCH
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(o.observations));
+    const auto launch = [&](auto g) {
+        constexpr int GG = decltype(g)::value;
+        const dim3 grid((unsigned)(((long long)o.batch_size * GG + 255) / 256));
+        const auto kernel = vec ? K::template get<GG, f4, DRAW>() : K::template get<GG, float, DRAW>();
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args);
+    };
+    switch (G) {
+    case 4: launch(std::integral_constant<int, 4>()); break;
+    case 8: launch(std::integral_constant<int, 8>()); break;
+    case 16: launch(std::integral_constant<int, 16>()); break;
+    case 32: launch(std::integral_constant<int, 32>()); break;
+    default: launch(std::integral_constant<int, 64>()); break;
+    }
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
 }
-
-template <typename V, bool DRAW>
-void launch_nstep_groups(int G, const NStepArgs &na, hipStream_t stream)
-{
-    const long long B = na.g.o.batch_size;
-#define FINENV_REPLAY_LAUNCH(GG)                                                                     \
-    hipLaunchKernelGGL((replay_nstep_kernel<GG, V, DRAW>), dim3((unsigned)((B * GG + 255) / 256)),  \
-                       dim3(256), 0, stream, na)
-    FINENV_REPLAY_GROUPS(FINENV_REPLAY_LAUNCH)
-#undef FINENV_REPLAY_LAUNCH
-}
-#undef FINENV_REPLAY_GROUPS
 
 // Shape checks of the two structs (no HIP call before they pass), then the row path and the lane
 // group: 16-byte units when the pitches and the three bases allow, and the smallest power of two in
@@ -384,23 +382,18 @@ int gather_group(const finenv_replay_view &v, const finenv_replay_batch &o, bool
 }
 
 template <bool DRAW>
-int launch_gather(GatherArgs &a, void *stream)
+int launch_gather(const GatherArgs &a, void *stream)
 {
     bool vec = false;
     const int G = gather_group(a.v, a.o, vec);
     if (G == 0) return FINENV_ERR_INVALID;
-    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(a.o.observations));
-    if (vec)
-        launch_gather_groups<f4, DRAW>(G, a, (hipStream_t)stream);
-    else
-        launch_gather_groups<float, DRAW>(G, a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+    return launch_sampler<GatherKernel, DRAW>(G, vec, a, a.o, stream);
 }
 
 // The n-step launch: the gather's checks, then 1 <= n_steps <= S - 1 (a window never reaches round
 // to its own start), gamma finite in [0, 1], head and discounts present.
 template <bool DRAW>
-int launch_nstep(GatherArgs &a, const finenv_replay_nstep *ns, void *stream)
+int launch_nstep(GatherArgs a, const finenv_replay_nstep *ns, void *stream)
 {
     bool vec = false;
     const int G = gather_group(a.v, a.o, vec);
@@ -409,12 +402,20 @@ int launch_nstep(GatherArgs &a, const finenv_replay_nstep *ns, void *stream)
         return FINENV_ERR_INVALID;
     if (!DRAW) a.head = ns->head;
     const NStepArgs na = {a, ns->discounts, ns->steps, ns->n_steps, ns->gamma};
-    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(a.o.observations));
-    if (vec)
-        launch_nstep_groups<f4, DRAW>(G, na, (hipStream_t)stream);
-    else
-        launch_nstep_groups<float, DRAW>(G, na, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+    return launch_sampler<NStepKernel, DRAW>(G, vec, na, a.o, stream);
+}
+
+// The kernel arguments of a drawn call and of a call with the caller's indices.
+GatherArgs drawn_args(const finenv_replay_view *view, const finenv_replay_batch *batch,
+                      const int32_t *head, const int64_t *draw, uint64_t seed, int32_t *indices_out)
+{
+    return {*view, *batch, head, draw, nullptr, indices_out, (uint32_t)seed, (uint32_t)(seed >> 32)};
+}
+
+GatherArgs index_args(const finenv_replay_view *view, const finenv_replay_batch *batch,
+                      const int32_t *indices)
+{
+    return {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
 }
 
 }  // namespace
@@ -444,17 +445,14 @@ extern "C" int finenv_replay_sample(const finenv_replay_view *view, const int32_
                                     const finenv_replay_batch *batch, int32_t *indices_out, void *stream)
 {
     if (!view || !batch || !head || !draw) return FINENV_ERR_INVALID;
-    GatherArgs a = {*view, *batch, head, draw, nullptr, indices_out, (uint32_t)seed,
-                    (uint32_t)(seed >> 32)};
-    return launch_gather<true>(a, stream);
+    return launch_gather<true>(drawn_args(view, batch, head, draw, seed, indices_out), stream);
 }
 
 extern "C" int finenv_replay_gather(const finenv_replay_view *view, const int32_t *indices,
                                     const finenv_replay_batch *batch, void *stream)
 {
     if (!view || !batch || !indices) return FINENV_ERR_INVALID;
-    GatherArgs a = {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
-    return launch_gather<false>(a, stream);
+    return launch_gather<false>(index_args(view, batch, indices), stream);
 }
 
 extern "C" int finenv_replay_sample_nstep(const finenv_replay_view *view, const int32_t *head,
@@ -464,9 +462,7 @@ extern "C" int finenv_replay_sample_nstep(const finenv_replay_view *view, const 
                                           void *stream)
 {
     if (!view || !batch || !head || !draw || !nstep) return FINENV_ERR_INVALID;
-    GatherArgs a = {*view, *batch, head, draw, nullptr, indices_out, (uint32_t)seed,
-                    (uint32_t)(seed >> 32)};
-    return launch_nstep<true>(a, nstep, stream);
+    return launch_nstep<true>(drawn_args(view, batch, head, draw, seed, indices_out), nstep, stream);
 }
 
 extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const int32_t *indices,
@@ -474,6 +470,5 @@ extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const 
                                           const finenv_replay_nstep *nstep, void *stream)
 {
     if (!view || !batch || !indices || !nstep) return FINENV_ERR_INVALID;
-    GatherArgs a = {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
-    return launch_nstep<false>(a, nstep, stream);
+    return launch_nstep<false>(index_args(view, batch, indices), nstep, stream);
 }

@@ -67,8 +67,7 @@ class ReplayBuffer:
         self.last_steps = None      # int32 [B]: the lengths m of the last n-step batch
         self._view = nat.ReplayViewPtrs(self._obs_buf.data_ptr(), self.actions.data_ptr(),
                                         self.rewards.data_ptr(), self.dones.data_ptr(), S, E, D, P, A, 0)
-        self._batches = {}          # batch size -> (samples, ctypes struct, indices)
-        self._nstep_batches = {}    # batch size -> (samples, ctypes struct, indices, steps)
+        self._batches = {}          # (n-step?, batch size) -> (samples, ctypes struct, indices, steps)
         self._slots = {}            # pos -> (actions[pos], the env's out tuple of that slot)
         self._lib = nat.lib()
 
@@ -115,22 +114,29 @@ class ReplayBuffer:
         return ret
 
     # ------------------------------------------------------------------ sampling
-    def _batch(self, B, out):
-        """(samples, finenv_replay_batch) of the persistent outputs of batch size B, or of ``out``."""
+    def _batch(self, B, out, nstep=False):
+        """(samples, finenv_replay_batch, index block, steps block or None) of batch size B in the
+        one-step or the n-step form: the persistent outputs of that form, or ``out`` (five tensors, six
+        for the n-step form) with a fresh steps block and no index block (a drawn call makes its own)."""
         import torch
         D, A = self.obs_dim, self.action_dim
+        kind = NStepReplayBufferSamples if nstep else ReplayBufferSamples
+        i32 = dict(dtype=torch.int32, device=self.device)
         if out is None:
-            if B not in self._batches:
+            if (nstep, B) not in self._batches:
                 kw = dict(dtype=torch.float32, device=self.device)
                 o, n = (torch.zeros(B, self.obs_pitch, **kw) for _ in range(2))
-                smp = ReplayBufferSamples(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
-                                          torch.zeros(B, 1, **kw), torch.zeros(B, 1, **kw))
-                self._batches[B] = (smp, self._batch_struct(smp, B, self.obs_pitch),
-                                    torch.zeros(2, B, dtype=torch.int32, device=self.device))
-            return self._batches[B][:2]
-        smp = ReplayBufferSamples(*out)
+                smp = kind(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
+                           *(torch.zeros(B, 1, **kw) for _ in range(3 if nstep else 2)))
+                self._batches[nstep, B] = (smp, self._batch_struct(smp, B, self.obs_pitch),
+                                           torch.zeros(2, B, **i32),
+                                           torch.zeros(B, **i32) if nstep else None)
+            return self._batches[nstep, B]
+        if nstep and len(out) != 6:
+            raise ValueError("out must be the six tensors of NStepReplayBufferSamples")
+        smp = kind(*out)
         pitch = self._check_out(smp, B)
-        return smp, self._batch_struct(smp, B, pitch)
+        return smp, self._batch_struct(smp, B, pitch), None, torch.empty(B, **i32) if nstep else None
 
     def _check_out(self, smp, B):
         """Validate a caller's output tuple (either namedtuple) -> the common observation row pitch."""
@@ -167,64 +173,51 @@ class ReplayBuffer:
         of that size) or of ``out``, the caller's five tensors in the same order;
         ``buf.last_indices`` is the int32 [2, B] block of (slots, envs) the kernel drew.  The draw is
         a pure function of (seed, draw number, ring head): Philox4x32-10, include/finenv.h."""
+        return self._drawn("sample", batch_size, out)
+
+    def _drawn(self, name, batch_size, out, nstep=None):
+        """The drawn call ``name`` (``nstep``: the (n_steps, gamma) of the n-step form): its checks, the
+        launch finenv_replay_<name>, the bump of the draw word, ``last_indices`` / ``last_steps``."""
         if self._n_valid == 0:
-            raise ValueError("sample: the buffer holds no complete transition yet")
+            raise ValueError(f"{name}: the buffer holds no complete transition yet")
         B = int(batch_size)
         if B < 1:
-            raise ValueError("sample: batch_size must be >= 1")
-        smp, bs = self._batch(B, out)
-        if out is None:
-            idx = self._batches[B][2]
-        else:
+            raise ValueError(f"{name}: batch_size must be >= 1")
+        smp, bs, idx, steps = self._batch(B, out, nstep is not None)
+        if idx is None:
             import torch
             idx = torch.empty(2, B, dtype=torch.int32, device=self.device)
-        nat.check(self._lib.finenv_replay_sample(
+        ns = () if nstep is None else (C.byref(self._nstep_struct(smp, steps, *nstep)),)
+        fn = "finenv_replay_" + name
+        nat.check(getattr(self._lib, fn)(
             C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
-            self.seed, C.byref(bs), C.c_void_p(idx.data_ptr()), self._stream()), None,
-            "finenv_replay_sample")
+            self.seed, C.byref(bs), *ns, C.c_void_p(idx.data_ptr()), self._stream()), None, fn)
         self.draw.add_(1)
         self.draws += 1
         self.last_indices = idx
+        if nstep is not None:
+            self.last_steps = steps
         return smp
+
+    def _index_block(self, name, indices):
+        """The caller's ``indices`` of ``name`` as the contiguous int32 [2, B] block the kernel reads."""
+        import torch
+        idx = indices.to(device=self.device, dtype=torch.int32).contiguous()
+        if idx.dim() != 2 or idx.shape[0] != 2 or idx.shape[1] < 1:
+            raise ValueError(f"{name}: indices must be [2, B]")
+        return idx
 
     def gather(self, indices, out=None):
         """The batch of caller-chosen transitions: ``indices`` int [2, B] on the device (row 0 slots,
         row 1 envs), clamped into the ring by the kernel.  One launch (finenv_replay_gather)."""
-        import torch
-        idx = indices.to(device=self.device, dtype=torch.int32).contiguous()
-        if idx.dim() != 2 or idx.shape[0] != 2 or idx.shape[1] < 1:
-            raise ValueError("gather: indices must be [2, B]")
-        smp, bs = self._batch(int(idx.shape[1]), out)
+        idx = self._index_block("gather", indices)
+        smp, bs = self._batch(int(idx.shape[1]), out)[:2]
         nat.check(self._lib.finenv_replay_gather(
             C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), self._stream()), None,
             "finenv_replay_gather")
         return smp
 
     # ------------------------------------------------------------------ n-step returns
-    def _nstep_batch(self, B, out):
-        """(samples, finenv_replay_batch, indices, steps) of the persistent n-step outputs of batch
-        size B, or of ``out`` (six tensors) with fresh index / steps blocks."""
-        import torch
-        D, A = self.obs_dim, self.action_dim
-        if out is None:
-            if B not in self._nstep_batches:
-                kw = dict(dtype=torch.float32, device=self.device)
-                o, n = (torch.zeros(B, self.obs_pitch, **kw) for _ in range(2))
-                smp = NStepReplayBufferSamples(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
-                                               *(torch.zeros(B, 1, **kw) for _ in range(3)))
-                self._nstep_batches[B] = (
-                    smp, self._batch_struct(smp, B, self.obs_pitch),
-                    torch.zeros(2, B, dtype=torch.int32, device=self.device),
-                    torch.zeros(B, dtype=torch.int32, device=self.device))
-            return self._nstep_batches[B]
-        if len(out) != 6:
-            raise ValueError("out must be the six tensors of NStepReplayBufferSamples")
-        smp = NStepReplayBufferSamples(*out)
-        pitch = self._check_out(smp, B)
-        return (smp, self._batch_struct(smp, B, pitch),
-                torch.empty(2, B, dtype=torch.int32, device=self.device),
-                torch.empty(B, dtype=torch.int32, device=self.device))
-
     def _nstep_struct(self, smp, steps, n_steps, gamma):
         n, g = int(n_steps), float(gamma)
         if not 1 <= n <= self.n_slots - 1:
@@ -248,21 +241,7 @@ class ReplayBuffer:
         ``sample`` and ``buf.last_steps`` (int32 [B]) holds m.  ``n_steps`` and ``gamma`` are
         by-value launch arguments: a captured call keeps the values it was captured with, while
         ring, head and draw number are read at each replay."""
-        if self._n_valid == 0:
-            raise ValueError("sample_nstep: the buffer holds no complete transition yet")
-        B = int(batch_size)
-        if B < 1:
-            raise ValueError("sample_nstep: batch_size must be >= 1")
-        smp, bs, idx, steps = self._nstep_batch(B, out)
-        ns = self._nstep_struct(smp, steps, n_steps, gamma)
-        nat.check(self._lib.finenv_replay_sample_nstep(
-            C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
-            self.seed, C.byref(bs), C.byref(ns), C.c_void_p(idx.data_ptr()), self._stream()), None,
-            "finenv_replay_sample_nstep")
-        self.draw.add_(1)
-        self.draws += 1
-        self.last_indices, self.last_steps = idx, steps
-        return smp
+        return self._drawn("sample_nstep", batch_size, out, (n_steps, gamma))
 
     def gather_nstep(self, indices, n_steps, gamma, out=None):
         """The n-step batch of caller-chosen starts: ``indices`` as for ``gather`` (clamped into the
@@ -270,11 +249,8 @@ class ReplayBuffer:
         ``sample_nstep`` with the horizon measured from the device head.  One launch
         (finenv_replay_gather_nstep); ``buf.last_steps`` holds m.  ``n_steps`` and ``gamma`` are
         by-value launch arguments, as in ``sample_nstep``."""
-        import torch
-        idx = indices.to(device=self.device, dtype=torch.int32).contiguous()
-        if idx.dim() != 2 or idx.shape[0] != 2 or idx.shape[1] < 1:
-            raise ValueError("gather_nstep: indices must be [2, B]")
-        smp, bs, _, steps = self._nstep_batch(int(idx.shape[1]), out)
+        idx = self._index_block("gather_nstep", indices)
+        smp, bs, _, steps = self._batch(int(idx.shape[1]), out, True)
         ns = self._nstep_struct(smp, steps, n_steps, gamma)
         nat.check(self._lib.finenv_replay_gather_nstep(
             C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), C.byref(ns),

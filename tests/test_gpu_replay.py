@@ -7,61 +7,15 @@ import numpy as np
 import pytest
 
 import replay_model as rm
+from replay_cases import POISON, coded_ring, host_ring, need_gpu, outs, set_head
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-POISON = -7777.0
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-
-
-def _coded_ring(S, E, D, P, A, seed=0):
-    """A ReplayBuffer whose ring holds a code of (slot, env, column) in every cell (exact in f32),
-    NaN in the pad columns of obs, plus host copies (obs without the pad)."""
-    from finrl_amd import ReplayBuffer
-    buf = ReplayBuffer(S, E, D, A, obs_pitch=P, seed=seed)
-    assert buf.obs_pitch == P and tuple(buf.obs.shape) == (S, E, D) and buf.obs.stride(1) == P
-    se = np.arange(S * E, dtype=np.float64).reshape(S, E)
-    obs = (se[:, :, None] * 512 + np.arange(D)).astype(np.float32)
-    act = (-(se[:, :, None] * 64 + np.arange(A) + 1)).astype(np.float32)
-    rew = (se + 0.5).astype(np.float32)
-    done = ((np.arange(S)[:, None] + np.arange(E)[None, :]) % 2).astype(np.uint8)
-    buf._obs_buf.fill_(float("nan"))
-    buf.obs.copy_(torch.from_numpy(obs))
-    buf.actions.copy_(torch.from_numpy(act))
-    buf.rewards.copy_(torch.from_numpy(rew))
-    buf.dones.copy_(torch.from_numpy(done))
-    return buf, (obs, act, rew, done)
-
-
-def _set_head(buf, pos, n_valid):
-    buf.pos, buf._n_valid = pos, n_valid
-    buf.head.copy_(torch.tensor([pos, n_valid], dtype=torch.int32))
 
 
 def _assert_batch(smp, want, tag):
     for name, g, w in zip(smp._fields, smp, want):
         np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=f"{name} {tag}")
-
-
-def _outs(B, D, A, kind):
-    """Caller outputs poisoned all over -> (the five tensors in ReplayBufferSamples order, the two
-    backing observation buffers).  "packed": rows D floats apart starting one float past an
-    allocation (4-byte aligned only); "slice": columns 4 .. 4+D of rows of their own pitch."""
-    kw = dict(dtype=torch.float32, device="cuda")
-    if kind == "packed":
-        back = [torch.full((B * D + 1,), POISON, **kw) for _ in range(2)]
-        o, n = (b[1:].view(B, D) for b in back)
-    else:
-        pitch = (D + 3) // 4 * 4 + 8
-        back = [torch.full((B, pitch), POISON, **kw) for _ in range(2)]
-        o, n = (b[:, 4:4 + D] for b in back)
-    return (o, torch.full((B, A), POISON, **kw), n, torch.full((B, 1), POISON, **kw),
-            torch.full((B, 1), POISON, **kw)), back
 
 
 # ------------------------------------------------------------------------------------------------
@@ -73,12 +27,12 @@ def test_gather_equals_model(D, P):
     (51, 51) and every unaligned output), every lane-group width (4: 2 or 3 units; 8: 12 or 13; 16: the
     25 units of (100, 112); 32: 51; 64: 76, 100 and, looping past two units per lane, 301), a tail block,
     the wrap S-1 -> 0, and output pad columns that stay as they were."""
-    _need_gpu()
+    need_gpu()
     rng = np.random.default_rng(D)
     for S in (2, 5):
         for E in (1, 70, 259):
             for A in (1, 3, 30):
-                buf, host = _coded_ring(S, E, D, P, A)
+                buf, host = coded_ring(S, E, D, P, A)
                 for B in (1, 64, 257):
                     pairs = np.stack([rng.integers(0, S, B), rng.integers(0, E, B)]).astype(np.int32)
                     pairs[:, 0] = (S - 1, E - 1)                      # the wrap, the last env
@@ -91,7 +45,7 @@ def test_gather_equals_model(D, P):
                     _assert_batch(smp, want, tag)
                     assert smp.observations.shape == (B, D) and smp.dones.shape == (B, 1)
                     for kind in ("packed", "slice"):
-                        out, back = _outs(B, D, A, kind)
+                        out, back = outs(B, D, A, kind, 5)
                         got = buf.gather(idx, out=out)
                         _assert_batch(got, want, f"{tag} out={kind}")
                         for b in back:                                 # nothing outside the D columns
@@ -107,14 +61,14 @@ def test_gather_equals_model(D, P):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", [0, 0x123456789ABCDEF])
 def test_draw_equals_model(seed):
-    _need_gpu()
+    need_gpu()
     S, E, D, P, A = 5, 70, 13, 13, 3
-    buf, host = _coded_ring(S, E, D, P, A, seed=seed)
+    buf, host = coded_ring(S, E, D, P, A, seed=seed)
     with pytest.raises(ValueError):
         buf.sample(4)                                                  # nothing stored yet
     draws = 0
     for pos, n_valid in ((3, 3), (1, 4)):                              # filling, full
-        _set_head(buf, pos, n_valid)
+        set_head(buf, pos, n_valid)
         assert len(buf) == n_valid
         for B in (1, 3, 257):
             for _ in range(3):                                         # consecutive draws differ
@@ -137,14 +91,14 @@ def test_draw_equals_model(seed):
 
 
 def test_draw_covers_every_valid_pair_and_never_the_head_slot():
-    _need_gpu()
+    need_gpu()
     S, E, B = 4, 3, 4096
     for pos in range(S):
         want = rm.draw_pairs(11, 0, B, pos, S - 1, S, E)
         valid = {(s, e) for s in range(S) if s != pos for e in range(E)}
         assert {tuple(p) for p in want.T.tolist()} == valid            # the model alone: all 9, no other
-        buf, _ = _coded_ring(S, E, 5, 5, 1, seed=11)
-        _set_head(buf, pos, S - 1)
+        buf, _ = coded_ring(S, E, 5, 5, 1, seed=11)
+        set_head(buf, pos, S - 1)
         buf.sample(B)
         got = buf.last_indices.cpu().numpy()
         np.testing.assert_array_equal(got, want)
@@ -153,11 +107,11 @@ def test_draw_covers_every_valid_pair_and_never_the_head_slot():
 
 def test_untrusted_head_words_do_not_leave_the_ring():
     """n_valid < 1 is taken as 1; whatever pos holds, the slot is reduced mod S."""
-    _need_gpu()
+    need_gpu()
     S, E = 5, 7
-    buf, host = _coded_ring(S, E, 5, 5, 1)
+    buf, host = coded_ring(S, E, 5, 5, 1)
     for pos, nv in ((2, 0), (2, -5), (12, 3), (-9, 2), (1, 1000)):
-        _set_head(buf, 2, 1)
+        set_head(buf, 2, 1)
         buf.head.copy_(torch.tensor([pos, nv], dtype=torch.int32))
         smp = buf.sample(64)
         idx = buf.last_indices.cpu().numpy()
@@ -173,17 +127,17 @@ def test_untrusted_head_words_do_not_leave_the_ring():
 def test_gather_clamps_indices():
     """The C ABI on a view of slots 1 .. 4 of a 7-slot ring: every address the kernel would form from
     the unclamped indices below lies inside the 7-slot tensors."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import _native as nat
     E, D, P, A, B = 6, 12, 12, 3, 6
-    big, host = _coded_ring(7, E, D, P, A)
+    big, host = coded_ring(7, E, D, P, A)
     Sv = 4
     view = nat.ReplayViewPtrs(big._obs_buf[1].data_ptr(), big.actions[1].data_ptr(),
                               big.rewards[1].data_ptr(), big.dones[1].data_ptr(), Sv, E, D, P, A, 0)
     host_v = tuple(h[1:1 + Sv] for h in host)
     raw = np.array([[-1, -1, Sv, Sv, 1, 2], [0, E + 1, -1, 3, -1, E + 1]], dtype=np.int32)
     clamped = np.array([[0, 0, Sv - 1, Sv - 1, 1, 2], [0, E - 1, 0, 3, 0, E - 1]], dtype=np.int32)
-    out, _ = _outs(B, D, A, "slice")
+    out, _ = outs(B, D, A, "slice", 5)
     o, a_o, n, d_o, r_o = out
     batch = nat.ReplayBatchPtrs(o.data_ptr(), n.data_ptr(), a_o.data_ptr(), r_o.data_ptr(),
                                 d_o.data_ptr(), B, o.stride(0))
@@ -269,7 +223,7 @@ def test_filling_through_the_env(make):
     4-slot ring every valid slot holds the twin's record of its step (rows of finished episodes, whose
     next observation is the next episode's first, included), sample(257) is a look-up in that record,
     and the host mirror and the device head agree."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     E, S, n_steps = 70, 4, 9
     (env, twin), pitch = make(E)
@@ -317,7 +271,7 @@ def test_filling_through_the_env(make):
 
 
 def test_packed_env_needs_a_packed_ring():
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     (env, _), _ = _crypto_pair(8)
     D = env.obs.shape[1]
@@ -331,12 +285,8 @@ def test_packed_env_needs_a_packed_ring():
 # ------------------------------------------------------------------------------------------------
 # 5. inside a captured graph
 # ------------------------------------------------------------------------------------------------
-def _host_ring(buf):
-    return tuple(x.cpu().numpy() for x in (buf.obs, buf.actions, buf.rewards, buf.dones))
-
-
 def test_captured_sample_follows_the_ring_and_the_draw_word():
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     E, S, B, seed = 70, 8, 257, 5
     (env, _), pitch = _crypto_pair(E)
@@ -366,7 +316,7 @@ def test_captured_sample_follows_the_ring_and_the_draw_word():
         pos, n_valid = rm.head_after(n_steps, S)
         want_idx = rm.draw_pairs(seed, draw, B, pos, n_valid, S, E)
         np.testing.assert_array_equal(idx.cpu().numpy(), want_idx, err_msg=f"after {n_steps} steps")
-        _assert_batch(smp, rm.lookup(*_host_ring(buf), want_idx), f"after {n_steps} steps")
+        _assert_batch(smp, rm.lookup(*host_ring(buf), want_idx), f"after {n_steps} steps")
         if n_steps == 2:
             assert set(want_idx[0].tolist()) <= {0, 1}
             for a in acts[2:]:
@@ -379,7 +329,7 @@ def test_captured_sample_follows_the_ring_and_the_draw_word():
 def test_captured_step_segment_publishes_its_own_head():
     """Three buf.step calls captured once: replayed twice from the same restored state they write
     the same slots and the same head, and what they write is what three eager steps write."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     E, S = 70, 4
     (env, _), pitch = _crypto_pair(E)
@@ -434,7 +384,7 @@ def test_ring_past_4_gib():
     """obs of 870 slots x 4,096 envs x 304 floats (4.33 GB): marker rows in slots 0, 868 and 869 only;
     the next observation of slot 869 wraps to slot 0.  A 32-bit row offset would land elsewhere in
     the (unwritten) tensor."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import _native as nat
     S, E, D, P, A, B = 870, 4096, 301, 304, 1, 6
     assert S * E * P * 4 > 2 ** 32

@@ -9,44 +9,17 @@ import pytest
 
 import replay_model as rm
 import replay_nstep_model as nm
+from replay_cases import POISON, RING_SEED, coded_ring, host_ring, need_gpu, outs, set_head
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-POISON = -7777.0
 FIELDS = ("observations", "actions", "next_observations", "dones", "rewards", "discounts")
-RING_SEED = 4          # chosen so that every way a return can end occurs (asserted on the model below)
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("no HIP device visible: GPU tests must run on the MI355X box")
-
-
-def _ring(S, E, D, P, A, seed=0, ring_seed=RING_SEED):
-    """A ReplayBuffer whose obs / action cells hold a code of (slot, env, column) (exact in f32; NaN in
-    the pad columns of obs), rewards of both signs with magnitudes 1e-3 .. 1e6 and Bernoulli(0.25)
-    dones, plus host copies (obs without the pad)."""
-    from finrl_amd import ReplayBuffer
-    buf = ReplayBuffer(S, E, D, A, obs_pitch=P, seed=seed)
-    assert buf.obs_pitch == P
-    rng = np.random.default_rng(ring_seed)
-    se = np.arange(S * E, dtype=np.float64).reshape(S, E)
-    obs = (se[:, :, None] * 512 + np.arange(D)).astype(np.float32)
-    act = (-(se[:, :, None] * 64 + np.arange(A) + 1)).astype(np.float32)
-    rew = (rng.choice([-1.0, 1.0], (S, E)) * 10.0 ** rng.uniform(-3, 6, (S, E))).astype(np.float32)
-    done = (rng.random((S, E)) < 0.25).astype(np.uint8)
-    buf._obs_buf.fill_(float("nan"))
-    buf.obs.copy_(torch.from_numpy(obs))
-    buf.actions.copy_(torch.from_numpy(act))
-    buf.rewards.copy_(torch.from_numpy(rew))
-    buf.dones.copy_(torch.from_numpy(done))
-    return buf, (obs, act, rew, done)
-
-
-def _set_head(buf, pos, n_valid):
-    buf.pos, buf._n_valid = pos, n_valid
-    buf.head.copy_(torch.tensor([pos, n_valid], dtype=torch.int32))
+def _ring(S, E, D, P, A, seed=0):
+    """The coded ring with the seeded rewards (both signs, 1e-3 .. 1e6) and Bernoulli(0.25) dones."""
+    return coded_ring(S, E, D, P, A, seed=seed, ring_seed=RING_SEED)
 
 
 def _assert_nstep(smp, steps, want, tag):
@@ -60,22 +33,6 @@ def _assert_nstep(smp, steps, want, tag):
 
 def _all_pairs(S, E):
     return np.stack([np.repeat(np.arange(S), E), np.tile(np.arange(E), S)]).astype(np.int32)
-
-
-def _outs(B, D, A, kind):
-    """Caller outputs poisoned all over -> (the six tensors in NStepReplayBufferSamples order, the two
-    backing observation buffers).  "packed": rows D floats apart starting one float past an
-    allocation (4-byte aligned only); "slice": columns 4 .. 4+D of rows of their own pitch."""
-    kw = dict(dtype=torch.float32, device="cuda")
-    if kind == "packed":
-        back = [torch.full((B * D + 1,), POISON, **kw) for _ in range(2)]
-        o, n = (b[1:].view(B, D) for b in back)
-    else:
-        pitch = (D + 3) // 4 * 4 + 8
-        back = [torch.full((B, pitch), POISON, **kw) for _ in range(2)]
-        o, n = (b[:, 4:4 + D] for b in back)
-    return (o, torch.full((B, A), POISON, **kw), n, torch.full((B, 1), POISON, **kw),
-            torch.full((B, 1), POISON, **kw), torch.full((B, 1), POISON, **kw)), back
 
 
 # ------------------------------------------------------------------------------------------------
@@ -99,19 +56,20 @@ def _assert_every_ending_occurs(rew, done, pairs, pos, n):
     assert ((m == n) & ~by_done).any(), f"pos={pos} n={n}: no full-length return without a done"
 
 
-@pytest.mark.parametrize("D,P,A", [(5, 16, 1), (13, 13, 3), (301, 304, 30), (51, 51, 10)])
+@pytest.mark.parametrize("D,P,A", [(5, 16, 1), (5, 16, 6), (13, 13, 3), (301, 304, 30), (51, 51, 10)])
 def test_gather_nstep_equals_model_on_every_pair(D, P, A):
     """(5, 16, 1) is the 4-lane group, where n = 7 exceeds the group and takes the chunk loop;
+    (5, 16, 6) the same group with more action floats than lanes, the loop behind the stores;
     (13, 13, 3) the unaligned dword path; (301, 304, 30) a whole wave per sample in 16-byte units;
     (51, 51, 10) half a wave in dwords.  E = 70: one full wave of lanes and a 6-lane tail."""
-    _need_gpu()
+    need_gpu()
     S, E = S8, E70
     buf, host = _ring(S, E, D, P, A)
     pairs = _all_pairs(S, E)
     idx = torch.from_numpy(pairs).cuda()
     for stored in HEADS:
         pos, n_valid = rm.head_after(stored, S)
-        _set_head(buf, pos, n_valid)
+        set_head(buf, pos, n_valid)
         for n in N_STEPS:
             _assert_every_ending_occurs(host[2], host[3], pairs, pos, n)
             for gamma in GAMMAS:
@@ -127,11 +85,11 @@ def test_gather_nstep_equals_model_on_every_pair(D, P, A):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D,P,A", [(13, 13, 3), (301, 304, 30)])
 def test_nstep_1_is_the_one_step_sampler(D, P, A):
-    _need_gpu()
+    need_gpu()
     S, E, B, seed = S8, E70, 257, 9
     buf, _ = _ring(S, E, D, P, A, seed=seed)
     for stored in HEADS:
-        _set_head(buf, *rm.head_after(stored, S))
+        set_head(buf, *rm.head_after(stored, S))
         for draw, gamma in ((0, 0.99), (5, 1.0), (2 ** 33 + 1, 0.0), (7, 0.5)):
             buf.draw.fill_(draw)
             one = [t.clone() for t in buf.sample(B)]
@@ -150,7 +108,7 @@ def test_nstep_1_is_the_one_step_sampler(D, P, A):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("seed", [0, 0x123456789ABCDEF])
 def test_sample_nstep_draws_the_one_step_pairs(seed):
-    _need_gpu()
+    need_gpu()
     S, E, D, P, A, n, gamma = S8, E70, 13, 13, 3, 3, 0.99
     buf, host = _ring(S, E, D, P, A, seed=seed)
     with pytest.raises(ValueError):
@@ -158,7 +116,7 @@ def test_sample_nstep_draws_the_one_step_pairs(seed):
     draws = 0
     for stored in HEADS:
         pos, n_valid = rm.head_after(stored, S)
-        _set_head(buf, pos, n_valid)
+        set_head(buf, pos, n_valid)
         for B in (1, 3, 257):
             seen = []
             for _ in range(2):
@@ -193,7 +151,7 @@ def test_sample_nstep_draws_the_one_step_pairs(seed):
 def test_untrusted_head_words_do_not_leave_the_ring():
     """Whatever pos holds every slot is reduced mod S; n_valid is clamped into [1, S - 1] for the
     draw.  The outputs equal the model evaluated with the words reduced in that way."""
-    _need_gpu()
+    need_gpu()
     S, E, D, P, A, B, n, gamma, seed = S8, E70, 13, 13, 3, 257, 3, 0.99, 21
     buf, host = _ring(S, E, D, P, A, seed=seed)
     all_pairs = _all_pairs(S, E)
@@ -201,7 +159,7 @@ def test_untrusted_head_words_do_not_leave_the_ring():
     draws = 0
     for pos in (-5, S, 2 ** 31 - 1):
         for nv in (-1, 0, S + 7):
-            _set_head(buf, 2, 1)
+            set_head(buf, 2, 1)
             buf.head.copy_(torch.tensor([pos, nv], dtype=torch.int32))
             smp = buf.sample_nstep(B, n, gamma)
             torch.cuda.synchronize()
@@ -225,7 +183,7 @@ def test_untrusted_head_words_do_not_leave_the_ring():
 def test_gather_nstep_clamps_indices():
     """The C ABI on a view of slots 1 .. 4 of a 7-slot ring: every address the kernel would form from
     the unclamped indices below lies inside the 7-slot tensors."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import _native as nat
     E, D, P, A, B, n, gamma = 6, 12, 12, 3, 6, 3, 0.5
     big, host = _ring(7, E, D, P, A)
@@ -235,7 +193,7 @@ def test_gather_nstep_clamps_indices():
     host_v = tuple(h[1:1 + Sv] for h in host)
     raw = np.array([[-1, -1, Sv, Sv, 1, 2], [0, E + 1, -1, 3, -1, E + 1]], dtype=np.int32)
     clamped = np.array([[0, 0, Sv - 1, Sv - 1, 1, 2], [0, E - 1, 0, 3, 0, E - 1]], dtype=np.int32)
-    out, _ = _outs(B, D, A, "slice")
+    out, _ = outs(B, D, A, "slice", 6)
     o, a_o, nx, d_o, r_o, g_o = out
     steps = torch.zeros(B, dtype=torch.int32, device="cuda")
     head = torch.tensor([pos, Sv - 1], dtype=torch.int32, device="cuda")
@@ -250,7 +208,7 @@ def test_gather_nstep_clamps_indices():
     for name, g, w in zip(FIELDS + ("steps",), out + (steps,), want):
         np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=name)
     # steps = NULL is allowed: the same six outputs
-    out2, _ = _outs(B, D, A, "slice")
+    out2, _ = outs(B, D, A, "slice", 6)
     o, a_o, nx, d_o, r_o, g_o = out2
     batch = nat.ReplayBatchPtrs(o.data_ptr(), nx.data_ptr(), a_o.data_ptr(), r_o.data_ptr(),
                                 d_o.data_ptr(), B, o.stride(0))
@@ -269,21 +227,21 @@ def test_gather_nstep_clamps_indices():
 def test_out_tensors_and_their_pad_columns(D, P, A):
     """out= with a pitched slice (and with packed rows one float past an allocation) for the two
     observation outputs: nothing outside the D columns is written."""
-    _need_gpu()
+    need_gpu()
     S, E, n, gamma = S8, E70, 3, 0.99
     buf, host = _ring(S, E, D, P, A, seed=2)
     pos, n_valid = rm.head_after(S + 3, S)
-    _set_head(buf, pos, n_valid)
+    set_head(buf, pos, n_valid)
     pairs = _all_pairs(S, E)[:, ::3]
     B = pairs.shape[1]
     idx = torch.from_numpy(np.ascontiguousarray(pairs)).cuda()
     want = nm.nstep_lookup(*host, pairs, pos, n, gamma)
     for kind in ("slice", "packed"):
-        out, back = _outs(B, D, A, kind)
+        out, back = outs(B, D, A, kind, 6)
         got = buf.gather_nstep(idx, n, gamma, out=out)
         assert all(g.data_ptr() == o.data_ptr() for g, o in zip(got, out))
         _assert_nstep(got, buf.last_steps, want, f"gather out={kind}")
-        out_s, back_s = _outs(B, D, A, kind)
+        out_s, back_s = outs(B, D, A, kind, 6)
         draw = buf.draws
         got = buf.sample_nstep(B, n, gamma, out=out_s)
         drawn = buf.last_indices.cpu().numpy()
@@ -298,7 +256,7 @@ def test_out_tensors_and_their_pad_columns(D, P, A):
                 assert (b[:, :4] == POISON).all() and (b[:, 4 + D:] == POISON).all()
     with pytest.raises(ValueError):
         buf.gather_nstep(idx, n, gamma, out=out[:5])                   # six tensors, not five
-    bad = list(_outs(B, D, A, "slice")[0])
+    bad = list(outs(B, D, A, "slice", 6)[0])
     bad[5] = torch.zeros(B, 2, device="cuda")[:, :1]                   # discounts not contiguous
     with pytest.raises(ValueError):
         buf.gather_nstep(idx, n, gamma, out=bad)
@@ -316,15 +274,11 @@ def _crypto_env(E):
     return VecCryptoEnv(cfg, E, lookback=1, auto_reset=True)
 
 
-def _host_ring(buf):
-    return tuple(x.cpu().numpy() for x in (buf.obs, buf.actions, buf.rewards, buf.dones))
-
-
 def test_captured_sample_nstep_follows_the_ring_and_the_draw_word():
     """One captured sample_nstep, replayed after further buf.step calls: each replay equals the model
     for the ring, the head and the draw number as they are at that replay, with the n and gamma of
     the capture."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     E, S, B, seed, n, gamma = E70, S8, 257, 5, 3, 0.99
     env = _crypto_env(E)
@@ -358,7 +312,7 @@ def test_captured_sample_nstep_follows_the_ring_and_the_draw_word():
         assert buf.head.tolist() == [pos, n_valid]
         want_idx = nm.draw_pairs(seed, draw, B, pos, n_valid, S, E)
         np.testing.assert_array_equal(idx.cpu().numpy(), want_idx, err_msg=f"after {stored} steps")
-        want = nm.nstep_lookup(*_host_ring(buf), want_idx, pos, n, gamma)
+        want = nm.nstep_lookup(*host_ring(buf), want_idx, pos, n, gamma)
         _assert_nstep(smp, steps, want, f"after {stored} steps")
         lengths |= set(want[6].tolist())
     assert lengths == {1, 2, 3}
@@ -367,7 +321,7 @@ def test_captured_sample_nstep_follows_the_ring_and_the_draw_word():
 def test_gather_nstep_through_a_real_env():
     """S + 3 buf.step calls of VecCryptoEnv on a 7-row panel (episodes end inside the 8-slot ring),
     then the n-step batch of every pair against the model on host copies of the ring."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import ReplayBuffer
     E, S = E70, S8
     env = _crypto_env(E)
@@ -379,7 +333,7 @@ def test_gather_nstep_through_a_real_env():
         buf.step(env, torch.from_numpy(rng.uniform(-1, 1, (E, A)).astype(np.float32)).cuda())
     pos, n_valid = rm.head_after(S + 3, S)
     assert buf.head.tolist() == [pos, n_valid]
-    host = _host_ring(buf)
+    host = host_ring(buf)
     pairs = _all_pairs(S, E)
     idx = torch.from_numpy(pairs).cuda()
     valid = np.isin(pairs[0], rm.valid_slots(pos, n_valid, S))
@@ -412,7 +366,7 @@ def test_ring_past_4_gib():
     only, head at pos = 1.  The late next-observation rows of the pairs below lie in slots 867, 868
     and 869, all beyond the 4 GiB offset, or wrap to slot 0; a 32-bit row offset would land elsewhere
     in the (unwritten) tensor."""
-    _need_gpu()
+    need_gpu()
     from finrl_amd import _native as nat
     S, E, D, P, A, n, gamma = 870, 4096, 301, 304, 1, 3, 0.5
     assert 867 * E * P * 4 > 2 ** 32
