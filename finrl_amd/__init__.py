@@ -19,6 +19,8 @@ _LAZY = {      # name -> module; lazy because these need the native library
     "VecStopLossEnv": "vec_cashpenalty", "CashPenaltyPanel": "vec_cashpenalty",
     "RolloutBuffer": "rollout", "ReplayBuffer": "replay", "GraphedSegment": "graph",
     "ReplayBufferSamples": "replay", "NStepReplayBufferSamples": "replay",
+    "PrioritizedReplayBuffer": "replay", "PrioritizedReplayBufferSamples": "replay",
+    "PrioritizedNStepReplayBufferSamples": "replay",
 }
 
 

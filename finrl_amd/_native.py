@@ -265,10 +265,18 @@ class ReplayNStepPtrs(C.Structure):
                 ("n_steps", C.c_int32), ("gamma", C.c_float)]
 
 
+class ReplayPerPtrs(C.Structure):
+    """finenv_replay_per: the tickets, the sum tree, the largest-ticket word and frac_bits."""
+    _fields_ = [("tickets", C.c_void_p), ("tree", C.c_void_p), ("max_ticket", C.c_void_p),
+                ("frac_bits", C.c_int32), ("reserved0", C.c_int32)]
+
+
 # the replay buffer's pointer structs (22 stays invalid, like 18)
 _REPLAY_STRUCTS = {23: ReplayViewPtrs, 24: ReplayBatchPtrs}
 # the n-step sampler's (25 stays invalid: the end of the list above)
 _REPLAY_NSTEP_STRUCTS = {26: ReplayNStepPtrs}
+# prioritised replay's (27 stays invalid: the end of the list above)
+_REPLAY_PER_STRUCTS = {28: ReplayPerPtrs}
 
 _lib = None
 
@@ -377,6 +385,23 @@ def lib():
         L.finenv_replay_gather_nstep.argtypes = [
             C.POINTER(ReplayViewPtrs), C.c_void_p, C.POINTER(ReplayBatchPtrs),
             C.POINTER(ReplayNStepPtrs), C.c_void_p]
+    if hasattr(L, "finenv_replay_per_sample"):             # prioritised replay (same rule)
+        per = C.POINTER(ReplayPerPtrs)
+        L.finenv_replay_per_tree_words.argtypes = [C.c_int64]
+        L.finenv_replay_per_tree_words.restype = C.c_int64
+        L.finenv_replay_per_rebuild.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p]
+        L.finenv_replay_per_put.argtypes = [per, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p]
+        L.finenv_replay_per_update.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p]
+        L.finenv_replay_per_find.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_void_p]
+        L.finenv_replay_per_sample.argtypes = [
+            C.POINTER(ReplayViewPtrs), per, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
+            C.c_void_p, C.c_void_p, C.c_void_p]
+        L.finenv_replay_per_sample_nstep.argtypes = [
+            C.POINTER(ReplayViewPtrs), per, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
+            C.POINTER(ReplayNStepPtrs), C.c_void_p, C.c_void_p, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
@@ -389,6 +414,8 @@ def lib():
         later += sorted(_REPLAY_STRUCTS.items())
     if hasattr(L, "finenv_replay_sample_nstep"):
         later += sorted(_REPLAY_NSTEP_STRUCTS.items())
+    if hasattr(L, "finenv_replay_per_sample"):
+        later += sorted(_REPLAY_PER_STRUCTS.items())
     for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(

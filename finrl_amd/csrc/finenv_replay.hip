@@ -5,6 +5,9 @@
 // sample (indices_out: + 8).  No LDS, no barrier; every offset is 64-bit (the ring may pass 4 GiB).
 // The n-step form (replay_nstep_kernel) adds the h reward / done words of a pair's window and the
 // discount: + 5h + 4 bytes per sample, and a second round trip for the late next-observation row.
+// Prioritised replay (per_*, replay_per_*_kernel) keeps uint32 tickets and a fan-out-64 tree of exact
+// uint64 sums beside the ring and puts the proportional draw, one round trip per tree level, in front
+// of the same two samplers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -117,23 +120,13 @@ __device__ __forceinline__ void copy_rest(const V *src0, const V *src1, V *dst0,
 // the action row's first unit, the tail and the reward / done words are all loaded before the first
 // store -- a load behind the wave's own stores waits for them.  The two rows alternate
 // unit by unit: one row after the other measured 4 % slower (profiles/replay_share.md).
-template <int G, typename V, bool DRAW>
-__global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
+// `last` runs on the group's lane 0 with the reward / done stores: what else a kernel stores per sample.
+template <int G, typename V, typename Last>
+__device__ __forceinline__ void gather_rows(const GatherArgs &a, long long b, int lane, int s, int e,
+                                            const Last &last)
 {
-    constexpr int PER_BLOCK = 256 / G;
     constexpr int VW = (int)(sizeof(V) / sizeof(float));
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
     const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
-
-    int s, e;
-    sample_pair<G, DRAW>(a, b, s, e);             // the age is not needed: one step ends at the newest
-    if (DRAW && a.indices_out != nullptr && lane == 0) {
-        a.indices_out[b] = s;
-        a.indices_out[(long long)B + b] = e;
-    }
     const int s1 = s + 1 == S ? 0 : s + 1;
     const long long se = (long long)s * E + e, se1 = (long long)s1 * E + e;
     const float *row0 = a.v.obs + se * a.v.obs_pitch;
@@ -185,8 +178,27 @@ __global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
     if (lane == 0) {
         a.o.rewards[b] = rew;
         a.o.dones[b] = (float)dn;
+        last();
     }
     copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
+}
+
+template <int G, typename V, bool DRAW>
+__global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
+{
+    constexpr int PER_BLOCK = 256 / G;
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+
+    int s, e;
+    sample_pair<G, DRAW>(a, b, s, e);             // the age is not needed: one step ends at the newest
+    if (DRAW && a.indices_out != nullptr && lane == 0) {
+        a.indices_out[b] = s;
+        a.indices_out[(long long)B + b] = e;
+    }
+    gather_rows<G, V>(a, b, lane, s, e, [] {});
 }
 
 struct NStepArgs {
@@ -208,22 +220,16 @@ struct NStepArgs {
 // round trip per further chunk of G steps.  All control flow but the loads' and stores' predicates is
 // uniform over the launch, so the ballot and the shuffles see every lane of a live group.  h <= n <=
 // S - 1 (host-checked) keeps every slot below 2S before its one conditional subtract.
-template <int G, typename V, bool DRAW>
-__global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
+template <int G, typename V, typename Last>
+__device__ __forceinline__ void nstep_rows(const NStepArgs &na, long long b, int lane, int s, int e,
+                                           int age, const Last &last)
 {
     const GatherArgs &a = na.g;
-    constexpr int PER_BLOCK = 256 / G;
     constexpr int VW = (int)(sizeof(V) / sizeof(float));
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
     const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
     const int n = na.n_steps;
     const float gamma = na.gamma;
 
-    int s, e;
-    const int age = sample_pair<G, DRAW>(a, b, s, e);
     int h = age + 1 < n ? age + 1 : n;            // the horizon ends at the newest step
     if (G == 64) h = __builtin_amdgcn_readfirstlane(h);
     const long long se = (long long)s * E + e;
@@ -320,12 +326,285 @@ __global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
         a.o.dones[b] = dlast;
         na.discounts[b] = g;
         if (na.steps != nullptr) na.steps[b] = m;
+        last();
+    }
+    copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
+}
+
+template <int G, typename V, bool DRAW>
+__global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
+{
+    const GatherArgs &a = na.g;
+    constexpr int PER_BLOCK = 256 / G;
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+
+    int s, e;
+    const int age = sample_pair<G, DRAW>(a, b, s, e);
+    nstep_rows<G, V>(na, b, lane, s, e, age, [&] {
         if (DRAW && a.indices_out != nullptr) {   // with the other stores, not ahead of the loads
             a.indices_out[b] = s;
             a.indices_out[(long long)B + b] = e;
         }
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Prioritised replay (contract: include/finenv.h, "Prioritised replay"): uint32 tickets per
+// transition, a fan-out-64 tree of exact uint64 sums stored top-down, and the descent that turns a
+// value u in [0, total) into the leaf whose ticket interval holds it.
+// ------------------------------------------------------------------------------------------------
+constexpr int PER_MAX_LEVELS = 6;         // 64^5 < 2^31 - 1 <= 64^6
+
+// The tree of N leaves: cnt[0] = N, cnt[k] = nodes of level k = ceil(cnt[k-1] / 64), levels = the k
+// with cnt[k] == 1; level k starts at word off[k] (off[levels] = 0: the root comes first).
+struct PerTree {
+    uint32_t *tickets;
+    uint64_t *tree;
+    int32_t levels;
+    long long cnt[PER_MAX_LEVELS + 1];
+    long long off[PER_MAX_LEVELS + 1];
+};
+
+// ticket of a shaped priority: 1 unless w > 0, else rint(w * 2^F) in double (exact), in [1, 2^32 - 1]
+__device__ __forceinline__ uint32_t per_ticket(float w, int frac_bits)
+{
+    if (!(w > 0.0f)) return 1u;
+    double x = rint((double)w * (double)(1ull << frac_bits));
+    x = x < 1.0 ? 1.0 : (x > 4294967295.0 ? 4294967295.0 : x);
+    return (uint32_t)x;
+}
+
+// 64 values -> their sum in every lane
+__device__ __forceinline__ uint64_t wave_sum(uint64_t x)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, d, 64);
+    return x;
+}
+
+// One level of sums: a wave per node, out[node] = the sum of in[64 node .. 64 node + 63] below n_in.
+template <typename T>
+__global__ void __launch_bounds__(256) per_sum_kernel(const T *in, long long n_in, uint64_t *out,
+                                                      long long n_out)
+{
+    const long long node = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (node >= n_out) return;
+    const long long i = node * 64 + ((int)threadIdx.x & 63);
+    const uint64_t sum = wave_sum(i < n_in ? (uint64_t)in[i] : 0ull);
+    if (((int)threadIdx.x & 63) == 0) out[node] = sum;
+}
+
+// The fill rule and level 1 under it: a wave per level-1 node of the two runs [a0, a0 + na) and
+// [b0, b0 + nb) (disjoint: the host merges runs that meet).  Leaves in [fill0, fill1) take the
+// largest ticket seen, leaves in [zero0, zero1) take 0, the rest stay; the wave owns its node, so
+// the node is a plain store of the new sum.
+__global__ void __launch_bounds__(256) per_put_kernel(uint32_t *tickets, uint64_t *level1,
+                                                      long long n_leaves, const uint32_t *max_ticket,
+                                                      long long fill0, long long fill1, long long zero0,
+                                                      long long zero1, long long a0, long long na,
+                                                      long long b0, long long nb)
+{
+    const long long w = (long long)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (w >= na + nb) return;
+    const long long node = w < na ? a0 + w : b0 + (w - na);
+    const long long i = node * 64 + ((int)threadIdx.x & 63);
+    uint32_t top = *max_ticket;
+    top = top == 0u ? 1u : top;
+    uint32_t q = 0u;
+    if (i < n_leaves) {
+        const bool fill = i >= fill0 && i < fill1, zero = i >= zero0 && i < zero1;
+        q = fill ? top : (zero ? 0u : tickets[i]);
+        if (fill || zero) tickets[i] = q;
     }
-    copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
+    const uint64_t sum = wave_sum(q);
+    if (((int)threadIdx.x & 63) == 0) level1[node] = sum;
+}
+
+// The write-back: entry i's ticket replaces a nonzero leaf (a zero leaf holds no transition and
+// stays); the exchanged old values make the level-1 deltas telescope whatever the order, so level 1
+// stays the exact sum under duplicate indices.  The levels above are summed again afterwards.
+__global__ void __launch_bounds__(256) per_update_kernel(uint32_t *tickets, uint64_t *level1,
+                                                         uint32_t *max_ticket, int S, int E,
+                                                         int frac_bits, const int32_t *indices,
+                                                         const float *weights, int B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t q = 0u;
+    if (i < B) {
+        q = per_ticket(weights[i], frac_bits);
+        int s = indices[i], e = indices[(long long)B + i];
+        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
+        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+        const long long leaf = (long long)s * E + e;
+        if (tickets[leaf] != 0u) {
+            const uint32_t old = atomicExch(&tickets[leaf], q);
+            atomicAdd((unsigned long long *)&level1[leaf >> 6],
+                      (unsigned long long)((long long)q - (long long)old));
+        }
+    }
+    uint32_t top = q;                              // one atomicMax per wave
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)top, d, 64);
+        top = o > top ? o : top;
+    }
+    if (((int)threadIdx.x & 63) == 0 && top != 0u) atomicMax(max_ticket, top);
+}
+
+// The descent, by a group of G lanes that share one u (< total, or total == 0): at each level the
+// group reads the 64 children of its node, 64 / G consecutive ones per lane, forms their inclusive
+// prefix sums and counts the children among the first 63 whose prefix is <= u: that count is the
+// child holding u, and u continues less the prefix before it.  Children past the end count as 0.
+// Tree words are not trusted: the child is at most 63 by construction and every index is clamped
+// to its level, so a wrong tree gives a wrong leaf and no address outside tickets / tree.  Returns
+// the leaf (the same in every lane of the group); q = its ticket as the tree saw it.
+template <int G>
+__device__ __forceinline__ long long per_descend(const PerTree &t, uint64_t u, int lane, uint32_t &q)
+{
+    constexpr int K = 64 / G;
+    const int gshift = ((int)threadIdx.x & 63) & ~(G - 1);
+    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
+    long long node = 0;
+    uint64_t val = 0;
+    for (int k = t.levels; k >= 1; --k) {
+        const long long n = t.cnt[k - 1];
+        const uint64_t *words = t.tree + t.off[k - 1];       // k == 1: not read
+        const long long first = node * 64 + (long long)lane * K;
+        uint64_t c[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const long long idx = first + i;
+            c[i] = idx < n ? (k == 1 ? (uint64_t)t.tickets[idx] : words[idx]) : 0ull;
+        }
+#pragma unroll
+        for (int i = 1; i < K; ++i) c[i] += c[i - 1];
+        uint64_t run = c[K - 1];                              // inclusive scan of the lanes' totals
+#pragma unroll
+        for (int d = 1; d < G; d *= 2) {
+            const uint64_t o = (uint64_t)__shfl_up((unsigned long long)run, d, G);
+            run += lane >= d ? o : 0ull;
+        }
+        const uint64_t before = run - c[K - 1];
+        int child = 0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const bool le = before + c[i] <= u && lane * K + i < 63;
+            child += __popcll((__ballot(le) >> gshift) & gmask);
+        }
+        uint64_t lo = before, hi = before + c[0];             // of child (child % K) of this lane
+#pragma unroll
+        for (int i = 1; i < K; ++i) {
+            if (i == (child & (K - 1))) {
+                lo = before + c[i - 1];
+                hi = before + c[i];
+            }
+        }
+        lo = (uint64_t)__shfl((unsigned long long)lo, child / K, G);
+        hi = (uint64_t)__shfl((unsigned long long)hi, child / K, G);
+        u -= lo;
+        val = hi - lo;
+        node = node * 64 + child;
+        node = node > n - 1 ? n - 1 : node;
+    }
+    q = (uint32_t)val;
+    return node;
+}
+
+// u -> the pair of its leaf: 16 lanes per value
+__global__ void __launch_bounds__(256) per_find_kernel(const PerTree t, int E, const uint64_t *u_in,
+                                                       int B, int32_t *indices_out)
+{
+    constexpr int G = 16;
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
+    if (b >= B) return;
+    const uint64_t total = t.tree[0];
+    uint64_t u = u_in[b];
+    u = total == 0 ? 0 : (u < total ? u : total - 1);
+    uint32_t q;
+    long long leaf = per_descend<G>(t, u, lane, q);
+    leaf = total == 0 ? 0 : leaf;
+    if (lane == 0) {
+        const int s = (int)(leaf / E);
+        indices_out[b] = s;
+        indices_out[(long long)B + b] = (int)(leaf - (long long)s * E);
+    }
+}
+
+struct PerDraw {
+    PerTree t;
+    float *probabilities;         // [B] or NULL
+};
+
+// The prioritised draw of sample b: the uniform draw's Philox counter and key, u = umul64hi(x0:x1,
+// total), the descent -> s, e and the probability q / total.
+template <int G>
+__device__ __forceinline__ void per_pair(const GatherArgs &a, const PerTree &t, long long b, int lane,
+                                         int &s, int &e, float &prob)
+{
+    const uint64_t total = t.tree[0];
+    const uint64_t draw = (uint64_t)*a.draw;
+    uint32_t x0, x1;
+    philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi, x0, x1);
+    const uint64_t u = __umul64hi(((uint64_t)x0 << 32) | x1, total);   // < total, or 0 == total
+    uint32_t q;
+    long long leaf = per_descend<G>(t, u, lane, q);
+    leaf = total == 0 ? 0 : leaf;
+    prob = (float)((double)q / (double)total);
+    s = (int)(leaf / a.v.n_envs);
+    e = (int)(leaf - (long long)s * a.v.n_envs);
+    if (G == 64) {
+        s = __builtin_amdgcn_readfirstlane(s);
+        e = __builtin_amdgcn_readfirstlane(e);
+    }
+}
+
+// The one-step sampler with the prioritised draw; pair and probability go out with the other stores.
+template <int G, typename V>
+__global__ void __launch_bounds__(256) replay_per_gather_kernel(const GatherArgs a, const PerDraw p)
+{
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+    int s, e;
+    float prob;
+    per_pair<G>(a, p.t, b, lane, s, e, prob);
+    gather_rows<G, V>(a, b, lane, s, e, [&] {
+        if (p.probabilities != nullptr) p.probabilities[b] = prob;
+        if (a.indices_out != nullptr) {
+            a.indices_out[b] = s;
+            a.indices_out[(long long)B + b] = e;
+        }
+    });
+}
+
+// The n-step sampler with the prioritised draw: the age of the drawn slot comes from the head word.
+template <int G, typename V>
+__global__ void __launch_bounds__(256) replay_per_nstep_kernel(const NStepArgs na, const PerDraw p)
+{
+    const GatherArgs &a = na.g;
+    const int lane = (int)threadIdx.x & (G - 1);
+    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
+    const int B = a.o.batch_size;
+    if (b >= B) return;
+    int s, e;
+    float prob;
+    per_pair<G>(a, p.t, b, lane, s, e, prob);
+    const int S = a.v.n_slots;
+    const long long back = ((long long)a.head[0] - 1 - s) % S;
+    int age = (int)(back < 0 ? back + S : back);
+    if (G == 64) age = __builtin_amdgcn_readfirstlane(age);
+    nstep_rows<G, V>(na, b, lane, s, e, age, [&] {
+        if (p.probabilities != nullptr) p.probabilities[b] = prob;
+        if (a.indices_out != nullptr) {
+            a.indices_out[b] = s;
+            a.indices_out[(long long)B + b] = e;
+        }
+    });
 }
 
 // The kernels are function templates: a functor each names the instantiation for the launcher.
@@ -337,18 +616,27 @@ struct NStepKernel {
     template <int G, typename V, bool DRAW>
     static constexpr auto get() { return &replay_nstep_kernel<G, V, DRAW>; }
 };
+struct PerGatherKernel {
+    template <int G, typename V, bool>
+    static constexpr auto get() { return &replay_per_gather_kernel<G, V>; }
+};
+struct PerNStepKernel {
+    template <int G, typename V, bool>
+    static constexpr auto get() { return &replay_per_nstep_kernel<G, V>; }
+};
 
 // One launch of K's kernel for lane groups of G and 16-byte (vec) or dword units: 256 / G samples per
-// block, on the device of the batch.
-template <typename K, bool DRAW, typename Args>
-int launch_sampler(int G, bool vec, const Args &args, const finenv_replay_batch &o, void *stream)
+// block, on the device of the batch.  `more`: the kernel's arguments after the first.
+template <typename K, bool DRAW, typename Args, typename... More>
+int launch_sampler(int G, bool vec, const Args &args, const finenv_replay_batch &o, void *stream,
+                   const More &...more)
 {
     const finenv_host::DeviceGuard guard(finenv_host::pointer_device(o.observations));
     const auto launch = [&](auto g) {
         constexpr int GG = decltype(g)::value;
         const dim3 grid((unsigned)(((long long)o.batch_size * GG + 255) / 256));
         const auto kernel = vec ? K::template get<GG, f4, DRAW>() : K::template get<GG, float, DRAW>();
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args, more...);
     };
     switch (G) {
     case 4: launch(std::integral_constant<int, 4>()); break;
@@ -392,14 +680,18 @@ int launch_gather(const GatherArgs &a, void *stream)
 
 // The n-step launch: the gather's checks, then 1 <= n_steps <= S - 1 (a window never reaches round
 // to its own start), gamma finite in [0, 1], head and discounts present.
+bool nstep_ok(const finenv_replay_view &v, const finenv_replay_nstep *ns)
+{
+    return ns->head && ns->discounts && ns->n_steps >= 1 && ns->n_steps <= v.n_slots - 1 &&
+           ns->gamma >= 0.0f && ns->gamma <= 1.0f;
+}
+
 template <bool DRAW>
 int launch_nstep(GatherArgs a, const finenv_replay_nstep *ns, void *stream)
 {
     bool vec = false;
     const int G = gather_group(a.v, a.o, vec);
-    if (G == 0 || !ns->head || !ns->discounts || ns->n_steps < 1 || ns->n_steps > a.v.n_slots - 1 ||
-        !(ns->gamma >= 0.0f && ns->gamma <= 1.0f))
-        return FINENV_ERR_INVALID;
+    if (G == 0 || !nstep_ok(a.v, ns)) return FINENV_ERR_INVALID;
     if (!DRAW) a.head = ns->head;
     const NStepArgs na = {a, ns->discounts, ns->steps, ns->n_steps, ns->gamma};
     return launch_sampler<NStepKernel, DRAW>(G, vec, na, a.o, stream);
@@ -416,6 +708,54 @@ GatherArgs index_args(const finenv_replay_view *view, const finenv_replay_batch 
                       const int32_t *indices)
 {
     return {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
+}
+
+// The level table of n leaves (1 <= n <= 2^31 - 1) -> the number of tree words.
+long long per_levels(long long n, PerTree &t)
+{
+    t.cnt[0] = n;
+    int k = 0;
+    do {
+        ++k;
+        t.cnt[k] = (t.cnt[k - 1] + 63) / 64;
+    } while (t.cnt[k] > 1);
+    t.levels = k;
+    long long words = 0;
+    for (int j = k; j >= 1; --j) {
+        t.off[j] = words;
+        words += t.cnt[j];
+    }
+    t.off[0] = 0;                                 // unused: level 0 is the tickets
+    for (int j = k + 1; j <= PER_MAX_LEVELS; ++j) t.cnt[j] = t.off[j] = 0;
+    return words;
+}
+
+// The struct's checks (no HIP call before they pass) and the level table of S x E leaves.
+bool per_tree(const finenv_replay_per *per, int32_t S, int32_t E, PerTree &t)
+{
+    if (!per || !per->tickets || !per->tree || !per->max_ticket || per->frac_bits < 0 ||
+        per->frac_bits > 31 || S < 2 || E < 1 || (long long)S * E > 0x7fffffffLL)
+        return false;
+    t.tickets = per->tickets;
+    t.tree = per->tree;
+    per_levels((long long)S * E, t);
+    return true;
+}
+
+// Levels `from` .. the root, each from the one below it: one launch per level.
+int per_sum_levels(const PerTree &t, int from, void *stream)
+{
+    for (int k = from; k <= t.levels; ++k) {
+        const dim3 grid((unsigned)((t.cnt[k] + 3) / 4));
+        if (k == 1)
+            hipLaunchKernelGGL(per_sum_kernel<uint32_t>, grid, dim3(256), 0, (hipStream_t)stream,
+                               (const uint32_t *)t.tickets, t.cnt[0], t.tree + t.off[1], t.cnt[1]);
+        else
+            hipLaunchKernelGGL(per_sum_kernel<uint64_t>, grid, dim3(256), 0, (hipStream_t)stream,
+                               (const uint64_t *)(t.tree + t.off[k - 1]), t.cnt[k - 1],
+                               t.tree + t.off[k], t.cnt[k]);
+    }
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
 }
 
 }  // namespace
@@ -471,4 +811,111 @@ extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const 
 {
     if (!view || !batch || !indices || !nstep) return FINENV_ERR_INVALID;
     return launch_nstep<false>(index_args(view, batch, indices), nstep, stream);
+}
+
+extern "C" int64_t finenv_replay_per_tree_words(int64_t n_leaves)
+{
+    if (n_leaves < 1 || n_leaves > 0x7fffffffLL) return -1;
+    PerTree t;
+    return per_levels(n_leaves, t);
+}
+
+extern "C" int finenv_replay_per_rebuild(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                                         void *stream)
+{
+    PerTree t;
+    if (!per_tree(per, n_slots, n_envs, t)) return FINENV_ERR_INVALID;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(per->tree));
+    return per_sum_levels(t, 1, stream);
+}
+
+extern "C" int finenv_replay_per_put(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                                     int32_t pos, int32_t pos_next, void *stream)
+{
+    PerTree t;
+    if (!per_tree(per, n_slots, n_envs, t) || pos < 0 || pos >= n_slots || pos_next < 0 ||
+        pos_next >= n_slots)
+        return FINENV_ERR_INVALID;
+    const long long E = n_envs;
+    const long long fill0 = pos * E, fill1 = fill0 + E;
+    const long long zero0 = pos_next * E, zero1 = pos_next == pos ? zero0 : zero0 + E;
+    // the level-1 nodes over the two runs of leaves; runs whose nodes meet become one
+    long long a0 = fill0 >> 6, a1 = (fill1 - 1) >> 6, b0 = 0, nb = 0;
+    if (zero1 > zero0) {
+        const long long z0 = zero0 >> 6, z1 = (zero1 - 1) >> 6;
+        if (z0 <= a1 && a0 <= z1) {
+            a0 = z0 < a0 ? z0 : a0;
+            a1 = z1 > a1 ? z1 : a1;
+        } else {
+            b0 = z0;
+            nb = z1 - z0 + 1;
+        }
+    }
+    const long long na = a1 - a0 + 1;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(per->tree));
+    hipLaunchKernelGGL(per_put_kernel, dim3((unsigned)((na + nb + 3) / 4)), dim3(256), 0,
+                       (hipStream_t)stream, t.tickets, t.tree + t.off[1], t.cnt[0],
+                       (const uint32_t *)per->max_ticket, fill0, fill1, zero0, zero1, a0, na, b0, nb);
+    return per_sum_levels(t, 2, stream);
+}
+
+extern "C" int finenv_replay_per_update(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                                        const int32_t *indices, const float *weights,
+                                        int32_t batch_size, void *stream)
+{
+    PerTree t;
+    if (!per_tree(per, n_slots, n_envs, t) || !indices || !weights || batch_size < 1)
+        return FINENV_ERR_INVALID;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(per->tree));
+    hipLaunchKernelGGL(per_update_kernel, dim3((unsigned)(((long long)batch_size + 255) / 256)),
+                       dim3(256), 0, (hipStream_t)stream, t.tickets, t.tree + t.off[1], per->max_ticket,
+                       n_slots, n_envs, per->frac_bits, indices, weights, batch_size);
+    return per_sum_levels(t, 2, stream);
+}
+
+extern "C" int finenv_replay_per_find(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                                      const uint64_t *u, int32_t batch_size, int32_t *indices_out,
+                                      void *stream)
+{
+    PerTree t;
+    if (!per_tree(per, n_slots, n_envs, t) || !u || !indices_out || batch_size < 1)
+        return FINENV_ERR_INVALID;
+    const finenv_host::DeviceGuard guard(finenv_host::pointer_device(per->tree));
+    hipLaunchKernelGGL(per_find_kernel, dim3((unsigned)(((long long)batch_size + 15) / 16)), dim3(256),
+                       0, (hipStream_t)stream, t, n_envs, u, batch_size, indices_out);
+    return hipGetLastError() == hipSuccess ? FINENV_OK : FINENV_ERR_HIP;
+}
+
+extern "C" int finenv_replay_per_sample(const finenv_replay_view *view, const finenv_replay_per *per,
+                                        const int64_t *draw, uint64_t seed,
+                                        const finenv_replay_batch *batch, float *probabilities_out,
+                                        int32_t *indices_out, void *stream)
+{
+    PerDraw p;
+    if (!view || !batch || !draw || !per_tree(per, view->n_slots, view->n_envs, p.t))
+        return FINENV_ERR_INVALID;
+    p.probabilities = probabilities_out;
+    const GatherArgs a = drawn_args(view, batch, nullptr, draw, seed, indices_out);
+    bool vec = false;
+    const int G = gather_group(a.v, a.o, vec);
+    if (G == 0) return FINENV_ERR_INVALID;
+    return launch_sampler<PerGatherKernel, true>(G, vec, a, a.o, stream, p);
+}
+
+extern "C" int finenv_replay_per_sample_nstep(const finenv_replay_view *view,
+                                              const finenv_replay_per *per, const int64_t *draw,
+                                              uint64_t seed, const finenv_replay_batch *batch,
+                                              const finenv_replay_nstep *nstep, float *probabilities_out,
+                                              int32_t *indices_out, void *stream)
+{
+    PerDraw p;
+    if (!view || !batch || !draw || !nstep || !per_tree(per, view->n_slots, view->n_envs, p.t))
+        return FINENV_ERR_INVALID;
+    p.probabilities = probabilities_out;
+    const GatherArgs a = drawn_args(view, batch, nstep->head, draw, seed, indices_out);
+    bool vec = false;
+    const int G = gather_group(a.v, a.o, vec);
+    if (G == 0 || !nstep_ok(a.v, nstep)) return FINENV_ERR_INVALID;
+    const NStepArgs na = {a, nstep->discounts, nstep->steps, nstep->n_steps, nstep->gamma};
+    return launch_sampler<PerNStepKernel, true>(G, vec, na, a.o, stream, p);
 }

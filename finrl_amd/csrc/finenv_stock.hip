@@ -312,6 +312,8 @@ int finenv_struct_size(int which)
     case 24: return (int)sizeof(finenv_replay_batch);
     // (25 stays invalid: bindings of the list that ended at 24 probe it as its end)
     case 26: return (int)sizeof(finenv_replay_nstep);
+    // (27 stays invalid: bindings of the list that ended at 26 probe it as its end)
+    case 28: return (int)sizeof(finenv_replay_per);
     default: return FINENV_ERR_INVALID;
     }
 }

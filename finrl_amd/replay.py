@@ -15,6 +15,11 @@ ReplayBufferSamples = namedtuple(
 # the n-step batch: the same five, then the bootstrap discount gamma^m [B, 1]
 NStepReplayBufferSamples = namedtuple(
     "NStepReplayBufferSamples", ReplayBufferSamples._fields + ("discounts",))
+# the prioritised batches: the same, then the probability each transition was drawn with [B, 1]
+PrioritizedReplayBufferSamples = namedtuple(
+    "PrioritizedReplayBufferSamples", ReplayBufferSamples._fields + ("probabilities",))
+PrioritizedNStepReplayBufferSamples = namedtuple(
+    "PrioritizedNStepReplayBufferSamples", NStepReplayBufferSamples._fields + ("probabilities",))
 
 
 class ReplayBuffer:
@@ -44,6 +49,8 @@ class ReplayBuffer:
     ``sample_nstep`` / ``gather_nstep`` return n-step batches (discounted reward sum, the observation
     m steps later, ``gamma^m``) from the same ring, head and draw, also in one launch."""
 
+    _drawn_kinds = (ReplayBufferSamples, NStepReplayBufferSamples)     # what sample / sample_nstep return
+
     def __init__(self, n_slots, num_envs, obs_dim, action_dim, obs_pitch=None, device="cuda", seed=0):
         import torch
         dev = torch.device(device)
@@ -67,7 +74,7 @@ class ReplayBuffer:
         self.last_steps = None      # int32 [B]: the lengths m of the last n-step batch
         self._view = nat.ReplayViewPtrs(self._obs_buf.data_ptr(), self.actions.data_ptr(),
                                         self.rewards.data_ptr(), self.dones.data_ptr(), S, E, D, P, A, 0)
-        self._batches = {}          # (n-step?, batch size) -> (samples, ctypes struct, indices, steps)
+        self._batches = {}          # (namedtuple, batch size) -> (samples, ctypes struct, indices, steps)
         self._slots = {}            # pos -> (actions[pos], the env's out tuple of that slot)
         self._lib = nat.lib()
 
@@ -114,26 +121,26 @@ class ReplayBuffer:
         return ret
 
     # ------------------------------------------------------------------ sampling
-    def _batch(self, B, out, nstep=False):
-        """(samples, finenv_replay_batch, index block, steps block or None) of batch size B in the
-        one-step or the n-step form: the persistent outputs of that form, or ``out`` (five tensors, six
-        for the n-step form) with a fresh steps block and no index block (a drawn call makes its own)."""
+    def _batch(self, B, out, kind=ReplayBufferSamples):
+        """(samples, finenv_replay_batch, index block, steps block or None) of batch size B as the
+        namedtuple ``kind``: the persistent outputs of that kind, or ``out`` (its tensors in order) with
+        a fresh steps block (n-step kinds) and no index block (a drawn call makes its own)."""
         import torch
         D, A = self.obs_dim, self.action_dim
-        kind = NStepReplayBufferSamples if nstep else ReplayBufferSamples
+        nstep = "discounts" in kind._fields
         i32 = dict(dtype=torch.int32, device=self.device)
         if out is None:
-            if (nstep, B) not in self._batches:
+            if (kind, B) not in self._batches:
                 kw = dict(dtype=torch.float32, device=self.device)
                 o, n = (torch.zeros(B, self.obs_pitch, **kw) for _ in range(2))
                 smp = kind(o[:, :D], torch.zeros(B, A, **kw), n[:, :D],
-                           *(torch.zeros(B, 1, **kw) for _ in range(3 if nstep else 2)))
-                self._batches[nstep, B] = (smp, self._batch_struct(smp, B, self.obs_pitch),
-                                           torch.zeros(2, B, **i32),
-                                           torch.zeros(B, **i32) if nstep else None)
-            return self._batches[nstep, B]
-        if nstep and len(out) != 6:
-            raise ValueError("out must be the six tensors of NStepReplayBufferSamples")
+                           *(torch.zeros(B, 1, **kw) for _ in kind._fields[3:]))
+                self._batches[kind, B] = (smp, self._batch_struct(smp, B, self.obs_pitch),
+                                          torch.zeros(2, B, **i32),
+                                          torch.zeros(B, **i32) if nstep else None)
+            return self._batches[kind, B]
+        if kind is not ReplayBufferSamples and len(out) != len(kind._fields):
+            raise ValueError(f"out must be the {len(kind._fields)} tensors of {kind.__name__}")
         smp = kind(*out)
         pitch = self._check_out(smp, B)
         return smp, self._batch_struct(smp, B, pitch), None, torch.empty(B, **i32) if nstep else None
@@ -145,15 +152,15 @@ class ReplayBuffer:
         fields = [(smp.observations, (B, D), "observations"), (smp.actions, (B, A), "actions"),
                   (smp.next_observations, (B, D), "next_observations"),
                   (smp.dones, (B, 1), "dones"), (smp.rewards, (B, 1), "rewards")]
-        if hasattr(smp, "discounts"):
-            fields.append((smp.discounts, (B, 1), "discounts"))
+        for what in smp._fields[5:]:                 # discounts, probabilities
+            fields.append((getattr(smp, what), (B, 1), what))
         for t, shape, what in fields:
             if t.dtype != torch.float32 or t.device != self.head.device or tuple(t.shape) != shape:
                 raise ValueError(f"out.{what} must be {shape} float32 on {self.head.device}")
         o, n = smp.observations, smp.next_observations
         if not all(t.is_contiguous() for t, _, what in fields[1:] if what != "next_observations"):
-            raise ValueError("out.actions / dones / rewards" +
-                             (" / discounts" if len(fields) == 6 else "") + " must be contiguous")
+            raise ValueError("out." + " / ".join(("actions", "dones", "rewards") + smp._fields[5:]) +
+                             " must be contiguous")
         pitch = D if B == 1 else o.stride(0)
         if o.stride(1) != 1 or n.stride(1) != 1 or pitch < D or (B > 1 and n.stride(0) != pitch):
             raise ValueError("out.observations / next_observations need unit column stride and one "
@@ -183,21 +190,25 @@ class ReplayBuffer:
         B = int(batch_size)
         if B < 1:
             raise ValueError(f"{name}: batch_size must be >= 1")
-        smp, bs, idx, steps = self._batch(B, out, nstep is not None)
+        smp, bs, idx, steps = self._batch(B, out, self._drawn_kinds[nstep is not None])
         if idx is None:
             import torch
             idx = torch.empty(2, B, dtype=torch.int32, device=self.device)
         ns = () if nstep is None else (C.byref(self._nstep_struct(smp, steps, *nstep)),)
-        fn = "finenv_replay_" + name
-        nat.check(getattr(self._lib, fn)(
-            C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
-            self.seed, C.byref(bs), *ns, C.c_void_p(idx.data_ptr()), self._stream()), None, fn)
+        self._launch_drawn(name, smp, bs, ns, idx)
         self.draw.add_(1)
         self.draws += 1
         self.last_indices = idx
         if nstep is not None:
             self.last_steps = steps
         return smp
+
+    def _launch_drawn(self, name, smp, bs, ns, idx):
+        """The launch of the drawn call ``name`` into ``smp``: the uniform draw from the head words."""
+        fn = "finenv_replay_" + name
+        nat.check(getattr(self._lib, fn)(
+            C.byref(self._view), C.c_void_p(self.head.data_ptr()), C.c_void_p(self.draw.data_ptr()),
+            self.seed, C.byref(bs), *ns, C.c_void_p(idx.data_ptr()), self._stream()), None, fn)
 
     def _index_block(self, name, indices):
         """The caller's ``indices`` of ``name`` as the contiguous int32 [2, B] block the kernel reads."""
@@ -250,10 +261,115 @@ class ReplayBuffer:
         (finenv_replay_gather_nstep); ``buf.last_steps`` holds m.  ``n_steps`` and ``gamma`` are
         by-value launch arguments, as in ``sample_nstep``."""
         idx = self._index_block("gather_nstep", indices)
-        smp, bs, _, steps = self._batch(int(idx.shape[1]), out, True)
+        smp, bs, _, steps = self._batch(int(idx.shape[1]), out, NStepReplayBufferSamples)
         ns = self._nstep_struct(smp, steps, n_steps, gamma)
         nat.check(self._lib.finenv_replay_gather_nstep(
             C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), C.byref(ns),
             self._stream()), None, "finenv_replay_gather_nstep")
         self.last_steps = steps
         return smp
+
+
+class PrioritizedReplayBuffer(ReplayBuffer):
+    """``ReplayBuffer`` with proportional prioritised replay on the device (include/finenv.h,
+    "Prioritised replay"): one uint32 fixed-point *ticket* per transition beside the ring
+    (``tickets`` int32 [S, E] holding the bit pattern), a fan-out-64 tree of exact uint64 sums
+    (``tree`` int64 [words], ``tree[0]`` the total) and ``max_ticket`` (int32 [1]), the largest ticket
+    seen, at which new transitions enter.  A ticket of 0 means the slot holds no complete transition,
+    so the draw needs no head word; every stored transition keeps a ticket >= 1.
+
+    ``sample`` / ``sample_nstep`` draw transition i with probability ticket_i / total, in the
+    sampler's one launch, and return the parent's fields plus ``probabilities`` [B, 1];
+    ``update_priorities`` writes TD errors back.  The shaped priority is ``(|p| + eps) ** alpha``,
+    computed in torch (``powf`` is not bit-reproducible; the kernels are integer and exact), stored as
+    ``rint(w * 2**frac_bits)`` clamped to [1, 2**32 - 1]: a priority below ``2**-frac_bits`` draws as
+    if it were ``2**-frac_bits``.  ``gather`` / ``gather_nstep`` are the parent's."""
+
+    _drawn_kinds = (PrioritizedReplayBufferSamples, PrioritizedNStepReplayBufferSamples)
+
+    def __init__(self, n_slots, num_envs, obs_dim, action_dim, obs_pitch=None, device="cuda", seed=0,
+                 alpha=0.6, eps=1e-6, frac_bits=16):
+        import torch
+        super().__init__(n_slots, num_envs, obs_dim, action_dim, obs_pitch, device, seed)
+        F = int(frac_bits)
+        if not 0 <= F <= 31:
+            raise ValueError("frac_bits must be in [0, 31]")
+        S, E = self.n_slots, self.num_envs
+        words = int(self._lib.finenv_replay_per_tree_words(S * E))
+        if words < 1:
+            raise ValueError("PrioritizedReplayBuffer needs n_slots * num_envs <= 2**31 - 1")
+        self.alpha, self.eps, self.frac_bits = float(alpha), float(eps), F
+        self.tickets = torch.zeros(S, E, dtype=torch.int32, device=self.device)
+        self.tree = torch.zeros(words, dtype=torch.int64, device=self.device)
+        one = 1 << F                                              # the ticket of 1.0
+        self.max_ticket = torch.tensor([one - (1 << 32) if one >= 1 << 31 else one],
+                                       dtype=torch.int32, device=self.device)
+        self._per = nat.ReplayPerPtrs(self.tickets.data_ptr(), self.tree.data_ptr(),
+                                      self.max_ticket.data_ptr(), F, 0)
+
+    @property
+    def total(self):
+        """The sum of all tickets (``tree[0]``; reads the device)."""
+        return int(self.tree[0].item()) & (2 ** 64 - 1)
+
+    def step(self, env, actions):
+        """The parent's step, plus finenv_replay_per_put: the stored slot's tickets take
+        ``max_ticket``, those of the slot whose observation was just overwritten take 0, and the sums
+        follow."""
+        pos = self.pos
+        ret = super().step(env, actions)
+        nat.check(self._lib.finenv_replay_per_put(
+            C.byref(self._per), self.n_slots, self.num_envs, pos, self.pos, self._stream()), None,
+            "finenv_replay_per_put")
+        return ret
+
+    def _launch_drawn(self, name, smp, bs, ns, idx):
+        fn = "finenv_replay_per_" + name
+        nat.check(getattr(self._lib, fn)(
+            C.byref(self._view), C.byref(self._per), C.c_void_p(self.draw.data_ptr()), self.seed,
+            C.byref(bs), *ns, C.c_void_p(smp.probabilities.data_ptr()), C.c_void_p(idx.data_ptr()),
+            self._stream()), None, fn)
+
+    def update_priorities(self, indices, priorities, shaped=False):
+        """Write priorities back for ``indices`` (int [2, B], e.g. ``buf.last_indices``):
+        ``w = (priorities.abs() + eps) ** alpha`` in torch, or ``priorities`` itself with
+        ``shaped=True``, then finenv_replay_per_update -- tickets, ``max_ticket`` and the sums.  An
+        entry for a slot that holds no complete transition (ticket 0) is dropped.  Duplicate indices
+        with different priorities leave one of them, unspecified which."""
+        import torch
+        idx = self._index_block("update_priorities", indices)
+        p = priorities.to(self.device, torch.float32).reshape(-1)
+        w = (p if shaped else (p.abs() + self.eps) ** self.alpha).contiguous()
+        if w.numel() != idx.shape[1]:
+            raise ValueError("update_priorities: one priority per index pair")
+        nat.check(self._lib.finenv_replay_per_update(
+            C.byref(self._per), self.n_slots, self.num_envs, C.c_void_p(idx.data_ptr()),
+            C.c_void_p(w.data_ptr()), int(w.numel()), self._stream()), None,
+            "finenv_replay_per_update")
+
+    def importance_weights(self, probabilities, beta):
+        """``(n_valid * E * P) ** -beta`` divided by its batch maximum (float32, formed in float64), in
+        torch from the device head word (so it is right inside a replayed graph)."""
+        import torch
+        n = self.head[1].to(torch.float64) * float(self.num_envs)
+        w = (n * probabilities.to(torch.float64)) ** (-float(beta))
+        return (w / w.max()).to(torch.float32)
+
+    def find(self, u):
+        """The pairs (int32 [2, B]) of the leaves selected by ``u``: uint64 values as a device tensor
+        of dtype uint64 or int64 (the bit pattern), taken as ``min(u, total - 1)``."""
+        import torch
+        u = u.to(self.device).contiguous().reshape(-1)
+        if u.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or u.numel() < 1:
+            raise ValueError("find: u must be a non-empty uint64 / int64 tensor")
+        out = torch.empty(2, u.numel(), dtype=torch.int32, device=self.device)
+        nat.check(self._lib.finenv_replay_per_find(
+            C.byref(self._per), self.n_slots, self.num_envs, C.c_void_p(u.data_ptr()), int(u.numel()),
+            C.c_void_p(out.data_ptr()), self._stream()), None, "finenv_replay_per_find")
+        return out
+
+    def rebuild(self):
+        """Recompute every tree node from ``tickets`` as they are (after restoring them)."""
+        nat.check(self._lib.finenv_replay_per_rebuild(
+            C.byref(self._per), self.n_slots, self.num_envs, self._stream()), None,
+            "finenv_replay_per_rebuild")

@@ -178,7 +178,7 @@ int         finenv_abi_version(void);
 /* sizeof() of the ABI structs as the library was compiled (0 = finenv_stock_config,
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
  * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio,
- * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep; 22 and 25, like 18, stay invalid as the ends of earlier lists):
+ * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep, 28 = finenv_replay_per; 22, 25 and 27, like 18, stay invalid as the ends of earlier lists):
  * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
  * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
  * bindings probe it as such. */
@@ -850,6 +850,98 @@ int finenv_replay_sample_nstep(const finenv_replay_view *view, const int32_t *he
 int finenv_replay_gather_nstep(const finenv_replay_view *view, const int32_t *indices,
                                const finenv_replay_batch *batch, const finenv_replay_nstep *nstep,
                                void *stream);
+
+/* Prioritised replay.  Per-transition priorities beside the ring, a sum tree kept consistent on the
+ * device, a proportional draw fused into the sampler's launch (one-step and n-step) and the priority
+ * write-back.  Everything is integer, so nothing depends on summation order and
+ * tests/replay_per_model.py restates it exactly.
+ *
+ * Tickets.  A priority is stored as an unsigned 32-bit fixed-point ticket.  For a shaped priority w
+ * (float32, the caller's (|delta| + eps)^alpha -- the powers stay with the caller: powf is not
+ * bit-reproducible) and F = frac_bits in [0, 31]:
+ *   q = 1                                          if !(w > 0)   (NaN, zero, negatives)
+ *   q = min(max(rint((double)w * 2^F), 1), 2^32 - 1)   otherwise (exact in double; ties to even)
+ * so a stored transition always has q >= 1 and stays drawable, and q == 0 means, and only means,
+ * "this slot holds no complete transition".  The resolution floor is 2^-F: a priority below it draws
+ * as if it were 2^-F.  Leaves are tickets[S][E] in the ring's order, leaf = s * E + e, N = S * E
+ * <= 2^31 - 1.
+ *
+ * Tree.  Fan-out 64.  Level 1 has n_1 = ceil(N / 64) nodes over the leaves, level k has
+ * ceil(n_{k-1} / 64); the last level is the one with a single node.  Every node is the exact uint64
+ * sum of its children; children past the end count as 0.  Levels are stored top-down: tree[0] is the
+ * root (the total), then the level below it, and so on; level 1 comes last.  N <= 64 is one word;
+ * N = 4617 is 1 + 2 + 73 = 76 words.
+ *
+ * Selection.  With c = the inclusive prefix sums of the tickets in leaf order, a value u in
+ * [0, total) selects the one leaf with c[leaf-1] <= u < c[leaf] (NumPy: searchsorted(c, u,
+ * side="right")): never a leaf at 0.  u >= total is taken as total - 1; total == 0 gives pair (0, 0).
+ *
+ * Validity lives in the tickets: the prioritised draw does not read n_valid.  When a step is stored
+ * in slot pos (finenv_replay_per_put), the E leaves of slot pos take *max_ticket (a value of 0 is
+ * taken as 1) -- new transitions enter at the largest priority seen -- and the E leaves of slot
+ * pos_next take 0: its observation has just been overwritten (the slot the uniform draw excludes by
+ * the head rule).  Unfilled slots are 0 from allocation.
+ *
+ * Draw.  For sample i the Philox4x32-10 counter (i, 0, draw lo, draw hi) and key of the uniform
+ * draw; with its first two words x = (x0 << 32) | x1 and u = umul64hi(x, total), the leaf is selected
+ * as above and the outputs are gathered exactly as finenv_replay_gather gathers them (n-step: by the
+ * n-step rule above, unchanged, the horizon measured from nstep->head).
+ * probabilities_out[b] = (float)((double)q / (double)total), q the leaf's ticket; may be NULL.
+ *
+ * Tree words are device data and are not trusted: the descent clamps the child to 63 and every index
+ * to its level, the leaf to N - 1.  A tree that disagrees with its leaves gives wrong samples, never
+ * an address outside the ring.
+ *
+ * Every entry point takes the caller's stream, allocates nothing, does not synchronise and is a fixed
+ * number of launches that depends only on (S, E): one per tree level for rebuild; one plus one per
+ * level above the first for put and update; one for find and for each sample form.  Arguments are
+ * checked on the host before any HIP call: NULL pointers, frac_bits outside [0, 31], S < 2, E < 1,
+ * S * E > 2^31 - 1, batch_size < 1, pos or pos_next outside [0, S) return FINENV_ERR_INVALID. */
+typedef struct finenv_replay_per {       /* finenv_struct_size 28 (27 stays invalid)            */
+    uint32_t *tickets;                   /* [S][E] leaves                                       */
+    uint64_t *tree;                      /* finenv_replay_per_tree_words(S * E) words           */
+    uint32_t *max_ticket;                /* one device word; a value of 0 is taken as 1         */
+    int32_t   frac_bits;                 /* 0 .. 31                                             */
+    int32_t   reserved0;                 /* 0                                                   */
+} finenv_replay_per;
+
+/* Host only: the words of the tree over n_leaves leaves; -1 for n_leaves < 1 or > 2^31 - 1. */
+int64_t finenv_replay_per_tree_words(int64_t n_leaves);
+
+/* Make every node the sum of its children from the leaves as they are (restoring state). */
+int finenv_replay_per_rebuild(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                              void *stream);
+
+/* The fill rule above for the step stored in slot pos, by value like finenv_replay_put, and the sums
+ * repaired.  pos_next == pos zeroes nothing. */
+int finenv_replay_per_put(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs, int32_t pos,
+                          int32_t pos_next, void *stream);
+
+/* The write-back.  indices int32 [2][B] (clamped as finenv_replay_gather clamps), weights float32 [B]
+ * (shaped priorities w).  A leaf at 0 stays 0: an update for an excluded or unfilled slot is dropped;
+ * any other leaf takes its entry's ticket.  *max_ticket = max(*max_ticket, every entry's ticket),
+ * dropped entries included.  Afterwards every node equals the sum of its children.  Duplicate
+ * indices with different weights: the leaf ends as one of them, unspecified which, and the tree is
+ * still consistent with the leaves (the sampler's own duplicates are the same transition and
+ * normally carry the same value). */
+int finenv_replay_per_update(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                             const int32_t *indices, const float *weights, int32_t batch_size,
+                             void *stream);
+
+/* The descent alone: u uint64 [B] on the device -> the pairs of the selected leaves, int32 [2][B]
+ * (for a caller with its own, e.g. stratified, u). */
+int finenv_replay_per_find(const finenv_replay_per *per, int32_t n_slots, int32_t n_envs,
+                           const uint64_t *u, int32_t batch_size, int32_t *indices_out, void *stream);
+
+/* One launch each: draw, descend, gather (S and E are the view's).  probabilities_out float32 [B] or
+ * NULL; indices_out int32 [2][B] or NULL.  The n-step form reads nstep->head for the horizon. */
+int finenv_replay_per_sample(const finenv_replay_view *view, const finenv_replay_per *per,
+                             const int64_t *draw, uint64_t seed, const finenv_replay_batch *batch,
+                             float *probabilities_out, int32_t *indices_out, void *stream);
+int finenv_replay_per_sample_nstep(const finenv_replay_view *view, const finenv_replay_per *per,
+                                   const int64_t *draw, uint64_t seed,
+                                   const finenv_replay_batch *batch, const finenv_replay_nstep *nstep,
+                                   float *probabilities_out, int32_t *indices_out, void *stream);
 
 /* =====================================================================================
  * Array-state StockTradingEnv (finrl/meta/env_stock_trading/env_stocktrading_np.py:8-169),
