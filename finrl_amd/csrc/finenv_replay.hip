@@ -3,11 +3,12 @@
 // take the caller's, then gather obs / next_obs / action / reward / done rows into a batch.  Contract:
 // include/finenv.h.  Pure data movement, HBM/L2-bound: 2 * (4D read + 4D write) + 8A + 21 bytes per
 // sample (indices_out: + 8).  No LDS, no barrier; every offset is 64-bit (the ring may pass 4 GiB).
-// The n-step form (replay_nstep_kernel) adds the h reward / done words of a pair's window and the
-// discount: + 5h + 4 bytes per sample, and a second round trip for the late next-observation row.
-// Prioritised replay (per_*, replay_per_*_kernel) keeps uint32 tickets and a fan-out-64 tree of exact
-// uint64 sums beside the ring and puts the proportional draw, one round trip per tree level, in front
-// of the same two samplers.
+// The n-step form (nstep_rows) adds the h reward / done words of a pair's window and the discount:
+// + 5h + 4 bytes per sample, and a second round trip for the late next-observation row.
+// Prioritised replay (per_*) keeps uint32 tickets and a fan-out-64 tree of exact uint64 sums beside
+// the ring; its proportional draw costs one round trip per tree level.
+// One sampler kernel, replay_sample_kernel<G, V, Draw, Args>: a draw source (UniformDraw, CallerDraw
+// or TicketDraw) yields the pair, the return form (Args: GatherArgs or NStepArgs) moves the rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,15 +35,65 @@ __global__ void __launch_bounds__(256) replay_put_kernel(const V *src, V *dst, i
     }
 }
 
+// The row arguments and the words a draw reads (the parent layout of the kernel's first argument: the
+// scalar argument loads of every form stay where they were)
 struct GatherArgs {
     finenv_replay_view v;
     finenv_replay_batch o;
-    const int32_t *head;          // DRAW: {pos, n_valid}
-    const int64_t *draw;          // DRAW: the draw number
-    const int32_t *indices;       // !DRAW: [2][B]
-    int32_t *indices_out;         // DRAW: [2][B] or NULL
+    const int32_t *head;          // {pos, n_valid}: the uniform draw, and the age of the n-step forms
+    const int64_t *draw;          // the draw number of the uniform and the ticket draw
+    const int32_t *indices;       // the caller's pairs [2][B]
+    int32_t *indices_out;         // the drawn pairs [2][B] or NULL
     uint32_t seed_lo, seed_hi;
 };
+
+// This thread's lane in its group of G and the sample b of that group: 256 / G samples per block
+template <int G>
+__device__ __forceinline__ long long group_sample(int &lane)
+{
+    lane = (int)threadIdx.x & (G - 1);
+    return (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
+}
+
+// __ballot(pred) of this thread's group of G lanes, in bits 0 .. G-1
+template <int G>
+__device__ __forceinline__ unsigned long long group_ballot(bool pred)
+{
+    const int gshift = ((int)threadIdx.x & 63) & ~(G - 1);
+    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
+    return (__ballot(pred) >> gshift) & gmask;
+}
+
+// 64 values -> op over all of them, in every lane
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T x, Op op)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x = op(x, (T)__shfl_xor(x, d, 64));
+    return x;
+}
+
+// A caller's (slot, env), clamped into the ring
+__device__ __forceinline__ void clamp_pair(int &s, int &e, int S, int E)
+{
+    s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
+    e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+}
+
+// (pos - 1 - x) mod S: the age of slot x, the stored steps between it and the newest -- and, the map
+// being its own inverse, the slot of age x
+__device__ __forceinline__ int steps_behind(int32_t pos, long long x, int S)
+{
+    const long long q = ((long long)pos - 1 - x) % S;
+    return (int)(q < 0 ? q + S : q);
+}
+
+// leaf s * E + e of the ticket array -> s, e
+__device__ __forceinline__ void leaf_pair(long long leaf, int E, int &s, int &e)
+{
+    s = (int)(leaf / E);
+    e = (int)(leaf - (long long)s * E);
+}
 
 // Philox4x32-10 (Salmon et al., SC'11; Random123): counter c[4], key k[2] -> first two output words
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
@@ -63,42 +114,85 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     x1 = c1;
 }
 
-// The clamped (slot, env) of sample b -> s, e; returns its age, the stored steps between it and the
-// newest.  DRAW: the Philox words give an age below n_valid (not trusted: clamped into [1, S - 1]) and
-// an env below E; the slot is (pos - 1 - age) mod S, never slot pos of a full ring.  !DRAW: the
-// caller's indices, clamped, and the age from (pos - 1 - s) mod S.  G = 64: (slot, env) is made scalar,
-// so the row bases are.  A kernel that ignores the age loses it and, !DRAW, the head load when compiled.
-template <int G, bool DRAW>
-__device__ __forceinline__ int sample_pair(const GatherArgs &a, long long b, int &s, int &e)
+// The random words of sample b: Philox counter (b, 0, draw number), key = the seed
+__device__ __forceinline__ void sample_words(const GatherArgs &a, long long b, uint32_t &x0, uint32_t &x1)
 {
-    const int S = a.v.n_slots, E = a.v.n_envs;
-    const int32_t pos = a.head[0];
-    long long age;
-    if (DRAW) {
+    const uint64_t n = (uint64_t)*a.draw;
+    philox4x32_10((uint32_t)b, 0u, (uint32_t)n, (uint32_t)(n >> 32), a.seed_lo, a.seed_hi, x0, x1);
+}
+
+// (s, e) of sample b -> the index block ([2][B] or NULL)
+__device__ __forceinline__ void store_pair(int32_t *out, long long b, int B, int s, int e)
+{
+    if (out != nullptr) {
+        out[b] = s;
+        out[(long long)B + b] = e;
+    }
+}
+
+// What a draw source yields for sample b: the clamped pair, the age of its slot where the n-step form
+// asks (NSTEP), and the probability of a ticket draw.
+struct Drawn {
+    int s, e, age;
+    float prob;
+};
+
+// G = 64: (slot, env) is made scalar, so the row bases are
+template <int G>
+__device__ __forceinline__ void scalar_pair(Drawn &d)
+{
+    if (G == 64) {
+        d.s = __builtin_amdgcn_readfirstlane(d.s);
+        d.e = __builtin_amdgcn_readfirstlane(d.e);
+    }
+}
+
+// The uniform draw from the head words {pos, n_valid}: the Philox words give an age below n_valid (not
+// trusted: clamped into [1, S - 1]) and an env below E; the slot is the one of that age, never slot
+// pos of a full ring.  Publishes the pair to indices_out -- in the one-step form straight away: held
+// across the row loads it costs the groups below a wave 2 VGPRs.
+struct UniformDraw {
+    template <int G, bool NSTEP>
+    __device__ __forceinline__ Drawn pair(const GatherArgs &a, long long b, int lane) const
+    {
+        const int S = a.v.n_slots, B = a.o.batch_size;
+        const int32_t pos = a.head[0];
         int32_t nv = a.head[1];
         nv = nv < 1 ? 1 : (nv > S - 1 ? S - 1 : nv);
-        const uint64_t draw = (uint64_t)*a.draw;
         uint32_t x0, x1;
-        philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi,
-                      x0, x1);
-        age = (long long)__umulhi(x0, (uint32_t)nv);
-        const long long q = ((long long)pos - 1 - age) % S;
-        s = (int)(q < 0 ? q + S : q);
-        e = (int)__umulhi(x1, (uint32_t)E);
-    } else {
-        s = a.indices[b];
-        e = a.indices[(long long)a.o.batch_size + b];
-        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
-        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
-        const long long q = ((long long)pos - 1 - s) % S;
-        age = q < 0 ? q + S : q;
+        sample_words(a, b, x0, x1);
+        Drawn d = {};
+        const uint32_t age = __umulhi(x0, (uint32_t)nv);
+        d.age = (int)age;
+        d.s = steps_behind(pos, age, S);
+        d.e = (int)__umulhi(x1, (uint32_t)a.v.n_envs);
+        scalar_pair<G>(d);
+        if (!NSTEP && lane == 0) store_pair(a.indices_out, b, B, d.s, d.e);
+        return d;
     }
-    if (G == 64) {
-        s = __builtin_amdgcn_readfirstlane(s);
-        e = __builtin_amdgcn_readfirstlane(e);
+    template <bool NSTEP>
+    __device__ __forceinline__ void publish(const GatherArgs &a, const Drawn &d, long long b) const
+    {
+        if (NSTEP) store_pair(a.indices_out, b, a.o.batch_size, d.s, d.e);
     }
-    return (int)age;
-}
+};
+
+// The caller's pairs, clamped; head is read only for the age.  Nothing to publish.
+struct CallerDraw {
+    template <int G, bool NSTEP>
+    __device__ __forceinline__ Drawn pair(const GatherArgs &a, long long b, int) const
+    {
+        Drawn d = {};
+        d.s = a.indices[b];
+        d.e = a.indices[(long long)a.o.batch_size + b];
+        clamp_pair(d.s, d.e, a.v.n_slots, a.v.n_envs);
+        if (NSTEP) d.age = steps_behind(a.head[0], d.s, a.v.n_slots);
+        scalar_pair<G>(d);
+        return d;
+    }
+    template <bool NSTEP>
+    __device__ __forceinline__ void publish(const GatherArgs &, const Drawn &, long long) const {}
+};
 
 // What the kernels' up-front loads leave: the units past 2G of both rows and the action floats past G,
 // behind the wave's stores (none of the shipped env shapes at their G has either).
@@ -114,13 +208,13 @@ __device__ __forceinline__ void copy_rest(const V *src0, const V *src1, V *dst0,
     for (int k = lane + G; k < A; k += G) aout[k] = arow[k];
 }
 
-// The one-step sampler: one sample per group of G lanes (G = 64: per wave).  A row is `nu` units of V
+// The one-step rows: one sample per group of G lanes (G = 64: per wave).  A row is `nu` units of V
 // (f4 where pitches and bases allow, else float) plus, for f4, a tail of D % 4 floats moved as dwords:
 // columns D .. pitch-1 of the outputs are never written.  The first two units per lane of both rows,
 // the action row's first unit, the tail and the reward / done words are all loaded before the first
 // store -- a load behind the wave's own stores waits for them.  The two rows alternate
 // unit by unit: one row after the other measured 4 % slower (profiles/replay_share.md).
-// `last` runs on the group's lane 0 with the reward / done stores: what else a kernel stores per sample.
+// `last` runs on the group's lane 0 with the reward / done stores: what the draw publishes.
 template <int G, typename V, typename Last>
 __device__ __forceinline__ void gather_rows(const GatherArgs &a, long long b, int lane, int s, int e,
                                             const Last &last)
@@ -183,35 +277,16 @@ __device__ __forceinline__ void gather_rows(const GatherArgs &a, long long b, in
     copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
 }
 
-template <int G, typename V, bool DRAW>
-__global__ void __launch_bounds__(256) replay_gather_kernel(const GatherArgs a)
-{
-    constexpr int PER_BLOCK = 256 / G;
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
-
-    int s, e;
-    sample_pair<G, DRAW>(a, b, s, e);             // the age is not needed: one step ends at the newest
-    if (DRAW && a.indices_out != nullptr && lane == 0) {
-        a.indices_out[b] = s;
-        a.indices_out[(long long)B + b] = e;
-    }
-    gather_rows<G, V>(a, b, lane, s, e, [] {});
-}
-
-struct NStepArgs {
-    GatherArgs g;                 // head is read in both forms: the horizon ends at the newest step
+struct NStepArgs : GatherArgs {
     float *discounts;             // [B]
     int32_t *steps;               // [B] or NULL
     int32_t n_steps;
     float gamma;
 };
 
-// The n-step sampler (contract: include/finenv.h, "n-step returns"): sample_pair, copy_rest and the
-// units per lane are those of replay_gather_kernel; what differs is that the next-observation row is
-// known only after the return's length m.  Round trip 1: lane i of the group loads the reward and done
+// The n-step rows (contract: include/finenv.h, "n-step returns"): copy_rest and the units per lane are
+// those of gather_rows; what differs is that the next-observation row is known only after the return's
+// length m.  Round trip 1: lane i of the group loads the reward and done
 // words of step i of the window (slot (s+i) mod S, i < h = min(age + 1, n)), beside the observation
 // row of s and the action row.  Then m by a ballot over the group's done words, the sum in the stated
 // order (every lane of the group forms it, from shuffled rewards), round trip 2 for the row of slot
@@ -224,7 +299,7 @@ template <int G, typename V, typename Last>
 __device__ __forceinline__ void nstep_rows(const NStepArgs &na, long long b, int lane, int s, int e,
                                            int age, const Last &last)
 {
-    const GatherArgs &a = na.g;
+    const GatherArgs &a = na;
     constexpr int VW = (int)(sizeof(V) / sizeof(float));
     const int S = a.v.n_slots, E = a.v.n_envs, D = a.v.obs_dim, A = a.v.action_dim;
     const int n = na.n_steps;
@@ -261,8 +336,6 @@ __device__ __forceinline__ void nstep_rows(const NStepArgs &na, long long b, int
         dn = a.v.dones[w];
     }
 
-    const int gshift = ((int)threadIdx.x & 63) & ~(G - 1);
-    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
     double acc = 0.0;
     float g = 1.0f, dlast = 0.0f;
     int m = 0;
@@ -280,7 +353,7 @@ __device__ __forceinline__ void nstep_rows(const NStepArgs &na, long long b, int
             }
         }
         const int cnt = h - base < G ? h - base : G;       // steps of the window in this chunk
-        const unsigned long long hit = (__ballot(dn != 0) >> gshift) & gmask;
+        const unsigned long long hit = group_ballot<G>(dn != 0);
         const int k = hit ? __builtin_ctzll(hit) : cnt - 1; // the chunk's last step of the return
         const int lim = n - base < G ? n - base : G;
         for (int i = 0; i < lim; ++i) {
@@ -331,26 +404,6 @@ __device__ __forceinline__ void nstep_rows(const NStepArgs &na, long long b, int
     copy_rest<G, V>(src0, src1, dst0, dst1, nu, arow, aout, A, lane);
 }
 
-template <int G, typename V, bool DRAW>
-__global__ void __launch_bounds__(256) replay_nstep_kernel(const NStepArgs na)
-{
-    const GatherArgs &a = na.g;
-    constexpr int PER_BLOCK = 256 / G;
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * PER_BLOCK + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
-
-    int s, e;
-    const int age = sample_pair<G, DRAW>(a, b, s, e);
-    nstep_rows<G, V>(na, b, lane, s, e, age, [&] {
-        if (DRAW && a.indices_out != nullptr) {   // with the other stores, not ahead of the loads
-            a.indices_out[b] = s;
-            a.indices_out[(long long)B + b] = e;
-        }
-    });
-}
-
 // ------------------------------------------------------------------------------------------------
 // Prioritised replay (contract: include/finenv.h, "Prioritised replay"): uint32 tickets per
 // transition, a fan-out-64 tree of exact uint64 sums stored top-down, and the descent that turns a
@@ -380,9 +433,7 @@ __device__ __forceinline__ uint32_t per_ticket(float w, int frac_bits)
 // 64 values -> their sum in every lane
 __device__ __forceinline__ uint64_t wave_sum(uint64_t x)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += (uint64_t)__shfl_xor((unsigned long long)x, d, 64);
-    return x;
+    return (uint64_t)wave_reduce((unsigned long long)x, [](auto p, auto q) { return p + q; });
 }
 
 // One level of sums: a wave per node, out[node] = the sum of in[64 node .. 64 node + 63] below n_in.
@@ -436,8 +487,7 @@ __global__ void __launch_bounds__(256) per_update_kernel(uint32_t *tickets, uint
     if (i < B) {
         q = per_ticket(weights[i], frac_bits);
         int s = indices[i], e = indices[(long long)B + i];
-        s = s < 0 ? 0 : (s > S - 1 ? S - 1 : s);
-        e = e < 0 ? 0 : (e > E - 1 ? E - 1 : e);
+        clamp_pair(s, e, S, E);
         const long long leaf = (long long)s * E + e;
         if (tickets[leaf] != 0u) {
             const uint32_t old = atomicExch(&tickets[leaf], q);
@@ -445,12 +495,8 @@ __global__ void __launch_bounds__(256) per_update_kernel(uint32_t *tickets, uint
                       (unsigned long long)((long long)q - (long long)old));
         }
     }
-    uint32_t top = q;                              // one atomicMax per wave
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)top, d, 64);
-        top = o > top ? o : top;
-    }
+    // one atomicMax per wave
+    const uint32_t top = wave_reduce(q, [](uint32_t p, uint32_t o) { return o > p ? o : p; });
     if (((int)threadIdx.x & 63) == 0 && top != 0u) atomicMax(max_ticket, top);
 }
 
@@ -465,8 +511,6 @@ template <int G>
 __device__ __forceinline__ long long per_descend(const PerTree &t, uint64_t u, int lane, uint32_t &q)
 {
     constexpr int K = 64 / G;
-    const int gshift = ((int)threadIdx.x & 63) & ~(G - 1);
-    const unsigned long long gmask = G == 64 ? ~0ull : (1ull << (G & 63)) - 1ull;
     long long node = 0;
     uint64_t val = 0;
     for (int k = t.levels; k >= 1; --k) {
@@ -492,7 +536,7 @@ __device__ __forceinline__ long long per_descend(const PerTree &t, uint64_t u, i
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             const bool le = before + c[i] <= u && lane * K + i < 63;
-            child += __popcll((__ballot(le) >> gshift) & gmask);
+            child += __popcll(group_ballot<G>(le));
         }
         uint64_t lo = before, hi = before + c[0];             // of child (child % K) of this lane
 #pragma unroll
@@ -518,8 +562,8 @@ __global__ void __launch_bounds__(256) per_find_kernel(const PerTree t, int E, c
                                                        int B, int32_t *indices_out)
 {
     constexpr int G = 16;
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
+    int lane;
+    const long long b = group_sample<G>(lane);
     if (b >= B) return;
     const uint64_t total = t.tree[0];
     uint64_t u = u_in[b];
@@ -528,114 +572,80 @@ __global__ void __launch_bounds__(256) per_find_kernel(const PerTree t, int E, c
     long long leaf = per_descend<G>(t, u, lane, q);
     leaf = total == 0 ? 0 : leaf;
     if (lane == 0) {
-        const int s = (int)(leaf / E);
+        int s, e;
+        leaf_pair(leaf, E, s, e);
         indices_out[b] = s;
-        indices_out[(long long)B + b] = (int)(leaf - (long long)s * E);
+        indices_out[(long long)B + b] = e;
     }
 }
 
-struct PerDraw {
+// The ticket draw: the uniform draw's Philox words, u = umul64hi(x0:x1, total), the descent -> s, e
+// and the probability q / total; head is read only for the age.  Publishes the probability ([B] or
+// NULL) and the pair.
+struct TicketDraw {
     PerTree t;
-    float *probabilities;         // [B] or NULL
-};
-
-// The prioritised draw of sample b: the uniform draw's Philox counter and key, u = umul64hi(x0:x1,
-// total), the descent -> s, e and the probability q / total.
-template <int G>
-__device__ __forceinline__ void per_pair(const GatherArgs &a, const PerTree &t, long long b, int lane,
-                                         int &s, int &e, float &prob)
-{
-    const uint64_t total = t.tree[0];
-    const uint64_t draw = (uint64_t)*a.draw;
-    uint32_t x0, x1;
-    philox4x32_10((uint32_t)b, 0u, (uint32_t)draw, (uint32_t)(draw >> 32), a.seed_lo, a.seed_hi, x0, x1);
-    const uint64_t u = __umul64hi(((uint64_t)x0 << 32) | x1, total);   // < total, or 0 == total
-    uint32_t q;
-    long long leaf = per_descend<G>(t, u, lane, q);
-    leaf = total == 0 ? 0 : leaf;
-    prob = (float)((double)q / (double)total);
-    s = (int)(leaf / a.v.n_envs);
-    e = (int)(leaf - (long long)s * a.v.n_envs);
-    if (G == 64) {
-        s = __builtin_amdgcn_readfirstlane(s);
-        e = __builtin_amdgcn_readfirstlane(e);
+    float *probabilities;
+    template <int G, bool NSTEP>
+    __device__ __forceinline__ Drawn pair(const GatherArgs &a, long long b, int lane) const
+    {
+        const uint64_t total = t.tree[0];
+        uint32_t x0, x1;
+        sample_words(a, b, x0, x1);
+        const uint64_t u = __umul64hi(((uint64_t)x0 << 32) | x1, total);   // < total, or 0 == total
+        uint32_t q;
+        long long leaf = per_descend<G>(t, u, lane, q);
+        leaf = total == 0 ? 0 : leaf;
+        Drawn d = {};
+        d.prob = (float)((double)q / (double)total);
+        leaf_pair(leaf, a.v.n_envs, d.s, d.e);
+        scalar_pair<G>(d);
+        if (NSTEP) d.age = steps_behind(a.head[0], d.s, a.v.n_slots);
+        if (NSTEP && G == 64) d.age = __builtin_amdgcn_readfirstlane(d.age);
+        return d;
     }
+    template <bool NSTEP>
+    __device__ __forceinline__ void publish(const GatherArgs &a, const Drawn &d, long long b) const
+    {
+        if (probabilities != nullptr) probabilities[b] = d.prob;
+        store_pair(a.indices_out, b, a.o.batch_size, d.s, d.e);
+    }
+};
+
+// The sampler: one sample per group of G lanes, its pair from the draw source, its rows by the return
+// form of Args (GatherArgs: one step, which ends at the newest and needs no age; NStepArgs).  The draw
+// publishes with the group's last stores, not ahead of the loads (but see UniformDraw).
+// `more`: the draw source where it holds anything -- an empty one is no kernel argument, so the uniform
+// and caller forms take the argument bytes they always took.
+template <int G, typename V, typename Draw, typename Args, typename... More>
+__global__ void __launch_bounds__(256) replay_sample_kernel(const Args args, const More... more)
+{
+    constexpr bool NSTEP = std::is_same<Args, NStepArgs>::value;
+    const Draw draw{more...};
+    const GatherArgs &a = args;
+    int lane;
+    const long long b = group_sample<G>(lane);
+    if (b >= a.o.batch_size) return;
+
+    const Drawn d = draw.template pair<G, NSTEP>(a, b, lane);
+    const auto last = [&] { draw.template publish<NSTEP>(a, d, b); };
+    if constexpr (NSTEP)
+        nstep_rows<G, V>(args, b, lane, d.s, d.e, d.age, last);
+    else
+        gather_rows<G, V>(args, b, lane, d.s, d.e, last);
 }
 
-// The one-step sampler with the prioritised draw; pair and probability go out with the other stores.
-template <int G, typename V>
-__global__ void __launch_bounds__(256) replay_per_gather_kernel(const GatherArgs a, const PerDraw p)
+// One launch of the sampler for lane groups of G and 16-byte (vec) or dword units: 256 / G samples per
+// block, on the device of the batch.  `more`: the draw source, unless it is empty.
+template <typename Draw, typename Args, typename... More>
+int launch_sampler(int G, bool vec, const Args &args, void *stream, const More &...more)
 {
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
-    int s, e;
-    float prob;
-    per_pair<G>(a, p.t, b, lane, s, e, prob);
-    gather_rows<G, V>(a, b, lane, s, e, [&] {
-        if (p.probabilities != nullptr) p.probabilities[b] = prob;
-        if (a.indices_out != nullptr) {
-            a.indices_out[b] = s;
-            a.indices_out[(long long)B + b] = e;
-        }
-    });
-}
-
-// The n-step sampler with the prioritised draw: the age of the drawn slot comes from the head word.
-template <int G, typename V>
-__global__ void __launch_bounds__(256) replay_per_nstep_kernel(const NStepArgs na, const PerDraw p)
-{
-    const GatherArgs &a = na.g;
-    const int lane = (int)threadIdx.x & (G - 1);
-    const long long b = (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
-    const int B = a.o.batch_size;
-    if (b >= B) return;
-    int s, e;
-    float prob;
-    per_pair<G>(a, p.t, b, lane, s, e, prob);
-    const int S = a.v.n_slots;
-    const long long back = ((long long)a.head[0] - 1 - s) % S;
-    int age = (int)(back < 0 ? back + S : back);
-    if (G == 64) age = __builtin_amdgcn_readfirstlane(age);
-    nstep_rows<G, V>(na, b, lane, s, e, age, [&] {
-        if (p.probabilities != nullptr) p.probabilities[b] = prob;
-        if (a.indices_out != nullptr) {
-            a.indices_out[b] = s;
-            a.indices_out[(long long)B + b] = e;
-        }
-    });
-}
-
-// The kernels are function templates: a functor each names the instantiation for the launcher.
-struct GatherKernel {
-    template <int G, typename V, bool DRAW>
-    static constexpr auto get() { return &replay_gather_kernel<G, V, DRAW>; }
-};
-struct NStepKernel {
-    template <int G, typename V, bool DRAW>
-    static constexpr auto get() { return &replay_nstep_kernel<G, V, DRAW>; }
-};
-struct PerGatherKernel {
-    template <int G, typename V, bool>
-    static constexpr auto get() { return &replay_per_gather_kernel<G, V>; }
-};
-struct PerNStepKernel {
-    template <int G, typename V, bool>
-    static constexpr auto get() { return &replay_per_nstep_kernel<G, V>; }
-};
-
-// One launch of K's kernel for lane groups of G and 16-byte (vec) or dword units: 256 / G samples per
-// block, on the device of the batch.  `more`: the kernel's arguments after the first.
-template <typename K, bool DRAW, typename Args, typename... More>
-int launch_sampler(int G, bool vec, const Args &args, const finenv_replay_batch &o, void *stream,
-                   const More &...more)
-{
+    const finenv_replay_batch &o = args.o;
     const finenv_host::DeviceGuard guard(finenv_host::pointer_device(o.observations));
     const auto launch = [&](auto g) {
         constexpr int GG = decltype(g)::value;
         const dim3 grid((unsigned)(((long long)o.batch_size * GG + 255) / 256));
-        const auto kernel = vec ? K::template get<GG, f4, DRAW>() : K::template get<GG, float, DRAW>();
+        const auto kernel = vec ? &replay_sample_kernel<GG, f4, Draw, Args, More...>
+                                : &replay_sample_kernel<GG, float, Draw, Args, More...>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, args, more...);
     };
     switch (G) {
@@ -669,32 +679,25 @@ int gather_group(const finenv_replay_view &v, const finenv_replay_batch &o, bool
     return G;
 }
 
-template <bool DRAW>
-int launch_gather(const GatherArgs &a, void *stream)
-{
-    bool vec = false;
-    const int G = gather_group(a.v, a.o, vec);
-    if (G == 0) return FINENV_ERR_INVALID;
-    return launch_sampler<GatherKernel, DRAW>(G, vec, a, a.o, stream);
-}
-
-// The n-step launch: the gather's checks, then 1 <= n_steps <= S - 1 (a window never reaches round
-// to its own start), gamma finite in [0, 1], head and discounts present.
+// 1 <= n_steps <= S - 1 (a window never reaches round to its own start), gamma finite in [0, 1], head
+// and discounts present.
 bool nstep_ok(const finenv_replay_view &v, const finenv_replay_nstep *ns)
 {
     return ns->head && ns->discounts && ns->n_steps >= 1 && ns->n_steps <= v.n_slots - 1 &&
            ns->gamma >= 0.0f && ns->gamma <= 1.0f;
 }
 
-template <bool DRAW>
-int launch_nstep(GatherArgs a, const finenv_replay_nstep *ns, void *stream)
+// The launch of every sampling call: the gather's checks, those of `ns` where the call is n-step
+// (else NULL), then the one kernel with the call's draw source (`more`: as in launch_sampler).
+template <typename Draw, typename... More>
+int launch_sample(const GatherArgs &a, const finenv_replay_nstep *ns, void *stream, const More &...more)
 {
     bool vec = false;
     const int G = gather_group(a.v, a.o, vec);
-    if (G == 0 || !nstep_ok(a.v, ns)) return FINENV_ERR_INVALID;
-    if (!DRAW) a.head = ns->head;
+    if (G == 0 || (ns && !nstep_ok(a.v, ns))) return FINENV_ERR_INVALID;
+    if (!ns) return launch_sampler<Draw>(G, vec, a, stream, more...);
     const NStepArgs na = {a, ns->discounts, ns->steps, ns->n_steps, ns->gamma};
-    return launch_sampler<NStepKernel, DRAW>(G, vec, na, a.o, stream);
+    return launch_sampler<Draw>(G, vec, na, stream, more...);
 }
 
 // The kernel arguments of a drawn call and of a call with the caller's indices.
@@ -705,9 +708,9 @@ GatherArgs drawn_args(const finenv_replay_view *view, const finenv_replay_batch 
 }
 
 GatherArgs index_args(const finenv_replay_view *view, const finenv_replay_batch *batch,
-                      const int32_t *indices)
+                      const int32_t *head, const int32_t *indices)
 {
-    return {*view, *batch, nullptr, nullptr, indices, nullptr, 0u, 0u};
+    return {*view, *batch, head, nullptr, indices, nullptr, 0u, 0u};
 }
 
 // The level table of n leaves (1 <= n <= 2^31 - 1) -> the number of tree words.
@@ -785,14 +788,15 @@ extern "C" int finenv_replay_sample(const finenv_replay_view *view, const int32_
                                     const finenv_replay_batch *batch, int32_t *indices_out, void *stream)
 {
     if (!view || !batch || !head || !draw) return FINENV_ERR_INVALID;
-    return launch_gather<true>(drawn_args(view, batch, head, draw, seed, indices_out), stream);
+    const GatherArgs a = drawn_args(view, batch, head, draw, seed, indices_out);
+    return launch_sample<UniformDraw>(a, nullptr, stream);
 }
 
 extern "C" int finenv_replay_gather(const finenv_replay_view *view, const int32_t *indices,
                                     const finenv_replay_batch *batch, void *stream)
 {
     if (!view || !batch || !indices) return FINENV_ERR_INVALID;
-    return launch_gather<false>(index_args(view, batch, indices), stream);
+    return launch_sample<CallerDraw>(index_args(view, batch, nullptr, indices), nullptr, stream);
 }
 
 extern "C" int finenv_replay_sample_nstep(const finenv_replay_view *view, const int32_t *head,
@@ -802,7 +806,8 @@ extern "C" int finenv_replay_sample_nstep(const finenv_replay_view *view, const 
                                           void *stream)
 {
     if (!view || !batch || !head || !draw || !nstep) return FINENV_ERR_INVALID;
-    return launch_nstep<true>(drawn_args(view, batch, head, draw, seed, indices_out), nstep, stream);
+    const GatherArgs a = drawn_args(view, batch, head, draw, seed, indices_out);
+    return launch_sample<UniformDraw>(a, nstep, stream);
 }
 
 extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const int32_t *indices,
@@ -810,7 +815,7 @@ extern "C" int finenv_replay_gather_nstep(const finenv_replay_view *view, const 
                                           const finenv_replay_nstep *nstep, void *stream)
 {
     if (!view || !batch || !indices || !nstep) return FINENV_ERR_INVALID;
-    return launch_nstep<false>(index_args(view, batch, indices), nstep, stream);
+    return launch_sample<CallerDraw>(index_args(view, batch, nstep->head, indices), nstep, stream);
 }
 
 extern "C" int64_t finenv_replay_per_tree_words(int64_t n_leaves)
@@ -891,15 +896,11 @@ extern "C" int finenv_replay_per_sample(const finenv_replay_view *view, const fi
                                         const finenv_replay_batch *batch, float *probabilities_out,
                                         int32_t *indices_out, void *stream)
 {
-    PerDraw p;
-    if (!view || !batch || !draw || !per_tree(per, view->n_slots, view->n_envs, p.t))
+    TicketDraw d = {{}, probabilities_out};
+    if (!view || !batch || !draw || !per_tree(per, view->n_slots, view->n_envs, d.t))
         return FINENV_ERR_INVALID;
-    p.probabilities = probabilities_out;
     const GatherArgs a = drawn_args(view, batch, nullptr, draw, seed, indices_out);
-    bool vec = false;
-    const int G = gather_group(a.v, a.o, vec);
-    if (G == 0) return FINENV_ERR_INVALID;
-    return launch_sampler<PerGatherKernel, true>(G, vec, a, a.o, stream, p);
+    return launch_sample<TicketDraw>(a, nullptr, stream, d);
 }
 
 extern "C" int finenv_replay_per_sample_nstep(const finenv_replay_view *view,
@@ -908,14 +909,9 @@ extern "C" int finenv_replay_per_sample_nstep(const finenv_replay_view *view,
                                               const finenv_replay_nstep *nstep, float *probabilities_out,
                                               int32_t *indices_out, void *stream)
 {
-    PerDraw p;
-    if (!view || !batch || !draw || !nstep || !per_tree(per, view->n_slots, view->n_envs, p.t))
+    TicketDraw d = {{}, probabilities_out};
+    if (!view || !batch || !draw || !nstep || !per_tree(per, view->n_slots, view->n_envs, d.t))
         return FINENV_ERR_INVALID;
-    p.probabilities = probabilities_out;
     const GatherArgs a = drawn_args(view, batch, nstep->head, draw, seed, indices_out);
-    bool vec = false;
-    const int G = gather_group(a.v, a.o, vec);
-    if (G == 0 || !nstep_ok(a.v, nstep)) return FINENV_ERR_INVALID;
-    const NStepArgs na = {a, nstep->discounts, nstep->steps, nstep->n_steps, nstep->gamma};
-    return launch_sampler<PerNStepKernel, true>(G, vec, na, a.o, stream, p);
+    return launch_sample<TicketDraw>(a, nstep, stream, d);
 }

@@ -221,11 +221,18 @@ class ReplayBuffer:
     def gather(self, indices, out=None):
         """The batch of caller-chosen transitions: ``indices`` int [2, B] on the device (row 0 slots,
         row 1 envs), clamped into the ring by the kernel.  One launch (finenv_replay_gather)."""
-        idx = self._index_block("gather", indices)
-        smp, bs = self._batch(int(idx.shape[1]), out)[:2]
-        nat.check(self._lib.finenv_replay_gather(
-            C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), self._stream()), None,
-            "finenv_replay_gather")
+        return self._indexed("gather", indices, out)
+
+    def _indexed(self, name, indices, out, nstep=None):
+        """``name`` on the caller's ``indices`` (``nstep`` as in ``_drawn``): the launch and ``last_steps``."""
+        idx = self._index_block(name, indices)
+        smp, bs, _, steps = self._batch(int(idx.shape[1]), out, ReplayBuffer._drawn_kinds[nstep is not None])
+        ns = () if nstep is None else (C.byref(self._nstep_struct(smp, steps, *nstep)),)
+        fn = "finenv_replay_" + name
+        nat.check(getattr(self._lib, fn)(
+            C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), *ns, self._stream()), None, fn)
+        if nstep is not None:
+            self.last_steps = steps
         return smp
 
     # ------------------------------------------------------------------ n-step returns
@@ -260,14 +267,7 @@ class ReplayBuffer:
         ``sample_nstep`` with the horizon measured from the device head.  One launch
         (finenv_replay_gather_nstep); ``buf.last_steps`` holds m.  ``n_steps`` and ``gamma`` are
         by-value launch arguments, as in ``sample_nstep``."""
-        idx = self._index_block("gather_nstep", indices)
-        smp, bs, _, steps = self._batch(int(idx.shape[1]), out, NStepReplayBufferSamples)
-        ns = self._nstep_struct(smp, steps, n_steps, gamma)
-        nat.check(self._lib.finenv_replay_gather_nstep(
-            C.byref(self._view), C.c_void_p(idx.data_ptr()), C.byref(bs), C.byref(ns),
-            self._stream()), None, "finenv_replay_gather_nstep")
-        self.last_steps = steps
-        return smp
+        return self._indexed("gather_nstep", indices, out, (n_steps, gamma))
 
 
 class PrioritizedReplayBuffer(ReplayBuffer):

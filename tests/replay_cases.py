@@ -1,5 +1,5 @@
-"""Shared by the replay buffer's GPU tests (tests/test_gpu_replay.py, tests/test_gpu_replay_nstep.py):
-the coded ring, the head setter, poisoned caller outputs and the host copy of a ring."""
+"""Shared by the replay buffer's GPU tests (tests/test_gpu_replay*.py): the coded ring, the head setter,
+poisoned caller outputs, the host copy of a ring, the small crypto env and the batch comparison."""
 import numpy as np
 import pytest
 
@@ -64,3 +64,52 @@ def outs(B, D, A, kind, n_fields):
 
 def host_ring(buf):
     return tuple(x.cpu().numpy() for x in (buf.obs, buf.actions, buf.rewards, buf.dones))
+
+
+def per_ring(S, E, D, P, A, seed=0, ring_seed=None):
+    """coded_ring's contents in a PrioritizedReplayBuffer, plus the host copies."""
+    from finrl_amd import PrioritizedReplayBuffer
+    src, host = coded_ring(S, E, D, P, A, ring_seed=ring_seed)
+    buf = PrioritizedReplayBuffer(S, E, D, A, obs_pitch=P, seed=seed)
+    for name in ("_obs_buf", "actions", "rewards", "dones"):
+        getattr(buf, name).copy_(getattr(src, name))
+    return buf, host
+
+
+def random_tickets(S, E, seed):
+    """uint32 [S, E]: a third zeros, some at 1 and at 2^32 - 1, the rest anywhere."""
+    rng = np.random.default_rng(seed)
+    t = rng.integers(1, 2 ** 32, (S, E), dtype=np.uint64)
+    kind = rng.integers(0, 6, (S, E))
+    t[kind < 2] = 0
+    t[kind == 2] = 2 ** 32 - 1
+    t[kind == 3] = 1
+    t.reshape(-1)[rng.integers(0, S * E)] = 12345          # never all zero
+    return t.astype(np.uint32)
+
+
+def set_tickets(buf, t):
+    buf.tickets.copy_(torch.from_numpy(np.ascontiguousarray(t).view(np.int32)))
+    buf.rebuild()
+
+
+def crypto_env(E, auto_reset=True):
+    """VecCryptoEnv on a 7-row panel of 3 coins: episodes end inside a ring of a few slots."""
+    from finrl_amd.vec_crypto import VecCryptoEnv
+    rng = np.random.default_rng(1)
+    T, N, W = 7, 3, 4
+    price = 10.0 ** rng.uniform(0, 3, N) * np.exp(np.cumsum(rng.normal(0, 5e-3, (T, N)), axis=0))
+    cfg = {"price_array": price, "tech_array": rng.normal(0, 3000, (T, W))}
+    return VecCryptoEnv(cfg, E, lookback=1, auto_reset=auto_reset)
+
+
+def assert_batch(smp, want, tag, steps=None):
+    """The fields of a samples namedtuple of any kind (the five, then discounts and / or probabilities
+    where it has them) and, where given, the steps block after them, against ``want`` in that order:
+    dtype, shape and every value."""
+    got = tuple(smp) + (() if steps is None else (steps,))
+    assert len(want) == len(got), f"{tag}: {len(want)} expected fields for {len(got)}"
+    for name, g, w in zip(smp._fields + ("steps",), got, want):
+        g = g.cpu().numpy()
+        assert g.dtype == w.dtype and g.shape == w.shape, f"{name} {tag}: {g.dtype}{g.shape}"
+        np.testing.assert_array_equal(g, w, err_msg=f"{name} {tag}")

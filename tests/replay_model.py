@@ -49,3 +49,15 @@ def lookup(obs, actions, rewards, dones, pairs):
     s, e = np.asarray(pairs[0], dtype=np.int64), np.asarray(pairs[1], dtype=np.int64)
     return (obs[s, e], actions[s, e], obs[(s + 1) % S, e],
             dones[s, e].astype(np.float32)[:, None], rewards[s, e][:, None])
+
+
+def gather_group(D, view_pitch, out_pitch, bases):
+    """(lanes per sample, bytes per unit) the sampler takes for rows of D floats: 16-byte units when
+    D >= 4, both pitches are multiples of 4 floats and the three observation bases are 16-byte
+    aligned, else dwords; the lanes are the smallest power of two in [4, 64] with 2 G >= units."""
+    vec = D >= 4 and view_pitch % 4 == 0 and out_pitch % 4 == 0 and all(b % 16 == 0 for b in bases)
+    units = (D + 3) // 4 if vec else D
+    G = 4
+    while G < 64 and 2 * G < units:
+        G *= 2
+    return G, 16 if vec else 4

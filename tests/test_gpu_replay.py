@@ -7,15 +7,10 @@ import numpy as np
 import pytest
 
 import replay_model as rm
-from replay_cases import POISON, coded_ring, host_ring, need_gpu, outs, set_head
+from replay_cases import POISON, assert_batch, coded_ring, crypto_env, host_ring, need_gpu, outs, set_head
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def _assert_batch(smp, want, tag):
-    for name, g, w in zip(smp._fields, smp, want):
-        np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=f"{name} {tag}")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -42,12 +37,12 @@ def test_gather_equals_model(D, P):
                     idx = torch.from_numpy(pairs).cuda()
                     tag = f"S={S} E={E} A={A} B={B}"
                     smp = buf.gather(idx)                              # the persistent outputs
-                    _assert_batch(smp, want, tag)
+                    assert_batch(smp, want, tag)
                     assert smp.observations.shape == (B, D) and smp.dones.shape == (B, 1)
                     for kind in ("packed", "slice"):
                         out, back = outs(B, D, A, kind, 5)
                         got = buf.gather(idx, out=out)
-                        _assert_batch(got, want, f"{tag} out={kind}")
+                        assert_batch(got, want, f"{tag} out={kind}")
                         for b in back:                                 # nothing outside the D columns
                             b = b.cpu().numpy()
                             if kind == "packed":
@@ -78,9 +73,9 @@ def test_draw_equals_model(seed):
                                               err_msg=f"pos={pos} B={B} draw={draws}")
                 assert pos not in set(want_idx[0].tolist())
                 want = rm.lookup(*host, want_idx)
-                _assert_batch(smp, want, f"sample B={B} draw={draws}")
+                assert_batch(smp, want, f"sample B={B} draw={draws}")
                 kept = [t.clone() for t in smp]
-                _assert_batch(buf.gather(buf.last_indices), want, "gather(last_indices)")
+                assert_batch(buf.gather(buf.last_indices), want, "gather(last_indices)")
                 for k, g in zip(kept, buf.gather(buf.last_indices)):
                     assert torch.equal(k, g)
                 draws += 1
@@ -116,7 +111,7 @@ def test_untrusted_head_words_do_not_leave_the_ring():
         smp = buf.sample(64)
         idx = buf.last_indices.cpu().numpy()
         assert idx[0].min() >= 0 and idx[0].max() < S and idx[1].min() >= 0 and idx[1].max() < E
-        _assert_batch(smp, rm.lookup(*host, idx), f"head=({pos}, {nv})")
+        assert_batch(smp, rm.lookup(*host, idx), f"head=({pos}, {nv})")
         if nv < 1:
             assert (idx[0] == (pos - 1) % S).all()
 
@@ -165,12 +160,7 @@ def _stock_pair(E, auto_reset=True):
 
 
 def _crypto_pair(E, auto_reset=True):
-    from finrl_amd.vec_crypto import VecCryptoEnv
-    rng = np.random.default_rng(1)
-    T, N, W = 7, 3, 4
-    price = 10.0 ** rng.uniform(0, 3, N) * np.exp(np.cumsum(rng.normal(0, 5e-3, (T, N)), axis=0))
-    cfg = {"price_array": price, "tech_array": rng.normal(0, 3000, (T, W))}
-    return [VecCryptoEnv(cfg, E, lookback=1, auto_reset=auto_reset) for _ in range(2)], "packed"
+    return [crypto_env(E, auto_reset) for _ in range(2)], "packed"
 
 
 def _btc_pair(E, auto_reset=True):
@@ -262,7 +252,7 @@ def test_filling_through_the_env(make):
                 np.stack([rw_[4][k] for rw_, k in zip(rows, e)]),
                 np.array([rw_[3][k] for rw_, k in zip(rows, e)], dtype=np.float32)[:, None],
                 np.array([rw_[2][k] for rw_, k in zip(rows, e)], dtype=np.float32)[:, None])
-        _assert_batch(smp, want, f"sample after step {n}")
+        assert_batch(smp, want, f"sample after step {n}")
     assert saw_done                                  # an episode ended inside a valid slot
     (manual, _), _ = make(E, auto_reset=False)
     manual.reset()
@@ -316,7 +306,7 @@ def test_captured_sample_follows_the_ring_and_the_draw_word():
         pos, n_valid = rm.head_after(n_steps, S)
         want_idx = rm.draw_pairs(seed, draw, B, pos, n_valid, S, E)
         np.testing.assert_array_equal(idx.cpu().numpy(), want_idx, err_msg=f"after {n_steps} steps")
-        _assert_batch(smp, rm.lookup(*host_ring(buf), want_idx), f"after {n_steps} steps")
+        assert_batch(smp, rm.lookup(*host_ring(buf), want_idx), f"after {n_steps} steps")
         if n_steps == 2:
             assert set(want_idx[0].tolist()) <= {0, 1}
             for a in acts[2:]:

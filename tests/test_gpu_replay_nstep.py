@@ -9,7 +9,8 @@ import pytest
 
 import replay_model as rm
 import replay_nstep_model as nm
-from replay_cases import POISON, RING_SEED, coded_ring, host_ring, need_gpu, outs, set_head
+from replay_cases import (POISON, RING_SEED, assert_batch, coded_ring, crypto_env, host_ring, need_gpu, outs,
+                          set_head)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -25,10 +26,7 @@ def _ring(S, E, D, P, A, seed=0):
 def _assert_nstep(smp, steps, want, tag):
     """The six fields of an NStepReplayBufferSamples and the steps block against the model's seven."""
     assert smp._fields == FIELDS
-    for name, g, w in zip(FIELDS + ("steps",), tuple(smp) + (steps,), want):
-        g = g.cpu().numpy()
-        assert g.dtype == w.dtype and g.shape == w.shape, f"{name} {tag}: {g.dtype}{g.shape}"
-        np.testing.assert_array_equal(g, w, err_msg=f"{name} {tag}")
+    assert_batch(smp, want, tag, steps=steps)
 
 
 def _all_pairs(S, E):
@@ -265,15 +263,6 @@ def test_out_tensors_and_their_pad_columns(D, P, A):
 # ------------------------------------------------------------------------------------------------
 # 7. inside a captured graph, and through a real env
 # ------------------------------------------------------------------------------------------------
-def _crypto_env(E):
-    from finrl_amd.vec_crypto import VecCryptoEnv
-    rng = np.random.default_rng(1)
-    T, N, W = 7, 3, 4
-    price = 10.0 ** rng.uniform(0, 3, N) * np.exp(np.cumsum(rng.normal(0, 5e-3, (T, N)), axis=0))
-    cfg = {"price_array": price, "tech_array": rng.normal(0, 3000, (T, W))}
-    return VecCryptoEnv(cfg, E, lookback=1, auto_reset=True)
-
-
 def test_captured_sample_nstep_follows_the_ring_and_the_draw_word():
     """One captured sample_nstep, replayed after further buf.step calls: each replay equals the model
     for the ring, the head and the draw number as they are at that replay, with the n and gamma of
@@ -281,7 +270,7 @@ def test_captured_sample_nstep_follows_the_ring_and_the_draw_word():
     need_gpu()
     from finrl_amd import ReplayBuffer
     E, S, B, seed, n, gamma = E70, S8, 257, 5, 3, 0.99
-    env = _crypto_env(E)
+    env = crypto_env(E)
     D, A = env.obs.shape[1], env.action_dim
     buf = ReplayBuffer(S, E, D, A, obs_pitch="packed", seed=seed)
     gen = torch.Generator(device="cuda")
@@ -324,7 +313,7 @@ def test_gather_nstep_through_a_real_env():
     need_gpu()
     from finrl_amd import ReplayBuffer
     E, S = E70, S8
-    env = _crypto_env(E)
+    env = crypto_env(E)
     D, A = env.obs.shape[1], env.action_dim
     buf = ReplayBuffer(S, E, D, A, obs_pitch="packed", seed=3)
     rng = np.random.default_rng(7)

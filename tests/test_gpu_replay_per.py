@@ -9,7 +9,8 @@ import pytest
 import replay_model as rm
 import replay_nstep_model as nm
 import replay_per_model as pm
-from replay_cases import POISON, RING_SEED, coded_ring, host_ring, need_gpu, outs, set_head
+from replay_cases import (POISON, RING_SEED, assert_batch, crypto_env, host_ring, need_gpu, outs, per_ring,
+                          random_tickets, set_head, set_tickets)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -23,33 +24,6 @@ TOP = pm.TOP
 def _buffer(S, E, **kw):
     from finrl_amd import PrioritizedReplayBuffer
     return PrioritizedReplayBuffer(S, E, 5, 1, obs_pitch="packed", **kw)
-
-
-def _per_ring(S, E, D, P, A, seed=0, ring_seed=None):
-    """coded_ring's contents in a PrioritizedReplayBuffer, plus the host copies."""
-    from finrl_amd import PrioritizedReplayBuffer
-    src, host = coded_ring(S, E, D, P, A, ring_seed=ring_seed)
-    buf = PrioritizedReplayBuffer(S, E, D, A, obs_pitch=P, seed=seed)
-    for name in ("_obs_buf", "actions", "rewards", "dones"):
-        getattr(buf, name).copy_(getattr(src, name))
-    return buf, host
-
-
-def _random_tickets(S, E, seed):
-    """uint32 [S, E]: a third zeros, some at 1 and at 2^32 - 1, the rest anywhere."""
-    rng = np.random.default_rng(seed)
-    t = rng.integers(1, 2 ** 32, (S, E), dtype=np.uint64)
-    kind = rng.integers(0, 6, (S, E))
-    t[kind < 2] = 0
-    t[kind == 2] = TOP
-    t[kind == 3] = 1
-    t.reshape(-1)[rng.integers(0, S * E)] = 12345          # never all zero
-    return t.astype(np.uint32)
-
-
-def _set_tickets(buf, t):
-    buf.tickets.copy_(torch.from_numpy(np.ascontiguousarray(t).view(np.int32)))
-    buf.rebuild()
 
 
 def _tickets(buf):
@@ -76,11 +50,6 @@ def _assert_state(buf, t, tag, top=None):
         assert _max(buf) == top, tag
 
 
-def _assert_batch(smp, want, tag):
-    for name, g, w in zip(smp._fields, smp, want):
-        np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=f"{name} {tag}")
-
-
 # ------------------------------------------------------------------------------------------------
 # 1. rebuild and find
 # ------------------------------------------------------------------------------------------------
@@ -93,8 +62,8 @@ def test_rebuild_and_find_equal_model(S, E, full):
     buf = _buffer(S, E)
     assert buf.tree.numel() == pm.tree_words(S * E) and buf.total == 0
     assert buf.find(_u_tensor([0, 7])).cpu().numpy().tolist() == [[0, 0], [0, 0]]     # total 0: pair (0, 0)
-    t = np.full((S, E), TOP, np.uint32) if full else _random_tickets(S, E, S * E)
-    _set_tickets(buf, t)
+    t = np.full((S, E), TOP, np.uint32) if full else random_tickets(S, E, S * E)
+    set_tickets(buf, t)
     _assert_state(buf, t, f"S={S} E={E}")
     flat = t.reshape(-1)
     c = np.cumsum(flat.astype(np.uint64), dtype=np.uint64)
@@ -118,8 +87,8 @@ def test_put_equals_model(S, E):
     need_gpu()
     from finrl_amd import _native as nat
     buf = _buffer(S, E)
-    t = _random_tickets(S, E, 7 * S + E)
-    _set_tickets(buf, t)
+    t = random_tickets(S, E, 7 * S + E)
+    set_tickets(buf, t)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     moves = [(p, (p + 1) % S) for p in range(S)] + [(1, 1), (0, 2), (S - 1, S - 1)]
     for n, (pos, nxt) in enumerate(moves):
@@ -130,22 +99,13 @@ def test_put_equals_model(S, E):
         _assert_state(buf, t, f"put {pos} -> {nxt}")
 
 
-def _crypto_env(E):
-    from finrl_amd.vec_crypto import VecCryptoEnv
-    rng = np.random.default_rng(1)
-    T, N, W = 7, 3, 4
-    price = 10.0 ** rng.uniform(0, 3, N) * np.exp(np.cumsum(rng.normal(0, 5e-3, (T, N)), axis=0))
-    return VecCryptoEnv({"price_array": price, "tech_array": rng.normal(0, 3000, (T, W))}, E, lookback=1,
-                        auto_reset=True)
-
-
 def test_step_fills_tickets():
     """3 S steps of a real env: after each, the nonzero slots are exactly the valid ones, all their
     leaves hold max_ticket (raised once on the way by an update), and the tree is the model's."""
     need_gpu()
     from finrl_amd import PrioritizedReplayBuffer
     E, S = 70, 4
-    env = _crypto_env(E)
+    env = crypto_env(E)
     D, A = env.obs.shape[1], env.action_dim
     buf = PrioritizedReplayBuffer(S, E, D, A, obs_pitch="packed", seed=3, frac_bits=10)
     assert _max(buf) == 1 << 10
@@ -184,8 +144,8 @@ def test_update_priorities_equals_model(S, E):
     F = 16
     buf = _buffer(S, E, frac_bits=F)
     rng = np.random.default_rng(S + E)
-    t = _random_tickets(S, E, 3 * S + E)
-    _set_tickets(buf, t)
+    t = random_tickets(S, E, 3 * S + E)
+    set_tickets(buf, t)
     top = _max(buf)
     assert top == 1 << F
     N = S * E
@@ -251,12 +211,12 @@ def test_sample_equals_model(D, P, A, seed):
     the draw word advances, and poisoned caller outputs keep their pad columns."""
     need_gpu()
     S, E, B, n, gamma = 5, 70, 257, 3, 0.9
-    buf, host = _per_ring(S, E, D, P, A, seed=seed, ring_seed=RING_SEED)
+    buf, host = per_ring(S, E, D, P, A, seed=seed, ring_seed=RING_SEED)
     pos = 1
     set_head(buf, pos, S - 1)
-    t = _random_tickets(S, E, D)
+    t = random_tickets(S, E, D)
     t[pos] = 0
-    _set_tickets(buf, t)
+    set_tickets(buf, t)
     draws = 0
     for rep in range(2):
         want_idx, want_p = pm.draw_pairs(seed, draws, B, t, E)
@@ -264,9 +224,9 @@ def test_sample_equals_model(D, P, A, seed):
         smp = buf.sample(B)
         tag = f"sample draw={draws}"
         np.testing.assert_array_equal(buf.last_indices.cpu().numpy(), want_idx, err_msg=tag)
-        _assert_batch(smp, rm.lookup(*host, want_idx) + (want_p[:, None],), tag)
+        assert_batch(smp, rm.lookup(*host, want_idx) + (want_p[:, None],), tag)
         assert type(smp).__name__ == "PrioritizedReplayBufferSamples" and smp.probabilities.shape == (B, 1)
-        _assert_batch(buf.gather(buf.last_indices), rm.lookup(*host, want_idx), "gather(last_indices)")
+        assert_batch(buf.gather(buf.last_indices), rm.lookup(*host, want_idx), "gather(last_indices)")
         draws += 1
         assert int(buf.draw.item()) == draws == buf.draws
         want_idx, want_p = pm.draw_pairs(seed, draws, B, t, E)
@@ -274,7 +234,7 @@ def test_sample_equals_model(D, P, A, seed):
         tag = f"sample_nstep draw={draws}"
         np.testing.assert_array_equal(buf.last_indices.cpu().numpy(), want_idx, err_msg=tag)
         want = nm.nstep_lookup(*host, want_idx, pos, n, gamma)
-        _assert_batch(smp, want[:6] + (want_p[:, None],), tag)
+        assert_batch(smp, want[:6] + (want_p[:, None],), tag)
         np.testing.assert_array_equal(buf.last_steps.cpu().numpy(), want[6], err_msg=tag)
         assert type(smp).__name__ == "PrioritizedNStepReplayBufferSamples"
         draws += 1
@@ -283,11 +243,11 @@ def test_sample_equals_model(D, P, A, seed):
         out, back = outs(B, D, A, kind, 6)
         want_idx, want_p = pm.draw_pairs(seed, draws, B, t, E)
         got = buf.sample(B, out=out)
-        _assert_batch(got, rm.lookup(*host, want_idx) + (want_p[:, None],), f"out={kind}")
+        assert_batch(got, rm.lookup(*host, want_idx) + (want_p[:, None],), f"out={kind}")
         out7, back7 = outs(B, D, A, kind, 7)
         want_idx7, want_p7 = pm.draw_pairs(seed, draws + 1, B, t, E)
         got = buf.sample_nstep(B, n, gamma, out=out7)
-        _assert_batch(got, nm.nstep_lookup(*host, want_idx7, pos, n, gamma)[:6] + (want_p7[:, None],),
+        assert_batch(got, nm.nstep_lookup(*host, want_idx7, pos, n, gamma)[:6] + (want_p7[:, None],),
                       f"n-step out={kind}")
         draws += 2
         for b in back + back7:
@@ -309,9 +269,9 @@ def test_corrupt_tree_words_do_not_leave_the_ring():
     the returned pairs."""
     need_gpu()
     S, E, D, A, B = 9, 513, 13, 3, 257
-    buf, host = _per_ring(S, E, D, D, A, seed=9)
+    buf, host = per_ring(S, E, D, D, A, seed=9)
     set_head(buf, 1, S - 1)
-    t = _random_tickets(S, E, 5)
+    t = random_tickets(S, E, 5)
     huge = 2 ** 64 - 1
     words = pm.tree_words(S * E)
     assert words == 76
@@ -320,7 +280,7 @@ def test_corrupt_tree_words_do_not_leave_the_ring():
              {k: 2 ** 63 + k for k in range(3, words)}]
     u = _u_tensor([0, 1, 2 ** 31, 2 ** 40, 2 ** 63, huge - 1, huge])
     for case in cases:
-        _set_tickets(buf, t)
+        set_tickets(buf, t)
         tree = pm.build_tree(t)
         for k, v in case.items():
             tree[k] = v
@@ -347,7 +307,7 @@ def test_captured_step_sample_update_follows_the_model():
     need_gpu()
     from finrl_amd import PrioritizedReplayBuffer
     E, S, B, seed, F = 70, 8, 257, 5, 12
-    env = _crypto_env(E)
+    env = crypto_env(E)
     D, A = env.obs.shape[1], env.action_dim
     buf = PrioritizedReplayBuffer(S, E, D, A, obs_pitch="packed", seed=seed, frac_bits=F)
     gen = torch.Generator(device="cuda")
@@ -392,7 +352,7 @@ def test_captured_step_sample_update_follows_the_model():
         t = pm.put(t, top, pos, (pos + 1) % S)
         pairs, prob = pm.draw_pairs(seed, draw, B, t, E)
         np.testing.assert_array_equal(idx.cpu().numpy(), pairs, err_msg=f"replay {rep}")
-        _assert_batch(smp, rm.lookup(*host_ring(buf), pairs) + (prob[:, None],), f"replay {rep}")
+        assert_batch(smp, rm.lookup(*host_ring(buf), pairs) + (prob[:, None],), f"replay {rep}")
         t, top = pm.update(t, top, pairs, model_w(pairs, draw + 1), F)
         _assert_state(buf, t, f"replay {rep}", top)
     assert top == pm.ticket(np.float32(7 * 0.75), F)
@@ -408,10 +368,10 @@ def test_importance_weights():
     S, E, B = 5, 70, 257
     buf = _buffer(S, E, seed=2)
     set_head(buf, 1, S - 1)
-    t = _random_tickets(S, E, 11)
+    t = random_tickets(S, E, 11)
     t[t == TOP] = 3                                          # a spread of probabilities, none dominant
     t[1] = 0
-    _set_tickets(buf, t)
+    set_tickets(buf, t)
     smp = buf.sample(B)
     p = smp.probabilities.cpu().numpy().astype(np.float64)
     for beta in (0.0, 0.4, 1.0):

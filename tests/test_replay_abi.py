@@ -7,13 +7,7 @@ import numpy as np
 import pytest
 
 import replay_model as rm
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
+from replay_abi_cases import FAKE, INV, assert_refusals, lib  # noqa: F401
 
 
 # Random123's kat_vectors, philox4x32 10 rounds: counter, key -> output
@@ -69,57 +63,12 @@ def test_struct_sizes(lib):
     assert lib.finenv_abi_version() == 3
 
 
-FAKE = 0x1000       # a non-null address that is never dereferenced: every call below is refused first
-
-
-def _view(nat, **kw):
-    f = dict(obs=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE, n_slots=4, n_envs=3, obs_dim=5,
-             obs_pitch=8, action_dim=2, reserved0=0)
-    f.update(kw)
-    return nat.ReplayViewPtrs(**f)
-
-
-def _batch(nat, **kw):
-    f = dict(observations=FAKE, next_observations=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE,
-             batch_size=7, obs_pitch=5)
-    f.update(kw)
-    return nat.ReplayBatchPtrs(**f)
-
-
-BAD_VIEWS = [dict(obs=None), dict(actions=None), dict(rewards=None), dict(dones=None),
-             dict(n_slots=1), dict(n_slots=0), dict(n_envs=0), dict(obs_dim=0), dict(action_dim=0),
-             dict(obs_pitch=4)]
-BAD_BATCHES = [dict(observations=None), dict(next_observations=None), dict(actions=None),
-               dict(rewards=None), dict(dones=None), dict(batch_size=0), dict(batch_size=-3),
-               dict(obs_pitch=4)]
-
-
 def test_sample_and_gather_reject_bad_arguments(lib):
-    from finrl_amd import _native as nat
-    INV = -1                                                     # FINENV_ERR_INVALID
-    good_v, good_b = _view(nat), _batch(nat)
-
-    def sample(v, b, head=FAKE, draw=FAKE):
-        return lib.finenv_replay_sample(v, head, draw, 1, b, None, None)
-
-    def gather(v, b, idx=FAKE):
-        return lib.finenv_replay_gather(v, idx, b, None)
-
-    for kw in BAD_VIEWS:
-        assert sample(C.byref(_view(nat, **kw)), C.byref(good_b)) == INV, kw
-        assert gather(C.byref(_view(nat, **kw)), C.byref(good_b)) == INV, kw
-    for kw in BAD_BATCHES:
-        assert sample(C.byref(good_v), C.byref(_batch(nat, **kw))) == INV, kw
-        assert gather(C.byref(good_v), C.byref(_batch(nat, **kw))) == INV, kw
-    assert sample(None, C.byref(good_b)) == INV and sample(C.byref(good_v), None) == INV
-    assert gather(None, C.byref(good_b)) == INV and gather(C.byref(good_v), None) == INV
-    assert sample(C.byref(good_v), C.byref(good_b), head=None) == INV
-    assert sample(C.byref(good_v), C.byref(good_b), draw=None) == INV
-    assert gather(C.byref(good_v), C.byref(good_b), idx=None) == INV
+    for name in ("sample", "gather"):
+        assert_refusals(lib, name)
 
 
 def test_put_rejects_bad_arguments(lib):
-    INV = -1
     put = lib.finenv_replay_put
     assert put(None, FAKE, 8, FAKE, 1, 1, None) == INV
     assert put(FAKE, None, 8, FAKE, 1, 1, None) == INV

@@ -7,13 +7,7 @@ import numpy as np
 import pytest
 
 import replay_nstep_model as nm
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
+from replay_abi_cases import assert_refusals, lib  # noqa: F401
 
 
 def test_struct_sizes(lib):
@@ -40,64 +34,9 @@ def test_python_surface():
     assert callable(ReplayBuffer.sample_nstep) and callable(ReplayBuffer.gather_nstep)
 
 
-FAKE = 0x1000       # a non-null address that is never dereferenced: every call below is refused first
-S_VIEW = 4
-
-
-def _view(nat, **kw):
-    f = dict(obs=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE, n_slots=S_VIEW, n_envs=3, obs_dim=5,
-             obs_pitch=8, action_dim=2, reserved0=0)
-    f.update(kw)
-    return nat.ReplayViewPtrs(**f)
-
-
-def _batch(nat, **kw):
-    f = dict(observations=FAKE, next_observations=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE,
-             batch_size=7, obs_pitch=5)
-    f.update(kw)
-    return nat.ReplayBatchPtrs(**f)
-
-
-def _nstep(nat, **kw):
-    f = dict(head=FAKE, discounts=FAKE, steps=FAKE, n_steps=2, gamma=0.99)
-    f.update(kw)
-    return nat.ReplayNStepPtrs(**f)
-
-
-BAD_NSTEPS = [dict(n_steps=0), dict(n_steps=-1), dict(n_steps=S_VIEW), dict(n_steps=S_VIEW + 5),
-              dict(gamma=float("nan")), dict(gamma=-0.1), dict(gamma=1.5), dict(gamma=float("inf")),
-              dict(gamma=float("-inf")), dict(head=None), dict(discounts=None)]
-
-
 def test_nstep_entry_points_reject_bad_arguments(lib):
-    from finrl_amd import _native as nat
-    INV = -1                                                     # FINENV_ERR_INVALID
-    good_v, good_b, good_n = _view(nat), _batch(nat), _nstep(nat)
-
-    def sample(v, b, n, head=FAKE, draw=FAKE):
-        return lib.finenv_replay_sample_nstep(v, head, draw, 1, b, n, None, None)
-
-    def gather(v, b, n, idx=FAKE):
-        return lib.finenv_replay_gather_nstep(v, idx, b, n, None)
-
-    for kw in BAD_NSTEPS:
-        assert sample(C.byref(good_v), C.byref(good_b), C.byref(_nstep(nat, **kw))) == INV, kw
-        assert gather(C.byref(good_v), C.byref(good_b), C.byref(_nstep(nat, **kw))) == INV, kw
-    # the largest n a view admits is S - 1; a 2-slot ring admits only n = 1
-    two = _view(nat, n_slots=2)
-    assert gather(C.byref(two), C.byref(good_b), C.byref(_nstep(nat, n_steps=2))) == INV
-    assert sample(C.byref(two), C.byref(good_b), C.byref(_nstep(nat, n_steps=2))) == INV
-    for f in (sample, gather):
-        assert f(None, C.byref(good_b), C.byref(good_n)) == INV
-        assert f(C.byref(good_v), None, C.byref(good_n)) == INV
-        assert f(C.byref(good_v), C.byref(good_b), None) == INV
-        assert f(C.byref(_view(nat, obs=None)), C.byref(good_b), C.byref(good_n)) == INV
-        assert f(C.byref(_view(nat, n_slots=1)), C.byref(good_b), C.byref(good_n)) == INV
-        assert f(C.byref(good_v), C.byref(_batch(nat, rewards=None)), C.byref(good_n)) == INV
-        assert f(C.byref(good_v), C.byref(_batch(nat, batch_size=0)), C.byref(good_n)) == INV
-    assert sample(C.byref(good_v), C.byref(good_b), C.byref(good_n), head=None) == INV
-    assert sample(C.byref(good_v), C.byref(good_b), C.byref(good_n), draw=None) == INV
-    assert gather(C.byref(good_v), C.byref(good_b), C.byref(good_n), idx=None) == INV
+    for name in ("sample_nstep", "gather_nstep"):
+        assert_refusals(lib, name)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -7,14 +7,7 @@ import numpy as np
 import pytest
 
 import replay_per_model as pm
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
-
+from replay_abi_cases import BAD_PERS, E_VIEW, FAKE, INV, S_VIEW, _per, assert_refusals, lib  # noqa: F401
 
 NAMES = ("tree_words", "rebuild", "put", "update", "find", "sample", "sample_nstep")
 
@@ -51,44 +44,8 @@ def test_tree_words(lib, n, want):
     assert pm.tree_words(n) == want
 
 
-FAKE = 0x1000       # a non-null address that is never dereferenced: every call below is refused first
-S_VIEW, E_VIEW = 4, 3
-
-
-def _per(nat, **kw):
-    f = dict(tickets=FAKE, tree=FAKE, max_ticket=FAKE, frac_bits=16, reserved0=0)
-    f.update(kw)
-    return nat.ReplayPerPtrs(**f)
-
-
-def _view(nat, **kw):
-    f = dict(obs=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE, n_slots=S_VIEW, n_envs=E_VIEW, obs_dim=5,
-             obs_pitch=8, action_dim=2, reserved0=0)
-    f.update(kw)
-    return nat.ReplayViewPtrs(**f)
-
-
-def _batch(nat, **kw):
-    f = dict(observations=FAKE, next_observations=FAKE, actions=FAKE, rewards=FAKE, dones=FAKE,
-             batch_size=7, obs_pitch=5)
-    f.update(kw)
-    return nat.ReplayBatchPtrs(**f)
-
-
-def _nstep(nat, **kw):
-    f = dict(head=FAKE, discounts=FAKE, steps=FAKE, n_steps=2, gamma=0.99)
-    f.update(kw)
-    return nat.ReplayNStepPtrs(**f)
-
-
-BAD_PERS = [dict(tickets=None), dict(tree=None), dict(max_ticket=None), dict(frac_bits=-1),
-            dict(frac_bits=32)]
-INV = -1                                                         # FINENV_ERR_INVALID
-
-
 def test_tree_entry_points_reject_bad_arguments(lib):
-    from finrl_amd import _native as nat
-    good = _per(nat)
+    good = _per()
     S, E = S_VIEW, E_VIEW
     calls = {
         "rebuild": lambda p, S=S, E=E: lib.finenv_replay_per_rebuild(p, S, E, None),
@@ -101,7 +58,7 @@ def test_tree_entry_points_reject_bad_arguments(lib):
     for name, f in calls.items():
         assert f(None) == INV, name
         for kw in BAD_PERS:
-            assert f(C.byref(_per(nat, **kw))) == INV, (name, kw)
+            assert f(C.byref(_per(**kw))) == INV, (name, kw)
         for s, e in ((1, 3), (0, 3), (-2, 3), (4, 0), (4, -1), (2 ** 16, 2 ** 15)):   # S < 2, E < 1, N = 2^31
             assert f(C.byref(good), S=s, E=e) == INV, (name, s, e)
     put, update, find = calls["put"], calls["update"], calls["find"]
@@ -114,34 +71,8 @@ def test_tree_entry_points_reject_bad_arguments(lib):
 
 
 def test_sample_entry_points_reject_bad_arguments(lib):
-    from finrl_amd import _native as nat
-    v, p, b, n = _view(nat), _per(nat), _batch(nat), _nstep(nat)
-
-    def one(v=v, p=p, b=b, draw=FAKE):
-        ref = [None if x is None else C.byref(x) for x in (v, p, b)]
-        return lib.finenv_replay_per_sample(ref[0], ref[1], draw, 1, ref[2], None, None, None)
-
-    def multi(v=v, p=p, b=b, n=n, draw=FAKE):
-        ref = [None if x is None else C.byref(x) for x in (v, p, b, n)]
-        return lib.finenv_replay_per_sample_nstep(ref[0], ref[1], draw, 1, ref[2], ref[3], None, None,
-                                                  None)
-
-    for f in (one, multi):
-        assert f(v=None) == INV and f(p=None) == INV and f(b=None) == INV and f(draw=None) == INV
-        for kw in BAD_PERS:
-            assert f(p=_per(nat, **kw)) == INV, kw
-        for kw in (dict(obs=None), dict(actions=None), dict(rewards=None), dict(dones=None),
-                   dict(n_slots=1), dict(n_slots=0), dict(n_envs=0), dict(obs_dim=0), dict(action_dim=0),
-                   dict(obs_pitch=4), dict(n_slots=2 ** 16, n_envs=2 ** 15)):
-            assert f(v=_view(nat, **kw)) == INV, kw
-        for kw in (dict(observations=None), dict(next_observations=None), dict(actions=None),
-                   dict(rewards=None), dict(dones=None), dict(batch_size=0), dict(batch_size=-3),
-                   dict(obs_pitch=4)):
-            assert f(b=_batch(nat, **kw)) == INV, kw
-    assert multi(n=None) == INV
-    for kw in (dict(n_steps=0), dict(n_steps=S_VIEW), dict(gamma=float("nan")), dict(gamma=1.5),
-               dict(gamma=-0.1), dict(head=None), dict(discounts=None)):
-        assert multi(n=_nstep(nat, **kw)) == INV, kw
+    for name in ("per_sample", "per_sample_nstep"):
+        assert_refusals(lib, name)
 
 
 def test_prioritized_buffer_needs_a_gpu(lib):

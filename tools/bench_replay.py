@@ -22,89 +22,28 @@ Algorithmic bytes per sample, B_sample = 2 * (4 D read + 4 D write) + 8 A + 21:
     write  two observation rows 8 D, the action row 4 A, reward 4, done 4
 (sample() writes the pair instead of reading it.)  Achieved bytes/s = B_sample * B / time; the
 fraction is of the 8 TB/s HBM peak, which a gather from a 5 GB ring cannot exceed."""
-import argparse
-import json
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-PEAK_BYTES_PER_S = 8e12
-POOL = 16            # sets of pairs the gather variants cycle through
-
-
-def sample_bytes(D, A):
-    return 2 * (4 * D + 4 * D) + 8 * A + 21
+import replay_bench_common as rb
+from replay_bench_common import PEAK_BYTES_PER_S, POOL, rounds_of, sample_bytes
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=65536)
-    ap.add_argument("--slots", type=int, default=16)
-    ap.add_argument("--batches", default="256,4096,65536")
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--md", default=None, help="also write the tables as markdown")
-    args = ap.parse_args()
-
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_replay: no HIP device (there is no CPU path to time)")
+    args = rb.parse_args("bench_replay")
     import bench
     from finrl_amd import ReplayBuffer, StockPanel
     from finrl_amd.vec_env import VecStockTradingEnv
     dev = torch.device("cuda", 0)
     E, S = args.envs, args.slots
-    out = open(args.out, "w") if args.out else None
-    md = ["| shape | B | variant | us (best) | us per round | GB/s | of 8 TB/s | vs torch |",
-          "|---|---:|---|---:|---|---:|---:|---:|"]
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters           # us per call
-
-    def rounds_of(variants, iters):
-        for fn in variants.values():                       # untimed warm-up of every variant
-            for _ in range(10):
-                fn()
-        torch.cuda.synchronize()
-        us = {name: [] for name in variants}
-        for _ in range(args.rounds):
-            for name, fn in variants.items():
-                us[name].append(timed(fn, iters))
-        return us
+    rep = rb.Report(args, "| shape | B | variant | us (best) | us per round | GB/s | of 8 TB/s | vs torch |",
+                    "|---|---:|---|---:|---|---:|---:|---:|")
 
     stock_buf = None
-    for shape, D, A, pitch in (("stock DOW30x8", 301, 30, None), ("crypto 10 assets", 51, 10, "packed")):
+    for shape, D, A, pitch in rb.SHAPES:
         buf = ReplayBuffer(S, E, D, A, obs_pitch=pitch, device=dev, seed=1)
-        g = torch.Generator(device=dev).manual_seed(2)
-        for s in range(S):                                 # slot by slot: no 5 GB temporary
-            buf._obs_buf[s].copy_(torch.rand(E, buf.obs_pitch, generator=g, device=dev))
-        buf.actions.copy_(torch.rand(S, E, A, generator=g, device=dev))
-        buf.rewards.copy_(torch.rand(S, E, generator=g, device=dev))
-        buf.dones.copy_((torch.rand(S, E, generator=g, device=dev) < 0.01).to(torch.uint8))
-        buf.pos, buf._n_valid = 3, S - 1                   # a full ring
-        buf.head.copy_(torch.tensor([3, S - 1], dtype=torch.int32))
-        obs2, act2 = buf._obs_buf.view(S * E, buf.obs_pitch), buf.actions.view(S * E, A)
-        rew2, done2 = buf.rewards.view(S * E), buf.dones.view(S * E)
+        obs2, act2, rew2, done2 = rb.fill_ring(buf, torch.Generator(device=dev).manual_seed(2))
         nbytes = sample_bytes(D, A)
-        for B in [int(x) for x in args.batches.split(",") if x]:      # --batches "": the step part only
-            # POOL sets of pairs, cycled: repeating ONE set would serve its rows from the Infinity Cache
-            # (a 65,536-sample crypto batch reads 27 MB) and time neither formulation on the ring
+        for B in args.batch_sizes:
             idx_pool, flat_pool = [], []
             for _ in range(POOL):
                 smp = buf.sample(B)
@@ -131,19 +70,19 @@ def main():
             assert torch.equal(got.dones[:, 0], ref[3].float()) and torch.equal(got.rewards[:, 0], ref[4])
             us = rounds_of({"sample (draw + gather + draw bump)": lambda: buf.sample(B),
                             "gather (caller pairs)": fused_gather,
-                            "torch, 5 index gathers": torch_five}, args.iters)
+                            "torch, 5 index gathers": torch_five}, args.iters, args.rounds)
             t_torch = min(us["torch, 5 index gathers"])
             for name, v in us.items():
                 best = min(v)
                 rate = nbytes * B / (best * 1e-6)
-                emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
-                          iters=args.iters, us_per_call=[round(x, 2) for x in v], us_best=round(best, 2),
-                          bytes_per_sample=nbytes, achieved_GBps=round(rate / 1e9, 1),
-                          fraction_of_8TBps=round(rate / PEAK_BYTES_PER_S, 4),
-                          torch_over_this=round(t_torch / best, 2)))
-                md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
-                          f"{', '.join(f'{x:.2f}' for x in v)} | {rate / 1e9:.1f} | "
-                          f"{rate / PEAK_BYTES_PER_S:.2%} | {t_torch / best:.2f}x |")
+                rep.emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
+                              iters=args.iters, us_per_call=[round(x, 2) for x in v], us_best=round(best, 2),
+                              bytes_per_sample=nbytes, achieved_GBps=round(rate / 1e9, 1),
+                              fraction_of_8TBps=round(rate / PEAK_BYTES_PER_S, 4),
+                              torch_over_this=round(t_torch / best, 2)))
+                rep.md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
+                              f"{', '.join(f'{x:.2f}' for x in v)} | {rate / 1e9:.1f} | "
+                              f"{rate / PEAK_BYTES_PER_S:.2%} | {t_torch / best:.2f}x |")
         if pitch is None:
             stock_buf = buf
         else:
@@ -173,35 +112,9 @@ def main():
         s = k[0] % S
         env.step(pool[k[0] & 7], out=(stock_buf.obs[(s + 1) % S], stock_buf.rewards[s], stock_buf.dones[s]))
 
-    def graphed(fn):
-        """S calls of fn captured once (a whole turn of the ring): what a launch-bound loop runs."""
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(S):
-                fn()
-        return graph.replay
-
-    variants = {"env.step": plain, "env.step(out=ring slots), no put": ring_no_put,
-                "buf.step (put + env.step into the ring)": ring}
-    us = rounds_of(variants, args.iters)
-    per_graph = rounds_of({name + f", {S} steps per graph replay": graphed(fn)
-                           for name, fn in variants.items()}, max(args.iters // S, 10))
-    us.update({name: [x / S for x in v] for name, v in per_graph.items()})
-    md += ["", "| stock env, E = %d | us per step (best) | us per round |" % E, "|---|---:|---|"]
-    for name, v in us.items():
-        emit(dict(shape="stock DOW30x8", envs=E, slots=S, variant=name, iters=args.iters,
-                  us_per_step=[round(x, 2) for x in v], us_best=round(min(v), 2)))
-        md.append(f"| {name} | {min(v):.2f} | {', '.join(f'{x:.2f}' for x in v)} |")
-    if out:
-        out.close()
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(md) + "\n")
+    rb.step_table(rep, args, {"env.step": plain, "env.step(out=ring slots), no put": ring_no_put,
+                              "buf.step (put + env.step into the ring)": ring})
+    rep.close()
 
 
 if __name__ == "__main__":

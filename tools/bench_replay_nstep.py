@@ -22,73 +22,24 @@ the gathers of the last done and of the discount from a table of float32 powers.
 
 Bytes per sample: B_sample + 5 h + 4 (+ 4 for the steps word the Python layer always asks for), with
 B_sample = 2 * (4 D + 4 D) + 8 A + 21 as in bench_replay.py and h the mean horizon of the pairs used."""
-import argparse
-import json
-import os
-import sys
+import numpy as np
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import replay_bench_common as rb
+from replay_bench_common import PEAK_BYTES_PER_S, POOL, rounds_of, sample_bytes
 
-PEAK_BYTES_PER_S = 8e12
-POOL = 16
 GAMMA = 0.99
 NS = (1, 3, 5)
 N_TORCH = 3
 
 
-def sample_bytes(D, A):
-    return 2 * (4 * D + 4 * D) + 8 * A + 21
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=65536)
-    ap.add_argument("--slots", type=int, default=16)
-    ap.add_argument("--batches", default="256,4096,65536")
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--md", default=None, help="also write the table as markdown")
-    args = ap.parse_args()
-
-    import numpy as np
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_replay_nstep: no HIP device (there is no CPU path to time)")
+    args = rb.parse_args("bench_replay_nstep")
     from finrl_amd import ReplayBuffer
     dev = torch.device("cuda", 0)
-    E, S = args.envs, args.slots
-    out = open(args.out, "w") if args.out else None
-    md = ["| shape | B | variant | us (best) | us per round | bytes / sample | GB/s | vs sample | torch / this |",
-          "|---|---:|---|---:|---|---:|---:|---:|---:|"]
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters           # us per call
-
-    def rounds_of(variants, iters):
-        for fn in variants.values():                       # untimed warm-up of every variant
-            for _ in range(10):
-                fn()
-        torch.cuda.synchronize()
-        us = {name: [] for name in variants}
-        for _ in range(args.rounds):
-            for name, fn in variants.items():
-                us[name].append(timed(fn, iters))
-        return us
+    E, S, pos = args.envs, args.slots, rb.HEAD_POS
+    rep = rb.Report(args, "| shape | B | variant | us (best) | us per round | bytes / sample | GB/s | vs sample "
+                    "| torch / this |", "|---|---:|---|---:|---|---:|---:|---:|---:|")
 
     # float32 powers of gamma by one multiply each, as the contract states them
     gtab_np = np.ones(max(NS) + 1, dtype=np.float32)
@@ -97,21 +48,11 @@ def main():
     gtab = torch.from_numpy(gtab_np).to(dev)
     gtab64 = gtab.double()
 
-    for shape, D, A, pitch in (("stock DOW30x8", 301, 30, None), ("crypto 10 assets", 51, 10, "packed")):
+    for shape, D, A, pitch in rb.SHAPES:
         buf = ReplayBuffer(S, E, D, A, obs_pitch=pitch, device=dev, seed=1)
-        g = torch.Generator(device=dev).manual_seed(2)
-        for s in range(S):                                 # slot by slot: no 5 GB temporary
-            buf._obs_buf[s].copy_(torch.rand(E, buf.obs_pitch, generator=g, device=dev))
-        buf.actions.copy_(torch.rand(S, E, A, generator=g, device=dev))
-        buf.rewards.copy_(torch.rand(S, E, generator=g, device=dev))
-        buf.dones.copy_((torch.rand(S, E, generator=g, device=dev) < 0.01).to(torch.uint8))
-        pos = 3
-        buf.pos, buf._n_valid = pos, S - 1                 # a full ring
-        buf.head.copy_(torch.tensor([pos, S - 1], dtype=torch.int32))
-        obs2, act2 = buf._obs_buf.view(S * E, buf.obs_pitch), buf.actions.view(S * E, A)
-        rew2, done2 = buf.rewards.view(S * E), buf.dones.view(S * E)
+        obs2, act2, rew2, done2 = rb.fill_ring(buf, torch.Generator(device=dev).manual_seed(2))
         base_bytes = sample_bytes(D, A)
-        for B in [int(x) for x in args.batches.split(",") if x]:
+        for B in args.batch_sizes:
             n = N_TORCH
             steps_i = torch.arange(n, device=dev)
             idx_pool, pre_pool, h_mean = [], [], {k: 0.0 for k in NS}
@@ -167,7 +108,7 @@ def main():
             variants["gather"] = (pooled(buf.gather), None)
             variants[f"gather_nstep n={n}"] = (pooled(lambda i: buf.gather_nstep(i, n, GAMMA)), n)
             variants[f"torch n-step n={n}"] = (torch_nstep, n)
-            us = rounds_of({name: fn for name, (fn, _) in variants.items()}, args.iters)
+            us = rounds_of({name: fn for name, (fn, _) in variants.items()}, args.iters, args.rounds)
             t_sample, t_torch = min(us["sample"]), min(us[f"torch n-step n={n}"])
             for name, v in us.items():
                 kk = variants[name][1]
@@ -175,22 +116,18 @@ def main():
                 best = min(v)
                 rate = nbytes * B / (best * 1e-6)
                 vs_torch = round(t_torch / best, 2) if kk == n else None
-                emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
-                          gamma=GAMMA, iters=args.iters, us_per_call=[round(x, 2) for x in v],
-                          us_best=round(best, 2), mean_horizon=None if kk is None else round(h_mean[kk], 3),
-                          bytes_per_sample=round(nbytes, 1), achieved_GBps=round(rate / 1e9, 1),
-                          fraction_of_8TBps=round(rate / PEAK_BYTES_PER_S, 4),
-                          this_over_sample=round(best / t_sample, 3), torch_over_this=vs_torch))
-                md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
-                          f"{', '.join(f'{x:.2f}' for x in v)} | {nbytes:.1f} | {rate / 1e9:.1f} | "
-                          f"{best / t_sample:.3f}x | {'' if vs_torch is None else f'{vs_torch:.2f}x'} |")
+                rep.emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
+                              gamma=GAMMA, iters=args.iters, us_per_call=[round(x, 2) for x in v],
+                              us_best=round(best, 2), mean_horizon=None if kk is None else round(h_mean[kk], 3),
+                              bytes_per_sample=round(nbytes, 1), achieved_GBps=round(rate / 1e9, 1),
+                              fraction_of_8TBps=round(rate / PEAK_BYTES_PER_S, 4),
+                              this_over_sample=round(best / t_sample, 3), torch_over_this=vs_torch))
+                rep.md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
+                              f"{', '.join(f'{x:.2f}' for x in v)} | {nbytes:.1f} | {rate / 1e9:.1f} | "
+                              f"{best / t_sample:.3f}x | {'' if vs_torch is None else f'{vs_torch:.2f}x'} |")
         del buf, obs2, act2, rew2, done2
         torch.cuda.empty_cache()
-    if out:
-        out.close()
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(md) + "\n")
+    rep.close()
 
 
 if __name__ == "__main__":

@@ -23,83 +23,29 @@ the gather of the pairs it reports, and its probabilities are ticket / total.
 Bytes per sample of the fused draw: the gather's 2 * (4 D + 4 D) + 8 A + 21 (+ 8 for the pair, + 4
 for the probability) plus the descent's 64 children per level: 3 levels of 512 B and the 256 B of
 leaves, all but the leaves and level 1 shared by the whole batch and L2-resident."""
-import argparse
-import json
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import replay_bench_common as rb
+from replay_bench_common import POOL, rounds_of
 
-POOL = 16
 GAMMA = 0.99
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=65536)
-    ap.add_argument("--slots", type=int, default=16)
-    ap.add_argument("--batches", default="256,4096,65536")
-    ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--md", default=None, help="also write the tables as markdown")
-    args = ap.parse_args()
-
-    import torch
-    if not torch.cuda.is_available():
-        sys.exit("bench_replay_per: no HIP device (there is no CPU path to time)")
+    args = rb.parse_args("bench_replay_per")
     import bench
     from finrl_amd import PrioritizedReplayBuffer, ReplayBuffer, StockPanel
     from finrl_amd.vec_env import VecStockTradingEnv
     dev = torch.device("cuda", 0)
-    E, S = args.envs, args.slots
-    out = open(args.out, "w") if args.out else None
-    md = ["| shape | B | variant | us (best) | us per round | vs uniform sample |", "|---|---:|---|---:|---|---:|"]
+    E, S, pos = args.envs, args.slots, rb.HEAD_POS
+    rep = rb.Report(args, "| shape | B | variant | us (best) | us per round | vs uniform sample |",
+                    "|---|---:|---|---:|---|---:|")
 
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-            out.flush()
-
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / iters           # us per call
-
-    def rounds_of(variants, iters):
-        for fn in variants.values():                       # untimed warm-up of every variant
-            for _ in range(10):
-                fn()
-        torch.cuda.synchronize()
-        us = {name: [] for name in variants}
-        for _ in range(args.rounds):
-            for name, fn in variants.items():
-                us[name].append(timed(fn, iters))
-        return us
-
-    for shape, D, A, pitch in (("stock DOW30x8", 301, 30, None), ("crypto 10 assets", 51, 10, "packed")):
+    for shape, D, A, pitch in rb.SHAPES:
         uni = ReplayBuffer(S, E, D, A, obs_pitch=pitch, device=dev, seed=1)
         buf = PrioritizedReplayBuffer(S, E, D, A, obs_pitch=pitch, device=dev, seed=1)
         g = torch.Generator(device=dev).manual_seed(2)
-        for s in range(S):                                 # slot by slot: no 5 GB temporary
-            buf._obs_buf[s].copy_(torch.rand(E, buf.obs_pitch, generator=g, device=dev))
-            uni._obs_buf[s].copy_(buf._obs_buf[s])
-        buf.actions.copy_(torch.rand(S, E, A, generator=g, device=dev))
-        buf.rewards.copy_(torch.rand(S, E, generator=g, device=dev))
-        buf.dones.copy_((torch.rand(S, E, generator=g, device=dev) < 0.01).to(torch.uint8))
-        for name in ("actions", "rewards", "dones"):
-            getattr(uni, name).copy_(getattr(buf, name))
-        pos = 3
-        for b in (uni, buf):
-            b.pos, b._n_valid = pos, S - 1                 # a full ring
-            b.head.copy_(torch.tensor([pos, S - 1], dtype=torch.int32))
+        obs2, act2, rew2, done2 = rb.fill_ring(buf, g, twin=uni)
         # tickets of (|N(0, 1)| + eps)^0.6 TD errors; the head slot holds no complete transition
         w = (torch.randn(S, E, generator=g, device=dev).abs() + buf.eps) ** buf.alpha
         q = torch.clamp(torch.round(w.double() * 2.0 ** buf.frac_bits), 1, 2 ** 32 - 1).long()
@@ -109,9 +55,7 @@ def main():
         total = buf.total
         assert total == int(q.sum())
         q_flat = q.view(-1)
-        obs2, act2 = buf._obs_buf.view(S * E, buf.obs_pitch), buf.actions.view(S * E, A)
-        rew2, done2 = buf.rewards.view(S * E), buf.dones.view(S * E)
-        for B in [int(x) for x in args.batches.split(",") if x]:
+        for B in args.batch_sizes:
             u_pool = [torch.randint(0, total, (B,), generator=g, device=dev, dtype=torch.int64)
                       for _ in range(POOL)]
             idx_pool, w_pool = [], []
@@ -158,19 +102,19 @@ def main():
                         "uniform sample_nstep n=3": lambda: uni.sample_nstep(B, 3, GAMMA),
                         "find + gather (two launches)": find_gather,
                         "torch cumsum + searchsorted + 5 gathers": torch_per}
-            us = rounds_of(variants, args.iters)
+            us = rounds_of(variants, args.iters, args.rounds)
             tickets_before = buf.tickets.clone()
-            us.update(rounds_of({"update_priorities": update}, args.iters))
+            us.update(rounds_of({"update_priorities": update}, args.iters, args.rounds))
             buf.tickets.copy_(tickets_before)              # the timed draws of the next B see the same tree
             buf.rebuild()
             t_uni = min(us["uniform sample"])
             for name, v in us.items():
                 best = min(v)
-                emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
-                          iters=args.iters, us_per_call=[round(x, 2) for x in v], us_best=round(best, 2),
-                          this_over_uniform=round(best / t_uni, 3)))
-                md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
-                          f"{', '.join(f'{x:.2f}' for x in v)} | {best / t_uni:.3f}x |")
+                rep.emit(dict(shape=shape, D=D, P=buf.obs_pitch, A=A, slots=S, envs=E, batch=B, variant=name,
+                              iters=args.iters, us_per_call=[round(x, 2) for x in v], us_best=round(best, 2),
+                              this_over_uniform=round(best / t_uni, 3)))
+                rep.md.append(f"| {shape} (D={D}, P={buf.obs_pitch}, A={A}) | {B} | {name} | {best:.2f} | "
+                              f"{', '.join(f'{x:.2f}' for x in v)} | {best / t_uni:.3f}x |")
         if D != 301:
             del uni, buf
         del obs2, act2, rew2, done2
@@ -194,33 +138,8 @@ def main():
             b.step(env, pool[k[0] & 7])
         variants[name] = step
 
-    def graphed(fn):
-        """S calls of fn captured once (a whole turn of the ring): what a launch-bound loop runs."""
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(S):
-                fn()
-        return graph.replay
-
-    us = rounds_of(variants, args.iters)
-    per_graph = rounds_of({name + f", {S} steps per graph replay": graphed(fn)
-                           for name, fn in variants.items()}, max(args.iters // S, 10))
-    us.update({name: [x / S for x in v] for name, v in per_graph.items()})
-    md += ["", "| stock env, E = %d | us per step (best) | us per round |" % E, "|---|---:|---|"]
-    for name, v in us.items():
-        emit(dict(shape="stock DOW30x8", envs=E, slots=S, variant=name, iters=args.iters,
-                  us_per_step=[round(x, 2) for x in v], us_best=round(min(v), 2)))
-        md.append(f"| {name} | {min(v):.2f} | {', '.join(f'{x:.2f}' for x in v)} |")
-    if out:
-        out.close()
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(md) + "\n")
+    rb.step_table(rep, args, variants)
+    rep.close()
 
 
 if __name__ == "__main__":
