@@ -17,7 +17,7 @@ _LAZY = {      # name -> module; lazy because these need the native library
     "VecStockPortfolioEnv": "vec_portfolio", "VecCryptoEnv": "vec_crypto",
     "VecBitcoinEnv": "vec_btc", "VecStockTradingEnvNP": "vec_stocknp", "VecCashPenaltyEnv": "vec_cashpenalty",
     "VecStopLossEnv": "vec_cashpenalty", "CashPenaltyPanel": "vec_cashpenalty",
-    "RolloutBuffer": "rollout", "ReplayBuffer": "replay", "GraphedSegment": "graph",
+    "RolloutBuffer": "rollout", "RolloutBufferSamples": "rollout", "ReplayBuffer": "replay", "GraphedSegment": "graph",
     "ReplayBufferSamples": "replay", "NStepReplayBufferSamples": "replay",
     "PrioritizedReplayBuffer": "replay", "PrioritizedReplayBufferSamples": "replay",
     "PrioritizedNStepReplayBufferSamples": "replay",

@@ -278,6 +278,25 @@ _REPLAY_NSTEP_STRUCTS = {26: ReplayNStepPtrs}
 # prioritised replay's (27 stays invalid: the end of the list above)
 _REPLAY_PER_STRUCTS = {28: ReplayPerPtrs}
 
+
+class RolloutViewPtrs(C.Structure):
+    """finenv_rollout_view: the six rollout tensors a minibatch reads and n_steps, E, D, P, A."""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p),
+                ("log_probs", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("n_steps", C.c_int32), ("n_envs", C.c_int32), ("obs_dim", C.c_int32),
+                ("obs_pitch", C.c_int32), ("action_dim", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class RolloutBatchPtrs(C.Structure):
+    """finenv_rollout_batch: the six outputs of a minibatch, B and the observation row pitch."""
+    _fields_ = [("observations", C.c_void_p), ("actions", C.c_void_p), ("old_values", C.c_void_p),
+                ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("batch_size", C.c_int32), ("obs_pitch", C.c_int32)]
+
+
+# the rollout minibatch's (29 stays invalid: the end of the list above)
+_ROLLOUT_STRUCTS = {30: RolloutViewPtrs, 31: RolloutBatchPtrs}
+
 _lib = None
 
 
@@ -402,6 +421,10 @@ def lib():
         L.finenv_replay_per_sample_nstep.argtypes = [
             C.POINTER(ReplayViewPtrs), per, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
             C.POINTER(ReplayNStepPtrs), C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "finenv_rollout_minibatch"):             # shuffled rollout minibatches (same rule)
+        L.finenv_rollout_minibatch.argtypes = [
+            C.POINTER(RolloutViewPtrs), C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(RolloutBatchPtrs),
+            C.c_void_p, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
@@ -416,6 +439,8 @@ def lib():
         later += sorted(_REPLAY_NSTEP_STRUCTS.items())
     if hasattr(L, "finenv_replay_per_sample"):
         later += sorted(_REPLAY_PER_STRUCTS.items())
+    if hasattr(L, "finenv_rollout_minibatch"):
+        later += sorted(_ROLLOUT_STRUCTS.items())
     for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(

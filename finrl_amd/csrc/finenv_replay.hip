@@ -16,10 +16,9 @@
 
 #include "finenv.h"
 #include "finenv_host.h"
+#include "finenv_group.h"       // f4, group_sample, philox4x32_10
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // actions -> their ring slot, and the head words after this step (set, never incremented: a replayed
 // capture publishes the head of the slots it writes)
@@ -46,14 +45,6 @@ struct GatherArgs {
     int32_t *indices_out;         // the drawn pairs [2][B] or NULL
     uint32_t seed_lo, seed_hi;
 };
-
-// This thread's lane in its group of G and the sample b of that group: 256 / G samples per block
-template <int G>
-__device__ __forceinline__ long long group_sample(int &lane)
-{
-    lane = (int)threadIdx.x & (G - 1);
-    return (long long)blockIdx.x * (256 / G) + ((int)threadIdx.x / G);
-}
 
 // __ballot(pred) of this thread's group of G lanes, in bits 0 .. G-1
 template <int G>
@@ -93,25 +84,6 @@ __device__ __forceinline__ void leaf_pair(long long leaf, int E, int &s, int &e)
 {
     s = (int)(leaf / E);
     e = (int)(leaf - (long long)s * E);
-}
-
-// Philox4x32-10 (Salmon et al., SC'11; Random123): counter c[4], key k[2] -> first two output words
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t &x0, uint32_t &x1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    x0 = c0;
-    x1 = c1;
 }
 
 // The random words of sample b: Philox counter (b, 0, draw number), key = the seed

@@ -314,6 +314,9 @@ int finenv_struct_size(int which)
     case 26: return (int)sizeof(finenv_replay_nstep);
     // (27 stays invalid: bindings of the list that ended at 26 probe it as its end)
     case 28: return (int)sizeof(finenv_replay_per);
+    // (29 stays invalid: bindings of the list that ended at 28 probe it as its end)
+    case 30: return (int)sizeof(finenv_rollout_view);
+    case 31: return (int)sizeof(finenv_rollout_batch);
     default: return FINENV_ERR_INVALID;
     }
 }

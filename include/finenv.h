@@ -178,7 +178,8 @@ int         finenv_abi_version(void);
 /* sizeof() of the ABI structs as the library was compiled (0 = finenv_stock_config,
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
  * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio,
- * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep, 28 = finenv_replay_per; 22, 25 and 27, like 18, stay invalid as the ends of earlier lists):
+ * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep, 28 = finenv_replay_per,
+ * 30 = finenv_rollout_view, 31 = finenv_rollout_batch; 22, 25, 27 and 29, like 18, stay invalid as the ends of earlier lists):
  * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
  * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
  * bindings probe it as such. */
@@ -712,6 +713,71 @@ int finenv_gae_scan(const float *rewards, const float *values, const uint8_t *do
 int finenv_rollout_put(const float *actions, const float *values, const float *log_probs,
                        float *actions_out, float *values_out, float *log_probs_out,
                        int32_t n_envs, int32_t action_dim, void *stream);
+
+/* Shuffled minibatches of a rollout (what SB3's RolloutBuffer.get(batch_size) yields, for PPO / A2C):
+ * one launch per minibatch that draws its rows from a stateless permutation and gathers the six fields.
+ *
+ * Rows.  M = n_steps * n_envs, 1 <= M < 2^31; the flat row r = t * E + e of the time-major tensors
+ *   obs [n_steps + 1][E][P] f32 (P = row pitch in floats >= D; slice n_steps, the observation after the
+ *   last step, is never drawn), actions [n_steps][E][A], values / log_probs / advantages / returns
+ *   [n_steps][E] f32.
+ *
+ * Permutation.  Position i in [0, M) of epoch n maps to row perm(i): a four-round Feistel network over
+ * the bits of M - 1, cycle-walked into [0, M).  tests/rollout_model.py restates it.
+ *   M == 1: the row is 0.  Otherwise bits = max(2, bit_length(M - 1)), a = bits / 2 (integer
+ *   division), b = bits - a.  Split x into L = x >> a (b bits) and R = x & (2^a - 1), and for
+ *   r = 0 .. 3:   even r:  L ^= F(R, r) & (2^b - 1);   odd r:  R ^= F(L, r) & (2^a - 1);
+ *   F(h, r) = the first output word of Philox4x32-10 with counter (h, r, n lo, n hi) and key
+ *   (seed lo, seed hi) -- the Philox of the replay draw below.  x' = L << a | R; while x' >= M the
+ *   four rounds are applied again to x' (cycle walking).
+ * Each round xors one half with a function of the other, so the rounds are a bijection of
+ * [0, 2^bits); cycle walking restricts a bijection to one of [0, M) and ends, and as 2^bits < 2 M the
+ * expected number of passes is below 2 (at M = 2^20 + 1 the longest walk of epochs 0, 1 and 5 under seed 7 takes 23 passes).
+ * Uniformity: over 16,384 epochs at M = 48 and M = 80 every (position, row) count lies within 4.3
+ * standard deviations of its mean.  For M < 16 a half holds one or two bits and the family of
+ * permutations is visibly NOT uniform (M = 5: about 20 standard deviations off); a PPO buffer is never
+ * that small.  The epoch number n is read from a device int64 the caller bumps in-stream, so a
+ * captured epoch of minibatches plus that bump draws a fresh permutation at every replay.
+ *
+ * Gather.  Sample j of the batch is position i = first + j, r = perm(i):  observations[j] = obs row r
+ * [:D] (columns D .. pitch-1 of the output are not written), actions[j] = actions row r, old_values[j]
+ * = values[r], old_log_prob[j] = log_probs[r], advantages[j] = advantages[r], returns[j] = returns[r],
+ * rows_out[j] = r.  8 D + 8 A + 36 bytes per sample with rows_out.  All offsets are 64-bit.  Rows move
+ * in 16-byte pieces when D >= 4, P and the output pitch are multiples of 4 floats and the two
+ * observation bases are 16-byte aligned, in dwords otherwise. */
+typedef struct finenv_rollout_view {     /* finenv_struct_size 30 (29 stays invalid)            */
+    const float *obs;                    /* [n_steps + 1][E][P]                                 */
+    const float *actions;                /* [n_steps][E][A]                                     */
+    const float *values;                 /* [n_steps][E]                                        */
+    const float *log_probs;              /* [n_steps][E]                                        */
+    const float *advantages;             /* [n_steps][E]                                        */
+    const float *returns;                /* [n_steps][E]                                        */
+    int32_t n_steps;                     /* >= 1                                                */
+    int32_t n_envs;                      /* E >= 1; n_steps * E < 2^31                          */
+    int32_t obs_dim;                     /* D >= 1                                              */
+    int32_t obs_pitch;                   /* P >= D, floats                                      */
+    int32_t action_dim;                  /* A >= 1                                              */
+    int32_t reserved0;                   /* 0                                                   */
+} finenv_rollout_view;
+
+typedef struct finenv_rollout_batch {    /* finenv_struct_size 31 */
+    float *observations;                 /* [B][pitch], columns 0 .. D-1 written                */
+    float *actions;                      /* [B][A] packed                                       */
+    float *old_values;                   /* [B]                                                 */
+    float *old_log_prob;                 /* [B]                                                 */
+    float *advantages;                   /* [B]                                                 */
+    float *returns;                      /* [B]                                                 */
+    int32_t batch_size;                  /* B >= 1                                              */
+    int32_t obs_pitch;                   /* row pitch of observations, >= D                     */
+} finenv_rollout_batch;
+
+/* One launch: positions first .. first + B - 1 of the epoch in `*epoch` (device int64, read by the
+ * kernel).  `first` and B are by value: first >= 0, first + B <= M.  rows_out: int32 [B] or NULL.
+ * FINENV_ERR_INVALID, before any HIP call, for a null pointer, a dimension below 1, a pitch below
+ * obs_dim, n_steps * n_envs >= 2^31 or broken bounds of first / B. */
+int finenv_rollout_minibatch(const finenv_rollout_view *view, const int64_t *epoch, uint64_t seed,
+                             int64_t first, const finenv_rollout_batch *batch, int32_t *rows_out,
+                             void *stream);
 
 /* =====================================================================================
  * Replay buffer for the off-policy agents (DDPG / TD3 / SAC; the reference configures them with
