@@ -21,6 +21,7 @@ _LAZY = {      # name -> module; lazy because these need the native library
     "ReplayBufferSamples": "replay", "NStepReplayBufferSamples": "replay",
     "PrioritizedReplayBuffer": "replay", "PrioritizedReplayBufferSamples": "replay",
     "PrioritizedNStepReplayBufferSamples": "replay",
+    "VecNormalize": "vecnorm", "RunningMeanStd": "vecnorm",
 }
 
 

@@ -297,6 +297,19 @@ class RolloutBatchPtrs(C.Structure):
 # the rollout minibatch's (29 stays invalid: the end of the list above)
 _ROLLOUT_STRUCTS = {30: RolloutViewPtrs, 31: RolloutBatchPtrs}
 
+
+class VecNormPtrs(C.Structure):
+    """finenv_vecnorm: a running-statistics block (mean / var / scale [dim], count), the partials
+    buffer and ticket word of its update launch, dim, the partials capacity, epsilon and clip."""
+    _fields_ = [("mean", C.c_void_p), ("var", C.c_void_p), ("scale", C.c_void_p), ("count", C.c_void_p),
+                ("partials", C.c_void_p), ("ticket", C.c_void_p), ("dim", C.c_int32),
+                ("partials_cap", C.c_int32), ("epsilon", C.c_double), ("clip", C.c_double)]
+
+
+VECNORM_MAX_TILES = 128         # FINENV_VECNORM_MAX_TILES: 2 * this * dim doubles of partials always suffice
+# the running statistics' (32 stays invalid: the end of the list above)
+_VECNORM_STRUCTS = {33: VecNormPtrs}
+
 _lib = None
 
 
@@ -425,6 +438,15 @@ def lib():
         L.finenv_rollout_minibatch.argtypes = [
             C.POINTER(RolloutViewPtrs), C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(RolloutBatchPtrs),
             C.c_void_p, C.c_void_p]
+    if hasattr(L, "finenv_vecnorm_step"):                  # running obs / return statistics (same rule)
+        vn = C.POINTER(VecNormPtrs)
+        L.finenv_vecnorm_refresh.argtypes = [vn, C.c_void_p]
+        L.finenv_vecnorm_update.argtypes = [vn, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.finenv_vecnorm_apply.argtypes = [vn, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_int32, C.c_void_p]
+        L.finenv_vecnorm_step.argtypes = [
+            vn, vn, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+            C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     if L.finenv_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
     L.finenv_struct_size.argtypes = [C.c_int]
@@ -441,6 +463,8 @@ def lib():
         later += sorted(_REPLAY_PER_STRUCTS.items())
     if hasattr(L, "finenv_rollout_minibatch"):
         later += sorted(_ROLLOUT_STRUCTS.items())
+    if hasattr(L, "finenv_vecnorm_step"):
+        later += sorted(_VECNORM_STRUCTS.items())
     for which, cls in list(enumerate(first)) + later:
         if L.finenv_struct_size(which) != C.sizeof(cls):
             raise NativeLibraryError(

@@ -317,6 +317,8 @@ int finenv_struct_size(int which)
     // (29 stays invalid: bindings of the list that ended at 28 probe it as its end)
     case 30: return (int)sizeof(finenv_rollout_view);
     case 31: return (int)sizeof(finenv_rollout_batch);
+    // (32 stays invalid: bindings of the list that ended at 31 probe it as its end)
+    case 33: return (int)sizeof(finenv_vecnorm);
     default: return FINENV_ERR_INVALID;
     }
 }

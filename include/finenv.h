@@ -179,7 +179,7 @@ int         finenv_abi_version(void);
  * 1 = finenv_stock_panel, 2 = finenv_stock_state, 3..5 = the finenv_portfolio_* trio, 6..8 = the finenv_crypto_* trio, 9..11 = the finenv_stocknp_* trio,
  * 12..14 = the finenv_cashpenalty_* trio, 15..17 = the finenv_stoploss_* trio, 19..21 = the finenv_btc_* trio,
  * 23 = finenv_replay_view, 24 = finenv_replay_batch, 26 = finenv_replay_nstep, 28 = finenv_replay_per,
- * 30 = finenv_rollout_view, 31 = finenv_rollout_batch; 22, 25, 27 and 29, like 18, stay invalid as the ends of earlier lists):
+ * 30 = finenv_rollout_view, 31 = finenv_rollout_batch, 33 = finenv_vecnorm; 22, 25, 27, 29 and 32, like 18, stay invalid as the ends of earlier lists):
  * lets a foreign-language binding verify its struct declarations at load time instead of corrupting
  * memory.  Index 18 stays FINENV_ERR_INVALID: it is what marked the end of the first v3 list, and
  * bindings probe it as such. */
@@ -778,6 +778,85 @@ typedef struct finenv_rollout_batch {    /* finenv_struct_size 31 */
 int finenv_rollout_minibatch(const finenv_rollout_view *view, const int64_t *epoch, uint64_t seed,
                              int64_t first, const finenv_rollout_batch *batch, int32_t *rows_out,
                              void *stream);
+
+/* =====================================================================================
+ * Running observation / return statistics (what stable-baselines3's VecNormalize and RunningMeanStd
+ * keep between a VecEnv and PPO / A2C / SAC; SB3 is not vendored in the reference: parity unpinned,
+ * defined against the documented formulas, restated in tests/vecnorm_model.py).
+ *
+ * Stats block (caller-owned device memory, float64): mean[dim] and var[dim], starting at 0 and 1; one
+ * count, starting at 1e-4; scale[d] = 1 / sqrt(var[d] + epsilon), stored so that applying takes no
+ * division or square root per element.
+ *
+ * Update with a batch x of n rows: bm[d], bv[d] = the batch mean and POPULATION variance of column d,
+ * then Chan's merge
+ *   delta = bm - mean;  tot = count + n;  mean += delta * n / tot;
+ *   var = (var * count + bv * n + delta^2 * count * n / tot) / tot;  count = tot;  scale recomputed.
+ * The batch moments come from one read of x: rows are cut into at most FINENV_VECNORM_MAX_TILES tiles
+ * of equal height (the last one ragged), each tile accumulates the float64 sums of (x - K) and
+ * (x - K)^2 with K the tile's own first row -- never a plain sum of x^2, which loses the variance of a
+ * column like 1e6 +- 1 to cancellation -- and the tiles' (n, mean, M2) merge by Chan's rule
+ * (mean += delta * w, M2 += M2_b + delta^2 * w', w = n_b / tot, w' = n * n_b / tot) in a fixed order:
+ * runs of consecutive tiles in tile order, then the runs in order.  The last block of the launch (one
+ * ticket per block on `ticket`) does that merge and the one into the running stats, then resets the
+ * ticket, so nothing waits, no floating-point atomic is used, and the same call on the same state gives
+ * the same bits.  The tiling depends on (n_rows, dim) and on
+ * whether rows move in 16-byte units (x 16-byte aligned, pitch a multiple of 4 floats, dim >= 4) or in
+ * dwords; within one of those forms the result is a pure function of the data.
+ *
+ * Apply:  y = (double(x) - mean[d]) * scale[d];  y < -clip ? -clip : y > clip ? clip : y;  one rounding
+ * to float32.  A NaN stays a NaN.  The subtract and the multiply round separately (the library builds
+ * with -ffp-contract=off).  SB3 divides by sqrt(var + epsilon); multiplying by the stored reciprocal
+ * differs from that by at most one rounding before the cast.  center = 0 drops the subtraction (the
+ * reward form).  out == x with equal pitches works; columns dim .. pitch_out-1 are never written.
+ * ===================================================================================== */
+#define FINENV_VECNORM_MAX_TILES 128
+typedef struct finenv_vecnorm {          /* finenv_struct_size 33 (32 stays invalid)            */
+    double   *mean;                      /* [dim]                                               */
+    double   *var;                       /* [dim]                                               */
+    double   *scale;                     /* [dim]  1 / sqrt(var + epsilon)                      */
+    double   *count;                     /* [1]                                                 */
+    double   *partials;                  /* [partials_cap] scratch of an update launch          */
+    uint32_t *ticket;                    /* one word, 0 between launches                        */
+    int32_t   dim;                       /* >= 1                                                */
+    int32_t   partials_cap;              /* doubles; 2 * FINENV_VECNORM_MAX_TILES * dim always
+                                            suffices (an update needs 2 * tiles * dim)          */
+    double    epsilon;
+    double    clip;
+} finenv_vecnorm;
+
+/* scale[d] = 1 / sqrt(var[d] + epsilon) from the block's var (after the caller wrote mean / var /
+ * count itself, e.g. loading saved statistics): one launch. */
+int finenv_vecnorm_refresh(const finenv_vecnorm *stats, void *stream);
+
+/* One launch: merge the n_rows x dim float32 batch x (rows `pitch` floats apart) into the stats.
+ * FINENV_ERR_INVALID, before any launch, for a null pointer, dim < 1, n_rows < 1, pitch < dim or a
+ * partials_cap too small for this launch. */
+int finenv_vecnorm_update(const finenv_vecnorm *stats, const float *x, int64_t n_rows, int64_t pitch,
+                          void *stream);
+
+/* One launch: out[r][d] = apply(x[r][d]) for d < dim with the stats as they are.  center != 0: subtract
+ * the mean; 0: scale and clip only.  Same refusals (pitch_in and pitch_out both >= dim). */
+int finenv_vecnorm_apply(const finenv_vecnorm *stats, const float *x, int64_t n_rows, int64_t pitch_in,
+                         float *out, int64_t pitch_out, int32_t center, void *stream);
+
+/* VecNormalize.step_wait in SB3's order, for the [E, dim] observation and the reward / done of one env
+ * step.  training != 0, two launches:
+ *   1. update obs_stats with obs               2. obs_out = apply(obs) with the NEW stats
+ *   3. returns[e] = returns[e] * gamma + reward[e]   (float64, * and + rounded separately)
+ *   4. update ret_stats (dim 1) with returns   5. reward_out[e] = clip(double(reward[e]) * ret scale)
+ *   6. returns[e] = 0 where done[e]
+ * (1, 3, 4 in the first launch; 2, 5, 6 in the second).  training == 0: one launch, steps 2 and 5 only,
+ * both stats blocks untouched.  norm_obs == 0 switches steps 1 and 2 off (obs_out is a copy of obs),
+ * norm_reward == 0 steps 3 to 6 (reward_out is a copy of reward).  done_out: NULL, or uint8 [E] that
+ * receives a copy of done in the last launch.  obs_out may be obs, reward_out may be reward.
+ * FINENV_ERR_INVALID, before any launch, for a null struct or pointer (done_out apart), n_envs < 1,
+ * a pitch below obs_stats->dim, ret_stats->dim != 1 or a partials_cap too small. */
+int finenv_vecnorm_step(const finenv_vecnorm *obs_stats, const finenv_vecnorm *ret_stats,
+                        const float *obs, int64_t obs_pitch, const float *reward, const uint8_t *done,
+                        double *returns, double gamma, float *obs_out, int64_t obs_out_pitch,
+                        float *reward_out, uint8_t *done_out, int32_t n_envs, int32_t training,
+                        int32_t norm_obs, int32_t norm_reward, void *stream);
 
 /* =====================================================================================
  * Replay buffer for the off-policy agents (DDPG / TD3 / SAC; the reference configures them with
