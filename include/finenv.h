@@ -1574,6 +1574,20 @@ int finenv_stoploss_history_metrics(finenv_stoploss *h, double annualization, do
  * after done, auto_reset off, no reset -- makes no trade and keeps its state; the step writes the
  * current observation, reward 0 (FINENV_BF_LAST_REWARD too) and done 1, and reads no row outside
  * the panel.
+ *
+ * Action and panel domain.  Prices are finite and > 0, at any magnitude (1e-4 .. 1e8 are tested), and
+ * the initial account is any positive value (1e2 .. 1e12 are tested).  The reference divides by
+ * price[day][0] unguarded (:87, :92): zero, negative, NaN and infinite prices are unspecified here --
+ * no access outside the panel, no fault, values not defined.  Actions are ANY float32, and with prices
+ * and account in the domain every state field, reward and observation stays finite:
+ *   +-0, NaN      trade nothing (neither `a < 0` nor `a > 0` holds, :85, :91)
+ *   |a| > 1       is not clipped; the two min()s are the only caps
+ *   +-inf         always binds the cap (a sale is still dropped when the cap is <= 0)
+ *   denormals     float32-denormal actions trade denormal amounts: while the tag is F32, `stocks +/- q`
+ *                 keeps them (a float32 operation without flush to zero), and the observation's
+ *                 stocks * 2^-4 is converted to a float32 denormal, not to 0
+ * tests/test_gpu_btc_domain.py holds the kernel to this bit for bit, at the narrowest and the widest
+ * row; tests/test_gpu_btc_launch_forms.py runs every launch form (D = 62 | 63, 126 | 127, 254).
  * ===================================================================================== */
 #define FINENV_BTC_MAX_PRICE_COLS 245   /* D <= 254: a wave's observation rows fit one block's LDS */
 

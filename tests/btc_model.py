@@ -21,6 +21,10 @@ TAG_TYPES = (float, np.float32, np.float64)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TECH_SCALE = (2.0 ** -1, 2.0 ** -15, 2.0 ** -15, 2.0 ** -6, 2.0 ** -6, 2.0 ** -15, 2.0 ** -15)
 OP_RESET, OP_STEP = 0, 1
+# float32 actions outside uniform(-1, 1): zeros, denormals, the largest finite values, +-inf, NaN,
+# values past +-1 and +-1 themselves (btc_domain, tests/test_gpu_btc_domain.py)
+SPECIAL_ACTIONS = np.array([0.0, -0.0, 1e-45, -1e-45, 1e-38, 1e30, -1e30, 3.4e38, -3.4e38, np.inf, -np.inf,
+                            np.nan, 2.5, -7.0, 1.0, -1.0], np.float32)
 
 
 def r32(x):
@@ -166,6 +170,28 @@ def check_against(case, i, obs, reward, done, state, what=""):
     assert int(state["tag"]) == int(case["tag"][i]), f"{msg}: tag"
 
 
+def fixture_branches(case):
+    """How often the recorded steps of a fixture case took each cap branch, from the recorded state in
+    front of each step alone (a case starts with a reset): the counts make_golden_btc.py's Recorder
+    kept when it ran."""
+    n = dict(short_cap=0, zero_sell=0, buy_cap=0, negative_buy=0)
+    day = 0
+    for i, op in enumerate(case["ops"]):
+        if op == OP_RESET:
+            day = 0
+            continue
+        a, adj = float(case["actions"][i]), float(case["price_ary"][day, 0])
+        if a < 0:
+            cap = 0.5 * float(case["total_asset"][i - 1]) / adj + float(case["stocks"][i - 1])
+            n["short_cap"] += 0 < cap < -a
+            n["zero_sell"] += cap <= 0
+        elif a > 0:
+            n["buy_cap"] += float(case["account"][i - 1]) / adj < a
+            n["negative_buy"] += float(case["account"][i - 1]) < 0
+        day += 1
+    return n
+
+
 # ---------------------------------------------------------------------- draw_cumulative_return
 class StubTensor:
     def __init__(self, a):
@@ -282,3 +308,41 @@ def assert_step_equal(env, got, want, what=""):
     st = env.state_numpy()
     np.testing.assert_array_equal(bits(st["last_reward"]), bits(m_rew), err_msg=f"{what}: last_reward")
     return st
+
+
+def assert_terminal_rows(term, want, what=""):
+    """The terminal-observation rows of the envs that ModelBatch.step reported done."""
+    rows = term.cpu().numpy()
+    for e, row in want[3].items():
+        np.testing.assert_array_equal(bits(rows[e]), bits(row), err_msg=f"{what}: terminal obs of env {e}")
+
+
+def replay_recording_with_auto_reset(env, case, to_device, what=""):
+    """A fixture case that is one reset and one episode, on every env of a batched env with auto_reset
+    on and terminal observations enabled: each env equals the recorded row after every op.  The step
+    that ends the episode returns the recorded reward, latches the recorded returns, leaves the
+    reference's last observation in the terminal rows, and shows the recorded reset: its observation,
+    the initial account, no stocks, tag PY."""
+    E = env.num_envs
+    term = env.enable_terminal_obs()
+    assert case["ops"][0] == OP_RESET and (case["ops"][1:] == OP_STEP).all()
+    for i, op in enumerate(case["ops"]):
+        msg = f"{what} op {i}"
+        fresh = op == OP_RESET or bool(case["done"][i])
+        if op == OP_RESET:
+            obs = env.reset().cpu().numpy()
+        else:
+            obs, rew, done, _ = env.step(to_device(np.full((E, 1), case["actions"][i], np.float32)))
+            obs = obs.cpu().numpy()
+            assert (bits(rew.cpu().numpy()) == bits(np.float32(case["reward"][i]))).all(), msg
+            assert (done.cpu().numpy() == case["done"][i]).all(), msg
+        assert (bits(obs) == bits(case["obs"][0 if fresh else i])[None, :]).all(), msg
+        st = env.state_numpy()
+        if op == OP_STEP:
+            assert (bits(st["last_reward"]) == bits(case["reward"][i])).all(), msg
+        for k in STATE_F64:
+            assert (bits(st[k]) == bits(case[k][0 if fresh and k in STATE_F64[:3] else i])).all(), f"{msg}: {k}"
+        assert (st["stocks_tag"] == case["tag"][0 if fresh else i]).all(), msg
+        assert (st["day"] == (0 if fresh else i)).all(), msg
+    assert case["done"][-1] == 1 and case["done"].sum() == 1
+    assert (bits(term.cpu().numpy()) == bits(case["obs"][-1])[None, :]).all(), f"{what}: terminal obs"

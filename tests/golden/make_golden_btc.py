@@ -15,12 +15,14 @@ import json
 import os
 import sys
 import tempfile
+import warnings
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from btc_model import OP_RESET, OP_STEP, RECORDED, StubArgs, StubTorch, tag_of  # noqa: E402
+from btc_model import (OP_RESET, OP_STEP, RECORDED, SPECIAL_ACTIONS, StubArgs, StubTorch,  # noqa: E402
+                       bits, tag_of)
 
 REFERENCE_ROOT = os.environ.get("FINRL_REFERENCE_ROOT")
 
@@ -98,6 +100,22 @@ class Recorder:
 
 def make(Env, price, tech, **kwargs):
     return Recorder(Env(price_ary=price, tech_ary=tech, **kwargs), kwargs)
+
+
+def reaches(recs, specials=()):
+    """What a whole fixture (its Recorders) must contain: every cap branch at least twice, all three
+    stocks tags, and every special action, by its bits, on a recorded step -- episode() stops at done,
+    so no recorded step is past the end.  Every recorded number must be finite."""
+    for r in recs:
+        steps = np.asarray(r.rows["ops"]) == OP_STEP
+        for k in RECORDED:
+            v = np.asarray(r.rows[k], np.float64)
+            assert np.isfinite(v[steps] if k == "reward" else v).all(), k
+    applied = {int(bits(np.float32(a))[0]) for r in recs for a, op in zip(r.rows["actions"], r.rows["ops"])
+               if op == OP_STEP}
+    return min(sum(r.branches[k] for r in recs) for k in recs[0].branches) >= 2 and \
+        set().union(*(r.rows["tag"] for r in recs)) == {0, 1, 2} and \
+        all(int(bits(np.float32(s))[0]) in applied for s in specials)
 
 
 def actions_for(rng, env, scale=1.0):
@@ -198,8 +216,56 @@ def btc_draw(Env):
     return {"draw": r}, extra
 
 
+# (P, W) of btc_widths: D = P + 9 = 62, 63, 126, 127, 254 -- both edges of the kernel's three launch
+# forms; price level x initial account of btc_domain, both extremes of each
+WIDTHS = ((53, 7), (54, 9), (117, 12), (118, 7), (245, 7))
+DOMAIN = ((1e-4, 1e2), (1e-4, 1e12), (300.0, 1e3), (3e4, 1e6), (1e8, 1e2), (1e8, 1e12))
+
+
+def btc_widths(Env):
+    for seed in range(256):
+        rng = np.random.default_rng(seed)
+        out = {}
+        for P, W in WIDTHS:
+            price, tech = panel(rng, 8, P, W)
+            r = make(Env, price, tech, initial_account=1e3, **WHOLE)
+            r.reset()
+            r.episode(actions_for(rng, r.env, scale=2.0))
+            assert r.env.state_dim == 2 + P + W and r.rows["obs"][0].shape == (P + 9,)
+            out[f"p{P}w{W}"] = r
+        if reaches(list(out.values())):
+            print("  btc_widths: seed", seed)
+            return out
+    raise AssertionError("no seed takes each cap branch twice")
+
+
+def domain_actions(rng, n):
+    """uniform(-1, 1) * 10^k, k in -3 .. 3 drawn per step, and every special value on one step."""
+    a = (rng.uniform(-1, 1, n) * 10.0 ** rng.integers(-3, 4, n)).astype(np.float32)
+    a[rng.permutation(n)[:len(SPECIAL_ACTIONS)]] = SPECIAL_ACTIONS
+    return a
+
+
+def btc_domain(Env):
+    for seed in range(256):
+        rng = np.random.default_rng(seed)
+        out = {}
+        for level, account in DOMAIN:
+            price, tech = panel(rng, 40, 1, 7, price=level)
+            r = make(Env, price, tech, initial_account=account, **WHOLE)
+            r.reset()
+            with warnings.catch_warnings():               # the reference warns of nothing in the domain
+                warnings.simplefilter("error")
+                r.episode(domain_actions(rng, r.env.max_step - 1))
+            out[f"price{level:g}_account{account:g}"] = r
+        if reaches(list(out.values()), SPECIAL_ACTIONS):
+            print("  btc_domain: seed", seed)
+            return out
+    raise AssertionError("no seed reaches every branch, tag and special action")
+
+
 FIXTURES = dict(btc_basic=btc_basic, btc_caps=btc_caps, btc_wide=btc_wide, btc_modes=btc_modes,
-                btc_midreset=btc_midreset, btc_draw=btc_draw)
+                btc_midreset=btc_midreset, btc_draw=btc_draw, btc_widths=btc_widths, btc_domain=btc_domain)
 
 
 def main(names):

@@ -7,7 +7,8 @@ import pytest
 
 import btc_model as bm
 
-FIXTURES = ("btc_basic", "btc_caps", "btc_wide", "btc_modes", "btc_midreset", "btc_draw")
+FIXTURES = ("btc_basic", "btc_caps", "btc_wide", "btc_modes", "btc_midreset", "btc_draw", "btc_widths",
+            "btc_domain")
 CASES = [(f, c) for f in FIXTURES for c in bm.load_fixture(f)]
 
 
@@ -41,6 +42,35 @@ def test_fixtures_reach_the_rules():
     mid = bm.load_fixture("btc_midreset")["midreset"]
     k = int(np.flatnonzero(mid["ops"] == bm.OP_RESET)[1])
     assert mid["gamma_return"][k] == mid["gamma_return"][k - 1] != 0.0
+
+
+@pytest.mark.parametrize("fixture", ["btc_widths", "btc_domain"])
+def test_wide_and_domain_fixtures_reach_the_rules(fixture):
+    """Over the whole fixture: every cap branch at least twice, all three tags, short and overdrawn
+    states, nothing non-finite; btc_widths has the five widths, btc_domain every special action (by
+    its bits) and both extremes of price level and account."""
+    cases = bm.load_fixture(fixture)
+    counts = [bm.fixture_branches(c) for c in cases.values()]
+    assert min(sum(n[k] for n in counts) for k in counts[0]) >= 2, counts
+    assert set(np.concatenate([c["tag"] for c in cases.values()]).tolist()) == {bm.PY, bm.F32, bm.F64}
+    assert any((c["stocks"] < 0).any() for c in cases.values())
+    assert any((c["account"] < 0).any() for c in cases.values())
+    for c in cases.values():
+        steps = c["ops"] == bm.OP_STEP
+        assert c["ops"][0] == bm.OP_RESET and c["done"].sum() == 1 and c["done"][-1] == 1
+        assert np.isfinite(c["obs"]).all() and np.isfinite(c["reward"][steps]).all()
+        assert all(np.isfinite(c[k]).all() for k in bm.STATE_F64)
+    if fixture == "btc_widths":
+        assert [c["obs"].shape[1] for c in cases.values()] == [62, 63, 126, 127, 254]
+        assert all(c["price_ary"].shape[0] == 8 for c in cases.values())
+    else:
+        assert len(cases) == 6 and all(c["price_ary"].shape == (40, 1) for c in cases.values())
+        for c in cases.values():
+            applied = set(bm.bits(c["actions"][c["ops"] == bm.OP_STEP]).tolist())
+            assert set(bm.bits(bm.SPECIAL_ACTIONS).tolist()) <= applied
+        level = sorted({round(float(np.log10(c["price_ary"][0, 0]))) for c in cases.values()})
+        account = sorted({c["kwargs"]["initial_account"] for c in cases.values()})
+        assert (level[0], level[-1]) == (-4, 8) and (account[0], account[-1]) == (1e2, 1e12)
 
 
 def test_mode_rows_equal_load_data():

@@ -9,7 +9,8 @@ import btc_model as bm
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-FIXTURES = ("btc_basic", "btc_caps", "btc_wide", "btc_modes", "btc_midreset", "btc_draw")
+FIXTURES = ("btc_basic", "btc_caps", "btc_wide", "btc_modes", "btc_midreset", "btc_draw", "btc_widths",
+            "btc_domain")
 CASES = [(f, c) for f in FIXTURES for c in bm.load_fixture(f)]
 SMALL = dict(initial_account=1e3, transaction_fee_percent=1e-3, gamma=0.99)   # btc_caps: the caps bind
 

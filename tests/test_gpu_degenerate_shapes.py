@@ -90,3 +90,80 @@ def test_crypto_and_stocknp_single_env():
     for s in range(T + 2):
         o, r, d, _ = np_env.step(torch.rand(1, N, device="cuda") * 2 - 1)
         assert bool(torch.isfinite(o).all()) and bool(torch.isfinite(r).all())
+
+
+def _btc_run(env, mb, a_of, steps, auto_reset):
+    """reset, then `steps` steps of a batched BitcoinEnv against one tests/btc_model.py model per env,
+    bit for bit; a step past the end (auto_reset off) is the defined no-trade step, then reset()."""
+    import btc_model as bm
+    term = env.enable_terminal_obs()
+    np.testing.assert_array_equal(bm.bits(env.reset().cpu().numpy()), bm.bits(np.stack(list(mb.reset().values()))))
+    bm.assert_state_equal(env.state_numpy(), mb.state(), "reset")
+    first = {k: v.copy() for k, v in mb.state().items()}
+    ends = np.zeros(env.num_envs, int)
+    for k in range(steps):
+        a = a_of(k)
+        past = mb.state()["day"] >= np.array([m.end - 1 for m in mb.m])
+        before = env.state_numpy()
+        obs_before = env.obs.clone()
+        got = env.step(torch.from_numpy(a[:, None]).cuda())
+        want = mb.step(a, auto_reset)
+        st = bm.assert_step_equal(env, got, want, f"step {k}")
+        bm.assert_state_equal(st, mb.state(), f"step {k}")
+        if past.any():                                            # auto_reset off, stepped on the terminal row
+            assert not auto_reset and past.all() and want[2].all() and (want[1] == 0).all()
+            assert torch.equal(got[0], obs_before) and (st["last_reward"] == 0).all()
+            bm.assert_state_equal(st, before, f"past the end {k}")
+            obs = env.reset().cpu().numpy()
+            np.testing.assert_array_equal(bm.bits(obs), bm.bits(np.stack(list(mb.reset().values()))))
+            bm.assert_state_equal(env.state_numpy(), mb.state(), f"reset after {k}")
+            continue
+        bm.assert_terminal_rows(term, want, f"step {k}")          # the row the reference's step() returned
+        ends += want[2]
+        done = want[2]
+        if auto_reset and done.any():                             # the env stands where reset() puts it
+            for f in ("account", "stocks", "total_asset", "stocks_tag", "day"):
+                np.testing.assert_array_equal(st[f][done], first[f][done], err_msg=f"step {k}: {f}")
+            assert (st["stocks_tag"][done] == bm.PY).all()
+    return ends
+
+
+@pytest.mark.parametrize("auto_reset", [True, False], ids=["auto", "manual"])
+@pytest.mark.parametrize("E,T,P,W", [(1, 2, 1, 7), (1, 3, 1, 12), (3, 2, 2, 7), (65, 2, 245, 7)])
+def test_btc_env_smallest_shapes(E, T, P, W, auto_reset):
+    """One env, two-row panels -- every step is terminal --, more indicator columns than rows, and one
+    full wave plus one lane at the widest row."""
+    _need_gpu()
+    import btc_model as bm
+    from finrl_amd.vec_btc import VecBitcoinEnv
+    rng = np.random.default_rng(1000 * E + 10 * T + P)
+    p0 = 300.0 * np.exp(np.cumsum(rng.normal(0, 0.01, T)))
+    price = np.ascontiguousarray(np.stack([p0 * (1 + 0.002 * k) for k in range(P)], 1))
+    tech = rng.normal(0, 3e3, (T, W))
+    kw = dict(initial_account=1e3, transaction_fee_percent=1e-3, gamma=0.99)
+    env = VecBitcoinEnv(price, tech, E, auto_reset=auto_reset, **kw)
+    assert env.obs_dim == P + 9 and env.max_step == T
+    ends = _btc_run(env, bm.ModelBatch(price, tech, E, **kw),
+                    lambda k: rng.uniform(-4, 4, E).astype(np.float32), 6, auto_reset)
+    assert (ends == (6 // (T - 1) if auto_reset else 6 // T)).all()
+
+
+@pytest.mark.parametrize("auto_reset", [True, False], ids=["auto", "manual"])
+def test_btc_env_two_row_windows(auto_reset):
+    """Windows of length 2 at every start of a six-row panel: each env's every step is terminal, on
+    its own rows."""
+    _need_gpu()
+    import btc_model as bm
+    from finrl_amd.vec_btc import VecBitcoinEnv
+    rng = np.random.default_rng(12)
+    T, E = 6, 5
+    price = np.ascontiguousarray((300.0 * np.exp(np.cumsum(rng.normal(0, 0.05, T))))[:, None])
+    tech = rng.normal(0, 3e3, (T, 7))
+    s = np.arange(E)
+    kw = dict(initial_account=1e3, transaction_fee_percent=1e-3, gamma=0.99)
+    env = VecBitcoinEnv(price, tech, E, auto_reset=auto_reset, windows=(s, s + 2), **kw)
+    assert env.max_step == 2
+    ends = _btc_run(env, bm.ModelBatch(price, tech, E, start=s, end=s + 2, **kw),
+                    lambda k: rng.uniform(-4, 4, E).astype(np.float32), 6, auto_reset)
+    assert (ends == (6 if auto_reset else 3)).all()
+    assert len(np.unique(env.state_numpy()["day"])) == E
