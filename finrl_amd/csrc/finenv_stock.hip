@@ -206,6 +206,7 @@ struct finenv_stock : finenv_host::Handle {
     int32_t *win;         // finenv_stock_set_windows
     int has_hist;         // finenv_stock_set_history
     finenv_stock_history hist;
+    finenv_stock_impl::StepPlan plan;     // how step() launches: plan_step()
 };
 
 namespace {
@@ -234,13 +235,53 @@ int launch_aux(finenv_stock *h, const Params &p, int mode, hipStream_t stream)
     return 0;
 }
 
-// step kernel: one 128-thread block per 64 envs; 33..64 tickers use the 128-wide code paths at
-// half the padding (34 KB of LDS, four blocks per CU instead of two)
-int launch_step(finenv_stock *h, const Params &p, bool turb, bool stats, hipStream_t stream)
+// Decide how step() launches, once per change of what decides it (bind, set_windows, set_desync_hint), so that
+// a step makes no HIP call but its launches.  The kernel: 33..64 tickers use the 128-wide code paths at half
+// the padding (34 KB of LDS, four blocks per CU instead of two).  The round: occupancy x CUs on the device
+// that owns the state block (the current one where none does, as for the launches).  A failed query leaves
+// one block per CU on 256 CUs and no error behind; only a refused LDS opt-in is reported, by step().
+void plan_step(finenv_stock *h)
 {
-    if (h->cfg.n_tickers <= 32) return finenv_stock_impl::launch_step_np32(p, turb, stats, h->device, stream);
-    if (h->cfg.n_tickers <= 64) return finenv_stock_impl::launch_step_np64(p, turb, stats, h->device, stream);
-    return finenv_stock_impl::launch_step_np128(p, turb, stats, h->device, stream);
+    const bool win = h->win != nullptr, desync = h->desync_hint != 0;
+    const int N = h->cfg.n_tickers;
+    finenv_stock_impl::StepPlan &pl = h->plan;
+    pl = N <= 32   ? finenv_stock_impl::choose_step_np32(h->cfg, win, desync)
+         : N <= 64 ? finenv_stock_impl::choose_step_np64(h->cfg, win, desync)
+                   : finenv_stock_impl::choose_step_np128(h->cfg, win, desync);
+    const void *fn = reinterpret_cast<const void *>(pl.kernel);
+    const finenv_host::DeviceGuard guard(h->device);
+    int dev = h->device, cus = 0, per_cu = 0;
+    if (dev < 0) (void)hipGetDevice(&dev);
+    // > 64 KiB of dynamic LDS needs an explicit opt-in on every device that runs the kernel
+    pl.lds_refused = pl.lds_bytes > 64 * 1024 &&
+                     hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kStepThreads, pl.lds_bytes) != hipSuccess || per_cu < 1)
+        per_cu = 1;
+    (void)hipGetLastError();
+    pl.round = per_cu * cus;
+}
+
+// The step kernels are built for ONE resident round of blocks (every block in the same phase: traders
+// loading while nobody stores yet, streamers streaming while traders compute).  Handed more blocks than
+// fit at once, the hardware refills slots as blocks finish, phases mix -- traders' loads queue behind
+// other blocks' stores -- and the per-env cost rises by a third (DOW30: 65,536 envs 0.64 of the
+// roofline, 262,144 envs 0.47; profiles/r03_placement.md).  So a large batch is stepped as
+// ceil(blocks / round) launches of equal size on the caller's stream, each one resident round or less.
+void launch_step_rounds(const finenv_stock_impl::StepPlan &pl, const Params &p, hipStream_t stream)
+{
+    // one 128-thread block per 64 envs
+    const int blocks = (p.cfg.n_envs + kWave - 1) / kWave;
+    const int k = (blocks + pl.round - 1) / pl.round;              // launches
+    const int chunk = k > 1 ? (blocks + k - 1) / k : blocks;
+    Params q = p;
+    int b = 0;
+    do {
+        q.block_base = b;
+        const int nb = blocks - b < chunk ? blocks - b : chunk;
+        hipLaunchKernelGGL(pl.kernel, dim3((unsigned)nb), dim3(kStepThreads), pl.lds_bytes, stream, q);
+        b += chunk;
+    } while (b < blocks);
 }
 
 HistoryArgs make_history_args(const finenv_stock *h)
@@ -383,7 +424,9 @@ int finenv_stock_obs_dim(const finenv_stock *h) { return finenv_host::obs_dim(h)
 int finenv_stock_set_desync_hint(finenv_stock *h, int32_t on)
 {
     if (!h) return FINENV_ERR_INVALID;
+    const int was = h->desync_hint;
     h->desync_hint = on != 0;
+    if (h->bound && was != h->desync_hint) plan_step(h);
     return FINENV_OK;
 }
 
@@ -406,7 +449,9 @@ int finenv_stock_bind(finenv_stock *h, const finenv_stock_panel *panel,
         return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null panel pointer");
     if (!st->f64 || !st->i32)
         return finenv_host::fail(h, FINENV_ERR_INVALID, "bind: null state pointer");
-    return finenv_host::bind(h, panel, st);
+    finenv_host::bind(h, panel, st);
+    plan_step(h);
+    return FINENV_OK;
 }
 
 int finenv_stock_init(finenv_stock *h, int32_t day0, void *stream)
@@ -481,9 +526,8 @@ int finenv_stock_step(finenv_stock *h, const float *actions, float *obs, float *
     }
 #endif
     const hipStream_t s = (hipStream_t)stream;
-    const bool turb = h->cfg.use_turbulence != 0, stats = h->cfg.track_stats != 0;
-    const int rc = launch_step(h, p, turb, stats, s);
-    if (rc) return finenv_host::fail(h, FINENV_ERR_HIP, "step: cannot raise the dynamic LDS limit");
+    if (h->plan.lds_refused) return finenv_host::fail(h, FINENV_ERR_HIP, "step: cannot raise the dynamic LDS limit");
+    launch_step_rounds(h->plan, p, s);
     if (h->has_hist) {      // behind the step kernel (its last round): reads done, realised and the new state
         HistoryArgs a = make_history_args(h);
         a.done = done;
@@ -517,7 +561,9 @@ int finenv_stock_set_last_episode(finenv_stock *h, double *last)
 int finenv_stock_set_windows(finenv_stock *h, int32_t *win)
 {
     if (!h) return FINENV_ERR_INVALID;
+    const bool was = h->win != nullptr;
     h->win = win;
+    if (h->bound && was != (win != nullptr)) plan_step(h);
     return FINENV_OK;
 }
 

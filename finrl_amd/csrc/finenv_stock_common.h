@@ -37,7 +37,7 @@ struct Params {
     int32_t day0;
     uint32_t magicN;      // ceil(2^32 / N) for N >= 2 (exact f / N for f < 2^16)
     int32_t block_base;   // first 64-env group of this launch (batches larger than one resident round of
-                          // blocks are stepped as several launches: launch_step_rounds below)
+                          // blocks are stepped as several launches: launch_step_rounds, finenv_stock.hip)
     int32_t diag;         // FINENV_DIAG builds only: phase-skip bitmask (timing experiments)
     unsigned long long *dbg;   // FINENV_DIAG builds only: [block][role][16] s_memrealtime stamps
     double *last;         // last-episode block [FINENV_STOCK_LAST_FIELDS][E] or NULL
@@ -52,61 +52,6 @@ constexpr int kStepThreads = 2 * kWave;
 
 using finenv_stock_impl::Params;
 
-// The step kernels are built for ONE resident round of blocks (every block in the same phase: traders
-// loading while nobody stores yet, streamers streaming while traders compute).  Handed more blocks than
-// fit at once, the hardware refills slots as blocks finish, phases mix -- traders' loads queue behind
-// other blocks' stores -- and the per-env cost rises by a third (DOW30: 65,536 envs 0.64 of the
-// roofline, 262,144 envs 0.47; profiles/r03_placement.md).  So a large batch is stepped as
-// ceil(blocks / round) launches of equal size on the caller's stream, each one resident round or less.
-// `Kernel` is a template VALUE: the occupancy figure and the LDS opt-in below are cached per kernel, which
-// is what they depend on (every stock_step_kernel<...> has the same function type).
-// Returns 0, or -1 when the dynamic-LDS limit could not be raised.
-template <auto Kernel>
-int launch_step_rounds(const Params &p, size_t lds_bytes, int device, hipStream_t stream)
-{
-    // > 64 KiB of dynamic LDS needs an explicit opt-in, once per device (a process may hold handles on
-    // several GPUs)
-    if (lds_bytes > 64 * 1024) {
-        static unsigned long long attr_set_mask = 0ull;
-        const int dev = device >= 0 && device < 64 ? device : 0;
-        if (!((attr_set_mask >> dev) & 1ull)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds_bytes) != hipSuccess)
-                return -1;
-            attr_set_mask |= 1ull << dev;
-        }
-    }
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-               prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    static int per_cu = 0;
-    if (per_cu == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(Kernel), kStepThreads,
-                                                         lds_bytes) != hipSuccess || nb < 1)
-            nb = 1;
-        per_cu = nb;
-    }
-    // one 128-thread block per 64 envs
-    const int blocks = (p.cfg.n_envs + kWave - 1) / kWave;
-    const int round = per_cu * cus;
-    const int k = (blocks + round - 1) / round;                    // launches
-    const int chunk = k > 1 ? (blocks + k - 1) / k : blocks;
-    Params q = p;
-    int b = 0;
-    do {
-        q.block_base = b;
-        const int nb = blocks - b < chunk ? blocks - b : chunk;
-        hipLaunchKernelGGL(Kernel, dim3((unsigned)nb), dim3(kStepThreads), lds_bytes, stream, q);
-        b += chunk;
-    } while (b < blocks);
-    return 0;
-}
-
 #ifdef FINENV_DIAG
 #define DIAG(bit) (p.diag & (bit))
 // phase stamps (100 MHz wall clock) for tools/phase_times.py; diagnostic build only
@@ -114,7 +59,7 @@ int launch_step_rounds(const Params &p, size_t lds_bytes, int device, hipStream_
     do {                                                                                  \
         if (p.dbg != nullptr && lane == 0) {                                              \
             __builtin_amdgcn_sched_barrier(0);                                            \
-            p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+            p.dbg[((size_t)(blockIdx.x + p.block_base) * 2 + role) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
             __builtin_amdgcn_sched_barrier(0);                                            \
         }                                                                                 \
     } while (0)
@@ -178,12 +123,20 @@ __device__ __forceinline__ void ce(int &a, int &b)
 
 }  // namespace
 
-// Launchers exported by the per-width translation units (C++ linkage, library-internal).
+// Exported by the per-width translation units (C++ linkage, library-internal).
 namespace finenv_stock_impl {
-// step(): returns 0, or -1 when the dynamic-LDS limit could not be raised
-int launch_step_np32(const Params &p, bool turb, bool stats, int device, hipStream_t stream);
-int launch_step_np64(const Params &p, bool turb, bool stats, int device, hipStream_t stream);
-int launch_step_np128(const Params &p, bool turb, bool stats, int device, hipStream_t stream);
+// How step() launches (kept in the handle, finenv_stock.hip).  Each width names the kernel instantiation that
+// steps a handle of this config and its dynamic LDS bytes -- `win`: per-env windows are attached, `desync`:
+// finenv_stock_set_desync_hint -- and launches nothing and touches no device; plan_step() fills in the rest.
+struct StepPlan {
+    void (*kernel)(Params);
+    size_t lds_bytes;
+    int round;            // blocks resident on the device at once: occupancy per CU x CUs
+    int lds_refused;      // the kernel needs > 64 KiB of LDS and the device refused the opt-in
+};
+StepPlan choose_step_np32(const finenv_stock_config &cfg, bool win, bool desync);
+StepPlan choose_step_np64(const finenv_stock_config &cfg, bool win, bool desync);
+StepPlan choose_step_np128(const finenv_stock_config &cfg, bool win, bool desync);
 // init / reset / observe (mode 0 / 1 / 2)
 void launch_aux_np32(const Params &p, int mode, hipStream_t stream);
 void launch_aux_np64(const Params &p, int mode, hipStream_t stream);

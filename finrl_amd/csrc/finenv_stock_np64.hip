@@ -1,5 +1,5 @@
 // finenv_stock_np64.hip -- step / aux kernels and launchers of the batched StockTradingEnv for
-// 32 < N <= 64 tickers: namespace np64, finenv_stock_impl::launch_{step,aux}_np64.
+// 32 < N <= 64 tickers: namespace np64, finenv_stock_impl::{choose_step,launch_aux}_np64.
 #define FINENV_NP 64
 #define FINENV_LOG2NP 6
 #define FINENV_SORTNET "sortnet64.inc"

@@ -206,10 +206,18 @@ int  finenv_stock_set_obs_pitch(finenv_stock *h, int32_t pitch);
  * (per-env start days, episodes that end at different steps).  step() then launches the kernel
  * instantiation whose per-env panel-row paths are tuned (16-byte row copies, row-wise price gather,
  * parked head chunks); with every env on the same day -- the reference's training setup, BASELINE's
- * configs -- leave it off: that instantiation carries none of that code. */
+ * configs -- leave it off: that instantiation carries none of that code.
+ * On a bound handle a call that flips the hint chooses the step kernel again and may query the device
+ * (see finenv_stock_bind); before bind it only stores the value. */
 int  finenv_stock_set_desync_hint(finenv_stock *h, int32_t on);
 
-/* Attach the panel and state buffers (replaces self.df / self.state ownership). */
+/* Attach the panel and state buffers (replaces self.df / self.state ownership).
+ * Also decides how finenv_stock_step will launch: the kernel instantiation (from the config, the desync
+ * hint and whether windows are attached) and how many blocks one launch takes (from the occupancy of
+ * that kernel on the device that owns the state block).  bind, and finenv_stock_set_desync_hint /
+ * finenv_stock_set_windows on a bound handle, may therefore query the device -- call them outside a
+ * stream capture; finenv_stock_step never does: it only launches.  A second bind, possibly to a state
+ * block on another device, decides again. */
 int finenv_stock_bind(finenv_stock *h, const finenv_stock_panel *panel,
                       const finenv_stock_state *state);
 
@@ -302,7 +310,10 @@ int finenv_stock_last_episode_stats(finenv_stock *h, double *out, void *stream);
  * block's CONTENTS).  step() reads t_e on every step and s_e only when it resets an env, so an
  * edited end applies from the next step and an edited start at the env's next reset.
  * NULL detaches (the default: every env runs rows 0 .. n_days-1).  Handle-wide settings (initial
- * amounts, costs) stay handle-wide. */
+ * amounts, costs) stay handle-wide.
+ * Attaching or detaching on a bound handle (NULL <-> non-NULL) chooses the step kernel again and may
+ * query the device (see finenv_stock_bind); another non-NULL pointer, or a call before bind, only
+ * stores it. */
 int finenv_stock_set_windows(finenv_stock *h, int32_t *win);
 
 /* Episode history: asset_memory, date_memory and actions_memory (:85-97, :332, :348-349) of every

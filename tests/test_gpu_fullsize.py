@@ -227,7 +227,7 @@ def test_fullsize_desynchronised_sampled_oracle(hint):
 @pytest.mark.parametrize("N,E", [(30, 69_700), (100, 66_000), (50, 40_000)])
 def test_batches_larger_than_one_round_of_blocks(N, E):
     """More 64-env groups than fit on the chip at once: the step is issued as several equal launches
-    (launch_rounds, finenv_stock_common.h), each with its own first group.  Every env of every round -- the
+    (launch_step_rounds, finenv_stock.hip), each with its own first group.  Every env of every round -- the
     last group is a partial wave -- against the oracle on sampled envs, plus size-independent properties
     over the whole batch, across an episode end."""
     _need_gpu()

@@ -158,7 +158,7 @@ def test_multi_round_step_under_graph_capture():
     b_env = VecStockTradingEnv(panel, E, hmax=30, initial_amount=40_000)
     acts = [torch.rand(E, N, device="cuda") * 2 - 1 for _ in range(4)]
     a_env.reset(); b_env.reset()
-    b_env.step(acts[0]); a_env.step(acts[0])          # first call outside the capture (occupancy query, caches)
+    b_env.step(acts[0]); a_env.step(acts[0])          # first call outside the capture (the code object loads lazily)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):

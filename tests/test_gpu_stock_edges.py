@@ -110,6 +110,48 @@ def test_every_step_launch_leaf_matches_the_oracle(N, hmax, desync_hint, windows
     np.testing.assert_array_equal(st["shares"], os_["shares"])
 
 
+# (N, hmax, E): one shape per width path -- np32 (three blocks), np64, WideGeom<100>, generic np128
+@pytest.mark.parametrize("N,hmax,E", [(5, 100, 130), (40, 100, 70), (100, 100, 70), (100, 300, 70)])
+def test_results_do_not_depend_on_the_chosen_step_kernel(N, hmax, E):
+    """The step kernel is chosen when the handle is bound and again when the desync hint flips or
+    windows are attached -- here in the middle of an episode, after steps have run.  Env B goes
+    lock-step -> hinted -> whole-panel windows (0, T) -> hint off and on through an episode end
+    with its auto-reset; its twin A stays lock-step throughout.  Every output and every state tensor
+    of the two are the same bits after every step."""
+    _need_gpu()
+    from finrl_amd import StockPanel
+    from finrl_amd.vec_env import VecStockTradingEnv
+    T, K = 12, 2
+    rng = np.random.default_rng(77 * N + hmax)
+    close = (50 + rng.uniform(0, 10, (T, N))).astype(np.float32).astype(np.float64)
+    tech = rng.normal(0, 1, (T, K, N)).astype(np.float32).astype(np.float64)
+    risk = np.abs(rng.normal(0, 30, T))
+    panel = StockPanel(close, tech, risk)
+    kw = dict(hmax=hmax, initial_amount=1_000_000, num_stock_shares=rng.integers(0, 40, N),
+              turbulence_threshold=float(np.median(risk)), auto_reset=True)
+    a_env, b_env = VecStockTradingEnv(panel, E, **kw), VecStockTradingEnv(panel, E, **kw)
+    for env in (a_env, b_env):
+        env.enable_terminal_obs()
+        env.enable_realised()
+    assert torch.equal(a_env.reset(), b_env.reset())
+    changes = {3: lambda: b_env.hint_desynchronised(True), 6: lambda: b_env.set_windows(0, T),
+               9: lambda: b_env.hint_desynchronised(False)}
+    n_done = 0
+    for s in range(T + 3):                       # the episode ends on step T, after the last change
+        if s in changes:
+            changes[s]()
+        act = torch.from_numpy(rng.uniform(-1, 1, (E, N)).astype(np.float32)).cuda()
+        a_out, b_out = a_env.step(act), b_env.step(act)
+        for name, x, y in zip(("obs", "reward", "done"), a_out, b_out):
+            assert torch.equal(x, y), f"{name}, step {s}"
+        for name in ("term_obs", "realised"):
+            assert torch.equal(getattr(a_env, name), getattr(b_env, name)), f"{name}, step {s}"
+        for name in a_env.state:
+            assert torch.equal(a_env.state[name], b_env.state[name]), f"state {name}, step {s}"
+        n_done += int(a_out[2].all())
+    assert n_done == 1
+
+
 def test_refresh_after_in_place_state_edit():
     """Editing day / price_day of a batch that already HOLDS shares (what bench.py --desync does
     after a reset) makes the carried begin asset stale; finenv_stock_refresh re-evaluates it.  Every

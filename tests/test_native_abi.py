@@ -145,3 +145,39 @@ def test_host_contract_every_kind(L, kind):
         assert launch("step", h) == -2                                   # still unbound
     finally:
         fn("destroy")(h)
+
+
+# one shape per step-kernel family: np32, np64, WideGeom<100>, generic np128 (> 64 KiB of LDS: the opt-in)
+@pytest.mark.parametrize("n_tickers,hmax", [(30, 100), (40, 100), (100, 100), (100, 300)])
+@pytest.mark.parametrize("hint_first", [True, False])
+def test_stock_step_plan_is_made_off_the_step(L, n_tickers, hmax, hint_first):
+    """bind, set_windows and set_desync_hint choose the step kernel and size its launch rounds.  On host
+    pointers that no device owns they succeed whatever the device queries answer, before and after
+    bind and in either order, and leave no error behind: the step that follows reports its own
+    null arguments, not a HIP error of a query."""
+    from finrl_amd import _native as nat
+    cfg = nat.StockConfig(64, n_tickers, 2, 12, hmax, 1, 1, 1, 1, 0, 1e-3, 1e-3, 1e-4, 40.0)
+    buf = np.zeros(4096, dtype=np.float64)                    # never read: nothing here launches
+    ptr = C.c_void_p(buf.ctypes.data)
+    panel, st = nat.StockPanelPtrs(ptr, ptr, ptr), nat.StockStatePtrs(ptr, ptr)
+
+    def setters(h, hint, win):
+        calls = [lambda: L.finenv_stock_set_desync_hint(h, hint),
+                 lambda: L.finenv_stock_set_windows(h, win)]
+        for call in (calls if hint_first else calls[::-1]):
+            assert call() == 0
+
+    h = C.c_void_p()
+    assert L.finenv_stock_create(C.byref(cfg), C.byref(h)) == 0
+    try:
+        setters(h, 1, ptr)                                    # unbound: stored only
+        assert L.finenv_stock_bind(h, C.byref(panel), C.byref(st)) == 0
+        assert L.finenv_stock_last_error(h) == b""
+        for hint, win in ((0, None), (1, ptr), (1, ptr), (0, ptr), (0, None)):   # every edge, and no change
+            setters(h, hint, win)
+            assert L.finenv_stock_last_error(h) == b""
+        assert L.finenv_stock_bind(h, C.byref(panel), C.byref(st)) == 0          # a second bind plans again
+        assert L.finenv_stock_step(h, None, None, None, None, None, None, 1, None) == -1
+        assert L.finenv_stock_last_error(h) == b"step: null actions/obs/reward/done"
+    finally:
+        L.finenv_stock_destroy(h)
