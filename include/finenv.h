@@ -814,6 +814,13 @@ int finenv_rollout_minibatch(const finenv_rollout_view *view, const int64_t *epo
  * the same bits.  The tiling depends on (n_rows, dim) and on
  * whether rows move in 16-byte units (x 16-byte aligned, pitch a multiple of 4 floats, dim >= 4) or in
  * dwords; within one of those forms the result is a pure function of the data.
+ * A NaN or an infinity in x stays in its own column: every other column gets the bits it would get
+ * with a finite value in that cell.  The column itself ends with var = scale = NaN and a non-finite
+ * mean, and stays so over later updates (apply then gives NaN in that column).  A NaN cell gives a NaN
+ * mean.  For an infinite cell the mean depends on where the cell sits: as the first row of its tile it
+ * is that tile's K, and inf - inf makes the mean NaN; elsewhere the tile's mean is that infinity, and
+ * it survives the merge only in the last tile, since any tile merged after it adds (finite - inf) to it,
+ * a NaN again; the next update does the same.
  *
  * Apply:  y = (double(x) - mean[d]) * scale[d];  y < -clip ? -clip : y > clip ? clip : y;  one rounding
  * to float32.  A NaN stays a NaN.  The subtract and the multiply round separately (the library builds

@@ -8,13 +8,12 @@ most n * 2^-53 relative to sum (x-K)^2, which is at most about 50 * n * var for 
 about 4e-10; 1e-8 leaves a margin of 25): var at rtol 1e-8, mean at atol 1e-8 * sigma (1e-8 * |mean|
 for a constant column), count exact.  A plain sum of x^2 misses this on the 1e6 column by orders of
 magnitude."""
-import functools
-
 import numpy as np
 import pytest
 
 import vecnorm_model as vm
 from replay_cases import need_gpu
+from vecnorm_cases import gaussian_columns
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -22,22 +21,6 @@ torch = pytest.importorskip("torch")
 SENTINEL = -7777.0
 ROWS = (1, 70, 259, 70001)
 DIMS = ((1, 1), (3, 3), (291, 291), (291, 304), (1001, 1001))      # (dim, row pitch)
-
-
-@functools.lru_cache(maxsize=2)
-def gaussian_columns(n, dim):
-    """float32 [n, dim]: column 0 has mean 1e6 and sigma 1, the last column (dim > 1) is constant, the
-    others have means and sigmas over six orders of magnitude -> (x, sigma per column, 0 = constant)."""
-    rng = np.random.default_rng(1000 * dim + n % 997)
-    mean = rng.uniform(-1, 1, dim) * 10.0 ** rng.integers(-2, 5, dim)
-    sigma = 10.0 ** rng.uniform(-2, 3, dim)
-    mean[0], sigma[0] = 1e6, 1.0
-    if dim > 1:
-        mean[-1], sigma[-1] = 123456.0, 0.0
-    x = rng.standard_normal((n, dim), dtype=np.float32)
-    x *= sigma.astype(np.float32)
-    x += mean.astype(np.float32)
-    return x, sigma
 
 
 def on_device(x, pitch, fill=float("nan")):

@@ -1,7 +1,86 @@
 """NumPy restatement of finrl_amd's VecNormalize (include/finenv.h, "Running observation / return
 statistics"): stable-baselines3's documented RunningMeanStd / VecNormalize formulas in float64 -- a
-two-pass batch mean and population variance, Chan's merge, the apply formula and the step order."""
+two-pass batch mean and population variance, Chan's merge, the apply formula and the step order.
+
+Two more restatements serve the tests only: `tiling` / `apply_tiling` repeat the host's choice of lane
+layout, row tiles and merge runs (finenv_vecnorm.hip: layout_for, tiles_for, finalize), so that a test
+can assert which path its shape takes, and `exact_stats` evaluates the documented recurrences in
+rational arithmetic, which is what this float64 model is itself checked against."""
+import collections
+import decimal
+import fractions
+
 import numpy as np
+
+MB, AB, APPLY_ROWS = 1024, 256, 16        # threads of a moments / an apply block; rows per apply lane
+MAX_TILES = 128                           # FINENV_VECNORM_MAX_TILES
+FIN_GROUPS, FIN_DEPTH = 16, 16            # merge runs per column at most; tiles in flight per run
+
+Tiling = collections.namedtuple("Tiling", "vec lg chunks rl tile_rows tiles runs per column_blocks")
+ApplyTiling = collections.namedtuple("ApplyTiling", "vec lg chunks tile_rows tiles")
+
+
+def _layout(dim, pitches_ok, aligned):
+    vec = bool(aligned and pitches_ok and dim >= 4)
+    units, cap = ((dim + 3) // 4, 16) if vec else (dim, 64)
+    lg = 0
+    while (1 << lg) < cap and (1 << lg) < units:
+        lg += 1
+    return vec, lg, (units + (1 << lg) - 1) >> lg
+
+
+def tiling(n_rows, dim, pitch, aligned=True):
+    """The moments launch of an [n_rows, dim] batch with rows `pitch` floats apart (`aligned`: its base
+    is 16-byte aligned): 16-byte units or dwords, log2 of the unit-lanes side by side, column chunks,
+    row-lanes of a block, rows per tile, tiles, then the last block's merge: runs per column, tiles per
+    run, and the blocks of 1024 columns it walks."""
+    vec, lg, chunks = _layout(dim, pitch % 4 == 0, aligned)
+    rl = MB >> lg
+    tile_rows = -(-n_rows // (rl * MAX_TILES)) * rl
+    tiles = -(-n_rows // tile_rows)
+    runs = min(MB // dim if dim <= MB else 1, FIN_GROUPS)
+    per = -(-tiles // runs)
+    runs = -(-tiles // per)
+    return Tiling(vec, lg, chunks, rl, tile_rows, tiles, runs, per, -(-dim // MB))
+
+
+def apply_tiling(n_rows, dim, pitch_in, pitch_out, aligned=True):
+    """The matrix part of an apply launch: the layout both tensors allow, rows per tile, row tiles."""
+    vec, lg, chunks = _layout(dim, (pitch_in | pitch_out) % 4 == 0, aligned)
+    tile_rows = (AB >> lg) * APPLY_ROWS
+    return ApplyTiling(vec, lg, chunks, tile_rows, -(-n_rows // tile_rows))
+
+
+def exact_stats(batches, epsilon=1e-8):
+    """The documented recurrences over float32 batches ([n, dim] each) in rational arithmetic, from
+    mean 0, var 1 and the float64 value of 1e-4 as the count -> (mean, var, count, scale): float64
+    roundings of the exact mean / var / count, and of 1 / sqrt(var + epsilon) taken at 50 digits.
+    Cost grows with every update (the denominators do): for small inputs only."""
+    F = fractions.Fraction
+    first = np.asarray(batches[0], np.float32)
+    dim = first.reshape(len(first), -1).shape[1]
+    mean, var, count = [F(0)] * dim, [F(1)] * dim, F(1e-4)
+    for x in batches:
+        x = np.asarray(x, np.float32).reshape(len(x), -1)
+        n = x.shape[0]
+        tot = count + n
+        for d in range(dim):
+            col = [F(float(v)) for v in x[:, d]]
+            bm = sum(col) / n
+            bv = sum((v - bm) ** 2 for v in col) / n
+            delta = bm - mean[d]
+            var[d] = (var[d] * count + bv * n + delta * delta * count * n / tot) / tot
+            mean[d] = mean[d] + delta * n / tot
+        count = tot
+    ctx = decimal.Context(prec=50)
+    eps = F(float(epsilon))
+    scale = []
+    for v in var:
+        v = v + eps
+        root = ctx.sqrt(ctx.divide(decimal.Decimal(v.numerator), decimal.Decimal(v.denominator)))
+        scale.append(float(ctx.divide(decimal.Decimal(1), root)))
+    as_f64 = lambda q: np.array([float(v) for v in q], np.float64)      # Fraction -> float rounds once
+    return as_f64(mean), as_f64(var), float(count), np.array(scale, np.float64)
 
 
 class RunningMeanStd:
