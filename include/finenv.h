@@ -387,6 +387,26 @@ int finenv_stock_history_metrics(finenv_stock *h, double annualization, double *
  *   reward  = new portfolio value, unscaled (:196-198)
  * Per-env state: portfolio_value, last reward (f64), day (i32).
  * ===================================================================================== */
+/* Portfolio action and panel domain (stated here once; tests/test_gpu_portfolio_domain.py holds the
+ * kernel to it).  The weights are the reference's softmax as written (:225-229), NOT a stabilised one:
+ * float32 exp of every score, their float32 sum in NumPy's order (left to right below 8 terms, 8
+ * accumulators combined pairwise from 8 on), one float32 division per weight.  No maximum is subtracted
+ * and nothing is clamped, so what IEEE arithmetic makes of a score is the contract:
+ *   - scores of any sign are fine; a score below about -87.3 has a subnormal exponential (coarse weights),
+ *     one below about -104, or -inf, the exponential 0;
+ *   - a score of 88.73 or more has the exponential +inf: that weight is inf / inf = NaN and every other
+ *     weight of the env 0;
+ *   - finite exponentials whose float32 sum exceeds FLT_MAX (two scores of 88.1, say) give weights that
+ *     are all exactly 0: the portfolio return is 0 and the value stays what it was;
+ *   - scores that all underflow (every one below about -104) give 0 / 0 = NaN in every weight.
+ * A NaN weight makes the portfolio return and the value NaN.  So does the panel: a close of 0 gives the
+ * return -1 into that day and +inf out of it (close[t+1] / 0), which is +inf in the value where the env
+ * holds weight on the ticker and inf * 0 = NaN where its weight is exactly 0; two zero closes in a row
+ * give 0 / 0 = NaN for every env.  A return of -1 held with weight exactly 1 leaves a value of exactly 0.
+ * A value that is NaN or +-inf STAYS so on every further step (reward = float32 of it) until the env is
+ * reset -- by finenv_portfolio_reset or by the auto-reset of its terminal step -- which restores
+ * initial_amount.  done, day and the observation rows do not depend on the value and stay exact.
+ * NaN and +inf scores are unspecified. */
 #define FINENV_PORTFOLIO_MAX_TICKERS 64
 
 typedef struct finenv_portfolio_config {

@@ -21,7 +21,9 @@ class PortfolioOracle:
         self.close = np.ascontiguousarray(close, dtype=np.float64)
         T, N = self.close.shape
         self.cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(T, N, N)
-        self.tech = np.ascontiguousarray(tech, dtype=np.float64).reshape(T, -1, N)
+        if tech is None or np.size(tech) == 0:
+            tech = np.zeros((T, 0, N))
+        self.tech = np.ascontiguousarray(tech, dtype=np.float64).reshape(T, np.size(tech) // (T * N), N)
         self.E, self.N, self.K, self.T = int(n_envs), N, self.tech.shape[1], T
         self.D = (N + self.K) * N
         L = lib()
@@ -52,6 +54,19 @@ class PortfolioOracle:
         lib().pf_oracle_vec_step(self._h, _p(a), _p(obs) if want_obs else None, _p(rew), _p(done),
                                  _p(term) if want_obs else None, C.c_int(int(auto_reset)))
         return obs, rew, done.astype(bool), term
+
+    def vec_step_weights(self, actions, auto_reset=True):
+        """vec_step that also returns the softmax weights f32 [E, N] (NaN rows for envs whose step was
+        terminal, which compute none) -> obs, rew, done, term, weights."""
+        a = np.ascontiguousarray(actions, dtype=np.float32).reshape(self.E, self.N)
+        obs, term = np.empty((self.E, self.D)), np.zeros((self.E, self.D))
+        rew, done = np.empty(self.E), np.empty(self.E, dtype=np.uint8)
+        w = np.full((self.E, self.N), np.nan, np.float32)
+        lib().pf_oracle_vec_step_w(self._h, _p(a), _p(obs), _p(rew), _p(done), _p(term),
+                                   C.c_int(int(auto_reset)), _p(w))
+        done = done.astype(bool)
+        w[done] = np.nan
+        return obs, rew, done, term, w
 
     def step(self, actions, want_obs=True):
         obs, rew, done, _ = self.vec_step(actions, auto_reset=False, want_obs=want_obs)

@@ -11,6 +11,9 @@
  * NumPy's SIMD expf and libm/GPU expf may differ in the last ulp, so weights (f32) can differ
  * by 1 ulp and the fp64 portfolio value by ~1e-8 relative; tests use rel 1e-6 there (the
  * north-star bound is 1e-5) and exact equality everywhere else (obs rows, done, day).
+ * Outside the usual score and price range (tests/golden/portfolio_domain.npz: overflowing, subnormal and
+ * zero exponentials, zero closes) no such tolerance exists; tests/portfolio_domain_cases.py derives the
+ * intervals used there, and NaN / inf / 0 must sit where the reference has them.
  */
 #include <math.h>
 #include <stdint.h>
@@ -116,18 +119,26 @@ void pf_oracle_step_env(pf_oracle *o, int e, const float *act, double *obs, doub
     *done = 0;
 }
 
-void pf_oracle_vec_step(pf_oracle *o, const float *act, double *obs, double *reward,
-                        uint8_t *done, double *term_obs, int auto_reset)
+/* weights: [E][N] softmax weights of the envs that stepped (a terminal env's row is left alone), or NULL */
+void pf_oracle_vec_step_w(pf_oracle *o, const float *act, double *obs, double *reward,
+                          uint8_t *done, double *term_obs, int auto_reset, float *weights)
 {
     const int E = o->cfg.n_envs, N = o->cfg.n_tickers, D = pf_oracle_obs_dim(o);
     for (int e = 0; e < E; e++) {
         double *ob = obs ? obs + (size_t)e * D : NULL;
-        pf_oracle_step_env(o, e, act + (size_t)e * N, ob, reward + e, done + e, NULL);
+        pf_oracle_step_env(o, e, act + (size_t)e * N, ob, reward + e, done + e,
+                           weights ? weights + (size_t)e * N : NULL);
         if (done[e] && auto_reset) {
             if (term_obs && ob) memcpy(term_obs + (size_t)e * D, ob, D * sizeof(double));
             pf_oracle_reset_env(o, e, ob);
         }
     }
+}
+
+void pf_oracle_vec_step(pf_oracle *o, const float *act, double *obs, double *reward,
+                        uint8_t *done, double *term_obs, int auto_reset)
+{
+    pf_oracle_vec_step_w(o, act, obs, reward, done, term_obs, auto_reset, NULL);
 }
 
 void pf_oracle_reset(pf_oracle *o, double *obs)

@@ -306,9 +306,12 @@ STOCK_SCENARIOS = {
 
 # ----------------------------------------------------------------- portfolio env
 def run_portfolio(name, *, seed, T, N, K, S, initial_amount=1_000_000, lookback=8,
-                  act_scale=1.0):
+                  act_scale=1.0, actions=None, edit_close=None, extra=None):
     """Unmodified reference StockPortfolioEnv (env_portfolio.py) on a synthetic frame with a
-    per-day covariance object column (`cov_list`), as the reference's tutorials build it."""
+    per-day covariance object column (`cov_list`), as the reference's tutorials build it.
+    actions(S, N) -> [S, N] f32: a script instead of uniform draws; edit_close(close) -> close: edits
+    the closes before the frame is built (the covariances stay those of the unedited walk); extra: further
+    arrays to store."""
     import pandas as pd
     mod = rh.load_portfolio()
     rng = np.random.default_rng(seed + 2000)
@@ -320,6 +323,9 @@ def run_portfolio(name, *, seed, T, N, K, S, initial_amount=1_000_000, lookback=
         cov[t] = np.cov(w.T) if len(w) > 1 else np.eye(N) * 1e-4
         if N == 1:
             cov[t] = np.atleast_2d(cov[t])
+    if edit_close is not None:
+        close = np.ascontiguousarray(edit_close(close), dtype=np.float64)
+        assert close.shape == (T, N)
     names = [f"ind{k}" for k in range(K)]
     cols = {"date": np.repeat([f"d{t:04d}" for t in range(T)], N),
             "tic": np.tile([f"TIC{i:03d}" for i in range(N)], T),
@@ -330,6 +336,9 @@ def run_portfolio(name, *, seed, T, N, K, S, initial_amount=1_000_000, lookback=
     df["cov_list"] = [cov[t] for t in range(T) for _ in range(N)]
     df.index = np.repeat(np.arange(T), N)
     act = (rng.uniform(0, 1, (S, N)) * act_scale).astype(np.float32)
+    if actions is not None:
+        act = np.ascontiguousarray(actions(S, N), dtype=np.float32)
+        assert act.shape == (S, N)
     rec = dict(obs=[], reward=[], done=[], value=[], day=[], weights=[], reset_step=[],
                reset_obs=[])
     printed = io.StringIO()
@@ -371,6 +380,7 @@ def run_portfolio(name, *, seed, T, N, K, S, initial_amount=1_000_000, lookback=
                meta=np.array(["variant=O-raw", f"seed={seed}", f"numpy={np.__version__}",
                               "source=finrl/meta/env_portfolio_allocation/env_portfolio.py "
                               "(unmodified)"]))
+    out.update(extra or {})
     path = os.path.join(HERE, f"portfolio_{name}.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {path}  ({os.path.getsize(path) / 1024:.0f} KiB) steps={S} "
@@ -382,7 +392,20 @@ PORTFOLIO_SCENARIOS = {
     "dow30": dict(seed=31, T=20, N=30, K=8, S=48),
     "n5": dict(seed=32, T=16, N=5, K=2, S=40, initial_amount=50_000, act_scale=3.0),
     "n2k1": dict(seed=33, T=12, N=2, K=1, S=30, initial_amount=1_000),
+    # tests/portfolio_domain_cases.py: every action kind in rotation (scores -300 .. 200, -inf) on a panel
+    # with zero closes, a flat day and x1e6 jumps; three episodes
+    "domain": dict(domain="zeros", seed=37, T=14, N=9, K=2, S=42),
 }
+
+
+def portfolio_domain_scenario(*, domain, seed, T, N, K, S):
+    """The action script and the panel edits of tests/portfolio_domain_cases.py as runner arguments."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import portfolio_domain_cases as pc
+    act, kinds = pc.fixture_actions(S, N, T, seed)
+    return dict(seed=seed, T=T, N=N, K=K, S=S, actions=lambda S_, N_: act,
+                edit_close=lambda close: pc.edit_close(close, domain),
+                extra=dict(kinds=np.array(kinds), panel_variant=np.array(domain)))
 
 
 # ----------------------------------------------------------------- multi-crypto env
@@ -1162,7 +1185,8 @@ def main(argv):
         if n in STOCK_SCENARIOS:
             run_stock(n, **STOCK_SCENARIOS[n])
         elif n.startswith("portfolio:") and n[10:] in PORTFOLIO_SCENARIOS:
-            run_portfolio(n[10:], **PORTFOLIO_SCENARIOS[n[10:]])
+            sc = PORTFOLIO_SCENARIOS[n[10:]]
+            run_portfolio(n[10:], **(portfolio_domain_scenario(**sc) if "domain" in sc else sc))
         elif n.startswith("cashpenalty:") and n[12:] in CASHPENALTY_SCENARIOS:
             sc = CASHPENALTY_SCENARIOS[n[12:]]
             run_cashpenalty(n[12:], **(domain_scenario("cashpenalty", **sc) if "domain" in sc else sc))

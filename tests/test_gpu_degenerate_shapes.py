@@ -1,7 +1,12 @@
 """Smallest shapes the kernels accept: one env, one asset, two days, no indicator columns -- a single
 partially filled wave per launch, panels of two rows, episodes that end on the first step."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -167,3 +172,53 @@ def test_btc_env_two_row_windows(auto_reset):
                     lambda k: rng.uniform(-4, 4, E).astype(np.float32), 6, auto_reset)
     assert (ends == (6 if auto_reset else 3)).all()
     assert len(np.unique(env.state_numpy()["day"])) == E
+
+
+@pytest.mark.parametrize("E,T,N,K", [
+    (1, 2, 1, 0),            # the smallest accepted shape
+    (1, 1, 3, 1),            # every step is terminal: the reward is the initial last reward
+    (3, 3, 2, 1),            # a small batch
+    (31, 4, 7, 1),           # wave 1 of the block has no row to write
+    (33, 4, 8, 0),           # wave 1 writes one row; N = 8 is the first pairwise-sum shape
+    (65, 4, 15, 1), (65, 4, 16, 1), (65, 4, 17, 2),      # the tail of the pairwise sum
+    (65, 3, 32, 32),         # D = 2048: all 8 register chunks of the row template
+    (65, 3, 32, 33),         # D = 2080: the first width on the per-row path
+    (40, 3, 64, 0),          # D = 4096
+])
+def test_portfolio_env_smallest_shapes(E, T, N, K):
+    """`signed` / `wide` scores against PortfolioOracle with the checks of test_gpu_portfolio_domain.py
+    (obs, term_obs, done, day exact; weights and value inside the derived bounds), then one masked reset
+    each for a single env, the upper half-wave of block 0 and the last (partial) block: the rows of the
+    envs not selected keep their observation, value and day."""
+    _need_gpu()
+    import portfolio_domain_cases as pc
+    import test_gpu_portfolio_domain as pd
+    steps = 3 * T + 2
+    close, cov, tech = pc.benign_panel(T, N, K, 100 * E + 10 * T + N)
+    acts = pc.actions(pc.SMALL_SHAPE_KINDS, E, N, steps, T, E + T + N + K)
+    names, _ = pc.kinds_of(E, pc.SMALL_SHAPE_KINDS)
+    obs0, trace = pc.oracle_trace(pd._oracle(close, cov, tech, E), acts)
+    env = pd._env(close, cov, tech, E)
+    assert env.state_dim == (N + K) * N
+    np.testing.assert_array_equal(env.reset().cpu().numpy(), obs0.astype(np.float32))
+    g = pc.gross_returns(close)
+    outs = [pd.checked_step(env, acts[s], trace[s], g, names, f"step {s}") for s in range(steps)]
+    assert sum(int(o["done"].all()) for o in outs) == steps // T          # (T = 1: every step)
+    if T == 1:
+        assert all((o["reward"] == 0).all() for o in outs)
+    assert sum(o["bounded"] for o in outs) == E * (steps - steps // T) == sum(o["values"] for o in outs)
+    e = np.arange(E)
+    masks = [m for m in (e == 40, (e >= 32) & (e < 64), e >= (E - 1) // 64 * 64) if m.any()]
+    for j, m in enumerate(masks):
+        for k in range(2):             # move on until a selected env is past day 0, so that its reset shows
+            if T > 1 and not (env.state_numpy()["day"][m] > 0).any():
+                env.step(torch.from_numpy(acts[k]).cuda())
+        before, obs_before = env.state_numpy(), env.obs.cpu().numpy().copy()
+        assert T == 1 or (before["day"][m] > 0).any()
+        obs = env.reset(torch.from_numpy(m.astype(np.uint8))).cpu().numpy()
+        st = env.state_numpy()
+        np.testing.assert_array_equal(obs[m], obs0[m].astype(np.float32), err_msg=f"mask {j}")
+        assert (st["value"][m] == pd.AMOUNT).all() and (st["day"][m] == 0).all(), f"mask {j}"
+        np.testing.assert_array_equal(obs[~m], obs_before[~m], err_msg=f"mask {j}")
+        np.testing.assert_array_equal(st["value"][~m], before["value"][~m], err_msg=f"mask {j}")
+        np.testing.assert_array_equal(st["day"][~m], before["day"][~m], err_msg=f"mask {j}")

@@ -402,7 +402,8 @@ def test_portfolio_latch_sums_and_twin():
 
 
 @pytest.mark.parametrize("name", sorted(os.path.basename(p)[len("portfolio_"):-4]
-                                        for p in glob.glob(os.path.join(GOLDEN, "portfolio_*.npz"))))
+                                        for p in glob.glob(os.path.join(GOLDEN, "portfolio_*.npz"))
+                                        if not p.endswith("portfolio_domain.npz")))
 def test_portfolio_latch_matches_reference_fixture(name):
     _need_gpu()
     from finrl_amd.panel import PortfolioPanel

@@ -15,6 +15,7 @@ torch = pytest.importorskip("torch")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = sorted(os.path.basename(p)[len("portfolio_"):-4]
                for p in glob.glob(os.path.join(GOLDEN, "portfolio_*.npz")))
+NAMES.remove("domain")      # NaN / inf values: checked with derived bounds by the *_portfolio_domain tests
 
 
 def _need_gpu():
