@@ -256,7 +256,7 @@ void plan_step(finenv_stock *h)
     pl.lds_refused = pl.lds_bytes > 64 * 1024 &&
                      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes) != hipSuccess;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kStepThreads, pl.lds_bytes) != hipSuccess || per_cu < 1)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, pl.threads, pl.lds_bytes) != hipSuccess || per_cu < 1)
         per_cu = 1;
     (void)hipGetLastError();
     pl.round = per_cu * cus;
@@ -270,7 +270,7 @@ void plan_step(finenv_stock *h)
 // ceil(blocks / round) launches of equal size on the caller's stream, each one resident round or less.
 void launch_step_rounds(const finenv_stock_impl::StepPlan &pl, const Params &p, hipStream_t stream)
 {
-    // one 128-thread block per 64 envs
+    // one block of pl.threads threads per 64 envs
     const int blocks = (p.cfg.n_envs + kWave - 1) / kWave;
     const int k = (blocks + pl.round - 1) / pl.round;              // launches
     const int chunk = k > 1 ? (blocks + k - 1) / k : blocks;
@@ -279,7 +279,7 @@ void launch_step_rounds(const finenv_stock_impl::StepPlan &pl, const Params &p, 
     do {
         q.block_base = b;
         const int nb = blocks - b < chunk ? blocks - b : chunk;
-        hipLaunchKernelGGL(pl.kernel, dim3((unsigned)nb), dim3(kStepThreads), pl.lds_bytes, stream, q);
+        hipLaunchKernelGGL(pl.kernel, dim3((unsigned)nb), dim3((unsigned)pl.threads), pl.lds_bytes, stream, q);
         b += chunk;
     } while (b < blocks);
 }

@@ -39,7 +39,7 @@ struct Params {
     int32_t block_base;   // first 64-env group of this launch (batches larger than one resident round of
                           // blocks are stepped as several launches: launch_step_rounds, finenv_stock.hip)
     int32_t diag;         // FINENV_DIAG builds only: phase-skip bitmask (timing experiments)
-    unsigned long long *dbg;   // FINENV_DIAG builds only: [block][role][16] s_memrealtime stamps
+    unsigned long long *dbg;   // FINENV_DIAG builds only: [block][kStampRoles][16] s_memrealtime stamps
     double *last;         // last-episode block [FINENV_STOCK_LAST_FIELDS][E] or NULL
     const int32_t *win;   // per-env windows [2][E] (starts, ends) or NULL (finenv_stock_set_windows)
 };
@@ -48,7 +48,8 @@ struct Params {
 namespace {
 
 constexpr int kWave = 64;
-constexpr int kStepThreads = 2 * kWave;
+constexpr int kStepThreads = 2 * kWave;       // trader + streamer (the lock-step 32-wide kernel adds a sorter wave)
+constexpr int kStampRoles = 3;                // stamp rows per block of the diagnostic build (tools/phase_times.py)
 
 using finenv_stock_impl::Params;
 
@@ -59,7 +60,7 @@ using finenv_stock_impl::Params;
     do {                                                                                  \
         if (p.dbg != nullptr && lane == 0) {                                              \
             __builtin_amdgcn_sched_barrier(0);                                            \
-            p.dbg[((size_t)(blockIdx.x + p.block_base) * 2 + role) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+            p.dbg[((size_t)(blockIdx.x + p.block_base) * kStampRoles + role) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); \
             __builtin_amdgcn_sched_barrier(0);                                            \
         }                                                                                 \
     } while (0)
@@ -131,6 +132,7 @@ namespace finenv_stock_impl {
 struct StepPlan {
     void (*kernel)(Params);
     size_t lds_bytes;
+    int threads = kStepThreads;   // threads per block
     int round;            // blocks resident on the device at once: occupancy per CU x CUs
     int lds_refused;      // the kernel needs > 64 KiB of LDS and the device refused the opt-in
 };

@@ -312,7 +312,8 @@ __device__ __forceinline__ void write_obs_rows(float *__restrict__ dst,
 // -------------------------------------------------------------------------------------
 // step(): env_stocktrading.py:220-357 (+ DummyVecEnv auto-reset when p.auto_reset)
 //
-// One 128-thread block per 64 envs, two specialised waves (lane = env in both):
+// One block per 64 envs, two specialised waves (lane = env in both) -- three in the lock-step 32-wide
+// instantiations, see kThreeWave below: there the sort is the sorter wave's, and so are the last rows of the stream:
 //   wave 0 "trader"  : owns the env state; staging (32-wide variant), sort, sells, buys,
 //                      assets, reward, state write-back.
 //   wave 1 "streamer": streams the market-data part of the observation rows (chunks that
@@ -340,7 +341,49 @@ constexpr int kR2 = kWide ? kNPad * 4 : kNPad * kPStride * 2;   // dwords (compa
 constexpr int kR3 = kWave * kRow;                 // dwords: sorted keys [rank][lane] / obs rows
 constexpr int kHeadMax = (2 * kNPad) / kWave + 1; // observation chunks holding cash / holdings
 constexpr int kR4 = kHeadMax * kWave;             // dwords: their template values (head_park)
-constexpr int kLdsStep = kR1 + kR2 + kR3 + kR4;   // dynamic LDS of the step kernel (dwords)
+constexpr int kR5 = kWide ? 0 : 4;                // dwords: the sorter's "keys are parked" flag (32-wide lock-step)
+constexpr int kLdsStep = kR1 + kR2 + kR3 + kR4 + kR5;   // dynamic LDS of the step kernel (dwords)
+
+// One float4 of the [nenv_w][N] action tile -> LDS rows of kRow dwords (magicN = ceil(2^32 / N), N >= 2).
+__device__ __forceinline__ void scatter_quad(float *tile, const float4 &v, int idx4, int N, unsigned magicN)
+{
+    const float c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int f = 4 * idx4 + u;
+        const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, magicN);
+        tile[el * kRow + (f - el * N)] = c[u];
+    }
+}
+// the < 4 floats of the tile behind its last whole float4
+__device__ __forceinline__ void scatter_leftover(float *tile, const float *__restrict__ act_src, int act_n4,
+                                                 int act_total, int N, unsigned magicN, int lane)
+{
+    for (int f = 4 * act_n4 + lane; f < act_total; f += kWave) {
+        const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, magicN);
+        tile[el * kRow + (f - el * N)] = *at(act_src, (unsigned)f);
+    }
+}
+
+// The keys of the canonical order from the transposed action tile: env `lane`, ticker i ->
+// trunc(action * hmax) clamped to +-kAMax, -hmax on a turbulent day, 0 where nothing trades; packed with the
+// ticker index so that the keys are unique and their order is the stable argsort of the actions (:317).
+__device__ __forceinline__ void build_keys(int (&keys)[kNPad], const float *tile, int lane, int N, int hmax,
+                                           bool turbulent, bool term)
+{
+    const float hmaxf = (float)hmax;
+#pragma unroll
+    for (int i = 0; i < kNPad; ++i) {
+        // (slots >= N of the row are padding: read unclamped so every ds_read gets an immediate
+        //  offset and issues back to back; the value is discarded by the select below)
+        const float x = tile[lane * kRow + i] * hmaxf;                        // f32 mul, :304
+        int a = (int)x;                                                       // trunc, :305
+        a = max(-kAMax, min(kAMax, a));
+        a = turbulent ? -hmax : a;
+        a = (term || i >= N) ? 0 : a;                                         // no trading
+        keys[i] = a * kNPad + i;          // unique; order == stable argsort(actions), :317
+    }
+}
 
 // DES: the instantiation for batches whose envs may sit on different days (finenv_stock_set_desync_hint):
 // 16-byte row copies in the streamer, row-wise price gather, staging barrier, parked head chunks, head
@@ -350,19 +393,121 @@ constexpr int kLdsStep = kR1 + kR2 + kR3 + kR4;   // dynamic LDS of the step ker
 // WIN: the instantiation for batches with per-env episode windows (Params::win != NULL): the terminal
 // test reads the env's window end, a reset goes back to its window start.  A template parameter for
 // the same reason: the no-window instantiations compile exactly as before.
+// kThreeWave<DES>: the lock-step 32-wide kernel runs a third wave per block, the SORTER (role 2).  The keys of
+// the canonical order depend on the action row, hmax and two per-lane flags (terminal, turbulent) that come
+// with the first round trip -- on nothing the trader's second round trip (cash, holdings, price row) brings.
+// So the sorter loads the tile, transposes it, builds and sorts the keys and parks them [rank][lane] in R3
+// while the trader's staging loads are in flight, and publishes a flag in LDS; the trader polls the flag and
+// reads the keys back by rank.  The sorter then streams the last rows of the block's observation stream and
+// ends.  192 threads, 3 waves per SIMD (four blocks per CU as before).  Measured, 65,536 envs x DOW30, same
+// process and buffers (profiles/stock_sorter_wave.md): two waves 19.5 us; the sorter without its rows 20.5 --
+// the trader reaches its reward 2.8 us sooner, but the streamer, then the long pole, is 1.6 us later --; with
+// 16 rows 18.2 - 18.3.
+template <bool DES>
+constexpr bool kThreeWave = !kWide && !DES;
+// s_setprio of the sorter while it holds up its trader (a `make variant EXTRA=-DFINENV_SORTER_PRIO=n` knob)
+#ifndef FINENV_SORTER_PRIO
+#define FINENV_SORTER_PRIO 3
+#endif
+// Once it has published the keys the sorter has nothing left to do while the streamer -- the launch's long
+// pole as soon as the trader no longer sorts -- still has most of its rows ahead: the sorter writes the
+// market-data chunks of the block's last FINENV_SORTER_ROWS rows, the streamer those before them.
+#ifndef FINENV_SORTER_ROWS
+#define FINENV_SORTER_ROWS 16
+#endif
+constexpr int kSorterRow0 = kWave - FINENV_SORTER_ROWS;
+template <bool DES>
+constexpr int kBlockThreads = kThreeWave<DES> ? 3 * kWave : kStepThreads;
+
+// The three-wave kernel's one barrier ahead of the hand-off (see the kernel).  The scheduling fences keep
+// hipcc from moving the first use of a loaded value -- and the s_waitcnt it brings -- above the barrier.
+__device__ __forceinline__ void flag_barrier()
+{
+    __builtin_amdgcn_sched_barrier(0);
+    lds_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// The sorter wave (role 2) of the three-wave kernel, lane = env as in the other roles.  term and turbulent are
+// per-lane values: the lock-step kernel also steps batches whose envs sit on different days.  Every path ends
+// with the flag published -- tail blocks (invalid lanes shadow env e0, their tile rows are never read back by a
+// valid lane) and blocks whose envs are all terminal (keys = ticker index) included.
+template <bool TURB, bool WIN>
+__device__ __forceinline__ void sorter_wave(const Params &p, float *tile, int *ldsk, int *sort_flag,
+                                            const float *act_src, int e0, int nenv_w, int e, int lane)
+{
+    // (act_src is not `__restrict__` on purpose: as a no-alias parameter its loads may sink below the barrier,
+    //  into the conditional block of their only use -- one exposed round trip per float4)
+    constexpr int role = 2;                          // (STAMP)
+    constexpr int kTileLoads = kNPad / 4;            // float4 loads per lane
+    const int E = p.cfg.n_envs, N = p.cfg.n_tickers, T = p.cfg.n_days, D = p.D;
+    const int act_total = nenv_w * N;
+    const int act_n4 = act_total >> 2;
+    // the action tile [nenv_w][N] f32 first (16-B coalesced loads), then the two flags' inputs
+    float4 av[kTileLoads];
+#pragma unroll
+    for (int j = 0; j < kTileLoads; ++j) {
+        const int idx4 = j * kWave + lane;
+        av[j] = reinterpret_cast<const float4 *>(act_src)[(idx4 < act_n4 && !DIAG(8)) ? idx4 : 0];
+    }
+    const int day = SI(FINENV_SI_DAY);
+    const int pd = SI(FINENV_SI_PRICE_DAY);
+    int wend = T;
+    if (WIN) wend = *at(p.win, (unsigned)E + (unsigned)e);
+    double turb = 0.0;
+    if (TURB) turb = SF(FINENV_SF_TURBULENCE);
+    flag_barrier();                                  // the trader has cleared the flag (see the kernel)
+    __builtin_amdgcn_s_setprio(FINENV_SORTER_PRIO);
+    const int last_day = WIN ? min(max(wend, 1), T) - 1 : T - 1;     // win_last_day
+    STAMP(1);
+#pragma unroll
+    for (int j = 0; j < kTileLoads; ++j) {
+        const int idx4 = j * kWave + lane;
+        if (idx4 < act_n4) scatter_quad(tile, av[j], idx4, N, p.magicN);
+    }
+    scatter_leftover(tile, act_src, act_n4, act_total, N, p.magicN, lane);
+    wave_sync();
+    STAMP(2);
+    int keys[kNPad];
+    build_keys(keys, tile, lane, N, p.cfg.hmax, TURB && (turb >= p.cfg.turbulence_threshold), day >= last_day);
+    STAMP(3);
+    if (!DIAG(4)) sort_keys(keys);
+    STAMP(4);
+#pragma unroll
+    for (int r = 0; r < kNPad; ++r) ldsk[r * kWave + lane] = keys[r];
+    // release: the keys, and the last read of the tile in R1, before the flag
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __hip_atomic_store(sort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    STAMP(5);
+    // ---- second streamer: its share of the rows' market-data chunks (row_obs as in the kernel) ----------
+    __builtin_amdgcn_s_setprio(0);
+    const bool term = day >= last_day;
+    const bool do_reset = term && p.auto_reset != 0;
+    int reset_row = 0;
+    if (WIN && !p.cfg.reset_quirk && __any(do_reset)) reset_row = win_start(p.win, e, T);
+    const int row_obs = do_reset ? (p.cfg.reset_quirk ? pd : reset_row) : (term ? pd : day + 1);
+    if (!DIAG(1))
+        write_obs_rows(p.obs, p.panel.obs_tmpl, D, p.obs_pitch, N, e0, nenv_w, row_obs, __ballot(lane < nenv_w), tile,
+                       lane, (2 * N) / kWave + 1, 1 << 30, kSorterRow0, kWave);
+    STAMP(6);
+}
+
 template <bool TURB, bool STATS, bool DES = false, bool WIN = false>
-__global__ void __launch_bounds__(kStepThreads, kWide ? 1 : 2)
+__global__ void __launch_bounds__(kBlockThreads<DES>, kWide ? 1 : (kThreeWave<DES> ? 3 : 2))
 stock_step_kernel(const Params p)
 {
-    extern __shared__ __attribute__((aligned(16))) float lds_all[];   // kR1 + kR2 + kR3 dwords
+    extern __shared__ __attribute__((aligned(16))) float lds_all[];   // kLdsStep dwords
+    constexpr bool kThree = kThreeWave<DES>;
     const int lane = threadIdx.x & (kWave - 1);
-    const int role = threadIdx.x >> 6;                    // 0 trader, 1 streamer
+    // 0 trader, 1 streamer, 2 sorter (scalar there: no role's registers are live in another's branch)
+    const int role = kThree ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     float *lds = lds_all;
     int *ldsh = reinterpret_cast<int *>(lds_all);         // [ticker][lane] view of R1
     double *ldsp = reinterpret_cast<double *>(lds_all + kR1);   // [ticker][lane] f64 prices
     int *ldsk = reinterpret_cast<int *>(lds_all + kR1 + kR2);   // [rank][lane] sorted keys
     float *rows = lds_all + kR1 + kR2;                          // later: obs rows [env][kRow]
     float *ldshead = lds_all + kR1 + kR2 + kR3;                 // head-chunk template values
+    int *sort_flag = reinterpret_cast<int *>(lds_all + kR1 + kR2 + kR3 + kR4);   // kThree: != 0 = keys parked
     // Action tile [env][kRow]: in R1 for the 32-wide variant (holdings move there from registers
     // once the keys are built); in R3 for the wide ones, whose holdings are staged straight
     // into R1 by the streamer (R3 is free until the sorted keys are parked).
@@ -378,7 +523,12 @@ stock_step_kernel(const Params p)
 
     STAMP(0);
 #ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 14] = __builtin_amdgcn_s_memtime();
+    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 14] = __builtin_amdgcn_s_memtime();
+    // where this wave runs, as in stock_step_wide_kernel: XCC_ID (hwreg 20) in bits 0..7, HW_ID (hwreg 4) above
+    if (p.dbg != nullptr && lane == 0)
+        p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 13] =
+            (unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xff) |
+            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8);
 #endif
     // ---- the action tile [nenv_w][N] f32, issued before anything else (16-B coalesced loads): all of
     // it in the trader (32-wide), or half per wave (wide: chunk `it` belongs to wave it & 1) ------
@@ -386,8 +536,14 @@ stock_step_kernel(const Params p)
     const int act_total = nenv_w * N;
     const int act_n4 = act_total >> 2;
     constexpr int kTileLoads = kWide ? kNPad / 8 : kNPad / 4;   // float4 loads per lane
+    if constexpr (kThree) {
+        if (role == 2) {          // its own loads, barrier and end: nothing of it is live in the other roles
+            sorter_wave<TURB, WIN>(p, lds_all, ldsk, sort_flag, act_src, e0, nenv_w, e, lane);
+            return;
+        }
+    }
     float4 av[kTileLoads];
-    if (kWide || role == 0) {
+    if (kWide || (!kThree && role == 0)) {
 #pragma unroll
         for (int j = 0; j < kTileLoads; ++j) {
             const int idx4 = (kWide ? 2 * j + role : j) * kWave + lane;
@@ -398,6 +554,16 @@ stock_step_kernel(const Params p)
     int day = SI(FINENV_SI_DAY);
     int pd = SI(FINENV_SI_PRICE_DAY);
     const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
+    if constexpr (kThree) {
+        // LDS is not initialised at block start, so the sorter's flag is cleared first, behind the ONE workgroup
+        // barrier ahead of the hand-off (the sorter meets it in sorter_wave): every wave has issued its first
+        // global loads and none has waited yet, so the barrier hides under the first round trip.  The streamer
+        // meets no other barrier until it has streamed.  The sorter never meets the hand-off barrier: it ends
+        // behind its last store, and a wave that has ended is not counted, so that barrier pairs trader and
+        // streamer (and falls once the sorter has ended, should it still be storing then).
+        if (role == 0) *sort_flag = 0;
+        flag_barrier();
+    }
     const bool term = day >= last_day;                                        // :221
     const bool do_reset = term && p.auto_reset != 0;
     const int pd_cur = pd;                            // row held in the current observation
@@ -569,7 +735,7 @@ stock_step_kernel(const Params p)
     }
     // ---- transpose the action tile into LDS rows (stride 33): half per wave, or all of it in the
     // trader (32-wide) --------------------------------------------------------------------------
-    if (kWide || role == 0) {
+    if (kWide || (!kThree && role == 0)) {
 #pragma unroll
     for (int j = 0; j < kTileLoads; ++j) {
         const int idx4 = (kWide ? 2 * j + role : j) * kWave + lane;
@@ -584,7 +750,7 @@ stock_step_kernel(const Params p)
         }
     }
     }
-    if (role == (kWide ? 1 : 0))
+    if (!kThree && role == (kWide ? 1 : 0))
         for (int f = 4 * act_n4 + lane; f < act_total; f += kWave) {          // < 4 leftover floats
             const int el = (N == 1) ? f : (int)__umulhi((unsigned)f, p.magicN);
             tile[el * kRow + (f - el * N)] = *at(act_src, (unsigned)f);
@@ -624,8 +790,9 @@ stock_step_kernel(const Params p)
                                term_mask, lds, lane, kpatch);
             // desynchronised instantiation: 16-byte row copies, this many chunks per batch (1 = dword form)
             constexpr int kDesyncCh = 4;
+            // (three-wave form: the block's last rows are the sorter's)
             write_obs_rows<(DES ? kDesyncCh : 1)>(p.obs, p.panel.obs_tmpl, D, P, N, e0, nenv_w, row_obs, valid_mask, lds,
-                              lane, kpatch);
+                              lane, kpatch, 1 << 30, 0, kThree ? kSorterRow0 : kWave);
         }
         STAMP(4);
         // ---- streamer, part 3: once the trader has published the (cash, holdings) rows in LDS,
@@ -674,9 +841,14 @@ stock_step_kernel(const Params p)
     const int hmax = p.cfg.hmax;
     const float hmaxf = (float)hmax;
     double risk_next = 0.0;
-    if (TURB) risk_next = *at(p.panel.risk, (unsigned)pd_next);
+    // (three-wave form, 168 VGPRs: loaded with the next-row prices below -- held from here it is the pair that
+    //  no longer fits beside the rank-ordered registers, and its spill waits for the load on the spot)
+    if (TURB && !kThree) risk_next = *at(p.panel.risk, (unsigned)pd_next);
 
+    // (the two-wave forms keep their own copy of the tile transposition above and of the key build here:
+    //  calling scatter_quad / build_keys from them changed the code of the wide kernels)
     int keys[kNPad];
+    if constexpr (!kThree) {
 #pragma unroll
     for (int i = 0; i < kNPad; ++i) {
         // (slots >= N of the row are padding: read unclamped so every ds_read gets an immediate
@@ -687,6 +859,7 @@ stock_step_kernel(const Params p)
         a = turbulent ? -hmax : a;
         a = (term || i >= N) ? 0 : a;                                         // no trading
         keys[i] = a * kNPad + i;          // unique; order == stable argsort(actions), :317
+    }
     }
     wave_sync();
 
@@ -703,14 +876,27 @@ stock_step_kernel(const Params p)
     // (FINENV_SF_BEGIN_ASSET; init / reset evaluate it afresh).  The sum used to cost the trader
     // ~1.3 us of its 15 us critical path (32 LDS reads + 32 fp64 multiply-adds, one wave per SIMD).
     double s = 0.0;
+    if constexpr (kThree) {
+        // R1 holds the sorter's tile until the keys are parked: poll its flag (acquire) before the
+        // holdings go there.  No barrier: the streamer must not stop while it streams.
+        STAMP(12);
+        while (__hip_atomic_load(sort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+            __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
     if (!kWide) {
 #pragma unroll
         for (int i = 0; i < kNPad; ++i) ldsh[i * kWave + lane] = hreg[i];
     }
     STAMP(4);
 
-    // ---- canonical order ------------------------------------------------------------------------
-    if (!DIAG(4)) sort_keys(keys);
+    // ---- canonical order (three-wave form: sorted by the sorter, read back by rank) --------------
+    if constexpr (kThree) {
+#pragma unroll
+        for (int r = 0; r < kNPad; ++r) keys[r] = ldsk[r * kWave + lane];
+    } else {
+        if (!DIAG(4)) sort_keys(keys);
+    }
     const double c_s = p.cfg.sell_cost_pct, c_b = p.cfg.buy_cost_pct;
     const double one_m_cs = 1 - c_s, one_p_cb = 1 + c_b;
     const int *kcol = ldsk + lane;                 // this env's sorted keys, stride kWave
@@ -773,7 +959,7 @@ stock_step_kernel(const Params p)
         // ---- park keys and the rank-ordered prices (in place: every gather above has issued) ----
 #pragma unroll
         for (int r = 0; r < kNPad; ++r) {
-            ldsk[r * kWave + lane] = keys[r];
+            if (!kThree) ldsk[r * kWave + lane] = keys[r];      // (three-wave form: the sorter parked them)
             ldsp[r * kWave + lane] = pS[r];
         }
         STAMP(6);
@@ -784,6 +970,7 @@ stock_step_kernel(const Params p)
 #pragma unroll
         for (int i = 0; i < kNPad; ++i)
             nreg[i] = *at(p.panel.close, (unsigned)(pd_next * N + (i < N ? i : 0)));
+        if (TURB && kThree) risk_next = *at(p.panel.risk, (unsigned)pd_next);
         // ---- buys: largest first (:319, :328-330, _buy_stock :171-213) -------------------------
         // Serial through cash: q = min(a, cash // unit), cash -= p*q*(1+c_b).  Keys and prices are
         // read by RANK (static stride, three ranks ahead); unit price and its refined reciprocal
@@ -1156,7 +1343,7 @@ stock_step_kernel(const Params p)
     }
     STAMP(11);
 #ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
+    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
 #endif
 }
 

@@ -102,10 +102,10 @@ stock_step_wide_kernel(const Params p)
 
     STAMP(0);
 #ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 14] = __builtin_amdgcn_s_memtime();
+    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 14] = __builtin_amdgcn_s_memtime();
     // where this wave runs: XCC_ID (hwreg 20) in bits 0..7, HW_ID (hwreg 4: wave / simd / cu / sh / se) above
     if (p.dbg != nullptr && lane == 0)
-        p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 13] =
+        p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 13] =
             (unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xff) |
             ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8);
 #endif
@@ -643,6 +643,6 @@ stock_step_wide_kernel(const Params p)
     STAMP(10);
     STAMP(11);
 #ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * 2 + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
+    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
 #endif
 }

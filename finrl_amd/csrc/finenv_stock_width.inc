@@ -36,7 +36,8 @@ finenv_stock_impl::StepPlan choose_step(const finenv_stock_config &cfg, bool win
         }
         if (win) return {stock_step_kernel<TURB, STATS, false, true>, lds};
     }
-    return {stock_step_kernel<TURB, STATS, false, false>, lds};
+    // (32-wide: the three-wave lock-step form, 192 threads per block)
+    return {stock_step_kernel<TURB, STATS, false, false>, lds, kBlockThreads<false>};
 }
 }  // namespace np<FINENV_NP>
 }  // namespace

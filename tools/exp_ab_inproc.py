@@ -3,7 +3,9 @@
 (so the same physical placement), only the library that launches the step kernel alternates.  The
 handle is created by the base build, so both builds must share the layout of the finenv_<kind> handle
 structs (variants of one source tree always do).
-usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|portfolio|portfolio-random63|stocknp> [rounds]
+usage: python3 tools/exp_ab_inproc.py <variant .so> <n100|n30|n<tickers>|portfolio|portfolio-random63|stocknp> [rounds] [ascending]
+  ascending: every action row sorted ascending in the ticker index, so the stock kernels' sort keys are in order
+    as built (what the diagnostic switch FINENV_DIAG=4, "skip the sorting network", needs to leave results alone)
   portfolio-random63: the portfolio env with random 63-day episode windows (VecStockPortfolioEnv.set_windows)
   cashpenalty:c<C>:<disc|cont>, stoploss:c<C>:<disc|cont>: VecCashPenaltyEnv / VecStopLossEnv as bench.py builds
     them (65,536 envs, 30 assets, hmax=2_000, random starts) but with C columns per asset and the given
@@ -21,6 +23,7 @@ sys.path.insert(0, ROOT)
 def main():
     variants, kind = sys.argv[1].split(","), sys.argv[2]
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    ascending = "ascending" in sys.argv[4:]
     import torch
     import bench
     from finrl_amd import _native as nat
@@ -51,7 +54,7 @@ def main():
     a = dict(env="crypto", tickers=30, turbulence_pct=None) if kind.startswith("crypto") else \
         dict(env="portfolio", tickers=30, turbulence_pct=None) if kind == "portfolio" else \
         dict(env="stocknp", tickers=30, turbulence_pct=None) if kind == "stocknp" else \
-        dict(env="stock", tickers=100 if kind == "n100" else 30, turbulence_pct=90.0 if kind == "n100" else None)
+        dict(env="stock", tickers=int(kind[1:]), turbulence_pct=90.0 if kind == "n100" else None)
     args = type("A", (), dict(envs_per_gpu=E, action_pool=8, rollout=0, desync=False, no_stats=False, **a))()
     w = bench.build_workload(args, torch, dev, 0)
     env = w.env
@@ -60,7 +63,8 @@ def main():
         g = torch.Generator(device=dev).manual_seed(7)
         env.set_windows(*random_windows(env.panel.T, E, 63, generator=g, device=dev))
         kind = "portfolio-random63"
-    alternate(libs, envs, nat, torch, env, w.pool, kind, rounds)
+    pool = [torch.sort(a, dim=1).values.contiguous() for a in w.pool] if ascending else w.pool
+    alternate(libs, envs, nat, torch, env, pool, kind + (" ascending" if ascending else ""), rounds)
 
 
 def two_wave_ab(libs, nat, torch, dev, E, kind, rounds):
@@ -100,6 +104,11 @@ def alternate(libs, envs, nat, torch, env, pool, kind, rounds):
             if envs.get(name):
                 os.environ[envs[name].split("=")[0]] = envs[name].split("=")[1]
             env._step_args = None                # BatchedEnv.step caches the previous library's function
+            if hasattr(env, "hint_desynchronised"):
+                # the stock handle keeps its step plan -- the kernel's address among it -- from the library that
+                # planned it: have this one plan again (a change of the hint does), or both arms launch one kernel
+                env.hint_desynchronised(True)
+                env.hint_desynchronised(False)
             for i in range(100):
                 env.step(pool[i % 8])
             torch.cuda.synchronize()

@@ -16,7 +16,8 @@ os.environ.setdefault("FINENV_LIB", os.path.join(ROOT, "finrl_amd", "lib", "libf
 def main():
     E = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
     NT = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-    desync = len(sys.argv) > 3 and sys.argv[3] == "desync"
+    desync = "desync" in sys.argv[3:]
+    ascending = "ascending" in sys.argv[3:]     # action rows ascending in the ticker index: keys in order as built
     import torch
     import bench
     from finrl_amd import StockPanel, _native as nat
@@ -30,8 +31,13 @@ def main():
             env.state[k].copy_(offs)
         env.hint_desynchronised(True)
     nb = (E + 63) // 64
-    buf = torch.zeros(nb * 2 * 16, dtype=torch.int64, device="cuda")
+    # stamp rows per block: trader, streamer, sorter (kStampRoles); "two-rows": a diagnostic library built from a
+    # tree before the sorter wave, whose stamp buffer is [block][2][16]
+    NR = 2 if "two-rows" in sys.argv[3:] else 3
+    buf = torch.zeros(nb * NR * 16, dtype=torch.int64, device="cuda")
     pool = [torch.rand(E, NT, device="cuda") * 2 - 1 for _ in range(8)]
+    if ascending:
+        pool = [torch.sort(a, dim=1).values.contiguous() for a in pool]
     for i in range(200):
         env.step(pool[i & 7])
     L = nat.lib()
@@ -42,9 +48,10 @@ def main():
         buf.zero_()
         env.step(pool[i & 7])
         torch.cuda.synchronize()
-        acc.append(buf.cpu().numpy().reshape(nb, 2, 16).astype(np.float64) * 0.01)  # -> us
+        acc.append(buf.cpu().numpy().reshape(nb, NR, 16).astype(np.float64) * 0.01)  # -> us
     a = np.stack(acc)                                   # [rep, block, role, stamp]
-    t0 = a[:, :, :, 0].min(axis=(1, 2), keepdims=True)[..., None]
+    three = NR == 3 and bool(a[:, :, 2, 0].any())                   # the three-wave kernel (lock-step, <= 32 tickers) ran
+    t0 = a[:, :, :3 if three else 2, 0].min(axis=(1, 2), keepdims=True)[..., None]
     rel = a - t0
     names_t = ["start", "day/pd loaded", "pre-barrier work done", "barrier passed",
                "begin asset", "sorted", "sells done", "buys done", "end asset", "reward/stats",
@@ -61,6 +68,31 @@ def main():
     for k, n in enumerate(names_s):
         v = rel[:, :, 1, k].reshape(-1)
         print(f"  {k:2d} {n:24s} {np.median(v):7.2f}  [{np.percentile(v, 95):7.2f}]  p99 {np.percentile(v, 99):6.2f}  max {v.max():6.2f}")
+    if three:
+        names_o = ["start", "flag barrier passed", "tile landed, transposed", "keys built", "sorted", "published",
+                   "its rows streamed"]
+        print("sorter wave:")
+        for k, n in enumerate(names_o):
+            v = rel[:, :, 2, k].reshape(-1)
+            print(f"  {k:2d} {n:24s} {np.median(v):7.2f}  [{np.percentile(v, 95):7.2f}]  p99 {np.percentile(v, 99):6.2f}  max {v.max():6.2f}")
+        w = (a[:, :, 0, 4] - a[:, :, 0, 12]).reshape(-1)        # stamp 12: the trader reaches the flag poll
+        print(f"trader at the flag {np.median(rel[:, :, 0, 12]):.2f}; waits there (to stamp 4, holdings parked) "
+              f"{np.median(w):.2f}  [{np.percentile(w, 95):.2f}]; published before the trader arrives in "
+              f"{100 * np.mean(a[:, :, 2, 5] <= a[:, :, 0, 12]):.0f} % of blocks")
+        # where the three waves of a block run (slot 13: XCC_ID | HW_ID << 8, as in the wide kernel)
+        raw = (a[0, :, :, 13] / 0.01).round().astype(np.int64)
+        hw = raw >> 8
+        simd = (hw >> 4) & 3
+        cu_key = (raw[:, 0] & 0xff) * 100000 + ((hw[:, 0] >> 13) & 7) * 1000 + ((hw[:, 0] >> 12) & 1) * 100 + ((hw[:, 0] >> 8) & 15)
+        from collections import Counter
+        pat, per_block = Counter(), Counter()
+        for b in range(nb):
+            per_block[len(set(simd[b].tolist()))] += 1
+        for key in set(cu_key.tolist()):
+            m = cu_key == key
+            pat[tuple(tuple(sorted(simd[m, r].tolist())) for r in range(3))] += 1
+        print("distinct SIMDs per block (3 = trader, streamer and sorter each on their own) -> blocks:", dict(per_block))
+        print("per CU: SIMD ids of its (traders, streamers, sorters) -> number of CUs:", dict(pat.most_common(4)))
     cyc = (a[:, :, 0, 15] - a[:, :, 0, 14]) / 0.01          # raw shader-clock ticks
     us = a[:, :, 0, 11] - a[:, :, 0, 0]
     print(f"trader shader clock: {np.median(cyc / us) / 1e3:.2f} GHz (s_memtime ticks / s_memrealtime us)")
