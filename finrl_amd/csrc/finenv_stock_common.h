@@ -114,6 +114,71 @@ __device__ __forceinline__ double *last_block()
 // kernels read the end every step (one coalesced 4-byte load beside SI(DAY)) and the start only on their
 // wave-uniform reset path.
 
+// ---- pieces of the step rule (env_stocktrading.py:220-357) that every form of stock_step_kernel and
+// stock_step_wide_kernel state the same way.  (SF / SI capture the names p, E and e: keep these parameter names.)
+
+// reciprocal + one Newton step of a unit price: floor(cash * x) is then within 1 of cash // unit for
+// |cash / unit| < 2^40, and the sign of one FMA remainder makes it exact (the buy loops)
+__device__ __forceinline__ double refined_rcp(double u)
+{
+    const double x = __builtin_amdgcn_rcp(u);
+    return fma(fma(-u, x, 1.0), x, x);
+}
+
+// reset(), :359-393: the scalars of a fresh episode that no step carries in registers (the aux kernel's reset
+// and the step kernels' auto-reset)
+__device__ __forceinline__ void store_episode_start(const Params &p, int E, int e, double asset0, int start)
+{
+    SF(FINENV_SF_ASSET0) = asset0;
+    SF(FINENV_SF_RET_SUM) = 0.0;
+    SF(FINENV_SF_RET_SUMSQ) = 0.0;
+    SI(FINENV_SI_START_DAY) = start;
+}
+
+// Running sums of pct_change(asset_memory) for the terminal Sharpe (:243-251), for a step that did not end the
+// episode.  asset_memory[-1] is this step's begin asset bit for bit (same cash, holdings, price row and
+// summation order as the previous step's end asset) -- except on the first step of an episode, where it is
+// asset_memory[0] (NumPy's pairwise sum, :364-378): no per-step copy is kept.
+__device__ __forceinline__ void store_sharpe_sums(const Params &p, int E, int e, bool valid, double begin, double end,
+                                                  bool first_step, double st_mean, double st_m2)
+{
+    double st_prev = begin;
+    if (__any(first_step)) {
+        const double a0 = SF(FINENV_SF_ASSET0);
+        st_prev = first_step ? a0 : begin;
+    }
+    const double ret = end / st_prev - 1.0;
+    if (valid) {
+        SF(FINENV_SF_RET_SUM) = st_mean + ret;
+        SF(FINENV_SF_RET_SUMSQ) = st_m2 + ret * ret;
+    }
+}
+
+// state write-back of the trader's scalars (end_carry: the next step's begin asset)
+template <bool TURB>
+__device__ __forceinline__ void store_trader(const Params &p, int E, int e, double cash, double end_carry, double cost,
+                                             int trades, int day, int pd, double last_reward, double turb,
+                                             int episode_inc)
+{
+    SF(FINENV_SF_CASH) = cash;
+    SF(FINENV_SF_BEGIN_ASSET) = end_carry;
+    SF(FINENV_SF_COST) = cost;
+    SI(FINENV_SI_TRADES) = trades;
+    SI(FINENV_SI_DAY) = day;
+    SI(FINENV_SI_PRICE_DAY) = pd;
+    SF(FINENV_SF_LAST_REWARD) = last_reward;
+    if (TURB) SF(FINENV_SF_TURBULENCE) = turb;
+    if (episode_inc) SI(FINENV_SI_EPISODE) += 1;
+}
+
+// Diagnostic build: the wave's end clock, slot 15 of its stamp row
+__device__ __forceinline__ void stamp_wave_end(const Params &p, int lane, int role)
+{
+#ifdef FINENV_DIAG
+    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
+#endif
+}
+
 __device__ __forceinline__ void ce(int &a, int &b)
 {
     const int lo = min(a, b);

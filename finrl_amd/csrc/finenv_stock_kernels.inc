@@ -452,13 +452,11 @@ __device__ __forceinline__ void sorter_wave(const Params &p, float *tile, int *l
     }
     const int day = SI(FINENV_SI_DAY);
     const int pd = SI(FINENV_SI_PRICE_DAY);
-    int wend = T;
-    if (WIN) wend = *at(p.win, (unsigned)E + (unsigned)e);
+    const int last_day = WIN ? win_last_day(p.win, E, e, T) : T - 1;         // window end - 1
     double turb = 0.0;
     if (TURB) turb = SF(FINENV_SF_TURBULENCE);
     flag_barrier();                                  // the trader has cleared the flag (see the kernel)
     __builtin_amdgcn_s_setprio(FINENV_SORTER_PRIO);
-    const int last_day = WIN ? min(max(wend, 1), T) - 1 : T - 1;     // win_last_day
     STAMP(1);
 #pragma unroll
     for (int j = 0; j < kTileLoads; ++j) {
@@ -979,10 +977,6 @@ stock_step_kernel(const Params p)
         //   q0 = min(floor(cash*x), a);  rem = cash - q0*unit (exact sign)
         //   rem < 0 -> q0-1;  rem >= unit and q0 < a -> q0+1;  else q0      == min(a, cash // unit)
         if (!DIAG(2)) {
-            auto refined_rcp = [](double u) {
-                const double x = __builtin_amdgcn_rcp(u);
-                return fma(fma(-u, x, 1.0), x, x);
-            };
             const double *pcol = ldsp + lane;
             int key0 = kcol[(kNPad - 1) * kWave], key1 = kcol[(kNPad - 2) * kWave];
             int key2 = kcol[(kNPad - 3) * kWave];
@@ -1075,10 +1069,6 @@ stock_step_kernel(const Params p)
         }
         STAMP(6);
         if (!DIAG(2)) {
-            auto refined_rcp = [](double u) {
-                const double x = __builtin_amdgcn_rcp(u);
-                return fma(fma(-u, x, 1.0), x, x);
-            };
             bool more = true;
             for (int c = kNPad - 16; c >= 0 && more; c -= 16) {    // buys: largest first
                 int kk[16];
@@ -1154,10 +1144,6 @@ stock_step_kernel(const Params p)
 
     // ---- buys (same arithmetic as the 32-wide variant; prices gathered per rank) ---------------
     if (!DIAG(2)) {
-        auto refined_rcp = [](double u) {
-            const double x = __builtin_amdgcn_rcp(u);
-            return fma(fma(-u, x, 1.0), x, x);
-        };
         int key0 = kcol[(kNPad - 1) * kWave];
         int key1 = kcol[(kNPad - 2) * kWave];
         double p0 = price_signed(key0 & (kNPad - 1));
@@ -1274,10 +1260,7 @@ stock_step_kernel(const Params p)
                 end_carry = initial_asset_lds(cash, hcol, p.panel.close, (unsigned)(pd * N), N, false);
                 day = WIN ? win_start(p.win, e, T) : 0;                       // day 0 of the window
                 if (valid) {
-                    SF(FINENV_SF_ASSET0) = a0;
-                    SF(FINENV_SF_RET_SUM) = 0.0;
-                    SF(FINENV_SF_RET_SUMSQ) = 0.0;
-                    SI(FINENV_SI_START_DAY) = day;
+                    store_episode_start(p, E, e, a0, day);
                 }
                 turb = 0.0;
                 cost = 0.0;
@@ -1302,35 +1285,10 @@ stock_step_kernel(const Params p)
                        0, kpatch);
     STAMP(10);
 
-    // ---- running sums of pct_change(asset_memory) for the terminal Sharpe (:243-251) ------------
-    // Placed after the observation stores: nothing waits on it but its own write-back.
-    // asset_memory[-1] is this step's begin asset bit for bit (same cash, holdings, price row and
-    // summation order as the previous step's end asset) -- except on the first step of an episode,
-    // where it is asset_memory[0] (NumPy's pairwise sum, :364-378): no per-step copy is kept.
-    if (STATS && !term) {
-        double st_prev = begin;
-        if (__any(first_step)) {
-            const double a0 = SF(FINENV_SF_ASSET0);
-            st_prev = first_step ? a0 : begin;
-        }
-        const double ret = end / st_prev - 1.0;
-        if (valid) {
-            SF(FINENV_SF_RET_SUM) = st_mean + ret;
-            SF(FINENV_SF_RET_SUMSQ) = st_m2 + ret * ret;
-        }
-    }
-    // ---- state write-back --------------------------------------------------------------------------
-    if (valid) {
-        SF(FINENV_SF_CASH) = cash;
-        SF(FINENV_SF_BEGIN_ASSET) = end_carry;
-        SF(FINENV_SF_COST) = cost;
-        SI(FINENV_SI_TRADES) = trades;
-        SI(FINENV_SI_DAY) = day;
-        SI(FINENV_SI_PRICE_DAY) = pd;
-        SF(FINENV_SF_LAST_REWARD) = last_reward;
-        if (TURB) SF(FINENV_SF_TURBULENCE) = turb;
-        if (episode_inc) SI(FINENV_SI_EPISODE) += 1;
-    }
+    // ---- the Sharpe sums, placed after the observation stores (nothing waits on them but their own
+    // write-back); then the state write-back ------------------------------------------------------------
+    if (STATS && !term) store_sharpe_sums(p, E, e, valid, begin, end, first_step, st_mean, st_m2);
+    if (valid) store_trader<TURB>(p, E, e, cash, end_carry, cost, trades, day, pd, last_reward, turb, episode_inc);
     if (park_heads) {
         if (!DIAG(1)) head_rows_parked(reinterpret_cast<const float *>(ldsp), rows, 0, kWave / 2);
     } else if (split_head && !DIAG(1)) {
@@ -1342,9 +1300,7 @@ stock_step_kernel(const Params p)
                            0, kpatch, 0, kWave / 2);
     }
     STAMP(11);
-#ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
-#endif
+    stamp_wave_end(p, lane, role);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1407,10 +1363,7 @@ __global__ void __launch_bounds__(kWave *kAuxWaves) stock_aux_kernel(const Param
 #pragma unroll
             for (int i = 0; i < kNPad; ++i)
                 if (i < N) HOLD(i) = hf[i];
-            SF(FINENV_SF_ASSET0) = a0;
-            SF(FINENV_SF_RET_SUM) = 0.0;
-            SF(FINENV_SF_RET_SUMSQ) = 0.0;
-            SI(FINENV_SI_START_DAY) = start;
+            store_episode_start(p, E, e, a0, start);
             SI(FINENV_SI_DAY) = start;
             SI(FINENV_SI_PRICE_DAY) = pd;
             SF(FINENV_SF_TURBULENCE) = 0.0;

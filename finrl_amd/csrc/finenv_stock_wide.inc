@@ -317,10 +317,6 @@ stock_step_wide_kernel(const Params p)
 
     const double c_s = p.cfg.sell_cost_pct, c_b = p.cfg.buy_cost_pct;
     const double one_m_cs = 1 - c_s, one_p_cb = 1 + c_b;
-    auto refined_rcp = [](double u) {
-        const double x = __builtin_amdgcn_rcp(u);
-        return fma(fma(-u, x, 1.0), x, x);
-    };
 
     if (uniform_pd) {
         // ---- lock-step days: rank-ordered register chunks.  Keys of a chunk are read back by rank
@@ -549,10 +545,7 @@ stock_step_wide_kernel(const Params p)
                                               kHS);
                 day = WIN ? win_start(p.win, e, T) : 0;                       // day 0 of the window
                 if (valid) {
-                    SF(FINENV_SF_ASSET0) = a0;
-                    SF(FINENV_SF_RET_SUM) = 0.0;
-                    SF(FINENV_SF_RET_SUMSQ) = 0.0;
-                    SI(FINENV_SI_START_DAY) = day;
+                    store_episode_start(p, E, e, a0, day);
                 }
                 turb = 0.0;
                 cost = 0.0;
@@ -610,20 +603,9 @@ stock_step_wide_kernel(const Params p)
     // overwrites what the streamer read at its start comes after it --------------------------------------
     lds_barrier();
     // ---- state write-back -----------------------------------------------------------------------------
-    if (valid) {
-        SF(FINENV_SF_CASH) = cash;
-        SF(FINENV_SF_BEGIN_ASSET) = end_carry;
-        SF(FINENV_SF_COST) = cost;
-        SI(FINENV_SI_TRADES) = trades;
-        SI(FINENV_SI_DAY) = day;
-        SI(FINENV_SI_PRICE_DAY) = pd;
-        SF(FINENV_SF_LAST_REWARD) = last_reward;
-        if (TURB) SF(FINENV_SF_TURBULENCE) = turb;
-        if (episode_inc) SI(FINENV_SI_EPISODE) += 1;
-    }
-    // running sums of pct_change(asset_memory) for the terminal Sharpe (:243-251)
-    // (asset_memory[-1] == this step's begin asset, except on an episode's first step: see
-    //  stock_step_kernel)
+    if (valid) store_trader<TURB>(p, E, e, cash, end_carry, cost, trades, day, pd, last_reward, turb, episode_inc);
+    // running sums for the terminal Sharpe (:243-251): the rule of store_sharpe_sums, finenv_stock_common.h; this
+    // kernel keeps its copy (the call changed the code of its four STATS instantiations, profiles/stock_one_rule.md)
     if (STATS && !term) {
         double st_prev = begin;
         if (__any(first_step)) {
@@ -642,7 +624,5 @@ stock_step_wide_kernel(const Params p)
     }
     STAMP(10);
     STAMP(11);
-#ifdef FINENV_DIAG
-    if (p.dbg != nullptr && lane == 0) p.dbg[((size_t)blockIdx.x * kStampRoles + role) * 16 + 15] = __builtin_amdgcn_s_memtime();
-#endif
+    stamp_wave_end(p, lane, role);
 }
