@@ -12,6 +12,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 
 FINENV_OK = 0
 ABI_VERSION = 3            # include/finenv.h FINENV_ABI_VERSION
+STOCK_MAX_TICKERS = 128    # FINENV_STOCK_MAX_TICKERS
 AUDIT_HEAD = 4             # FINENV_AUDIT_HEAD: begin cash, asset value, reward, flags
 AUDIT_F_LAST_DATE, AUDIT_F_CASH_SHORTAGE, AUDIT_F_TURBULENCE, AUDIT_F_STOP_LOSS, \
     AUDIT_F_LOW_PROFIT, AUDIT_F_HIGH_PROFIT = 1, 2, 4, 8, 16, 32
@@ -239,11 +240,6 @@ class BtcStatePtrs(C.Structure):
     _fields_ = [("f64", C.c_void_p), ("i32", C.c_void_p)]
 
 
-# finenv_struct_size indices of the struct trios added after the first v3 list (0 .. 17 are the six
-# kinds of lib()'s table in order; 18 stays invalid)
-_LATER_STRUCTS = {19: BtcConfig, 20: BtcPanelPtrs, 21: BtcStatePtrs}
-
-
 class ReplayViewPtrs(C.Structure):
     """finenv_replay_view: the four ring tensors of a replay buffer and S, E, D, P, A."""
     _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p),
@@ -271,14 +267,6 @@ class ReplayPerPtrs(C.Structure):
                 ("frac_bits", C.c_int32), ("reserved0", C.c_int32)]
 
 
-# the replay buffer's pointer structs (22 stays invalid, like 18)
-_REPLAY_STRUCTS = {23: ReplayViewPtrs, 24: ReplayBatchPtrs}
-# the n-step sampler's (25 stays invalid: the end of the list above)
-_REPLAY_NSTEP_STRUCTS = {26: ReplayNStepPtrs}
-# prioritised replay's (27 stays invalid: the end of the list above)
-_REPLAY_PER_STRUCTS = {28: ReplayPerPtrs}
-
-
 class RolloutViewPtrs(C.Structure):
     """finenv_rollout_view: the six rollout tensors a minibatch reads and n_steps, E, D, P, A."""
     _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("values", C.c_void_p),
@@ -294,10 +282,6 @@ class RolloutBatchPtrs(C.Structure):
                 ("batch_size", C.c_int32), ("obs_pitch", C.c_int32)]
 
 
-# the rollout minibatch's (29 stays invalid: the end of the list above)
-_ROLLOUT_STRUCTS = {30: RolloutViewPtrs, 31: RolloutBatchPtrs}
-
-
 class VecNormPtrs(C.Structure):
     """finenv_vecnorm: a running-statistics block (mean / var / scale [dim], count), the partials
     buffer and ticket word of its update launch, dim, the partials capacity, epsilon and clip."""
@@ -307,8 +291,153 @@ class VecNormPtrs(C.Structure):
 
 
 VECNORM_MAX_TILES = 128         # FINENV_VECNORM_MAX_TILES: 2 * this * dim doubles of partials always suffice
-# the running statistics' (32 stays invalid: the end of the list above)
-_VECNORM_STRUCTS = {33: VecNormPtrs}
+
+
+# Every struct of include/finenv.h: (C name, finenv_struct_size index, ctypes class).  The history structs
+# have no index; 18, 22, 25, 27, 29 and 32 are no struct's (the library answers -1 there).
+STRUCTS = (
+    ("finenv_stock_config", 0, StockConfig),
+    ("finenv_stock_panel", 1, StockPanelPtrs),
+    ("finenv_stock_state", 2, StockStatePtrs),
+    ("finenv_portfolio_config", 3, PortfolioConfig),
+    ("finenv_portfolio_panel", 4, PortfolioPanelPtrs),
+    ("finenv_portfolio_state", 5, PortfolioStatePtrs),
+    ("finenv_crypto_config", 6, CryptoConfig),
+    ("finenv_crypto_panel", 7, CryptoPanelPtrs),
+    ("finenv_crypto_state", 8, CryptoStatePtrs),
+    ("finenv_stocknp_config", 9, StockNpConfig),
+    ("finenv_stocknp_panel", 10, StockNpPanelPtrs),
+    ("finenv_stocknp_state", 11, StockNpStatePtrs),
+    ("finenv_cashpenalty_config", 12, CashPenaltyConfig),
+    ("finenv_cashpenalty_panel", 13, CashPenaltyPanelPtrs),
+    ("finenv_cashpenalty_state", 14, CashPenaltyStatePtrs),
+    ("finenv_stoploss_config", 15, StopLossConfig),
+    ("finenv_stoploss_panel", 16, StopLossPanelPtrs),
+    ("finenv_stoploss_state", 17, StopLossStatePtrs),
+    ("finenv_btc_config", 19, BtcConfig),
+    ("finenv_btc_panel", 20, BtcPanelPtrs),
+    ("finenv_btc_state", 21, BtcStatePtrs),
+    ("finenv_replay_view", 23, ReplayViewPtrs),
+    ("finenv_replay_batch", 24, ReplayBatchPtrs),
+    ("finenv_replay_nstep", 26, ReplayNStepPtrs),
+    ("finenv_replay_per", 28, ReplayPerPtrs),
+    ("finenv_rollout_view", 30, RolloutViewPtrs),
+    ("finenv_rollout_batch", 31, RolloutBatchPtrs),
+    ("finenv_vecnorm", 33, VecNormPtrs),
+    ("finenv_stock_history", None, StockHistoryPtrs),
+    ("finenv_portfolio_history", None, PortfolioHistoryPtrs),
+    ("finenv_crypto_history", None, CryptoHistoryPtrs),
+    ("finenv_stocknp_history", None, StockNpHistoryPtrs),
+    ("finenv_twowave_history", None, TwoWaveHistoryPtrs),
+)
+V3_BASELINE_STRUCTS = 18        # indices 0 .. 17: what every ABI v3 build answers
+
+# Every function of include/finenv.h: name -> (restype, argtypes).  A pointer to a struct above is
+# POINTER(its class), `finenv_<kind> **` is POINTER(c_void_p), every other pointer (handles, device
+# buffers, streams) is c_void_p; tests/test_native_abi.py holds each entry to its prototype.
+INT, P, I32, I64, U64, F32, F64 = C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+_view, _batch, _nstep, _per, _vn = (C.POINTER(s) for s in (
+    ReplayViewPtrs, ReplayBatchPtrs, ReplayNStepPtrs, ReplayPerPtrs, VecNormPtrs))
+_STEP = [P] * 6 + [I32, P]      # handle, actions, obs, reward, done, term_obs, auto_reset, stream
+
+SIGNATURES = {
+    "finenv_abi_version": (INT, []),
+    "finenv_struct_size": (INT, [INT]),
+    "finenv_strerror": (C.c_char_p, [INT]),
+    "finenv_device_count": (INT, []),
+    "finenv_stock_set_obs_pitch": (INT, [P, I32]),
+    "finenv_stock_set_desync_hint": (INT, [P, I32]),
+    "finenv_stock_init": (INT, [P, I32, P]),
+    "finenv_stock_observe": (INT, [P] * 3),
+    "finenv_stock_refresh": (INT, [P] * 2),
+    "finenv_stock_step": (INT, [P] * 7 + [I32, P]),             # realised before auto_reset
+    "finenv_stock_episode_stats": (INT, [P] * 3),
+    "finenv_stock_set_last_episode": (INT, [P] * 2),
+    "finenv_stock_last_episode_stats": (INT, [P] * 3),
+    "finenv_portfolio_step": (INT, [P] * 7 + [I32, P]),         # weights_out before auto_reset
+    "finenv_portfolio_set_last_episode": (INT, [P] * 2),
+    "finenv_portfolio_last_episode_stats": (INT, [P] * 3),
+    "finenv_crypto_step": (INT, _STEP),
+    "finenv_crypto_step_record": (INT, [P] * 6 + [I32] + [P] * 6),
+    "finenv_stocknp_set_obs_pitch": (INT, [P, I32]),
+    "finenv_stocknp_step": (INT, _STEP),
+    "finenv_cashpenalty_step": (INT, _STEP),
+    "finenv_cashpenalty_set_random_start": (INT, [P, I32, U64]),
+    "finenv_cashpenalty_set_audit": (INT, [P] * 2),
+    "finenv_stoploss_step": (INT, _STEP),
+    "finenv_stoploss_set_random_start": (INT, [P, I32, U64]),
+    "finenv_stoploss_set_audit": (INT, [P] * 2),
+    "finenv_btc_step": (INT, _STEP),
+    "finenv_riskpre_returns": (INT, [P, P, I32, I32, P]),
+    "finenv_riskpre_turbulence": (INT, [P, P, P, I32, I32, I32, P]),
+    "finenv_riskpre_rolling_cov": (INT, [P, P, I32, I32, I32, P]),
+    "finenv_gae_scan": (INT, [P] * 6 + [I32, I32, F32, F32, P]),
+    "finenv_rollout_put": (INT, [P] * 6 + [I32, I32, P]),
+    "finenv_rollout_minibatch": (INT, [C.POINTER(RolloutViewPtrs), P, U64, I64, C.POINTER(RolloutBatchPtrs),
+                                       P, P]),
+    "finenv_replay_put": (INT, [P, P, I32, P, I32, I32, P]),
+    "finenv_replay_sample": (INT, [_view, P, P, U64, _batch, P, P]),
+    "finenv_replay_gather": (INT, [_view, P, _batch, P]),
+    "finenv_replay_sample_nstep": (INT, [_view, P, P, U64, _batch, _nstep, P, P]),
+    "finenv_replay_gather_nstep": (INT, [_view, P, _batch, _nstep, P]),
+    "finenv_replay_per_tree_words": (I64, [I64]),
+    "finenv_replay_per_rebuild": (INT, [_per, I32, I32, P]),
+    "finenv_replay_per_put": (INT, [_per, I32, I32, I32, I32, P]),
+    "finenv_replay_per_update": (INT, [_per, I32, I32, P, P, I32, P]),
+    "finenv_replay_per_find": (INT, [_per, I32, I32, P, I32, P, P]),
+    "finenv_replay_per_sample": (INT, [_view, _per, P, U64, _batch, P, P, P]),
+    "finenv_replay_per_sample_nstep": (INT, [_view, _per, P, U64, _batch, _nstep, P, P, P]),
+    "finenv_vecnorm_refresh": (INT, [_vn, P]),
+    "finenv_vecnorm_update": (INT, [_vn, P, I64, I64, P]),
+    "finenv_vecnorm_apply": (INT, [_vn, P, I64, I64, P, I64, I32, P]),
+    "finenv_vecnorm_step": (INT, [_vn, _vn, P, I64, P, P, P, F64, P, I64, P, P, I32, I32, I32, I32, P]),
+}
+# the entry points every kind has: (config, panel, state, history struct or None, set_windows pointers)
+for _kind, (_cfg, _panel, _state, _hist, _win) in {
+        "stock": (StockConfig, StockPanelPtrs, StockStatePtrs, StockHistoryPtrs, 1),
+        "portfolio": (PortfolioConfig, PortfolioPanelPtrs, PortfolioStatePtrs, PortfolioHistoryPtrs, 1),
+        "crypto": (CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs, CryptoHistoryPtrs, 2),   # + norm_rows
+        "stocknp": (StockNpConfig, StockNpPanelPtrs, StockNpStatePtrs, StockNpHistoryPtrs, 1),
+        "cashpenalty": (CashPenaltyConfig, CashPenaltyPanelPtrs, CashPenaltyStatePtrs, TwoWaveHistoryPtrs, 1),
+        "stoploss": (StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs, TwoWaveHistoryPtrs, 1),
+        "btc": (BtcConfig, BtcPanelPtrs, BtcStatePtrs, None, 1)}.items():
+    SIGNATURES.update({
+        f"finenv_{_kind}_create": (INT, [C.POINTER(_cfg), C.POINTER(P)]),
+        f"finenv_{_kind}_destroy": (None, [P]),
+        f"finenv_{_kind}_last_error": (C.c_char_p, [P]),
+        f"finenv_{_kind}_obs_dim": (INT, [P]),
+        f"finenv_{_kind}_bind": (INT, [P, C.POINTER(_panel), C.POINTER(_state)]),
+        f"finenv_{_kind}_reset": (INT, [P] * 4),
+        f"finenv_{_kind}_set_windows": (INT, [P] * (1 + _win)),
+    })
+    if _hist is not None:
+        SIGNATURES.update({
+            f"finenv_{_kind}_set_history": (INT, [P, C.POINTER(_hist)]),
+            f"finenv_{_kind}_history_arm": (INT, [P] * 3),
+            f"finenv_{_kind}_history_metrics": (INT, [P, F64, P, P]),
+        })
+
+
+def declare(L):
+    """Declare the tables on a loaded library and check it against them.  One rule lets a build of an
+    earlier commit load beside the current one (tools/exp_ab_inproc.py): a function the library does not
+    export is not declared, and past the v3 baseline a struct index it answers -1 for is one it predates.
+    Any other size than the class's, or -1 inside the baseline, raises."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    if L.finenv_abi_version() != ABI_VERSION:
+        raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
+    for _, which, cls in STRUCTS:
+        if which is None:
+            continue
+        size = L.finenv_struct_size(which)
+        if size != C.sizeof(cls) and not (size == -1 and which >= V3_BASELINE_STRUCTS):
+            raise NativeLibraryError(
+                f"ABI struct size mismatch for {cls.__name__}: python {C.sizeof(cls)} vs library {size}")
+    return L
+
 
 _lib = None
 
@@ -322,156 +451,8 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C finrl_amd/csrc` (needs hipcc). finrl_amd has no CPU "
             "fallback.")
-    L = C.CDLL(LIB_PATH)
-    L.finenv_abi_version.restype = C.c_int
-    L.finenv_strerror.restype = C.c_char_p
-    L.finenv_strerror.argtypes = [C.c_int]
-    L.finenv_device_count.restype = C.c_int
-    # entry points every kind has; each *_step is declared below (their signatures differ)
-    for kind, cfg, panel, state in (
-            ("stock", StockConfig, StockPanelPtrs, StockStatePtrs),
-            ("portfolio", PortfolioConfig, PortfolioPanelPtrs, PortfolioStatePtrs),
-            ("crypto", CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs),
-            ("stocknp", StockNpConfig, StockNpPanelPtrs, StockNpStatePtrs),
-            ("cashpenalty", CashPenaltyConfig, CashPenaltyPanelPtrs, CashPenaltyStatePtrs),
-            ("stoploss", StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs),
-            ("btc", BtcConfig, BtcPanelPtrs, BtcStatePtrs)):
-        if kind == "btc" and not hasattr(L, "finenv_btc_create"):
-            continue            # (a build of an earlier commit: see the note on the windows below)
-        create, destroy, last_error, obs_dim, bind, reset = (
-            getattr(L, f"finenv_{kind}_{name}")
-            for name in ("create", "destroy", "last_error", "obs_dim", "bind", "reset"))
-        create.argtypes = [C.POINTER(cfg), C.POINTER(C.c_void_p)]
-        destroy.argtypes = [C.c_void_p]
-        destroy.restype = None
-        last_error.argtypes = [C.c_void_p]
-        last_error.restype = C.c_char_p
-        obs_dim.argtypes = [C.c_void_p]
-        bind.argtypes = [C.c_void_p, C.POINTER(panel), C.POINTER(state)]
-        reset.argtypes = [C.c_void_p] * 4
-    L.finenv_stock_set_obs_pitch.argtypes = [C.c_void_p, C.c_int32]
-    L.finenv_stock_set_desync_hint.argtypes = [C.c_void_p, C.c_int32]
-    L.finenv_stock_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_stock_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.finenv_stock_refresh.argtypes = [C.c_void_p, C.c_void_p]
-    L.finenv_stock_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_stock_episode_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.finenv_portfolio_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                        C.c_void_p]
-    L.finenv_crypto_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_crypto_step_record.argtypes = [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 6
-    L.finenv_stocknp_set_obs_pitch.argtypes = [C.c_void_p, C.c_int32]
-    L.finenv_stocknp_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_cashpenalty_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.finenv_stoploss_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    if hasattr(L, "finenv_btc_create"):
-        L.finenv_btc_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_int32, C.c_void_p]
-        L.finenv_btc_set_windows.argtypes = [C.c_void_p] * 2
-    L.finenv_riskpre_returns.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-    L.finenv_riskpre_turbulence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                            C.c_int32, C.c_int32, C.c_void_p]
-    L.finenv_riskpre_rolling_cov.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
-                                             C.c_int32, C.c_void_p]
-    L.finenv_cashpenalty_set_random_start.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
-    L.finenv_stoploss_set_random_start.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
-    L.finenv_cashpenalty_set_audit.argtypes = [C.c_void_p, C.c_void_p]
-    L.finenv_stoploss_set_audit.argtypes = [C.c_void_p, C.c_void_p]
-    # Last-episode block, episode windows.  Bound only where exported: tools/exp_ab_inproc.py loads a build of an
-    # earlier commit through this function beside the current one (tests/test_native_abi.py checks
-    # that the current build exports every symbol the header declares).
-    for name, n in (("finenv_stock_set_last_episode", 2), ("finenv_stock_last_episode_stats", 3),
-                    ("finenv_portfolio_set_last_episode", 2),
-                    ("finenv_portfolio_last_episode_stats", 3), ("finenv_stock_set_windows", 2),
-                    ("finenv_portfolio_set_windows", 2), ("finenv_crypto_set_windows", 3),
-                    ("finenv_stocknp_set_windows", 2), ("finenv_cashpenalty_set_windows", 2),
-                    ("finenv_stoploss_set_windows", 2)):
-        if hasattr(L, name):
-            getattr(L, name).argtypes = [C.c_void_p] * n
-    for kind, ptrs in (("stock", StockHistoryPtrs), ("portfolio", PortfolioHistoryPtrs),
-                       ("crypto", CryptoHistoryPtrs), ("stocknp", StockNpHistoryPtrs),
-                       ("cashpenalty", TwoWaveHistoryPtrs), ("stoploss", TwoWaveHistoryPtrs)):
-        if hasattr(L, f"finenv_{kind}_set_history"):       # episode history (same rule)
-            getattr(L, f"finenv_{kind}_set_history").argtypes = [C.c_void_p, C.POINTER(ptrs)]
-            getattr(L, f"finenv_{kind}_history_arm").argtypes = [C.c_void_p] * 3
-            getattr(L, f"finenv_{kind}_history_metrics").argtypes = [C.c_void_p, C.c_double,
-                                                                     C.c_void_p, C.c_void_p]
-    if hasattr(L, "finenv_replay_put"):                    # replay buffer (same rule)
-        L.finenv_replay_put.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                        C.c_int32, C.c_void_p]
-        L.finenv_replay_sample.argtypes = [C.POINTER(ReplayViewPtrs), C.c_void_p, C.c_void_p,
-                                           C.c_uint64, C.POINTER(ReplayBatchPtrs), C.c_void_p,
-                                           C.c_void_p]
-        L.finenv_replay_gather.argtypes = [C.POINTER(ReplayViewPtrs), C.c_void_p,
-                                           C.POINTER(ReplayBatchPtrs), C.c_void_p]
-    if hasattr(L, "finenv_replay_sample_nstep"):           # n-step sampler (same rule)
-        L.finenv_replay_sample_nstep.argtypes = [
-            C.POINTER(ReplayViewPtrs), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
-            C.POINTER(ReplayNStepPtrs), C.c_void_p, C.c_void_p]
-        L.finenv_replay_gather_nstep.argtypes = [
-            C.POINTER(ReplayViewPtrs), C.c_void_p, C.POINTER(ReplayBatchPtrs),
-            C.POINTER(ReplayNStepPtrs), C.c_void_p]
-    if hasattr(L, "finenv_replay_per_sample"):             # prioritised replay (same rule)
-        per = C.POINTER(ReplayPerPtrs)
-        L.finenv_replay_per_tree_words.argtypes = [C.c_int64]
-        L.finenv_replay_per_tree_words.restype = C.c_int64
-        L.finenv_replay_per_rebuild.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p]
-        L.finenv_replay_per_put.argtypes = [per, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                            C.c_void_p]
-        L.finenv_replay_per_update.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                               C.c_int32, C.c_void_p]
-        L.finenv_replay_per_find.argtypes = [per, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                             C.c_void_p, C.c_void_p]
-        L.finenv_replay_per_sample.argtypes = [
-            C.POINTER(ReplayViewPtrs), per, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
-            C.c_void_p, C.c_void_p, C.c_void_p]
-        L.finenv_replay_per_sample_nstep.argtypes = [
-            C.POINTER(ReplayViewPtrs), per, C.c_void_p, C.c_uint64, C.POINTER(ReplayBatchPtrs),
-            C.POINTER(ReplayNStepPtrs), C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "finenv_rollout_minibatch"):             # shuffled rollout minibatches (same rule)
-        L.finenv_rollout_minibatch.argtypes = [
-            C.POINTER(RolloutViewPtrs), C.c_void_p, C.c_uint64, C.c_int64, C.POINTER(RolloutBatchPtrs),
-            C.c_void_p, C.c_void_p]
-    if hasattr(L, "finenv_vecnorm_step"):                  # running obs / return statistics (same rule)
-        vn = C.POINTER(VecNormPtrs)
-        L.finenv_vecnorm_refresh.argtypes = [vn, C.c_void_p]
-        L.finenv_vecnorm_update.argtypes = [vn, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        L.finenv_vecnorm_apply.argtypes = [vn, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
-                                           C.c_int32, C.c_void_p]
-        L.finenv_vecnorm_step.argtypes = [
-            vn, vn, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
-            C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-    if L.finenv_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfinenv.so ABI version mismatch; rebuild (make -C finrl_amd/csrc)")
-    L.finenv_struct_size.argtypes = [C.c_int]
-    first = (StockConfig, StockPanelPtrs, StockStatePtrs, PortfolioConfig, PortfolioPanelPtrs,
-             PortfolioStatePtrs, CryptoConfig, CryptoPanelPtrs, CryptoStatePtrs, StockNpConfig,
-             StockNpPanelPtrs, StockNpStatePtrs, CashPenaltyConfig, CashPenaltyPanelPtrs,
-             CashPenaltyStatePtrs, StopLossConfig, StopLossPanelPtrs, StopLossStatePtrs)
-    later = sorted(_LATER_STRUCTS.items()) if hasattr(L, "finenv_btc_create") else []
-    if hasattr(L, "finenv_replay_put"):
-        later += sorted(_REPLAY_STRUCTS.items())
-    if hasattr(L, "finenv_replay_sample_nstep"):
-        later += sorted(_REPLAY_NSTEP_STRUCTS.items())
-    if hasattr(L, "finenv_replay_per_sample"):
-        later += sorted(_REPLAY_PER_STRUCTS.items())
-    if hasattr(L, "finenv_rollout_minibatch"):
-        later += sorted(_ROLLOUT_STRUCTS.items())
-    if hasattr(L, "finenv_vecnorm_step"):
-        later += sorted(_VECNORM_STRUCTS.items())
-    for which, cls in list(enumerate(first)) + later:
-        if L.finenv_struct_size(which) != C.sizeof(cls):
-            raise NativeLibraryError(
-                f"ABI struct size mismatch for {cls.__name__}: python {C.sizeof(cls)} vs "
-                f"library {L.finenv_struct_size(which)}")
-    _lib = L
-    return L
+    _lib = declare(C.CDLL(LIB_PATH))
+    return _lib
 
 
 def check(code: int, handle=None, what: str = "", kind: str = "stock"):

@@ -21,6 +21,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._native import STOCK_MAX_TICKERS
+
 
 class StockPanel:
     def __init__(self, close, tech=None, risk=None, *, tech_names=None, dates=None,
@@ -110,8 +112,8 @@ class StockPanel:
         """f64 [T, N]: the closes with the fork's "untradable" flag in the sign bit -- set iff the
         first indicator of that ticker equals 1.0 on that day (fp64 compare; :105, :174).  The
         kernels use |close| for every valuation and the sign only in the trade rules."""
-        if self.N > 128:
-            raise ValueError("the stock kernels support N <= 128 tickers")
+        if self.N > STOCK_MAX_TICKERS:
+            raise ValueError(f"the stock kernels support N <= {STOCK_MAX_TICKERS} tickers")
         if (self.close < 0).any():
             raise ValueError("closes must be >= 0 (the sign bit is the untradable flag)")
         out = np.abs(self.close)              # also turns any -0.0 into +0.0

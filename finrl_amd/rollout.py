@@ -59,7 +59,6 @@ class RolloutBuffer:
         """Store the policy's outputs of step t (one launch: finenv_rollout_put)."""
         import torch
         L = nat.lib()
-        L.finenv_rollout_put.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p]
         dev = self.rewards.device
         a = actions.to(dev, torch.float32).contiguous()
         v = values.to(dev, torch.float32).contiguous()
@@ -103,8 +102,6 @@ class RolloutBuffer:
     def compute_returns_and_advantage(self, last_values, gamma=0.99, gae_lambda=0.95):
         import torch
         L = nat.lib()
-        L.finenv_gae_scan.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_float,
-                                                          C.c_float, C.c_void_p]
         lv = last_values.to(self.rewards.device, torch.float32).contiguous()
         stream = C.c_void_p(torch.cuda.current_stream(self.rewards.device).cuda_stream)
         nat.check(L.finenv_gae_scan(

@@ -3,14 +3,10 @@ finenv_crypto_set_windows and the library exports it, the setter validates its a
 GPU, the ABI version, the crypto struct sizes and field enums are those of v3, the per-row
 normaliser table equals action_norm_vector row by row, and the Python classes expose the API."""
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
 
 
 @pytest.fixture(scope="module")
@@ -21,9 +17,8 @@ def L():
 
 
 def test_header_declares_and_library_exports_set_windows(L):
-    hdr = open(HDR).read()
-    assert re.search(r"\bint\s+finenv_crypto_set_windows\s*\(\s*finenv_crypto\s*\*\s*h\s*,"
-                     r"\s*int32_t\s*\*\s*win\s*,\s*const\s+double\s*\*\s*norm_rows\s*\)", hdr)
+    assert H.prototypes()["finenv_crypto_set_windows"] == \
+        ("int", [("finenv_crypto *", "h"), ("int32_t *", "win"), ("const double *", "norm_rows")])
     assert hasattr(L, "finenv_crypto_set_windows")
 
 
@@ -55,15 +50,15 @@ def test_set_windows_validates_handle_and_table(L):
 def test_abi_version_struct_sizes_and_enums_unchanged(L):
     from finrl_amd import _native as nat
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    assert "#define FINENV_ABI_VERSION 3" in re.sub(r"[ \t]+", " ", open(HDR).read())
+    assert H.constants()["FINENV_ABI_VERSION"] == 3
     cls = (nat.CryptoConfig, nat.CryptoPanelPtrs, nat.CryptoStatePtrs)
     for which, c in zip((6, 7, 8), cls):
         assert L.finenv_struct_size(which) == C.sizeof(c)
     assert tuple(C.sizeof(c) for c in cls) == (56, 24, 24)
-    hdr = re.sub(r"\s+", " ", open(HDR).read())
-    assert ("enum { FINENV_CF_CASH = 0, FINENV_CF_TOTAL_ASSET, FINENV_CF_GAMMA_RETURN, "
-            "FINENV_CF_EPISODE_RETURN, FINENV_CF_LAST_REWARD, FINENV_CRYPTO_F64_FIELDS };") in hdr
-    assert "enum { FINENV_CI_TIME = 0, FINENV_CRYPTO_I32_FIELDS };" in hdr
+    assert H.enum("FINENV_CRYPTO_F64_FIELDS") == [
+        "FINENV_CF_CASH", "FINENV_CF_TOTAL_ASSET", "FINENV_CF_GAMMA_RETURN", "FINENV_CF_EPISODE_RETURN",
+        "FINENV_CF_LAST_REWARD", "FINENV_CRYPTO_F64_FIELDS"]
+    assert H.enum("FINENV_CRYPTO_I32_FIELDS") == ["FINENV_CI_TIME", "FINENV_CRYPTO_I32_FIELDS"]
     assert nat.CRYPTO_F64_FIELDS == ("cash", "total_asset", "gamma_return", "episode_return",
                                      "last_reward")
     assert nat.CRYPTO_I32_FIELDS == ("time",)

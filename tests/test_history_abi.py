@@ -5,14 +5,12 @@ validate their arguments without a GPU.  What is a kind's own (builders, readers
 tests/test_<kind>_history_abi.py."""
 import ctypes as C
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
+
 E, N = 64, 5
 DTYPES = {"double": np.float64, "int32_t": np.int32, "float": np.float32, "uint8_t": np.uint8}
 # the v3 structs, by their sizes as that version laid them out (the history structs are in no size table)
@@ -78,33 +76,33 @@ def _host_history(nat, kind, cap=5, off=()):
 def test_header_declares_and_library_exports_the_history_api(L, kind):
     from finrl_amd import _native as nat
     k = KINDS[kind]
-    hdr = open(HDR).read()
     for name in ("set_history", "history_arm", "history_metrics"):
         fn = f"finenv_{kind}_{name}"
-        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
+        assert H.prototypes()[fn][0] == "int", fn
         assert hasattr(L, fn), fn
-    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (k["struct"], k["struct"]), hdr, flags=re.S)
-    assert m, "struct " + k["struct"]
+    assert k["struct"] in H.structs(), "struct " + k["struct"]
+    members = H.structs()[k["struct"]]
     want = [(t, f) for t, f, _ in k["fields"]] + [("int32_t", "capacity")]
-    assert re.findall(r"^\s*(double|int32_t|float|uint8_t)\s+\*?(\w+);", m.group(1), flags=re.M) == want
-    pointers = re.findall(r"^\s*\w+\s+\*(\w+);", m.group(1), flags=re.M)
+    assert [(t.rstrip(" *"), f) for t, f in members] == want
+    pointers = [f for t, f in members if t.endswith("*")]
     assert pointers == [f for _, f in want[:-1]]             # every member but capacity is a pointer
     ptrs = getattr(nat, k["ptrs"])
     assert [f[0] for f in ptrs._fields_] == [f for _, f in want]
     assert [f[1] for f in ptrs._fields_] == [C.c_void_p] * (len(want) - 1) + [C.c_int32]
-    cols = re.findall(r"^\s+FINENV_HM_([A-Z0-9_]+)", hdr, flags=re.M)
-    assert tuple(c.lower() for c in cols) == getattr(nat, k["metrics"]) == nat.STOCK_HISTORY_METRICS == METRICS
+    assert all(c.startswith("FINENV_HM_") for c in H.enum("FINENV_STOCK_HISTORY_METRICS")[:-1])
+    assert H.fields("FINENV_STOCK_HISTORY_METRICS") == getattr(nat, k["metrics"]) == \
+        nat.STOCK_HISTORY_METRICS == METRICS
 
 
 def test_flag_values_abi_version_and_struct_sizes(L):
     """What no kind changes: the flag bits, and that the history API is additive -- same ABI version, same
     v3 structs."""
     from finrl_amd import _native as nat
-    hdr = open(HDR).read()
-    assert re.search(r"FINENV_HIST_COMPLETE\s*=\s*1\b", hdr) and nat.HIST_COMPLETE == 1
-    assert re.search(r"FINENV_HIST_OVERFLOW\s*=\s*2\b", hdr) and nat.HIST_OVERFLOW == 2
-    assert re.search(r"FINENV_HIST_ARMED\s*=\s*4\b", hdr) and nat.HIST_ARMED == 4
-    assert "#define FINENV_ABI_VERSION 3" in hdr
+    k = H.constants()
+    assert k["FINENV_HIST_COMPLETE"] == 1 and nat.HIST_COMPLETE == 1
+    assert k["FINENV_HIST_OVERFLOW"] == 2 and nat.HIST_OVERFLOW == 2
+    assert k["FINENV_HIST_ARMED"] == 4 and nat.HIST_ARMED == 4
+    assert k["FINENV_ABI_VERSION"] == 3
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
     assert [L.finenv_struct_size(i) for i in range(18)] == V3_STRUCT_SIZES
     assert L.finenv_struct_size(18) == -1

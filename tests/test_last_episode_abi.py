@@ -2,14 +2,10 @@
 FINENV_SL_* / FINENV_PL_* field enums, the library exports them, the Python field tuples follow the
 header, and the entry points validate their arguments without a GPU."""
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
 
 
 @pytest.fixture(scope="module")
@@ -19,23 +15,24 @@ def L():
     return _native.lib()
 
 
-def _enum(prefix):
-    return re.findall(rf"^\s+FINENV_{prefix}_([A-Z0-9_]+)", open(HDR).read(), flags=re.M)
+def _enum(prefix, count_name):
+    names = H.enum(count_name)[:-1]
+    assert all(n.startswith(f"FINENV_{prefix}_") for n in names)
+    return [n[len(f"FINENV_{prefix}_"):] for n in names]
 
 
 def test_header_declares_and_library_exports_the_block_api(L):
-    hdr = open(HDR).read()
     for fn in ("finenv_stock_set_last_episode", "finenv_stock_last_episode_stats",
                "finenv_portfolio_set_last_episode", "finenv_portfolio_last_episode_stats"):
-        assert re.search(rf"\bint\s+{fn}\s*\(", hdr), fn
+        assert H.prototypes()[fn][0] == "int", fn
         assert hasattr(L, fn), fn
-    assert "FINENV_STOCK_LAST_FIELDS" in hdr and "FINENV_PORTFOLIO_LAST_FIELDS" in hdr
+    assert "FINENV_STOCK_LAST_FIELDS" in H.constants() and "FINENV_PORTFOLIO_LAST_FIELDS" in H.constants()
 
 
 def test_field_tuples_match_the_header():
     from finrl_amd import _native as nat
-    assert tuple(x.lower() for x in _enum("SL")) == nat.STOCK_LAST_FIELDS
-    assert tuple(x.lower() for x in _enum("PL")) == nat.PORTFOLIO_LAST_FIELDS
+    assert tuple(x.lower() for x in _enum("SL", "FINENV_STOCK_LAST_FIELDS")) == nat.STOCK_LAST_FIELDS
+    assert tuple(x.lower() for x in _enum("PL", "FINENV_PORTFOLIO_LAST_FIELDS")) == nat.PORTFOLIO_LAST_FIELDS
     assert nat.STOCK_LAST_FIELDS[0] == nat.PORTFOLIO_LAST_FIELDS[0] == "count"
 
 

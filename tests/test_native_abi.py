@@ -1,6 +1,7 @@
 """CPU-side checks of the C-ABI library: it loads (hipcc-built, no GPU needed), exports every
-symbol include/finenv.h declares, the ctypes struct layouts match the compiled ones, argument
-validation works, and launches fail loudly (never fall back) when no HIP device exists."""
+symbol include/finenv.h declares, the whole ctypes binding (signatures, struct layouts, constants)
+agrees with that header, argument validation works, and launches fail loudly (never fall back) when no
+HIP device exists."""
 import ctypes as C
 import os
 import re
@@ -8,39 +9,150 @@ import re
 import numpy as np
 import pytest
 
+import abi_header as H
+from finrl_amd import _native as nat
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLASSES = {cname: cls for cname, _, cls in nat.STRUCTS}
 
 
 @pytest.fixture(scope="module")
 def L():
-    from finrl_amd import _native
-    _native.build()
-    return _native.lib()
+    nat.build()
+    return nat.lib()
 
 
 def test_exports_every_declared_symbol(L):
-    hdr = open(os.path.join(ROOT, "include", "finenv.h")).read()
-    names = sorted(set(re.findall(r"\b(finenv_[a-z0-9_]+)\s*\(", hdr)))
+    names = sorted(H.prototypes())
     assert len(names) >= 13
     for n in names:
         assert hasattr(L, n), f"libfinenv.so does not export {n}"
 
 
 def test_struct_layouts_match(L):
-    from finrl_amd import _native as nat
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
     assert L.finenv_struct_size(0) == C.sizeof(nat.StockConfig)
     assert L.finenv_struct_size(1) == C.sizeof(nat.StockPanelPtrs)
     assert L.finenv_struct_size(2) == C.sizeof(nat.StockStatePtrs)
-    hdr = open(os.path.join(ROOT, "include", "finenv.h")).read()
-    f64 = re.findall(r"^\s+FINENV_SF_([A-Z0-9_]+)", hdr, flags=re.M)
-    i32 = re.findall(r"^\s+FINENV_SI_([A-Z0-9_]+)", hdr, flags=re.M)
-    assert tuple(x.lower() for x in f64) == nat.STOCK_F64_FIELDS
-    assert tuple(x.lower() for x in i32) == nat.STOCK_I32_FIELDS
+    assert H.fields("FINENV_STOCK_F64_FIELDS") == nat.STOCK_F64_FIELDS
+    assert H.fields("FINENV_STOCK_I32_FIELDS") == nat.STOCK_I32_FIELDS
+
+
+# ------------------------------------------------------------------ the binding against the header
+def test_tables_and_header_name_the_same_functions_and_structs():
+    assert set(nat.SIGNATURES) == set(H.prototypes()) and len(nat.SIGNATURES) == 116
+    assert set(CLASSES) == set(H.structs()) and len(nat.STRUCTS) == len(CLASSES) == 33
+    assert H.binding_errors(nat) == []
+
+
+@pytest.mark.parametrize("name", sorted(H.prototypes()))
+def test_signature_follows_the_prototype(L, name):
+    restype, argtypes = H.expected_signature(name, CLASSES)
+    fn = getattr(L, name)
+    assert fn.restype is restype and list(fn.argtypes) == argtypes
+    assert nat.SIGNATURES[name] == (restype, argtypes)
+
+
+@pytest.mark.parametrize("cname,which,cls", nat.STRUCTS, ids=[s[0] for s in nat.STRUCTS])
+def test_struct_follows_the_header(L, cname, which, cls):
+    assert cls._fields_ == H.expected_fields(cname)
+    if which is not None:
+        assert L.finenv_struct_size(which) == C.sizeof(cls)
+
+
+def test_struct_size_gaps_stay_invalid(L):
+    indexed = sorted(which for _, which, _ in nat.STRUCTS if which is not None)
+    gaps = sorted(set(range(indexed[-1] + 2)) - set(indexed))
+    assert gaps == [18, 22, 25, 27, 29, 32, 34]
+    for which in gaps:
+        assert L.finenv_struct_size(which) == -1, which
+
+
+def test_field_tuples_and_constants_mirror_the_header():
+    k = H.constants()
+    assert len(H.FIELD_TUPLES) == 18                  # the 17 field tuples and STOPLOSS_BOOKS
+    for tup in H.FIELD_TUPLES:
+        assert getattr(nat, tup) == H.fields("FINENV_" + tup), tup
+        assert len(getattr(nat, tup)) == k["FINENV_" + tup], tup
+    for alias in ("PORTFOLIO", "CRYPTO", "STOCKNP", "TWOWAVE"):      # one enum of columns serves every env
+        assert getattr(nat, alias + "_HISTORY_METRICS") is nat.STOCK_HISTORY_METRICS
+    assert nat.ABI_VERSION == k["FINENV_ABI_VERSION"] and nat.FINENV_OK == k["FINENV_OK"] == 0
+    # check() treats every nonzero code as an error and asks the library for its text: each has one
+    errors = {n: v for n, v in k.items() if n.startswith("FINENV_ERR_")}
+    assert sorted(errors.values()) == [-4, -3, -2, -1]
+    for name in ("HIST_COMPLETE", "HIST_OVERFLOW", "HIST_ARMED", "AUDIT_HEAD", "AUDIT_F_LAST_DATE",
+                 "AUDIT_F_CASH_SHORTAGE", "AUDIT_F_TURBULENCE", "AUDIT_F_STOP_LOSS", "AUDIT_F_LOW_PROFIT",
+                 "AUDIT_F_HIGH_PROFIT", "BTC_MAX_PRICE_COLS", "VECNORM_MAX_TILES", "STOCK_MAX_TICKERS"):
+        assert getattr(nat, name) == k["FINENV_" + name], name
+    from finrl_amd import vec_btc, vec_stocknp
+    for mod in (vec_stocknp, vec_btc):
+        assert (mod.TAG_PY, mod.TAG_F32, mod.TAG_F64) == \
+            (k["FINENV_NT_PY"], k["FINENV_NT_F32"], k["FINENV_NT_F64"]), mod.__name__
+
+
+def test_strerror_knows_every_error_code(L):
+    for name, code in H.constants().items():
+        if name == "FINENV_OK" or name.startswith("FINENV_ERR_"):
+            assert L.finenv_strerror(code) not in (None, b"", b"unknown error"), name
+
+
+def _edited(pattern, repl):
+    src = open(H.HEADER).read()
+    out, n = re.subn(pattern, repl, src, count=1, flags=re.S)
+    assert n == 1, pattern
+    return out
+
+
+# the checker can fail: each edit of the header text is reported, with the function, struct or tuple named
+@pytest.mark.parametrize("pattern,repl,culprit", [
+    # two same-sized fields of a struct swapped (the first such pair is finenv_stock_config's)
+    (r"int32_t n_envs;(.*?)int32_t n_tickers;", r"int32_t n_tickers;\1int32_t n_envs;", "finenv_stock_config"),
+    # one argument dropped from a prototype
+    (r"(finenv_stock_step\([^)]*?), int32_t auto_reset", r"\1", "finenv_stock_step"),
+    # an int32_t argument changed to double
+    (r"(finenv_stock_init\(finenv_stock \*h, )int32_t", r"\1double", "finenv_stock_init"),
+    # an enumerator inserted in the middle of a field enum
+    (r"(FINENV_SF_COST,)", r"\1 FINENV_SF_EXTRA,", "STOCK_F64_FIELDS"),
+    # a prototype added with no table entry
+    (r"(int\s+finenv_struct_size\(int which\);)", r"\1\nint finenv_stock_new_call(finenv_stock *h);",
+     "finenv_stock_new_call"),
+], ids=["fields-swapped", "argument-dropped", "int32-to-double", "enumerator-inserted", "prototype-added"])
+def test_checker_reports_an_edited_header(pattern, repl, culprit):
+    errs = H.binding_errors(nat, _edited(pattern, repl))
+    assert len(errs) == 1 and errs[0].startswith(culprit + ": "), errs
+
+
+class _EarlierBuild:
+    """The real library as a build from before `hidden` existed: those symbols are missing, and
+    finenv_struct_size answers -1 past the v3 baseline (and `sizes` where a test says otherwise)."""
+
+    def __init__(self, L, hidden, sizes=()):
+        self._L, self._hidden, sizes = L, hidden, dict(sizes)
+        # (a plain function: declare() sets restype / argtypes on it like on any other entry point)
+        self.finenv_struct_size = lambda which: sizes.get(
+            which, -1 if which > 17 else L.finenv_struct_size(which))
+
+    def __getattr__(self, name):
+        if name.startswith(self._hidden):
+            raise AttributeError(name)
+        return getattr(self._L, name)
+
+
+@pytest.mark.parametrize("hidden", [("finenv_btc_",), ("finenv_replay_", "finenv_rollout_", "finenv_vecnorm_"),
+                                    ("finenv_vecnorm_",)])
+def test_an_earlier_build_still_declares_and_checks(L, hidden):
+    old = _EarlierBuild(L, hidden)
+    assert not hasattr(old, hidden[0] + "step") and hasattr(old, "finenv_stock_step")
+    assert nat.declare(old) is old
+    with pytest.raises(nat.NativeLibraryError, match="StockNpConfig"):      # the baseline must match
+        nat.declare(_EarlierBuild(L, hidden, {9: C.sizeof(nat.StockNpConfig) + 8}))
+    with pytest.raises(nat.NativeLibraryError, match="StockPanelPtrs"):     # ... and -1 is no answer there
+        nat.declare(_EarlierBuild(L, hidden, {1: -1}))
+    with pytest.raises(nat.NativeLibraryError, match="BtcConfig"):          # past it, only -1 or sizeof
+        nat.declare(_EarlierBuild(L, hidden, {19: C.sizeof(nat.BtcConfig) + 8}))
 
 
 def test_create_validates_arguments(L):
-    from finrl_amd import _native as nat
     h = C.c_void_p()
     ok = nat.StockConfig(64, 30, 8, 100, 100, 0, 1, 1, 1, 0, 1e-3, 1e-3, 1e-4, 0.0)
     assert L.finenv_stock_create(C.byref(ok), C.byref(h)) == 0
@@ -64,7 +176,6 @@ def test_no_cpu_fallback():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
     from finrl_amd import StockPanel
-    from finrl_amd import _native as nat
     from finrl_amd.vec_env import VecStockTradingEnv
     panel = StockPanel(np.ones((4, 3)), np.zeros((4, 2, 3)), np.zeros(4))
     with pytest.raises((nat.FinenvError, RuntimeError, AssertionError)):
@@ -90,26 +201,22 @@ def test_product_never_imports_oracle():
             assert line.startswith("    "), line
 
 
-# One valid config per handle kind, the obs_dim it gives, and the entry points that launch work
-# (name, argument count after the handle).  The host contract below holds for every kind alike.
+# One valid config per handle kind, the obs_dim it gives, and the entry points that launch work (their
+# argument counts come from the header).  The host contract below holds for every kind alike.
 def _kind_cases():
-    from finrl_amd import _native as nat
     cash = (64, 4, 3, 50, 0, 1, 0, 0, 10.0, 3e-3, 3e-3, 1e6, 0.1, 0.0)
     return {
         "stock": (nat.StockConfig(64, 30, 8, 100, 100, 0, 1, 1, 1, 0, 1e-3, 1e-3, 1e-4, 0.0),
                   nat.StockPanelPtrs, 301,
-                  (("init", 2), ("reset", 3), ("observe", 2), ("refresh", 1), ("step", 8),
-                   ("episode_stats", 2), ("last_episode_stats", 2))),
+                  ("init", "reset", "observe", "refresh", "step", "episode_stats", "last_episode_stats")),
         "portfolio": (nat.PortfolioConfig(64, 5, 4, 50, 1e6), nat.PortfolioPanelPtrs, 45,
-                      (("reset", 3), ("step", 8), ("last_episode_stats", 2))),
+                      ("reset", "step", "last_episode_stats")),
         "crypto": (nat.CryptoConfig(64, 3, 4, 50, 2, 0, 1e6, 1e-3, 1e-3, 0.99),
-                   nat.CryptoPanelPtrs, 12, (("reset", 3), ("step", 7), ("step_record", 12))),
+                   nat.CryptoPanelPtrs, 12, ("reset", "step", "step_record")),
         "stocknp": (nat.StockNpConfig(64, 5, 7, 50, 10, 0, 100.0, 1e-3, 1e-3, 2 ** -11, 0.99, 0.0),
-                    nat.StockNpPanelPtrs, 25, (("reset", 3), ("step", 7))),
-        "cashpenalty": (nat.CashPenaltyConfig(*cash), nat.CashPenaltyPanelPtrs, 17,
-                        (("reset", 3), ("step", 7))),
-        "stoploss": (nat.StopLossConfig(*cash, 0.9, 1.2), nat.StopLossPanelPtrs, 17,
-                     (("reset", 3), ("step", 7))),
+                    nat.StockNpPanelPtrs, 25, ("reset", "step")),
+        "cashpenalty": (nat.CashPenaltyConfig(*cash), nat.CashPenaltyPanelPtrs, 17, ("reset", "step")),
+        "stoploss": (nat.StopLossConfig(*cash, 0.9, 1.2), nat.StopLossPanelPtrs, 17, ("reset", "step")),
     }
 
 
@@ -122,13 +229,13 @@ def test_host_contract_every_kind(L, kind):
 
     def launch(name, h):        # a private function object: the library's own argtypes stay as declared
         f = L[f"finenv_{kind}_{name}"]
-        nargs = dict(launches)[name]
+        nargs = len(H.prototypes()[f"finenv_{kind}_{name}"][1]) - 1          # the arguments after the handle
         f.argtypes = [C.c_void_p] * (1 + nargs)
         return f(h, *([None] * nargs))
 
     assert fn("last_error")(None) == b"null handle"
     assert fn("obs_dim")(None) == -1
-    for name, _ in launches:
+    for name in launches:
         assert launch(name, None) == -1, name
     h = C.c_void_p()
     assert fn("create")(C.byref(cfg), C.byref(h)) == 0

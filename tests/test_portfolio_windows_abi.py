@@ -3,15 +3,11 @@ finenv_portfolio_set_windows and the library exports it, the setter validates it
 GPU, the ABI version, the portfolio struct sizes and field enums are those of v3, and
 finrl_amd.data.windows_from_dates over a PortfolioPanel's dates selects the rows data_split selects."""
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pandas as pd
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
 
 
 @pytest.fixture(scope="module")
@@ -22,9 +18,8 @@ def L():
 
 
 def test_header_declares_and_library_exports_set_windows(L):
-    hdr = open(HDR).read()
-    assert re.search(r"\bint\s+finenv_portfolio_set_windows\s*\(\s*finenv_portfolio\s*\*\s*h\s*,"
-                     r"\s*int32_t\s*\*\s*win\s*\)", hdr)
+    assert H.prototypes()["finenv_portfolio_set_windows"] == \
+        ("int", [("finenv_portfolio *", "h"), ("int32_t *", "win")])
     assert hasattr(L, "finenv_portfolio_set_windows")
 
 
@@ -50,16 +45,17 @@ def test_set_windows_validates_the_handle(L):
 def test_abi_version_struct_sizes_and_enums_unchanged(L):
     from finrl_amd import _native as nat
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    assert "#define FINENV_ABI_VERSION 3" in re.sub(r"[ \t]+", " ", open(HDR).read())
+    assert H.constants()["FINENV_ABI_VERSION"] == 3
     cls = (nat.PortfolioConfig, nat.PortfolioPanelPtrs, nat.PortfolioStatePtrs)
     for which, c in zip((3, 4, 5), cls):
         assert L.finenv_struct_size(which) == C.sizeof(c)
     assert tuple(C.sizeof(c) for c in cls) == (24, 16, 16)
-    hdr = re.sub(r"\s+", " ", open(HDR).read())
-    assert "enum { FINENV_PF_VALUE = 0, FINENV_PF_LAST_REWARD, FINENV_PORTFOLIO_F64_FIELDS };" in hdr
-    assert "enum { FINENV_PI_DAY = 0, FINENV_PORTFOLIO_I32_FIELDS };" in hdr
-    pl = re.search(r"enum \{ (FINENV_PL_COUNT = 0,.*?FINENV_PORTFOLIO_LAST_FIELDS) \};", hdr).group(1)
-    names = re.findall(r"FINENV_PL_(\w+)", re.sub(r"/\*.*?\*/", "", pl))
+    assert H.enum("FINENV_PORTFOLIO_F64_FIELDS") == [
+        "FINENV_PF_VALUE", "FINENV_PF_LAST_REWARD", "FINENV_PORTFOLIO_F64_FIELDS"]
+    assert H.enum("FINENV_PORTFOLIO_I32_FIELDS") == ["FINENV_PI_DAY", "FINENV_PORTFOLIO_I32_FIELDS"]
+    pl = H.enum("FINENV_PORTFOLIO_LAST_FIELDS")[:-1]
+    assert all(n.startswith("FINENV_PL_") for n in pl)
+    names = [n[len("FINENV_PL_"):] for n in pl]
     assert names == ["COUNT", "BEGIN_VALUE", "END_VALUE", "RET_N", "RET_SUM", "RET_SUMSQ", "RUN_SUM",
                      "RUN_SUMSQ"]
     assert nat.PORTFOLIO_F64_FIELDS == ("value", "last_reward")

@@ -3,15 +3,11 @@ finenv_stock_set_windows and the library exports it, the setter validates its ha
 the ABI version and struct sizes are those of v3, and finrl_amd.data.windows_from_dates maps date
 pairs to the panel rows data_split selects."""
 import ctypes as C
-import os
-import re
-
 import numpy as np
 import pandas as pd
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
 
 
 @pytest.fixture(scope="module")
@@ -22,16 +18,14 @@ def L():
 
 
 def test_header_declares_and_library_exports_set_windows(L):
-    hdr = open(HDR).read()
-    assert re.search(r"\bint\s+finenv_stock_set_windows\s*\(\s*finenv_stock\s*\*\s*h\s*,\s*int32_t\s*\*\s*win\s*\)",
-                     hdr)
+    assert H.prototypes()["finenv_stock_set_windows"] == ("int", [("finenv_stock *", "h"), ("int32_t *", "win")])
     assert hasattr(L, "finenv_stock_set_windows")
 
 
 def test_abi_version_and_struct_sizes_unchanged(L):
     from finrl_amd import _native as nat
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    assert "#define FINENV_ABI_VERSION 3" in re.sub(r"[ \t]+", " ", open(HDR).read())
+    assert H.constants()["FINENV_ABI_VERSION"] == 3
     for which, cls in enumerate((nat.StockConfig, nat.StockPanelPtrs, nat.StockStatePtrs)):
         assert L.finenv_struct_size(which) == C.sizeof(cls)
     # the v3 layouts, as a foreign binding written against them declares them

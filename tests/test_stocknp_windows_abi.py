@@ -3,14 +3,12 @@ declares finenv_stocknp_set_windows and the library exports it, the setter valid
 without a GPU, the ABI version, the stocknp struct sizes and field enums are those of v3, and the
 Python class exposes the API through the shared WindowedEnv code."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "finenv.h")
+import abi_header as H
 
 
 @pytest.fixture(scope="module")
@@ -21,9 +19,8 @@ def L():
 
 
 def test_header_declares_and_library_exports_set_windows(L):
-    hdr = open(HDR).read()
-    assert re.search(r"\bint\s+finenv_stocknp_set_windows\s*\(\s*finenv_stocknp\s*\*\s*h\s*,"
-                     r"\s*int32_t\s*\*\s*win\s*\)", hdr)
+    hdr = H.source()
+    assert H.prototypes()["finenv_stocknp_set_windows"] == ("int", [("finenv_stocknp *", "h"), ("int32_t *", "win")])
     assert hasattr(L, "finenv_stocknp_set_windows")
     # the contract names the [4][E] pending / active layout
     body = re.sub(r"\s+", " ", hdr[hdr.index("Per-env episode windows of the array-state env"):
@@ -56,17 +53,16 @@ def test_set_windows_validates_the_handle(L):
 def test_abi_version_struct_sizes_and_enums_unchanged(L):
     from finrl_amd import _native as nat
     assert L.finenv_abi_version() == nat.ABI_VERSION == 3
-    assert "#define FINENV_ABI_VERSION 3" in re.sub(r"[ \t]+", " ", open(HDR).read())
+    assert H.constants()["FINENV_ABI_VERSION"] == 3
     cls = (nat.StockNpConfig, nat.StockNpPanelPtrs, nat.StockNpStatePtrs)
     for which, c in zip((9, 10, 11), cls):
         assert L.finenv_struct_size(which) == C.sizeof(c)
     assert tuple(C.sizeof(c) for c in cls) == (72, 24, 24)
-    hdr = re.sub(r"\s+", " ", open(HDR).read())
-    assert ("enum { FINENV_NF_AMOUNT = 0, FINENV_NF_TOTAL_ASSET, FINENV_NF_GAMMA_REWARD, "
-            "FINENV_NF_INITIAL_TOTAL_ASSET, FINENV_NF_EPISODE_RETURN, FINENV_NF_LAST_REWARD, "
-            "FINENV_NF_AMOUNT0, FINENV_STOCKNP_F64_FIELDS };") in hdr
-    assert ("enum { FINENV_NI_DAY = 0, FINENV_NI_TAGS, FINENV_NI_AMOUNT0_TAG, "
-            "FINENV_STOCKNP_I32_FIELDS };") in hdr
+    assert H.enum("FINENV_STOCKNP_F64_FIELDS") == [
+        "FINENV_NF_AMOUNT", "FINENV_NF_TOTAL_ASSET", "FINENV_NF_GAMMA_REWARD", "FINENV_NF_INITIAL_TOTAL_ASSET",
+        "FINENV_NF_EPISODE_RETURN", "FINENV_NF_LAST_REWARD", "FINENV_NF_AMOUNT0", "FINENV_STOCKNP_F64_FIELDS"]
+    assert H.enum("FINENV_STOCKNP_I32_FIELDS") == [
+        "FINENV_NI_DAY", "FINENV_NI_TAGS", "FINENV_NI_AMOUNT0_TAG", "FINENV_STOCKNP_I32_FIELDS"]
     assert nat.STOCKNP_F64_FIELDS == ("amount", "total_asset", "gamma_reward",
                                       "initial_total_asset", "episode_return", "last_reward",
                                       "amount0")
