@@ -97,12 +97,43 @@ __device__ __forceinline__ Num n_div(Num a, Num b)
     const double r32 = (double)((float)a.v / (float)b.v), r64 = a.v / b.v;
     return mk(t == FINENV_NT_F32 ? r32 : r64, t);
 }
+// np.float32 // np.float32 (npy_floor_dividef) for b > 0, given the exact floor q of a / b.  NumPy takes
+// fmodf(a, b), divides a - mod by b IN FLOAT32, and rounds that quotient to a whole number: below 2^22 the
+// two roundings cannot move it by 0.5 and the result is the floor; from there on it is whatever they leave
+// (at 2^24 and above usually no whole number's neighbour), and min(amount // price, a) returns it wherever
+// the scaled action a is the larger -- which needs an action beyond 2^22 shares.  fmodf(a, b) is
+// a - b * trunc(a / b), one exact FMA on q: a and b are float32 and |q| >= 2^22, so it is a multiple of
+// ulp(b) below b.
+__device__ __forceinline__ double floordiv_f32(float a, float b, double q)
+{
+    const double r = fma(-q, (double)b, (double)a);          // a - b * floor(a / b), in [0, b)
+    const float mod = (float)((a < 0.0f && r != 0.0) ? r - (double)b : r);
+    float div = (a - mod) / b;
+    if (mod < 0.0f) div -= 1.0f;
+    float fl = floorf(div);                                  // (div != 0 here)
+    if (div - fl > 0.5f) fl += 1.0f;
+    return (double)fl;
+}
 __device__ __forceinline__ Num n_floordiv(Num a, Num b)      // b > 0 (floordiv_true: finenv_dev.h)
 {
     const int t = promote(a.tag, b.tag);
-    // float32 case: operands are first rounded to float32, the quotient is exact in fp64
+    // float32 case: operands are first rounded to float32; the exact floor is NumPy's result below 2^22
     const double av = (t == FINENV_NT_F32) ? (double)(float)a.v : a.v;
-    return mk(floordiv_true(av, b.v), t);
+    const double q = floordiv_true(av, b.v);
+    if (t == FINENV_NT_F32 && fabs(q) >= 0x1p22) return mk(floordiv_f32((float)av, (float)b.v, q), t);
+    return mk(q, t);
+}
+
+// (actions * max_stock).astype(int), :104, on the stated action domain (include/finenv.h, "Action domain"
+// of this env): the float32 product bounded to [-S, S], S = 2^31 - 128 the largest float32 an int32 holds,
+// then truncated toward zero.  Without the bound a product at or below -2^31 converts to int32's minimum,
+// whose negation is itself: the sale of -2^31 shares grew the holdings by 2^31
+// (profiles/stocknp_action_domain.md).  One v_med3_f32 per ticker, off the cash chain; a NaN comes out as
+// a bound (med3 returns min3 then), never as a fault.
+__device__ __forceinline__ int scaled_action(float action, float max_stock)
+{
+    constexpr float kS = 2147483520.0f;
+    return (int)__builtin_amdgcn_fmed3f(action * max_stock, -kS, kS);
 }
 
 // heads[el*kRowH + 0] = amount*2^-12 (f32), [1..N] stocks*2^-6, [1+N..2N] cool_down
@@ -485,7 +516,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
 #pragma unroll
         for (int i = 0; i < kMaxN; ++i) {
             const int ic = min(i, N - 1);
-            ai[i] = (int)(arow[ic] * ms);                                         // :104
+            ai[i] = scaled_action(arow[ic], ms);                                  // :104
             pr_[i] = 0.0f;
         }
         if (uni) {                           // (a branch, not a select: no global load at all)
@@ -581,7 +612,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             for (int j = 0; j < kPB; ++j) {
             const int i = i0 + j;
             if (i >= N) break;
-            const int a = (int)(arow[i] * ms);                                        // :104
+            const int a = scaled_action(arow[i], ms);                                 // :104
             const float pr = prb[j];
             if (calm && a < -min_action && pr > 0.0f) {
                 const float s = scol[i * kWave];
@@ -615,7 +646,7 @@ __global__ void __launch_bounds__(kWave *kWaves *(RESET_ONLY ? 1 : 2)) stocknp_k
             for (int j = 0; j < kPB; ++j) {
             const int i = i0 + j;
             if (i >= N) break;
-            const int a = (int)(arow[i] * ms);
+            const int a = scaled_action(arow[i], ms);
             const float pr = prb[j];
             if (calm && a > min_action && pr > 0.0f) {
                 const Num q = n_floordiv(amount, mk((double)pr, FINENV_NT_F32));      // amount // price

@@ -1155,6 +1155,23 @@ typedef struct finenv_stocknp_config {
                                      (env_nas100_wrds.py:154, floor = 1e4)                 */
 } finenv_stocknp_config;
 
+/* Action domain of finenv_stocknp_step.  An action is any finite f32: the reference does not clip, it
+ * trades a = (actions * max_stock).astype(int) shares (:104) -- the product taken in float32, then truncated
+ * toward zero -- so an action of 3.0 asks for 3 * max_stock shares and |action * max_stock| < 1 for none.
+ * [-1, 1] is only the env's nominal action_space.  Both compares against min_action are strict (:112,
+ * :120): a == +-min_action trades nothing, and with min_action == 0 a == +-1 trades.  Both min() calls
+ * return their first, float32, operand at equality: min(stocks[i], -a) with -a == stocks[i] sells on the
+ * float32 product chain, min(amount // price, a) at equality buys the quotient, and the dtype tag the env
+ * carries from then on follows (:114, :124).  `amount // price` is NumPy's: the exact floor in float64 and,
+ * for a float32 amount, what npy_floor_dividef returns -- the floor below 2^22, its two float32 roundings
+ * from there on.
+ * For |trunc(action * max_stock)| <= S = 2^31 - 128, the largest float32 an int32 holds, the step equals
+ * the reference exactly, whatever binds the trade.  Beyond S an action trades exactly as +-S does: same
+ * sign, never a wrapped value (the reference's int64 would ask for more; holdings and cash cut both short
+ * alike unless more than S shares are there to sell or to pay for).  NaN and +-inf actions are unspecified
+ * (the reference's own cast is undefined there); they trade some amount within +-S and never fault.
+ * tests/test_gpu_stocknp_action_domain.py holds the kernel to this. */
+
 /* Prices are finite f32 >= 0.  A trade needs price > 0, as in the reference (:112-129): at a price of
  * 0 neither a sell nor a buy touches holdings, amount or the cool-down, which goes on counting; the
  * turbulent liquidation (:131-134) sells everything and values a zero-priced holding at 0.  A day is

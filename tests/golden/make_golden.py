@@ -483,9 +483,12 @@ def _tag(x):
 
 def run_stocknp(name, *, seed, T, N, K, S, if_train=False, initial_capital=1e6, max_stock=1e2,
                 turb_scale=60.0, buy_cost_pct=1e-3, sell_cost_pct=1e-3, gamma=0.99, nas100=False,
-                data_gap=1, turbulence_thresh=99, panel=None):
+                data_gap=1, turbulence_thresh=99, panel=None, script=None, **ctor):
     """Unmodified reference env_stocktrading_np.StockTradingEnv (NumPy-version dependent mixed
     float32/float64 arithmetic: the dtype of every scalar is recorded next to its value).
+    panel=(price, tech, turb): these arrays instead of the seeded walk; script(s, amount, tag, stocks,
+    price_row) -> [N] f32: the step's actions from the env's state before it; ctor: further constructor
+    arguments (initial_stocks).
     nas100=True: env_nas100_wrds.StockEnvNAS100 instead -- the same step on float32 arrays handed
     over directly (cwd=None, if_eval=True: rows [0:211210:data_gap]), a random start state at
     every reset and an observation that shows max(amount, 1e4)."""
@@ -515,10 +518,14 @@ def run_stocknp(name, *, seed, T, N, K, S, if_train=False, initial_capital=1e6, 
         if panel == "pricedomain":  # levels 1e-3 .. 1e5 with zero prices; a day on the threshold, one above
             price = pricedomain_prices(rng, T, N, -3.0, 5.0, 0.01, keep_row0=True)
             turb[[4, 6]] = turbulence_thresh, 150.0
+        elif panel is not None:
+            price, tech, turb = panel
+            assert price.shape == (T, N) and tech.shape == (T, N * K) and turb.shape == (T,)
         cfg = {"price_array": price, "tech_array": tech, "turbulence_array": turb,
                "if_train": if_train}
         env = mod.StockTradingEnv(cfg, initial_capital=initial_capital, max_stock=max_stock,
-                                  buy_cost_pct=buy_cost_pct, sell_cost_pct=sell_cost_pct, gamma=gamma)
+                                  buy_cost_pct=buy_cost_pct, sell_cost_pct=sell_cost_pct, gamma=gamma,
+                                  **ctor)
     act = rng.uniform(-1, 1, (S, N)).astype(np.float32)
     rec = {k: [] for k in ("obs", "reward", "reward_tag", "done", "amount", "amount_tag",
                            "total_asset", "ta_tag", "gamma_reward", "g_tag", "stocks",
@@ -537,6 +544,9 @@ def run_stocknp(name, *, seed, T, N, K, S, if_train=False, initial_capital=1e6, 
 
     do_reset(-1)
     for s in range(S):
+        if script is not None:
+            act[s] = script(s, float(env.amount), _tag(env.amount), np.asarray(env.stocks, np.float32).copy(),
+                            np.asarray(env.price_ary[env.day + 1], np.float32))
         obs, rew, done, info = env.step(act[s].copy())
         rec["obs"].append(np.asarray(obs, np.float32))
         rec["reward"].append(float(rew)); rec["reward_tag"].append(_tag(rew))
@@ -596,7 +606,27 @@ STOCKNP_SCENARIOS = {
                          turbulence_thresh=30, turb_scale=25.0),
     "nas100_poor": dict(seed=56, T=24, N=5, K=2, S=55, nas100=True, data_gap=4, gamma=0.999,
                         turbulence_thresh=30, turb_scale=25.0, initial_capital=3e4),
+    # tests/stocknp_action_cases.py, one env each at max_stock 128: k / max_stock and its float32 neighbours
+    # around 0, +-min_action and +-max_stock;
+    "actdom_boundary": dict(actdom="boundary", seed=58),
+    # sales of exactly the holdings and buys of exactly amount // price on dyadic prices, scripted on the
+    # env's own state;
+    "actdom_ties": dict(actdom="ties", seed=59),
+    # scaled actions 2^8 .. 2^31 - 128 against 2^30-share holdings and 1e12 of cash, one turbulent day,
+    # and +-2^40 on step 1 (the reference's int64 cast holds it)
+    "actdom_beyond": dict(actdom="beyond", seed=60),
 }
+
+
+def actdom_scenario(*, actdom, seed):
+    """One env of a case of tests/stocknp_action_cases.py as runner arguments."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import stocknp_action_cases as sc
+    fx = sc.fixture(actdom, seed)
+    return dict(seed=seed, T=fx["T"], N=fx["N"], K=fx["K"], S=fx["S"], panel=(fx["price"], fx["tech"], fx["turb"]),
+                script=fx["script"], initial_capital=fx["initial_capital"], max_stock=fx["max_stock"],
+                buy_cost_pct=fx["buy_cost_pct"], sell_cost_pct=fx["sell_cost_pct"], gamma=fx["gamma"],
+                initial_stocks=fx["initial_stocks"])
 
 
 # ----------------------------------------------------------------- cash-penalty env
@@ -1198,7 +1228,8 @@ def main(argv):
         elif n.startswith("riskpre:") and n[8:] in RISKPRE_SCENARIOS:
             run_riskpre(n[8:], **RISKPRE_SCENARIOS[n[8:]])
         elif n.startswith("stocknp:") and n[8:] in STOCKNP_SCENARIOS:
-            run_stocknp(n[8:], **STOCKNP_SCENARIOS[n[8:]])
+            sc = STOCKNP_SCENARIOS[n[8:]]
+            run_stocknp(n[8:], **(actdom_scenario(**sc) if "actdom" in sc else sc))
         elif n.startswith("crypto:") and n[7:] in CRYPTO_SCENARIOS:
             run_crypto(n[7:], **CRYPTO_SCENARIOS[n[7:]])
         elif n == "data_formats":

@@ -112,7 +112,7 @@ def test_fixture_episodes_are_recorded_under_auto_reset(name):
     the state no longer holds -- and stays so through the second episode; reset() re-arms and the second
     record is the second episode."""
     _need_gpu()
-    assert len(NAMES) == 7
+    assert len(NAMES) == 10
     z, env = _fixture_env(name)
     E, N = env.num_envs, env.action_dim
     T = z["price_array"].shape[0]

@@ -176,7 +176,7 @@ def test_fixture_windows_in_a_nan_padded_panel(name):
     a window is read."""
     _need_gpu()
     from finrl_amd.vec_stocknp import VecStockTradingEnvNP
-    assert len(NAMES) == 7
+    assert len(NAMES) == 10
     z = np.load(os.path.join(GOLDEN, f"stocknp_{name}.npz"), allow_pickle=False)
     T, N, K, S, if_train = z["cfg_int"].tolist()
     cap, ms, bc, sc, g = z["cfg_float"].tolist()

@@ -79,7 +79,7 @@ SEEN_KINDS = {}
 @pytest.mark.parametrize("name", NAMES)
 def test_builders_reproduce_the_reference_list_and_its_element_types(name):
     from finrl_amd import history as H
-    assert len(NAMES) == 7
+    assert len(NAMES) == 10
     z = _fixture(name)
     rng = np.random.default_rng(len(name))
     eps = _episodes(z)
